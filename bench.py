@@ -7,8 +7,18 @@ in HBM when the timed region starts.  One step = one pass of the hot path over t
 build the range tree (the streaming pass over a,b: 16 B/site) + answer every window.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline figure needs: it builds the columns, warms up (about PREWARM_S seconds of
+untimed steps, then --warmup steps), times exactly --steps steps and prints the line; "ms_per_step" is one timed step.
+Everything else this script measures or checks — the roofline events, the sanity and reference checks, the CPU
+baseline, the 10^8-site configs, the sustained and exchange-overhead legs, telemetry and, for N > 1, rank 0's
+single-GPU recomputation of the table — runs only with --full.  --dump-outputs DIR writes the rows of the timed path's
+last step (the table a caller of the scan receives) as DIR/<field>.npy, float64, at most 64 MB in all; the inputs are
+seeded, so two builds given the same arguments can be compared array for array.
 
 Plain `python bench.py --gpus N` with N > 1 (no WORLD_SIZE in the environment) starts the N ranks itself:
 the parent — which never touches the GPU and imports neither torch nor the library — runs the second
@@ -20,10 +30,10 @@ site_hi) of the genome (counter-based generator keyed on the global site index, 
 and reduces its block.  Rows reach rank 0 by an asynchronous double-buffered RCCL gather (--exchange auto, the
 default: the transport north_star names, and the only one an unattended run takes) or by peer stores over xGMI into
 rank 0's row buffer (no per-step collective; opt-in).  With --exchange both, BOTH transports are timed — the peer
-stores after the gather's line has been secured — and each assembled table is checked; "value" is the gather's
+stores after the gather's line has been secured — and, with --full, each assembled table is checked; "value" is the gather's
 unless the peer-store run was verified bitwise in this very run AND was faster; both timings are in "extra"
 (exchange_gather / exchange_peer).  STRONG scaling: total work is fixed at
---sites; value = --sites x steps / max-over-ranks time.  After each timed region rank 0 rebuilds the whole
+--sites; value = --sites x steps / max-over-ranks time.  With --full, after each timed region rank 0 rebuilds the whole
 genome (once), runs the single-GPU scan and demands the assembled multi-GPU table to be bitwise equal
 ("rows_check"); the table's SHA-256 ("rows_sha256") is the same for every N.  --scaling weak instead gives
 every rank --sites sites (genome = N x --sites).
@@ -32,7 +42,8 @@ every rank --sites sites (genome = N x --sites).
 batched in one launch per step over one window table, site ranges sharded over the N GPUs, the 28 x windows
 rows of every rank delivered to rank 0 and checked bit for bit against the single-GPU call.
 
-Unattended N > 1 runs (the driver's): every phase — init / columns / gather timed / verify / roofline / peer timed —
+Unattended N > 1 runs (the driver's): every phase — init / columns / gather timed / verify / roofline / peer timed (verify
+and roofline with --full) —
 is announced on stderr by every rank with its elapsed seconds and runs under its own deadline (PHASE_DEADLINES_S; a
 watchdog thread per rank).  A phase that overruns ends the rank with exit code 124 and a line naming the phase, so a
 wedged rank reads as "rank 3: phase 'gather timed' exceeded its deadline of 60 s", not as a driver timeout; only the
@@ -45,7 +56,7 @@ config.collective_backend.  Budget of `--gpus 8` on the 10^9-site genome: < 180 
 init + probe ~15 s, columns ~5 s, gather timed ~1 s, rank 0's rebuild of the whole 20-GB genome + single-GPU scan ~15 s,
 roofline ~1 s; the deadlines (sum 480 s) stay inside the driver's 600 s.
 
-The default N=1 run also times BASELINE configs 2, 3 and 5 in their one-GPU form at 10^8 sites
+The N=1 run with --full also times BASELINE configs 2, 3 and 5 in their one-GPU form at 10^8 sites
 ("extra"; --headline-only skips them, e.g. under rocprofv3 --stats) and the reference CPU path on a
 bounded sample ("cpu_baseline").  That leg is also the run's LIVE PARITY CHECK: the TSV the reference prints for the
 sample (the first 5x10^7 sites = the first two chromosomes, ~5000 windows) is compared with the rows the timed GPU run
@@ -100,7 +111,17 @@ def parse_args(argv=None):
                     help="fst = the headline 2-population scan (default); pairs = BASELINE configs[4]: all --pairs population pairs "
                          "batched over one window table (use --sites 1e8 --chroms 20), sharded by site range like the headline")
     ap.add_argument("--pairs", type=int, default=28, help="population pairs of --workload pairs (8 populations = 28)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: roofline events, sanity and reference checks, CPU baseline, "
+                         "the 10^8-site configs, the sustained and exchange-overhead legs, telemetry, and (N > 1) the single-GPU "
+                         "recomputation on rank 0.  Without it: set up, warm up, time --steps steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the rows of the timed path's last step as DIR/<field>.npy (float64; at most 64 MB in all, a seeded "
+                         "sample of the windows beyond that)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def self_launch(args) -> int:
@@ -274,6 +295,29 @@ from gpu_telemetry import Telemetry, pci_bus_id_of  # noqa: E402
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md: 8.0 TB/s; 6.29 TB/s measured copy ceiling)
 BYTES_PER_SITE = 16.0  # algorithmic: a,b f64 read once by the tree-build kernel
 SEED = 12345
+
+
+DUMP_LIMIT_BYTES = 60 << 20  # --dump-outputs: the arrays' payload stays below 64 MB with room for the .npy headers
+
+
+def dump_outputs(out_dir, table, n_tables, n_windows):
+    """--dump-outputs: the row table of the timed path's last step, one float64 array per field of FST_ROW_DTYPE
+    (DIR/<field>.npy, shape (windows,), or (pairs, windows) with --workload pairs; the u32 fields are exact in float64).
+    A table above DUMP_LIMIT_BYTES is cut to a fixed sample of its windows (seeded, sorted, the same windows in every
+    table), whose indices go to DIR/window_index.npy."""
+    rows = np.frombuffer(table.tobytes(), dtype=FST_ROW_DTYPE).reshape(n_tables, n_windows)
+    fields = FST_ROW_DTYPE.names
+    idx = None
+    if n_tables * n_windows * len(fields) * 8 > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES // (n_tables * len(fields) * 8 + 8)
+        idx = np.sort(np.random.default_rng(SEED).choice(n_windows, size=keep, replace=False))
+        rows = rows[:, idx]
+    os.makedirs(out_dir, exist_ok=True)
+    for f in fields:
+        col = rows[f].astype(np.float64)
+        np.save(os.path.join(out_dir, f + ".npy"), col if n_tables > 1 else col[0])
+    if idx is not None:
+        np.save(os.path.join(out_dir, "window_index.npy"), idx.astype(np.float64))
 
 
 def fmt_g6(x):
@@ -940,7 +984,7 @@ def main():
     dev_index = 0 if os.environ.get("PGT_BENCH_SHARE_GPU") == "1" else local_rank
     torch.cuda.set_device(dev_index)
     dev = torch.device("cuda", dev_index)
-    tel = Telemetry(pci_bus_id_of(dev_index)) if rank == 0 else None  # sysfs / amdsmi only: no HIP call, no process started
+    tel = Telemetry(pci_bus_id_of(dev_index)) if rank == 0 and args.full else None  # sysfs / amdsmi only: no HIP call, no process started
     telemetry = {"reader": tel.describe(), "at_start": tel.snapshot()} if tel else {}
     group, coll_dev, backend_desc = None, dev, "none (single GPU)"
     if world > 1:
@@ -975,7 +1019,7 @@ def main():
         win_d = windows_to_device(local, dev)
         ctx = pgt.Context(dev_index)
         ctx.set_max_window(int((win["hi"] - win["lo"]).max()))  # = W: tree levels above 8192 sites are not needed
-        want_extra = world == 1 and not args.headline_only and not pairs_mode
+        want_extra = args.full and world == 1 and not args.headline_only and not pairs_mode
         tree_bytes = max(ctx.tree_bytes(PGT_STAT_FST, n), 28 * ctx.tree_bytes(PGT_STAT_FST, 100_000_000),
                          ctx.tree_bytes(PGT_STAT_DXY, 100_000_000) + 2 * ctx.tree_bytes(PGT_STAT_HET, 100_000_000)) \
             if want_extra else n_tables * ctx.tree_bytes(PGT_STAT_FST, n)
@@ -1046,7 +1090,7 @@ def main():
             torch.cuda.empty_cache()
         return single["t"]
 
-    can_verify = world > 1 and not args.no_verify and (args.scaling == "strong" or n_total <= 2_000_000_000)
+    can_verify = args.full and world > 1 and not args.no_verify and (args.scaling == "strong" or n_total <= 2_000_000_000)
 
     def run_transport(mode, degradable=False):
         """One row transport: timed region + the table of its last step + the bitwise check.  Collective."""
@@ -1070,7 +1114,7 @@ def main():
                 dt_ = timed_region(ex)
             table_ = ex.finish()  # rank 0: the assembled table of the last step (uint8 numpy)
         res = {"mode": ex.mode, "available": True, "dt": dt_, "table": table_, "verified": None}
-        if world > 1:
+        if world > 1 and args.full:
             with ph("verify", degradable=degradable):
                 verdict = torch.zeros(1, dtype=torch.int32)
                 if rank == 0 and can_verify:
@@ -1134,6 +1178,7 @@ def main():
         rows_check = ref_check  # N = 1: the reference's own TSV for the CPU-baseline sample against this run's rows (or None: --no-cpu)
         if world > 1:
             rows_check = ("bitwise equal to the single-GPU scan of the whole genome" if can_verify else
+                          "skipped (checked with --full)" if not args.full else
                           ("skipped (--no-verify)" if args.no_verify else "skipped (weak-scaling genome too large to rebuild on one GPU)"))
         sha = hashlib.sha256(table.tobytes()).hexdigest()
         rows = np.frombuffer(table.tobytes(), dtype=FST_ROW_DTYPE)
@@ -1151,8 +1196,16 @@ def main():
             extra["note"] = note
         extra["phase_seconds"] = {k: round(v, 3) for k, v in ph.taken.items()}
         extra["seconds_since_start"] = round(time.perf_counter() - T_START, 2)
-        achieved = BYTES_PER_SITE * n_tables * n / (build_avg * 1e-3) / 1e9  # GB/s
-        traffic, traffic_source = pmc_traffic(n, n_tables)
+        roofline = None  # a plain run takes no roofline events (--full)
+        if build_avg is not None:
+            achieved = BYTES_PER_SITE * n_tables * n / (build_avg * 1e-3) / 1e9  # GB/s
+            traffic, traffic_source = pmc_traffic(n, n_tables)
+            roofline = {"bound": "hbm", "kernel": "fst_build_kernel", "achieved": achieved, "peak": HBM_PEAK_GBS,
+                        "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                        "traffic_unit": "HBM bytes per launch of the build kernel (read + written)",
+                        "traffic_source": traffic_source,
+                        "kernel_ms": build_avg, "query_kernel_ms": query_avg, "measured": roof_detail,
+                        "algorithmic_bytes_per_launch": BYTES_PER_SITE * n_tables * n, "sites_per_launch": n}
         per_gpu = [int(s_["site_hi"] - s_["site_lo"]) for s_ in shards]
         degraded = world > 1 and "FALLBACK" in backend_desc  # RCCL could not be brought up: rows went through the CPU over gloo
         line = {
@@ -1193,12 +1246,7 @@ def main():
                        "parallelism": f"site-range shards x{world}" if world > 1 else "single GPU"},
             "rows_sha256": sha,
             "rows_check": rows_check,
-            "roofline": {"bound": "hbm", "kernel": "fst_build_kernel", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "traffic_unit": "HBM bytes per launch of the build kernel (read + written)",
-                         "traffic_source": traffic_source,
-                         "kernel_ms": build_avg, "query_kernel_ms": query_avg, "measured": roof_detail,
-                         "algorithmic_bytes_per_launch": BYTES_PER_SITE * n_tables * n, "sites_per_launch": n},
+            "roofline": roofline,
             "cpu_baseline": cpu,
             "extra": extra,
         }
@@ -1226,9 +1274,13 @@ def main():
             print(f"bench.py: the table assembled by '{runs[0]['mode']}' differs from the single-GPU table of the same genome",
                   file=sys.stderr, flush=True)
         raise SystemExit(3)
-    if rank == 0:
-        sanity(runs[0]["table"])
-    build_avg, query_avg, roof_detail = roofline_events()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, runs[0]["table"], n_tables, int(win.size))
+    build_avg, query_avg, roof_detail = None, None, None
+    if args.full:
+        if rank == 0:
+            sanity(runs[0]["table"])
+        build_avg, query_avg, roof_detail = roofline_events()
     if len(modes) > 1:
         # the gather's line is secured: whatever the opt-in second transport does (a mapping that never returns, stores
         # that never land) can no longer cost the run its result
@@ -1241,7 +1293,7 @@ def main():
                   "(\"ok\": false in the line)", file=sys.stderr, flush=True)
 
     extra, cpu, ref_check = {}, None, None
-    if rank == 0 and world == 1 and not pairs_mode:
+    if rank == 0 and world == 1 and not pairs_mode and args.full:
         if not args.headline_only:
             with ph("extra configs"):
                 extra = extra_configs(ctx, dev, W, S, tree, check_het=not args.no_cpu)

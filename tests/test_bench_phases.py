@@ -239,3 +239,46 @@ def test_library_banners_do_not_reach_stdout_and_the_secured_line_still_does():
     lines = r.stdout.strip().splitlines()
     assert len(lines) == 1 and json.loads(lines[0])["secured"] is True, r.stdout
     assert "BANNER" in r.stderr
+
+
+def test_dump_outputs_writes_every_row_field_and_samples_a_large_table(tmp_path, monkeypatch):
+    """--dump-outputs: one float64 array per row field — (windows,) for one table, (pairs, windows) for the batched pairs —
+    and, above the size limit, the same seeded sample of windows in every table, with their indices beside them."""
+    import numpy as np
+    from popgenomicstools_amd._lib import FST_ROW_DTYPE
+    n_tables, n_win = 3, 1000
+    rows = np.zeros(n_tables * n_win, dtype=FST_ROW_DTYPE)
+    k = np.arange(rows.size)
+    rows["start"], rows["end"], rows["mid"], rows["n"] = k + 1, k + 50_000, k + 25_000, 4_000_000_000 - k
+    rows["fst"], rows["asum"], rows["bsum"] = k / 7.0, k * 0.5, np.sqrt(k)
+    bench.dump_outputs(str(tmp_path / "one"), rows[:n_win].view(np.uint8), 1, n_win)
+    bench.dump_outputs(str(tmp_path / "all"), rows.view(np.uint8), n_tables, n_win)
+    for f in FST_ROW_DTYPE.names:
+        one, every = np.load(tmp_path / "one" / f"{f}.npy"), np.load(tmp_path / "all" / f"{f}.npy")
+        assert one.dtype == np.float64 and one.shape == (n_win,) and np.array_equal(one, rows[f][:n_win].astype(np.float64))
+        assert every.shape == (n_tables, n_win) and np.array_equal(every, rows[f].reshape(n_tables, n_win).astype(np.float64))
+    assert not (tmp_path / "one" / "window_index.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 20_000)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), rows.view(np.uint8), n_tables, n_win)
+    idx = np.load(tmp_path / "a" / "window_index.npy")
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "window_index.npy")) and 0 < idx.size < n_win
+    assert np.all(np.diff(idx) > 0) and idx.dtype == np.float64
+    total = 0
+    for f in FST_ROW_DTYPE.names:
+        got = np.load(tmp_path / "a" / f"{f}.npy")
+        assert got.shape == (n_tables, idx.size)
+        assert np.array_equal(got, rows[f].reshape(n_tables, n_win)[:, idx.astype(np.int64)].astype(np.float64))
+        total += got.nbytes
+    assert total + idx.nbytes <= 20_000
+
+
+def test_plain_and_full_options():
+    """--full and --dump-outputs are off by default; --steps below 1 is refused rather than divided by."""
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120,
+                       cwd=ROOT, env=dict(os.environ, PYTHONPATH=ROOT))
+    assert r.returncode == 2 and "--steps" in r.stderr

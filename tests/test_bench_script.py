@@ -10,7 +10,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--sites", "3e6", "--chroms", "5", "--steps", "3", "--warmup", "1", "--headline-only", "--no-cpu"]
+# --full: these tests check the roofline, the single-GPU recomputation (N > 1) and the phases that run only with it
+SMALL = ["--sites", "3e6", "--chroms", "5", "--steps", "3", "--warmup", "1", "--headline-only", "--no-cpu", "--full"]
 
 
 def _line(r):
@@ -37,6 +38,44 @@ def test_bench_single_and_two_rank_tables_agree(workload):
         assert two["rows_sha256"] == one["rows_sha256"]
         assert sum(two["config"]["sites_resident_per_gpu"]) < 1.2 * one["config"]["sites_total"]
         assert two["extra"]["exchange_" + mode]["rows_check"] == "bitwise equal" and two["extra"]["exchange_" + mode]["headline"]
+
+
+@pytest.mark.timeout(900)
+def test_plain_bench_run_is_the_headline_alone_and_dumps_the_rows_of_its_last_step(tmp_path):
+    """Without --full the run sets up, warms up, times exactly --steps steps and prints the line, with nothing measured or
+    checked beside it.  --dump-outputs writes the row table of the last timed step: the same arrays in two plain runs, in a
+    --full run and in a two-rank run, and the very bytes rows_sha256 hashes."""
+    import hashlib
+    import numpy as np
+    from popgenomicstools_amd._lib import FST_ROW_DTYPE
+    env = _rehearsal_env()
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--sites", "3e6", "--chroms", "5", "--steps", "4", "--warmup", "1"]
+    lines, dumps, errs = [], [], []
+    for k, extra in enumerate((["--gpus", "1"], ["--gpus", "1"], ["--gpus", "1", "--full", "--headline-only", "--no-cpu"], ["--gpus", "2"])):
+        out = tmp_path / f"out{k}"
+        r = subprocess.run(base + extra + ["--dump-outputs", str(out)], capture_output=True, text=True, env=env, timeout=400)
+        lines.append(_line(r))
+        errs.append(r.stderr)
+        dumps.append({f: np.load(out / f"{f}.npy") for f in FST_ROW_DTYPE.names})
+        assert sorted(os.listdir(out)) == sorted(f + ".npy" for f in FST_ROW_DTYPE.names)
+    plain, full, two = lines[0], lines[2], lines[3]
+    assert plain["unit"] == "sites/s" and plain["higher_is_better"] is True and plain["dtype"] == "f64" and plain["ok"] is True
+    assert plain["steps"] == 4 and plain["warmup"] == 1 and plain["ms_per_step"] > 0
+    assert abs(plain["value"] - 3e6 / (plain["ms_per_step"] * 1e-3)) <= 1e-9 * plain["value"]
+    assert plain["roofline"] is None and plain["cpu_baseline"] is None and plain["rows_check"] is None
+    assert set(plain["extra"]["phase_seconds"]) == {"columns", "local timed"}, plain["extra"]
+    assert "roofline:" not in errs[0] and "verify:" not in errs[3]
+    assert full["roofline"]["frac"] > 0 and two["rows_check"] == "skipped (checked with --full)" and two["n_gpus"] == 2
+    assert len({ln["rows_sha256"] for ln in lines}) == 1
+    nwin = plain["config"]["windows"]
+    for f in FST_ROW_DTYPE.names:
+        assert dumps[0][f].dtype == np.float64 and dumps[0][f].shape == (nwin,)
+        for d in dumps[1:]:
+            assert np.array_equal(d[f], dumps[0][f]), f
+    rows = np.zeros(nwin, dtype=FST_ROW_DTYPE)
+    for f in FST_ROW_DTYPE.names:
+        rows[f] = dumps[0][f]
+    assert hashlib.sha256(rows.tobytes()).hexdigest() == plain["rows_sha256"]
 
 
 @pytest.mark.timeout(600)

@@ -1045,69 +1045,50 @@ def test_cli_in_passes_prints_the_resident_tsv(hosts, tmp_path, oracle):
 
 
 @pytest.mark.gpu
-def test_cli_live_against_the_reference_binaries(hosts, hosts_ext, tmp_path):
-    """Where oracle/_ref holds the compiled, unmodified reference tools (this container, and the GPU box, which
-    receives them with the snapshot): fresh random inputs — other seeds than the committed goldens — through the
-    reference binary and through the host, stdout compared (fstWindow: the %g column to its last printed digit;
-    hetWindow, ihsWindow, xpehhWindow: byte for byte)."""
-    import importlib.util
-    import random
+def test_cli_live_against_the_reference_binaries(hosts, hosts_ext, tmp_path, oracle):
+    """Random inputs — other seeds than the committed goldens — through the host, stdout compared with the reference's
+    (fstWindow: the %g column to its last printed digit; hetWindow, ihsWindow, xpehhWindow: byte for byte).  The reference's
+    stdout is the oracle port's output for the same input, which must hash to the SHA-256 the unmodified reference printed
+    (tests/golden/ref_sha256.json); where oracle/_ref holds the compiled reference tools they run beside the host as well
+    and must print those very bytes.  The "large" cases have S << W with windows of two and more level-2 tiles: the group
+    query (steps 1 .. 1024), the sliding query (short windows, steps up to 32) and one wave per window, each against the
+    reference's own re-summation (fstWindow.cpp:80-83,95-99) — larger tables than the fixtures can hold."""
+    import sys
     import oracle_bind
-    if not all(oracle_bind.ref_binary(t) for t in ("fstWindow", "hetWindow", "ihsWindow", "xpehhWindow")):
-        pytest.skip("oracle/_ref not built (no /root/reference here)")
-    spec = importlib.util.spec_from_file_location("make_golden", os.path.join(ROOT, "tests", "golden", "make_golden.py"))
-    mg = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mg)
-    rng = random.Random(20261004)
-    exact = total = 0
-    for tool in ("fstWindow", "hetWindow"):
-        for _ in range(15):
-            text, W, S = mg.random_case(rng, tool, max_chr=6, max_sites=60, max_w=25)
-            f = tmp_path / "in.txt"
-            f.write_text(text)
-            ref, mine = run_all([([oracle_bind.ref_binary(tool), str(f), str(W), str(S)], None), ([hosts[tool], str(f), str(W), str(S)], None)])
-            assert mine.returncode == 0 and ref.returncode == 0, (tool, W, S, mine.stderr)
-            if tool == "fstWindow":
-                tsv_equal(mine.stdout, ref.stdout, 4)
-            else:
-                assert mine.stdout == ref.stdout, (tool, W, S)
-            exact += mine.stdout == ref.stdout
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    import make_ref_sha256 as rs
+    stored = rs.load()
+    exact = total = n = 0
+    for case in rs.cli_cases():
+        key, tool = case["key"], case["tool"]
+        want = stored[key]
+        assert want["input_sha256"] == rs.input_sha256(case) and want["rc"] == 0, key
+        d = tmp_path / key
+        d.mkdir()
+        rc, expect = rs.oracle_stdout(oracle, case, d)
+        assert rc == 0 and rs.sha256(expect) == want["stdout_sha256"], key  # = what the reference printed
+        argv = rs.materialise(case, d)
+        jobs = [([(hosts_ext if case["kind"] == "extreme" else hosts)[tool]] + argv, None)]
+        ref = oracle_bind.ref_binary(tool)
+        if ref:
+            jobs.append(([ref] + argv, None))
+        res = run_all(jobs, workers=2)
+        mine = res[0]
+        assert mine.returncode == 0, (key, tool, case["args"], mine.stderr)
+        if ref:
+            assert res[1].returncode == 0 and res[1].stdout == expect, (key, tool, case["args"])
+        if case["kind"] == "large":
+            assert len(expect.splitlines()) > 10, key
+        if tool == "fstWindow":
+            tsv_equal(mine.stdout, expect, 4)
+        else:
+            assert mine.stdout == expect, (key, tool, case["args"])
+        if case["kind"] != "large":
+            exact += mine.stdout == expect
             total += 1
-    for tool in ("ihsWindow", "xpehhWindow"):
-        for _ in range(12):
-            files, args = mg.extreme_case(rng, tool, max_chr=5, max_sites=60)
-            paths = {}
-            for name, text in files.items():
-                p = tmp_path / name
-                p.write_text(text)
-                paths[name] = str(p)
-            argv = [paths[a[1:]] if a.startswith("@") else a for a in args]
-            ref, mine = run_all([([oracle_bind.ref_binary(tool)] + argv, None), ([hosts_ext[tool]] + argv, None)])
-            assert mine.returncode == 0 and ref.returncode == 0, (tool, args, mine.stderr)
-            assert mine.stdout == ref.stdout, (tool, args)
-            exact += 1
-            total += 1
+        n += 1
+    assert n == len(stored) - 80 and total == 54
     assert exact >= total - 3  # fstWindow rows may differ in the sixth digit of a ratio; in practice none does
-    # S << W with windows of two and more level-2 tiles: the group query (steps 1 .. 1024), the sliding query (short
-    # windows, steps up to 32) and one wave per window, each against the reference's own re-summation
-    # (fstWindow.cpp:80-83,95-99) — larger tables than the fixtures can hold
-    import synth
-    nrng = np.random.default_rng(20261004)
-    for n, n_chr, W, S in ((60_000, 3, 20_000, 1), (90_000, 2, 16_384, 7), (150_000, 4, 50_000, 100), (150_000, 1, 24_577, 64),
-                           (200_000, 5, 30_000, 1000), (30_000, 2, 3_000, 5), (200_000, 3, 50_000, 2500), (400_000, 2, 140_000, 300)):
-        chr_ids, pos = synth.chromosomes(nrng, n, n_chr, equal=False)
-        a_, b_ = synth.fst_columns(nrng, n)
-        g_ = synth.het_column(nrng, n)
-        f = tmp_path / "big.txt"
-        f.write_text("".join(f"chr{c}\t{p}\t{x:.6f}\t{y:.6f}\n" for c, p, x, y in zip(chr_ids, pos, a_, b_)))
-        fh_ = tmp_path / "big.het.txt"
-        fh_.write_text("".join(f"chr{c}\t{p}\t{v}\n" for c, p, v in zip(chr_ids, pos, g_)))
-        ref, mine, refh, mineh = run_all([([oracle_bind.ref_binary("fstWindow"), str(f), str(W), str(S)], None), ([hosts["fstWindow"], str(f), str(W), str(S)], None),
-                                          ([oracle_bind.ref_binary("hetWindow"), str(fh_), str(W), str(S)], None), ([hosts["hetWindow"], str(fh_), str(W), str(S)], None)],
-                                         workers=4)  # two of the four are the CPU reference
-        assert mine.returncode == 0 and ref.returncode == 0 and len(ref.stdout.splitlines()) > 10, (W, S, mine.stderr)
-        tsv_equal(mine.stdout, ref.stdout, 4)
-        assert mineh.returncode == 0 and mineh.stdout == refh.stdout, ("hetWindow", W, S)
 
 
 @pytest.mark.gpu

@@ -45,10 +45,10 @@ def _env(**kw):
 
 @pytest.mark.timeout(900)
 def test_bench_two_gpus_rccl_gather_and_peer_stores():
-    """`python bench.py --gpus 2 --sites 2e8 --exchange both` exactly as a user would type it: two ranks on two GPUs, the row
+    """`python bench.py --gpus 2 --sites 2e8 --exchange both --full` exactly as a user would type it: two ranks on two GPUs, the row
     collectives on RCCL, both transports timed, each assembled table bitwise the single-GPU table of the same genome."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--sites", "2e8", "--chroms", "8", "--steps", "5",
-                        "--warmup", "2", "--exchange", "both"], capture_output=True, text=True,
+                        "--warmup", "2", "--exchange", "both", "--full"], capture_output=True, text=True,
                        env=dict(_env(), PGT_BENCH_BACKEND="gloo", PGT_BENCH_SHARE_GPU="1") if PRETEND else _env(), timeout=850)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -184,7 +184,7 @@ def test_bench_two_gpus_pairs_workload_rccl_gather_and_peer_stores():
     pairs batched per launch, site ranges sharded, 28 x windows rows per rank delivered by the RCCL gather and by peer stores,
     each assembled (re-interleaved: table-major over ALL windows) table bitwise the single-GPU call's."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "pairs", "--pairs", "28", "--sites", "2e7",
-                        "--chroms", "6", "--steps", "5", "--warmup", "2", "--exchange", "both"], capture_output=True, text=True,
+                        "--chroms", "6", "--steps", "5", "--warmup", "2", "--exchange", "both", "--full"], capture_output=True, text=True,
                        env=dict(_env(), PGT_BENCH_BACKEND="gloo", PGT_BENCH_SHARE_GPU="1") if PRETEND else _env(), timeout=850)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

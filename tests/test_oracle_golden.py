@@ -207,23 +207,26 @@ def test_oracle_rejects_out_of_domain(oracle):
         oracle.fst_scan(z, z, d, d, 0, 1)  # W == 0 (reference: exit 255)
 
 
-@pytest.mark.skipif(oracle_bind.ref_binary("fstWindow") is None, reason="oracle/_ref not built here")
 def test_live_reference_fuzz(oracle, tmp_path):
-    """Where the compiled reference is present, fuzz the oracle against it live as well."""
-    import random
+    """80 random fstWindow / hetWindow runs: the oracle's stdout must be the reference's, byte for byte — by the SHA-256 of
+    what the reference printed for each (tests/golden/ref_sha256.json), and live as well where the compiled reference is present."""
     import subprocess
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
-    import make_golden
-    rng = random.Random(99)
-    for i in range(80):
-        tool = rng.choice(["fstWindow", "hetWindow"])
-        text, W, S = make_golden.random_case(rng, tool)
-        src = tmp_path / "f.txt"
-        src.write_text(text)
-        ref = subprocess.run([oracle_bind.ref_binary(tool), str(src), str(W), str(S)], capture_output=True, timeout=10)
-        rc, out = _run_text(oracle, tool, text, W, S, tmp_path)
-        assert rc == 0 and out.encode() == ref.stdout
+    import make_ref_sha256 as rs
+    stored = rs.load()
+    n = 0
+    for case in rs.oracle_fuzz_cases():
+        want = stored[case["key"]]
+        assert want["input_sha256"] == rs.input_sha256(case) and want["rc"] == 0, case["key"]
+        rc, out = rs.oracle_stdout(oracle, case, tmp_path)
+        assert rc == 0 and rs.sha256(out) == want["stdout_sha256"], case["key"]
+        ref = oracle_bind.ref_binary(case["tool"])
+        if ref:
+            live = subprocess.run([ref] + rs.materialise(case, tmp_path), capture_output=True, timeout=10)
+            assert live.returncode == 0 and live.stdout == out.encode(), case["key"]
+        n += 1
+    assert n == 80
 
 
 def test_extreme_tools_byte_identical(oracle, tmp_path):

@@ -1,7 +1,7 @@
 #!/bin/bash
 # bench.py N > 1 on a one-GPU box: every rank on GPU 0, collectives over gloo (logic only).  Prints one summary line per variant.
 export PGT_BENCH_BACKEND=gloo PGT_BENCH_SHARE_GPU=1
-S="--sites 3e6 --chroms 5 --steps 3 --warmup 1 --headline-only --no-cpu"
+S="--sites 3e6 --chroms 5 --steps 3 --warmup 1 --headline-only --no-cpu --full"
 for args in "--gpus 3" "--gpus 3 --workload pairs --pairs 3" "--gpus 2 --scaling weak" "--gpus 2 --exchange gather" "--gpus 2 --exchange peer" "--gpus 3 --exchange both" "--gpus 2 --no-verify" "--gpus 5 --stepsize 100"; do
   python bench.py $args $S > /tmp/out.txt 2>/tmp/err.txt; rc=$?
   python - "$args" $rc <<'PY'

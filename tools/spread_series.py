@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Process-to-process spread of the headline build kernel, with telemetry.
 
-Runs `python bench.py --no-cpu --no-exchange-overhead` N times as CHILD processes (this parent never touches the GPU) and
+Runs `python bench.py --full --no-cpu --no-exchange-overhead` N times as CHILD processes (this parent never touches the GPU) and
 tabulates, per process, the build kernel's fraction of the HBM peak next to what the GPU's own telemetry said during that
 process' timed region and sustained leg: shader clock, socket power against the cap, the growth of the power-limiter
 (PPT) residency counter, HBM / junction temperature, memory and fabric clocks.  Markdown on stdout.
@@ -26,7 +26,7 @@ def main():
     extra_args = sys.argv[2:]
     rows = []
     for i in range(n):
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu", "--no-exchange-overhead"] + extra_args,
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu", "--no-exchange-overhead"] + extra_args,
                            capture_output=True, text=True, timeout=900)
         if r.returncode != 0:
             print(f"run {i}: exit {r.returncode}: {r.stderr[-500:]}", file=sys.stderr)
@@ -53,7 +53,7 @@ def main():
             "vbios": t.get("reader", {}).get("identity", {}).get("vbios", {}).get("version")})
     if not rows:
         sys.exit("no run succeeded")
-    print(f"{len(rows)} processes of `python bench.py --no-cpu --no-exchange-overhead {' '.join(extra_args)}` back to back on one box "
+    print(f"{len(rows)} processes of `python bench.py --full --no-cpu --no-exchange-overhead {' '.join(extra_args)}` back to back on one box "
           f"(GPU at PCI {rows[0]['pci']}, ASIC serial {rows[0]['serial']}, VBIOS {rows[0]['vbios']}); t_ = during the headline's timed region (0.5 s), s_ = during the sustained leg (2.5 s)\n")
     cols = ["run", "frac", "kernel_ms", "ms_per_step", "sust_GBs", "fst1e8", "af8", "t_sclk", "t_sclk_max", "t_power", "t_ppt", "t_acc", "t_hbm_c",
             "s_sclk", "s_sclk_max", "s_power", "s_ppt", "s_acc", "s_hbm_c", "s_hot_c", "uclk", "fclk", "other_thr", "start_power", "start_hbm_c"]
