@@ -178,3 +178,88 @@ def hand_walked_product_expectation(case, run):
     if case["product"].get("rc", 0) != 0:  # the product refuses this input (exit status, a phrase of the message); nothing on stdout
         return None, case["product"]["stderr_contains"]
     return case["product"]["stdout"], case["product"]["stderr"]
+
+
+# ---- workspace contract (tests/test_workspace_contract.py) ---------------------------------------------------------------
+GUARD = 4096
+
+
+class GuardedBuffers:
+    """The buffers one call receives (tree, out, tot, ...), carved from ONE allocation: every buffer starts 256-byte aligned
+    and lies between guards of at least 4 KiB, which (with the slack up to the next 256 bytes) hold a seeded byte pattern.
+    check() synchronises and asserts that no guard byte changed."""
+
+    def __init__(self, sizes, seed, device):
+        import torch
+        self.spans, off = [], GUARD
+        for s in sizes:
+            self.spans.append((off, off + int(s)))
+            off += (int(s) + 255) // 256 * 256 + GUARD
+        gen = torch.Generator(device=device)
+        gen.manual_seed(int(seed))
+        self.pattern = torch.randint(0, 256, (off,), dtype=torch.uint8, device=device, generator=gen)
+        self.arena = self.pattern.clone()
+        assert self.arena.data_ptr() % 256 == 0
+        self.bufs = [self.arena[a:b] for a, b in self.spans]
+
+    def check(self, what=""):
+        import torch
+        torch.cuda.synchronize()
+        prev = 0
+        for a, b in self.spans + [(self.arena.numel(), self.arena.numel())]:
+            if not torch.equal(self.arena[prev:a], self.pattern[prev:a]):
+                bad = torch.nonzero(self.arena[prev:a] != self.pattern[prev:a])[:4].flatten().tolist()
+                raise AssertionError(f"{what}: guard bytes [{prev}, {a}) changed at offsets {[prev + x for x in bad]} "
+                                     f"(buffers at {self.spans})")
+            prev = b
+
+
+def padded_column(x, fill, device, pad_bytes=GUARD):
+    """x (numpy) as a 16-byte-aligned view into a larger device tensor whose pad_bytes before and after hold `fill`: a kernel
+    that reads outside [0, n) picks up the fill value."""
+    import torch
+    t = torch.from_numpy(np.ascontiguousarray(x))
+    k = pad_bytes // t.element_size()
+    full = torch.full((t.numel() + 2 * k,), fill, dtype=t.dtype, device=device)
+    full[k:k + t.numel()].copy_(t)
+    view = full[k:k + t.numel()]
+    assert view.data_ptr() % 16 == 0
+    return view
+
+
+EXT_POISON_NODE = np.array([(1e300, 0xFFFFFFFF, 0x40000000)], dtype=[("key", "<f8"), ("idx", "<u4"), ("count", "<u4")])
+
+
+def poison_tree(tree, kind, other=None, ext=False):
+    """Fill a tree workspace before a call.  kind 0: every byte 0xFF (a stale f64 is NaN, a stale count 0xFFFFFFFF) — for the
+    extreme-score tree, whose query dereferences pos[node.idx], nodes {key +1e300, idx 0xFFFFFFFF (the index the query
+    guards), count 2^30} instead, so that any stale node read wins the maximum and shows in the row; kind 1: `other`, the
+    fully built tree of a different dataset of the same size (finite, indices below n); kind 2: zeros."""
+    import torch
+    if kind == 0:
+        if ext:
+            node = torch.from_numpy(EXT_POISON_NODE.view(np.uint8).copy()).to(tree.device)
+            tree.view(-1, 16).copy_(node.expand(tree.numel() // 16, 16))
+        else:
+            tree.fill_(0xFF)
+    elif kind == 1:
+        tree.copy_(other[:tree.numel()])
+    else:
+        tree.zero_()
+
+
+def rows_equal(got, want, what):
+    """Structured rows equal bit for bit, the pad_ fields excepted; the message names the first differing row and field."""
+    got, want = got.copy(), want.copy()
+    assert got.dtype == want.dtype and got.size == want.size, (what, got.dtype, want.dtype, got.size, want.size)
+    if "pad_" in got.dtype.names:
+        got["pad_"] = 0
+        want["pad_"] = 0
+    if got.tobytes() == want.tobytes():
+        return
+    g8 = got.view(np.uint8).reshape(got.size, -1)
+    w8 = want.view(np.uint8).reshape(want.size, -1)
+    i = int(np.flatnonzero((g8 != w8).any(axis=1))[0])
+    fields = [f for f in got.dtype.names if got[f][i].tobytes() != want[f][i].tobytes()]
+    raise AssertionError(f"{what}: {int((g8 != w8).any(axis=1).sum())} of {got.size} rows differ; first row {i}, fields {fields}: "
+                         f"got {got[i]}, want {want[i]}")

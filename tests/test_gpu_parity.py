@@ -328,12 +328,12 @@ def test_dxy_site_value_is_bitwise_the_host_formula(pgt, ctx):
 # ---------------------------------------------------------------------------------------------
 # device-resident entry points, properties at scale
 # ---------------------------------------------------------------------------------------------
-def _device_fst(ctx, pos, a, b, win):
+def _device_fst(ctx, pos, a, b, win, tree=None):
     import torch
     dev = torch.device("cuda:0")
     tp = torch.from_numpy(pos.view(np.int32)).to(dev)
     ta, tb = torch.from_numpy(a).to(dev), torch.from_numpy(b).to(dev)
-    out, tree = ctx.fst_reduce_dev(tp, ta, tb, windows_to_device(win, dev))
+    out, tree = ctx.fst_reduce_dev(tp, ta, tb, windows_to_device(win, dev), tree=tree)
     torch.cuda.synchronize()
     return rows_from_device(out, FST_ROW_DTYPE)
 
@@ -548,25 +548,35 @@ def test_rccl_gather_single_rank(pgt, ctx):
 
 def test_max_window_hint_only_changes_speed(pgt, ctx):
     """pgt_set_max_window: with the exact bound the rows are the same bytes (the skipped levels were
-    never touched); with a bound that is too small the answers are still right (1e-9)."""
+    never touched); with a bound that is too small the answers are still right (1e-9).  The hinted calls get a tree
+    workspace poisoned first with 0xFF bytes, then with the fully built tree of another dataset: a query that read a level
+    the hinted build skipped would show (a fresh workspace is usually the block the unhinted call just filled)."""
     import torch
     rng = np.random.default_rng(41)
     n = 3_000_000
     chr_ids, pos = synth.chromosomes(rng, n, 2)
     a, b = synth.fst_columns(rng, n)
+    a2, b2 = synth.fst_columns(rng, n)
     win = pgt.build_windows_sites(pgt.run_lengths(chr_ids), 1_200_000, 400_000)  # windows contain level-3 nodes
     base = _device_fst(ctx, pos, a, b, win)
+    dev = torch.device("cuda:0")
+    other = torch.empty(ctx.tree_bytes(_lib.PGT_STAT_FST, n), dtype=torch.uint8, device=dev)
+    _device_fst(ctx, pos, a2, b2, win, tree=other)  # no hint: every level of the other dataset's tree
     try:
-        ctx.set_max_window(1_200_000)
-        assert _device_fst(ctx, pos, a, b, win).tobytes() == base.tobytes()
-        ctx.set_max_window(1000)  # wrong on purpose
-        low = _device_fst(ctx, pos, a, b, win)
+        for poison in ("0xFF", "other"):
+            tree = torch.full_like(other, 0xFF) if poison == "0xFF" else other.clone()
+            ctx.set_max_window(1_200_000)
+            assert _device_fst(ctx, pos, a, b, win, tree=tree).tobytes() == base.tobytes(), poison
+            tree = torch.full_like(other, 0xFF) if poison == "0xFF" else other.clone()
+            ctx.set_max_window(1000)  # wrong on purpose
+            low = _device_fst(ctx, pos, a, b, win, tree=tree)
+            ctx.set_max_window(0)
+            for f in ("start", "end", "mid", "n"):
+                assert np.array_equal(low[f], base[f])
+            assert_close(low["fst"], base["fst"], f"fst under a too-small hint, {poison} workspace")
+            assert_close(low["asum"], base["asum"], f"asum under a too-small hint, {poison} workspace")
     finally:
         ctx.set_max_window(0)
-    for f in ("start", "end", "mid", "n"):
-        assert np.array_equal(low[f], base[f])
-    assert_close(low["fst"], base["fst"], "fst under a too-small hint")
-    assert_close(low["asum"], base["asum"], "asum under a too-small hint")
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1488,11 +1498,17 @@ def test_fast_query_paths_equal_the_general_path_at_their_edges(pgt, ctx, n):
     tp, ta, tb, t1, t2, tn1, tn2, tg = t(pos.view(np.int32)), t(a), t(b), t(p1), t(p2), t(n1), t(n2), t(g)
     wd = windows_to_device(win, dev)
 
-    def rows():
-        f, _ = ctx.fst_reduce_dev(tp, ta, tb, wd)
-        h, _ = ctx.het_reduce_dev(tp, tg, wd)
-        d, tot, _ = ctx.dxy_reduce_dev(tp, t1, t2, tn1, tn2, 3, wd)
-        fused = ctx.dxy_het_reduce_dev(tp, t1, t2, tn1, tn2, tg, tg, 3, wd)
+    def poisoned(stat_bytes):  # the hinted calls' own workspaces, 0xFF: a level the hinted build skipped must not be read
+        return torch.full((stat_bytes,), 0xFF, dtype=torch.uint8, device=dev)
+
+    def rows(poison=False):
+        ws = lambda stat: poisoned(ctx.tree_bytes(stat, n)) if poison else None  # noqa: E731
+        f, _ = ctx.fst_reduce_dev(tp, ta, tb, wd, tree=ws(_lib.PGT_STAT_FST))
+        h, _ = ctx.het_reduce_dev(tp, tg, wd, tree=ws(_lib.PGT_STAT_HET))
+        d, tot, _ = ctx.dxy_reduce_dev(tp, t1, t2, tn1, tn2, 3, wd, tree=ws(_lib.PGT_STAT_DXY))
+        fused = ctx.dxy_het_reduce_dev(tp, t1, t2, tn1, tn2, tg, tg, 3, wd,
+                                       tree=poisoned(ctx.tree_bytes(_lib.PGT_STAT_DXY, n) + 2 * ctx.tree_bytes(_lib.PGT_STAT_HET, n))
+                                       if poison else None)
         torch.cuda.synchronize()
         return [x.cpu().numpy().tobytes() for x in (f, h, d, fused[0], fused[2], fused[3])], rows_from_device(tot, DXY_TOTAL_DTYPE)[0]
 
@@ -1508,7 +1524,7 @@ def test_fast_query_paths_equal_the_general_path_at_their_edges(pgt, ctx, n):
         assert np.array_equal(hr["nhet"], (nh[win["hi"].astype(np.int64)] - nh[win["lo"].astype(np.int64)]).astype(np.uint32))
         for mw in (50_000, 65_535, 65_536):
             ctx.set_max_window(mw)
-            got, gtot = rows()
+            got, gtot = rows(poison=True)
             inside = (win["hi"] - win["lo"]) <= mw  # windows the hint is true for: the same bytes; longer ones: a too-small hint
             # only changes the order of a float sum (test_max_window_hint_only_changes_speed) — integers exact, floats to 1e-9
             for k, (name, dt) in enumerate((("fst", FST_ROW_DTYPE), ("het", HET_ROW_DTYPE), ("dxy", DXY_ROW_DTYPE), ("fused dxy", DXY_ROW_DTYPE),
