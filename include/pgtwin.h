@@ -37,7 +37,8 @@ extern "C" {
  * includes the build waves' partial sums; pgt_extreme_reduce_cols, PGT_TOK_CHR_PREFIX and 12 tokens per line (added under
  * version 4 in round 4) are part of it.  A binding written for one version never calls a library of another. */
 /* 6 (round 6): pgt_prepare_host_io added; the host-buffer entry points stage their uploads through a per-context pinned
- * ring and keep a per-context workspace (no argument list changed). */
+ * ring and keep a per-context workspace (no argument list changed).
+ * Still 6: pgt_dxy_pops_tree_bytes / pgt_dxy_pops_reduce_dev / pgt_dxy_pops_reduce added (additive: nothing that existed changed). */
 #define PGT_ABI_VERSION 6
 
 enum {
@@ -189,6 +190,33 @@ size_t pgt_af_tree_bytes(uint32_t n_pops, uint64_t n_sites);
 int pgt_fst_af_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const double *nsamp,
                           uint32_t n_pops, uint64_t n, const pgt_win *win, uint64_t n_win, pgt_fst_row *out,
                           size_t out_bytes, void *tree, size_t tree_bytes, void *stream);
+
+/* ---- dxy of all population pairs from per-population columns ----------------------------------- */
+/* dxyWindow's window rows for ALL pairs i<j of n_pops populations over ONE position column and ONE window table, in one
+ * pass over each population's own columns (12 B/site/population) instead of one pgt_dxy_reduce_dev per pair (24 B/site/pair).
+ *   pos    DEVICE pointer, u32 position per site; may be NULL only when there is no window (n_win == 0) or no site
+ *   freq   host array of n_pops DEVICE pointers: f64 allele frequency per site (in [0,1], as the MAF ingest admits), 16-byte aligned
+ *   nind   host array of n_pops DEVICE pointers: i32 individuals with data per site, 16-byte aligned
+ *   out    n_pairs * n_win rows, pair-major, pairs ordered (0,1),(0,2),..,(0,n_pops-1),(1,2),.. as for pgt_fst_af_reduce_dev
+ *   tot    DEVICE array of n_pairs genome-wide lines, or NULL; n_win == 0 with tot: the global-only form (-winsize 0 -fixedsite 1)
+ *   tree   pgt_dxy_pops_tree_bytes(n_pops, n) bytes (0 for n_pops outside 2 ... 8).    2 <= n_pops <= 8, n < 2^32.
+ * Per pair the semantics are those of dxyWindow.cpp:172-209,381-385 as pgt_dxy_reduce_dev implements them on the pair's columns:
+ * a site counts when both populations have at least minind individuals and then adds p_i(1-p_j) + p_j(1-p_i), rounded
+ * exactly as there (a one-site window has the same bits); neff and coordinates are equal, sums agree to the last bits (the
+ * tree has 512-site leaves here, 128-site ones there); nskip is (sites of the window) - neff: every site of a range is a data
+ * site.  The pointer arrays are read before the call returns (the columns are kernel arguments: the call can be captured
+ * into a graph).  pgt_set_max_window is honoured; pgt_set_window_step is ignored (always one wave per window; rows do not
+ * depend on the window table's other rows).  Parity note: held to the two-population path and the CPU restatement (oracle/);
+ * dxy parity itself is unpinned.
+ * Host-buffer form: columns (host arrays of n_pops HOST pointers), table, rows and the n_pairs totals in host memory. */
+size_t pgt_dxy_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites);
+int pgt_dxy_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq,
+                            const int32_t *const *nind, uint32_t n_pops, uint64_t n, int minind,
+                            const pgt_win *win, uint64_t n_win, pgt_dxy_row *out, size_t out_bytes,
+                            pgt_dxy_total *tot, void *tree, size_t tree_bytes, void *stream);
+int pgt_dxy_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq,
+                        const int32_t *const *nind, uint32_t n_pops, uint64_t n, int minind,
+                        const pgt_win *win, uint64_t n_win, pgt_dxy_row *out, pgt_dxy_total *tot);
 
 /* ---- ihsWindow / xpehhWindow: extreme score in non-overlapping bp windows ---- */
 /* Replaces the window bookkeeping and per-window scan of ihsWindow.cpp:123-221 and

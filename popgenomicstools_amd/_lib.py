@@ -50,6 +50,7 @@ SYMBOLS = [
     "pgt_fst_reduce_cols", "pgt_het_reduce_cols", "pgt_dxy_reduce_cols", "pgt_extreme_reduce_cols", "pgt_ingest_download", "pgt_ingest_text", "pgt_ingest_rows", "pgt_ingest_bad_line", "pgt_ingest_column", "pgt_ingest_runs", "pgt_ingest_free",
     "pgt_wintab_sites", "pgt_wintab_size", "pgt_wintab_first", "pgt_wintab_device", "pgt_wintab_free",
     "pgt_fst_reduce_tab", "pgt_het_reduce_tab", "pgt_dxy_reduce_tab",
+    "pgt_dxy_pops_tree_bytes", "pgt_dxy_pops_reduce_dev", "pgt_dxy_pops_reduce",
 ]
 PGT_TOK_CHR, PGT_TOK_SKIP, PGT_TOK_U32, PGT_TOK_F64, PGT_TOK_I8, PGT_TOK_I32, PGT_TOK_FREQ, PGT_TOK_CHR_PREFIX = range(8)
 
@@ -120,6 +121,10 @@ def load() -> C.CDLL:
     lib.pgt_af_tree_bytes.restype = sz
     lib.pgt_af_tree_bytes.argtypes = [u32, u64]
     lib.pgt_fst_af_reduce_dev.argtypes = [vp, vp, vp, vp, u32, u64, vp, u64, vp, sz, vp, sz, vp]
+    lib.pgt_dxy_pops_tree_bytes.restype = sz
+    lib.pgt_dxy_pops_tree_bytes.argtypes = [u32, u64]
+    lib.pgt_dxy_pops_reduce_dev.argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, u64, vp, sz, vp, vp, sz, vp]
+    lib.pgt_dxy_pops_reduce.argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, u64, vp, vp]
     lib.pgt_set_max_window.argtypes = [vp, u64]
     lib.pgt_set_window_step.argtypes = [vp, u64]
     lib.pgt_set_profiling.argtypes = [vp, i32]

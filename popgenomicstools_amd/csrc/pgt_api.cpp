@@ -371,7 +371,7 @@ pgt_ctx *pgt_open(int device) {
         ~Restore() { if (dev >= 0 && dev != ctx_dev) (void)hipSetDevice(dev); }
     } restore{caller_device, device};
     std::string init_err;
-    if (init_kernels(&init_err) != PGT_OK || init_af_kernels(&init_err) != PGT_OK) {
+    if (init_kernels(&init_err) != PGT_OK || init_af_kernels(&init_err) != PGT_OK || init_dxy_pops_kernels(&init_err) != PGT_OK) {
         set_global_error("pgt_open: " + init_err);
         return nullptr;
     }
@@ -582,6 +582,42 @@ int pgt_fst_af_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const
                          ctx->hints);
 }
 
+size_t pgt_dxy_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites) {
+    if (n_pops < 2 || n_pops > (uint32_t)kDxyPopsMaxPops) return 0;
+    return dxy_pops_tree_view(tree_layout(PGT_STAT_FST, n_sites), (int)(n_pops * (n_pops - 1) / 2), nullptr, 0).bytes;
+}
+
+int pgt_dxy_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind,
+                            uint32_t n_pops, uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_dxy_row *out,
+                            size_t out_bytes, pgt_dxy_total *tot, void *tree, size_t tree_bytes, void *stream) {
+    PGT_USE_DEVICE(ctx);
+    if (n_pops < 2 || n_pops > (uint32_t)kDxyPopsMaxPops) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: n_pops must be 2 ... 8");
+    if (n == 0 && n_win == 0 && !tot) return PGT_OK;
+    if (!freq) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: freq is NULL");
+    if (!nind) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: nind is NULL");
+    if (!tree) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: tree is NULL");
+    if (n_win && !win) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: win is NULL");
+    if (n_win && !out) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: out is NULL");
+    if (n_win && n && !pos) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: pos is NULL");  // windows without PGT_WIN_COORDS read pos[lo], pos[hi-1]
+    for (uint32_t k = 0; k < n_pops; ++k) {
+        if (!freq[k]) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: freq[" + std::to_string(k) + "] is NULL");
+        if (!nind[k]) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: nind[" + std::to_string(k) + "] is NULL");
+        if (!aligned16(freq[k])) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: freq[" + std::to_string(k) + "] is not 16-byte aligned");
+        if (!aligned16(nind[k])) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: nind[" + std::to_string(k) + "] is not 16-byte aligned");
+    }
+    if (n >= (1ull << 32)) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: n: at most 2^32-1 sites per call");
+    if (!aligned16(tree)) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: tree is not 16-byte aligned");
+    if (tree_bytes < pgt_dxy_pops_tree_bytes(n_pops, n))
+        return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: tree_bytes too small (" + std::to_string(tree_bytes) + " bytes, " +
+                                           std::to_string(pgt_dxy_pops_tree_bytes(n_pops, n)) + " needed)");
+    const uint64_t n_pairs = (uint64_t)n_pops * (n_pops - 1) / 2;
+    if (n_win > UINT64_MAX / n_pairs) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: n_pairs * n_win overflows");
+    if (int rc = room_check(ctx, "pgt_dxy_pops_reduce: out_bytes", n_pairs * n_win, sizeof(pgt_dxy_row), out_bytes)) return rc;
+    const EvSet e = events_for(ctx);
+    return launch_dxy_pops(pos, freq, nind, n_pops, n, minind, win, n_win, out, tot, tree, stream, e.b0, e.b1, e.q1, &ctx->error,
+                           ctx->hints);
+}
+
 int pgt_extreme_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *score, uint64_t n, int mode, double cutoff,
                            const pgt_win *win, uint64_t n_win, pgt_ext_row *out, size_t out_bytes, void *tree,
                            size_t tree_bytes, void *stream) {
@@ -728,20 +764,22 @@ namespace {
 
 // What every *_cols entry point does around its device call: window table up (cached workspace), rows and tree from the
 // cached workspace, kernels, rows down.  `run` gets (device windows, device rows, tree, tree bytes, device total or NULL).
+// `tables` row tables of n_win rows each (pair-major) and as many totals where `tot` is given; tb = the tree's bytes.
 template <class Row, class Run>
-int reduce_with_workspace(pgt_ctx *ctx, const char *who, int stat, uint64_t n, const pgt_win *win, uint64_t n_win, Row *out, size_t out_bytes,
-                          pgt_dxy_total *tot, Run run) {
+int reduce_tables_with_workspace(pgt_ctx *ctx, const char *who, size_t tb, uint64_t tables, uint64_t n, const pgt_win *win, uint64_t n_win,
+                                 Row *out, size_t out_bytes, pgt_dxy_total *tot, Run run) {
     ApiTrace trace(who);
-    if (int rc = room_check(ctx, who, n_win, sizeof(Row), out_bytes)) return rc;
+    if (n_win > UINT64_MAX / tables) return ctx_fail(ctx, PGT_EARG, std::string(who) + ": the number of rows overflows");
+    const uint64_t n_rows = tables * n_win;
+    if (int rc = room_check(ctx, who, n_rows, sizeof(Row), out_bytes)) return rc;
     if (int rc = check_windows_host(ctx, win, n_win, n, true)) return rc;
     const HintScope hint(ctx, win, n_win);
     void *dwin = nullptr, *dout = nullptr, *dtree = nullptr, *dtot = nullptr;
-    const size_t tb = pgt_tree_bytes(stat, n);
     if (int rc = workspace(ctx, HostIo::kWin, n_win * sizeof(pgt_win), &dwin)) return rc;
-    if (int rc = workspace(ctx, HostIo::kRows, n_win * sizeof(Row), &dout)) return rc;
+    if (int rc = workspace(ctx, HostIo::kRows, n_rows * sizeof(Row), &dout)) return rc;
     if (int rc = workspace(ctx, HostIo::kTree, tb, &dtree)) return rc;
     if (tot)
-        if (int rc = workspace(ctx, HostIo::kTot, sizeof(pgt_dxy_total), &dtot)) return rc;
+        if (int rc = workspace(ctx, HostIo::kTot, tables * sizeof(pgt_dxy_total), &dtot)) return rc;
     trace.lap("workspace");
     if (n_win)
         if (int rc = hip_check(ctx, hipMemcpy(dwin, win, n_win * sizeof(pgt_win), hipMemcpyHostToDevice), "upload windows")) return rc;
@@ -750,11 +788,17 @@ int reduce_with_workspace(pgt_ctx *ctx, const char *who, int stat, uint64_t n, c
     if (int rc = hip_check(ctx, hipStreamSynchronize(nullptr), "kernels")) return rc;
     trace.lap("kernels");
     if (n_win)
-        if (int rc = hip_check(ctx, hipMemcpy(out, dout, n_win * sizeof(Row), hipMemcpyDeviceToHost), "download rows")) return rc;
+        if (int rc = hip_check(ctx, hipMemcpy(out, dout, n_rows * sizeof(Row), hipMemcpyDeviceToHost), "download rows")) return rc;
     if (tot)
-        if (int rc = hip_check(ctx, hipMemcpy(tot, dtot, sizeof(pgt_dxy_total), hipMemcpyDeviceToHost), "download total")) return rc;
-    trace.lap("download rows", n_win * sizeof(Row));
+        if (int rc = hip_check(ctx, hipMemcpy(tot, dtot, tables * sizeof(pgt_dxy_total), hipMemcpyDeviceToHost), "download total")) return rc;
+    trace.lap("download rows", n_rows * sizeof(Row));
     return PGT_OK;
+}
+
+template <class Row, class Run>
+int reduce_with_workspace(pgt_ctx *ctx, const char *who, int stat, uint64_t n, const pgt_win *win, uint64_t n_win, Row *out, size_t out_bytes,
+                          pgt_dxy_total *tot, Run run) {
+    return reduce_tables_with_workspace<Row>(ctx, who, pgt_tree_bytes(stat, n), 1, n, win, n_win, out, out_bytes, tot, run);
 }
 
 }  // namespace
@@ -857,6 +901,38 @@ int pgt_dxy_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *p1, const do
     return pgt_dxy_reduce_cols(ctx, static_cast<uint32_t *>(dpos.p), static_cast<double *>(d1.p), static_cast<double *>(d2.p),
                                static_cast<int32_t *>(dn1.p), static_cast<int32_t *>(dn2.p), n, minind, win, n_win, out,
                                n_win * sizeof(pgt_dxy_row), tot);
+}
+
+/* all pairs of n_pops populations: columns, table and rows in HOST memory.  Rows and totals are written by every call (the
+ * query stores every row of every pair, the build every tree level the query reads): nothing of the cached workspace survives */
+int pgt_dxy_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
+                        uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_dxy_row *out, pgt_dxy_total *tot) {
+    PGT_USE_DEVICE(ctx);
+    if (n_pops < 2 || n_pops > (uint32_t)kDxyPopsMaxPops) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: n_pops must be 2 ... 8");
+    if (!freq || !nind || (n && !pos) || (n_win && (!win || !out))) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: NULL argument");
+    for (uint32_t k = 0; k < n_pops; ++k)
+        if (n && (!freq[k] || !nind[k])) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: NULL column");
+    ApiTrace trace("pgt_dxy_pops_reduce");
+    const uint64_t n_pairs = (uint64_t)n_pops * (n_pops - 1) / 2;
+    if (n_win > UINT64_MAX / n_pairs / sizeof(pgt_dxy_row)) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: n_pairs * n_win overflows");
+    DevBuf dpos, df[kDxyPopsMaxPops], dn[kDxyPopsMaxPops];
+    UploadJob jobs[1 + 2 * kDxyPopsMaxPops];
+    int n_jobs = 0;
+    jobs[n_jobs++] = {&dpos, pos, n * sizeof(uint32_t), "upload pos"};
+    for (uint32_t k = 0; k < n_pops; ++k) {
+        jobs[n_jobs++] = {&df[k], freq[k], n * sizeof(double), "upload freq"};
+        jobs[n_jobs++] = {&dn[k], nind[k], n * sizeof(int32_t), "upload nind"};
+    }
+    if (int rc = upload_columns(ctx, jobs, n_jobs, trace)) return rc;
+    const double *pf[kDxyPopsMaxPops];
+    const int32_t *pn[kDxyPopsMaxPops];
+    for (uint32_t k = 0; k < n_pops; ++k) { pf[k] = static_cast<double *>(df[k].p); pn[k] = static_cast<int32_t *>(dn[k].p); }
+    return reduce_tables_with_workspace<pgt_dxy_row>(ctx, "pgt_dxy_pops_reduce", pgt_dxy_pops_tree_bytes(n_pops, n), n_pairs, n, win, n_win, out,
+        (size_t)(n_pairs * n_win) * sizeof(pgt_dxy_row), tot,
+        [&](const pgt_win *dw, pgt_dxy_row *dr, void *tree, size_t tb, pgt_dxy_total *dtot) {
+            return pgt_dxy_pops_reduce_dev(ctx, static_cast<uint32_t *>(dpos.p), pf, pn, n_pops, n, minind, dw, n_win, dr,
+                                           (size_t)(n_pairs * n_win) * sizeof(pgt_dxy_row), dtot, tree, tb, nullptr);
+        });
 }
 
 /* ---------------- window tables built on the device ---------------- */

@@ -128,6 +128,45 @@ inline AfTree af_tree_view(const TreeLayout &t, int n_vals, void *tree, int leve
     return v;
 }
 
+// ---- dxy of all population pairs (pgt_dxy_pops_kernels.hip): nodes of P = NP(NP-1)/2 {Σd, neff}, node-major ------
+// A level holds two arrays: P doubles per node (the pairs' Σd) and P u32 per node (their neff); nskip is not stored
+// (every site of a range is a data site: nskip = sites - neff).  Level 1: 512-site nodes, 16 per level-2 node; levels 2
+// and up are those of the f64 layout (8192 sites, x64 per level).  Behind the levels one {Σd, neff} per pair and build
+// wave: the genome-wide lines are their sums in wave order (as TreeLayout::partials for the two-population tree).
+constexpr int kDxyPopsMaxPops = 8;
+constexpr int kDxyPopsLeafPieces = 4;  // 128-site pieces per level-1 node
+struct DxyPopsTree {
+    char *base;
+    size_t sum_off[kMaxLevels];  // byte offset of level slot k: P doubles per node
+    size_t cnt_off[kMaxLevels];  // ... P u32 per node
+    size_t part_sum, part_cnt;   // [build wave][P] doubles / u32
+    size_t bytes;
+    int n_levels;
+    int n_pairs;
+    uint32_t n_partials;         // build waves that left a partial (0: no sites)
+};
+inline DxyPopsTree dxy_pops_tree_view(const TreeLayout &t, int n_pairs, void *tree, int levels) {
+    DxyPopsTree v{};
+    v.base = static_cast<char *>(tree);
+    v.n_levels = levels;
+    v.n_pairs = n_pairs;
+    auto pad = [](size_t b) { return ((b + 255) / 256) * 256; };
+    size_t off = 0;
+    for (int k = 0; k < t.n_levels; ++k) {
+        const uint64_t nodes = k == 0 ? t.count[0] / kDxyPopsLeafPieces : t.count[k];
+        v.sum_off[k] = off;
+        off += pad(nodes * (size_t)n_pairs * 8);
+        v.cnt_off[k] = off;
+        off += pad(nodes * (size_t)n_pairs * 4);
+    }
+    v.part_sum = off;
+    off += pad((size_t)kMaxBuildWaves * n_pairs * 8);
+    v.part_cnt = off;
+    off += pad((size_t)kMaxBuildWaves * n_pairs * 4);
+    v.bytes = off;
+    return v;
+}
+
 // Speed-only hints of a context (pgt_set_max_window, pgt_set_window_step); 0 = unknown.
 struct Hints {
     uint64_t max_window = 0;   // longest window in sites: tree levels with larger nodes are not built
@@ -185,6 +224,12 @@ int launch_fst_af(const uint32_t *pos, const double *const *freq, const double *
                   uint64_t n, const pgt_win *win, uint64_t n_win, pgt_fst_row *out, void *tree, void *stream,
                   void *ev_build0, void *ev_build1, void *ev_query1, std::string *err, const Hints &hints);
 
+// pgt_dxy_pops_kernels.hip: tot = n_pairs device totals or NULL
+int launch_dxy_pops(const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
+                    uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_dxy_row *out, pgt_dxy_total *tot,
+                    void *tree, void *stream, void *ev_build0, void *ev_build1, void *ev_query1, std::string *err,
+                    const Hints &hints);
+
 // pgt_windows.cpp: the site-window rules per chromosome run in closed form (see there); plain data, also read by
 // the kernel that writes a window table on the device (pgt_kernels.hip: launch_windows_from_plan)
 struct RunPlan {
@@ -208,6 +253,7 @@ size_t ingest_column_bytes(const pgt_ingest *ing, int token);  // rows * element
 
 int init_kernels(std::string *err);     // pgt_kernels.hip: one-time kernel attributes (called by pgt_open)
 int init_af_kernels(std::string *err);  // pgt_af_kernels.hip
+int init_dxy_pops_kernels(std::string *err);  // pgt_dxy_pops_kernels.hip
 
 // thread-local message for the ctx-less entry points
 void set_global_error(const std::string &msg);
