@@ -38,7 +38,8 @@ extern "C" {
  * version 4 in round 4) are part of it.  A binding written for one version never calls a library of another. */
 /* 6 (round 6): pgt_prepare_host_io added; the host-buffer entry points stage their uploads through a per-context pinned
  * ring and keep a per-context workspace (no argument list changed).
- * Still 6: pgt_dxy_pops_tree_bytes / pgt_dxy_pops_reduce_dev / pgt_dxy_pops_reduce added (additive: nothing that existed changed). */
+ * Still 6: pgt_dxy_pops_tree_bytes / pgt_dxy_pops_reduce_dev / pgt_dxy_pops_reduce added (additive: nothing that existed changed).
+ * Still 6: pgt_align_segments / pgt_align_workspace_bytes / pgt_sites_align / pgt_gather_dev added (additive as well). */
 #define PGT_ABI_VERSION 6
 
 enum {
@@ -217,6 +218,42 @@ int pgt_dxy_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *con
 int pgt_dxy_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq,
                         const int32_t *const *nind, uint32_t n_pops, uint64_t n, int minind,
                         const pgt_win *win, uint64_t n_win, pgt_dxy_row *out, pgt_dxy_total *tot);
+
+/* ---- the sites common to K files, aligned on the device ------------------------------------------ */
+/* Replaces the two-file synchronisation of dxyWindow.cpp:315-331 (one current line per file; the file that is behind reads
+ * on until chromosome and position agree), generalised to 2 <= K <= 8 files as the intersection by (chromosome, position):
+ * what those loops produce where they are defined (identical or nested site lists), and defined for any
+ * lists.  The result is one u32 index column per file — idx[k][m] is the row of common site m in file k — with which
+ * pgt_gather_dev brings every column of every file onto ONE shared position column: the input pgt_dxy_pops_reduce_dev
+ * (and every other *_dev entry point over several files' columns) expects.  Exact integers: the result does not depend on
+ * how the work is cut.
+ *
+ * pgt_align_segments (host, no device): per file the chromosome id of every run (the caller maps names to ids: equal names,
+ * equal ids) and the run lengths -> one pgt_seg {first row, rows} per (matched chromosome, file), chromosome-major, in file
+ * 0's order.  A chromosome is matched when every file has it.  PGT_EDOMAIN when a file lists an id in two runs or the matched
+ * chromosomes do not come in the same relative order in every file ("Both input MAF files need to have the same chromosomes
+ * in the same order", dxyWindow.cpp:49); the message names the id.  out may be NULL (count only); PGT_ECAP when cap < *n_out.
+ *
+ * pgt_sites_align: pos = HOST array of n_files DEVICE pointers (u32 positions, strictly increasing inside a segment; below
+ * 2^32 - 1 rows per file); seg = the plan above (n_seg = n_files * matched chromosomes, at most 4096 of them); idx = HOST
+ * array of n_files DEVICE pointers with room for cap u32 each; seg_count (n_seg / n_files common sites per matched
+ * chromosome) and n_common are HOST outputs.  Synchronous: the caller needs n_common to size what follows.  PGT_ECAP with
+ * *n_common (and seg_count) set when cap is too small; the first cap sites are then written and nothing beyond.
+ * work: pgt_align_workspace_bytes(n_files, n_rows[0]) bytes of DEVICE memory, 16-byte aligned — at most
+ * 4 * (n_files + 1) * n_rows_file0 + 1 MiB; 0 for n_files outside 2 ... 8.  File 0 is the pivot: pass the shortest list
+ * first where there is a choice.
+ *
+ * pgt_gather_dev: dst[m] = src[idx[m]], m < n, elements of 4 or 8 bytes; asynchronous on `stream`; dst and src must not
+ * overlap.  16-byte stores where dst and idx are 16-byte aligned. */
+typedef struct { uint64_t off, len; } pgt_seg;
+int pgt_align_segments(const uint32_t *const *run_chr, const uint64_t *const *run_len, const size_t *n_runs, uint32_t n_files,
+                       pgt_seg *out, size_t cap, size_t *n_out);
+size_t pgt_align_workspace_bytes(uint32_t n_files, uint64_t n_rows_file0);
+int pgt_sites_align(pgt_ctx *ctx, const uint32_t *const *pos, const uint64_t *n_rows, uint32_t n_files, const pgt_seg *seg,
+                    size_t n_seg, uint32_t *const *idx, uint64_t cap, uint64_t *seg_count, uint64_t *n_common, void *work,
+                    size_t work_bytes, void *stream);
+int pgt_gather_dev(pgt_ctx *ctx, void *dst, const void *src, const uint32_t *idx, uint64_t n, uint32_t elem_bytes /* 4 or 8 */,
+                   void *stream);
 
 /* ---- ihsWindow / xpehhWindow: extreme score in non-overlapping bp windows ---- */
 /* Replaces the window bookkeeping and per-window scan of ihsWindow.cpp:123-221 and

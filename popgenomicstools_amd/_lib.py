@@ -32,10 +32,12 @@ DXY_TOTAL_DTYPE = np.dtype([("sum", "<f8"), ("neff", "<u8"), ("nskip", "<u8")])
 EXT_ROW_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("nsites", "<u4"), ("nbig", "<u4"),
                           ("position", "<u4"), ("pad_", "<u4"), ("value", "<f8")])
 SHARD_DTYPE = np.dtype([("win_begin", "<u8"), ("win_end", "<u8"), ("site_lo", "<u8"), ("site_hi", "<u8")])
+SEG_DTYPE = np.dtype([("off", "<u8"), ("len", "<u8")])  # pgt_seg: the rows of one matched chromosome in one file
 
 assert WIN_DTYPE.itemsize == 32 and FST_ROW_DTYPE.itemsize == 40 and HET_ROW_DTYPE.itemsize == 32
 assert EXT_ROW_DTYPE.itemsize == 32
 assert DXY_ROW_DTYPE.itemsize == 24 and DXY_TOTAL_DTYPE.itemsize == 24 and SHARD_DTYPE.itemsize == 32
+assert SEG_DTYPE.itemsize == 16
 
 # every symbol include/pgtwin.h declares (tests/test_abi.py checks the list against the header)
 SYMBOLS = [
@@ -51,6 +53,7 @@ SYMBOLS = [
     "pgt_wintab_sites", "pgt_wintab_size", "pgt_wintab_first", "pgt_wintab_device", "pgt_wintab_free",
     "pgt_fst_reduce_tab", "pgt_het_reduce_tab", "pgt_dxy_reduce_tab",
     "pgt_dxy_pops_tree_bytes", "pgt_dxy_pops_reduce_dev", "pgt_dxy_pops_reduce",
+    "pgt_align_segments", "pgt_align_workspace_bytes", "pgt_sites_align", "pgt_gather_dev",
 ]
 PGT_TOK_CHR, PGT_TOK_SKIP, PGT_TOK_U32, PGT_TOK_F64, PGT_TOK_I8, PGT_TOK_I32, PGT_TOK_FREQ, PGT_TOK_CHR_PREFIX = range(8)
 
@@ -125,6 +128,11 @@ def load() -> C.CDLL:
     lib.pgt_dxy_pops_tree_bytes.argtypes = [u32, u64]
     lib.pgt_dxy_pops_reduce_dev.argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, u64, vp, sz, vp, vp, sz, vp]
     lib.pgt_dxy_pops_reduce.argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, u64, vp, vp]
+    lib.pgt_align_segments.argtypes = [vp, vp, vp, u32, vp, sz, C.POINTER(sz)]
+    lib.pgt_align_workspace_bytes.restype = sz
+    lib.pgt_align_workspace_bytes.argtypes = [u32, u64]
+    lib.pgt_sites_align.argtypes = [vp, vp, vp, u32, vp, sz, vp, u64, vp, C.POINTER(u64), vp, sz, vp]
+    lib.pgt_gather_dev.argtypes = [vp, vp, vp, vp, u64, u32, vp]
     lib.pgt_set_max_window.argtypes = [vp, u64]
     lib.pgt_set_window_step.argtypes = [vp, u64]
     lib.pgt_set_profiling.argtypes = [vp, i32]

@@ -618,6 +618,63 @@ int pgt_dxy_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *con
                            ctx->hints);
 }
 
+size_t pgt_align_workspace_bytes(uint32_t n_files, uint64_t n_rows_file0) {
+    if (n_files < 2 || n_files > (uint32_t)kAlignMaxFiles) return 0;
+    return align_layout(n_files, n_rows_file0).bytes;
+}
+
+int pgt_sites_align(pgt_ctx *ctx, const uint32_t *const *pos, const uint64_t *n_rows, uint32_t n_files, const pgt_seg *seg,
+                    size_t n_seg, uint32_t *const *idx, uint64_t cap, uint64_t *seg_count, uint64_t *n_common, void *work,
+                    size_t work_bytes, void *stream) {
+    PGT_USE_DEVICE(ctx);
+    if (n_files < 2 || n_files > (uint32_t)kAlignMaxFiles) return ctx_fail(ctx, PGT_EARG, "pgt_sites_align: n_files must be 2 ... 8");
+    if (!pos) return ctx_fail(ctx, PGT_EARG, "pgt_sites_align: pos is NULL");
+    if (!n_rows) return ctx_fail(ctx, PGT_EARG, "pgt_sites_align: n_rows is NULL");
+    if (!idx) return ctx_fail(ctx, PGT_EARG, "pgt_sites_align: idx is NULL");
+    if (!n_common) return ctx_fail(ctx, PGT_EARG, "pgt_sites_align: n_common is NULL");
+    if (n_seg && !seg) return ctx_fail(ctx, PGT_EARG, "pgt_sites_align: seg is NULL");
+    if (n_seg && !seg_count) return ctx_fail(ctx, PGT_EARG, "pgt_sites_align: seg_count is NULL");
+    if (!work) return ctx_fail(ctx, PGT_EARG, "pgt_sites_align: work is NULL");
+    if (n_seg % n_files != 0) return ctx_fail(ctx, PGT_EARG, "pgt_sites_align: n_seg is not a multiple of n_files");
+    const size_t n_chr = n_seg / n_files;
+    if (n_chr > kAlignMaxChr) return ctx_fail(ctx, PGT_EARG, "pgt_sites_align: at most " + std::to_string(kAlignMaxChr) + " matched chromosomes per call");
+    for (uint32_t k = 0; k < n_files; ++k) {
+        const std::string at = "[" + std::to_string(k) + "]";
+        if (n_rows[k] >= 0xFFFFFFFFull) return ctx_fail(ctx, PGT_EARG, "pgt_sites_align: n_rows" + at + ": at most 2^32-2 rows per file");
+        if (n_rows[k] && !pos[k]) return ctx_fail(ctx, PGT_EARG, "pgt_sites_align: pos" + at + " is NULL");
+        if (n_rows[k] && (reinterpret_cast<uintptr_t>(pos[k]) & 3u)) return ctx_fail(ctx, PGT_EARG, "pgt_sites_align: pos" + at + " is not 4-byte aligned");
+        if (cap && !idx[k]) return ctx_fail(ctx, PGT_EARG, "pgt_sites_align: idx" + at + " is NULL");
+        uint64_t end = 0;  // a file's segments follow one another
+        for (size_t m = 0; m < n_chr; ++m) {
+            const pgt_seg &sg = seg[m * n_files + k];
+            if (sg.off > n_rows[k] || sg.len > n_rows[k] - sg.off)
+                return ctx_fail(ctx, PGT_EARG, "pgt_sites_align: seg[" + std::to_string(m * n_files + k) + "] runs beyond n_rows" + at);
+            if (sg.off < end) return ctx_fail(ctx, PGT_EARG, "pgt_sites_align: seg[" + std::to_string(m * n_files + k) + "] starts before the end of the file's previous segment");
+            end = sg.off + sg.len;
+        }
+    }
+    if (!aligned16(work)) return ctx_fail(ctx, PGT_EARG, "pgt_sites_align: work is not 16-byte aligned");
+    if (work_bytes < pgt_align_workspace_bytes(n_files, n_rows[0]))
+        return ctx_fail(ctx, PGT_EARG, "pgt_sites_align: work_bytes too small (" + std::to_string(work_bytes) + " bytes, " +
+                                           std::to_string(pgt_align_workspace_bytes(n_files, n_rows[0])) + " needed)");
+    if (int rc = launch_sites_align(pos, n_rows, n_files, seg, n_chr, idx, cap, seg_count, n_common, work, stream, &ctx->error)) return rc;
+    if (*n_common > cap) return ctx_fail(ctx, PGT_ECAP, "pgt_sites_align: output capacity too small");
+    return PGT_OK;
+}
+
+int pgt_gather_dev(pgt_ctx *ctx, void *dst, const void *src, const uint32_t *idx, uint64_t n, uint32_t elem_bytes, void *stream) {
+    PGT_USE_DEVICE(ctx);
+    if (elem_bytes != 4 && elem_bytes != 8) return ctx_fail(ctx, PGT_EARG, "pgt_gather: elem_bytes must be 4 or 8");
+    if (n == 0) return PGT_OK;
+    if (!dst) return ctx_fail(ctx, PGT_EARG, "pgt_gather: dst is NULL");
+    if (!src) return ctx_fail(ctx, PGT_EARG, "pgt_gather: src is NULL");
+    if (!idx) return ctx_fail(ctx, PGT_EARG, "pgt_gather: idx is NULL");
+    if (n >= (1ull << 32)) return ctx_fail(ctx, PGT_EARG, "pgt_gather: n: at most 2^32-1 elements per call");
+    if ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & (elem_bytes - 1)) return ctx_fail(ctx, PGT_EARG, "pgt_gather: dst / src are not aligned to elem_bytes");
+    if (reinterpret_cast<uintptr_t>(idx) & 3u) return ctx_fail(ctx, PGT_EARG, "pgt_gather: idx is not 4-byte aligned");
+    return launch_gather(dst, src, idx, n, elem_bytes, stream, &ctx->error);
+}
+
 int pgt_extreme_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *score, uint64_t n, int mode, double cutoff,
                            const pgt_win *win, uint64_t n_win, pgt_ext_row *out, size_t out_bytes, void *tree,
                            size_t tree_bytes, void *stream) {

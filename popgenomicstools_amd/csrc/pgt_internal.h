@@ -230,6 +230,26 @@ int launch_dxy_pops(const uint32_t *pos, const double *const *freq, const int32_
                     void *tree, void *stream, void *ev_build0, void *ev_build1, void *ev_query1, std::string *err,
                     const Hints &hints);
 
+// pgt_align_kernels.hip: the sites common to K position columns (pgt_sites_align) and the gather behind it.
+// The workspace, every part 256-byte aligned: the plan (segments as u32 pairs, first tile per chromosome), the first output
+// row per chromosome, per tile of 1024 pivot rows its count and first output row, and per file k >= 1 the row found for
+// every pivot row.  A call handles at most kAlignMaxChr matched chromosomes (the plan's share of the workspace is fixed:
+// pgt_align_workspace_bytes knows only the files and the pivot's rows).
+constexpr int kAlignMaxFiles = 8;
+constexpr uint32_t kAlignMaxChr = 4096;
+struct AlignLayout {
+    size_t seg, tile_first, chr_first, tile_count, tile_row;
+    size_t prov[kAlignMaxFiles];
+    uint64_t max_tiles;
+    size_t bytes;
+};
+AlignLayout align_layout(uint32_t n_files, uint64_t n_rows_file0);
+// synchronous; arguments checked by the caller (pgt_api.cpp); seg: n_chr * n_files entries, chromosome-major
+int launch_sites_align(const uint32_t *const *pos, const uint64_t *n_rows, uint32_t n_files, const pgt_seg *seg, size_t n_chr,
+                       uint32_t *const *idx, uint64_t cap, uint64_t *seg_count, uint64_t *n_common, void *work, void *stream,
+                       std::string *err);
+int launch_gather(void *dst, const void *src, const uint32_t *idx, uint64_t n, uint32_t elem_bytes, void *stream, std::string *err);
+
 // pgt_windows.cpp: the site-window rules per chromosome run in closed form (see there); plain data, also read by
 // the kernel that writes a window table on the device (pgt_kernels.hip: launch_windows_from_plan)
 struct RunPlan {

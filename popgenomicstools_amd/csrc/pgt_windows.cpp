@@ -16,6 +16,7 @@
 #include <cstring>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "pgt_internal.h"
@@ -299,5 +300,51 @@ extern "C" int pgt_plan_shards(const pgt_win *win, uint64_t n_win, uint32_t n_ra
         }
         out[r] = s;
     }
+    return PGT_OK;
+}
+
+// The segment plan of pgt_sites_align: which rows of every file belong to the chromosomes all files have.  The reference
+// walks its two files side by side and expects "the same chromosomes in the same order" (dxyWindow.cpp:49 of its help;
+// the catch-up loops :315-331 never go back): a chromosome listed twice by a file, or two matched chromosomes in opposite
+// order in two files, are outside its domain and refused here.  O(total runs).
+extern "C" int pgt_align_segments(const uint32_t *const *run_chr, const uint64_t *const *run_len, const size_t *n_runs,
+                                  uint32_t n_files, pgt_seg *out, size_t cap, size_t *n_out) {
+    if (!n_out || !run_chr || !run_len || !n_runs) return fail(PGT_EARG, "pgt_align_segments: NULL argument");
+    if (n_files < 2 || n_files > 8) return fail(PGT_EARG, "pgt_align_segments: n_files must be 2 ... 8");
+    for (uint32_t k = 0; k < n_files; ++k)
+        if (n_runs[k] && (!run_chr[k] || !run_len[k])) return fail(PGT_EARG, "pgt_align_segments: NULL run table of file " + std::to_string(k));
+    struct Where { size_t run; uint64_t off; };
+    std::vector<std::unordered_map<uint32_t, Where>> where(n_files);
+    for (uint32_t k = 0; k < n_files; ++k) {
+        uint64_t off = 0;
+        where[k].reserve(n_runs[k] * 2);
+        for (size_t r = 0; r < n_runs[k]; ++r) {
+            if (!where[k].insert({run_chr[k][r], Where{r, off}}).second)
+                return fail(PGT_EDOMAIN, "pgt_align_segments: chromosome id " + std::to_string(run_chr[k][r]) + " has two runs in file " + std::to_string(k));
+            off += run_len[k][r];
+        }
+    }
+    size_t count = 0;
+    std::vector<size_t> last(n_files, 0);  // 1 + the run of the previous matched chromosome
+    for (size_t r = 0; r < n_runs[0]; ++r) {
+        const uint32_t chr = run_chr[0][r];
+        const Where *at[8];
+        bool everywhere = true;
+        for (uint32_t k = 0; k < n_files && everywhere; ++k) {
+            const auto it = where[k].find(chr);
+            everywhere = it != where[k].end();
+            if (everywhere) at[k] = &it->second;
+        }
+        if (!everywhere) continue;
+        for (uint32_t k = 0; k < n_files; ++k) {
+            if (at[k]->run + 1 <= last[k])
+                return fail(PGT_EDOMAIN, "pgt_align_segments: chromosome id " + std::to_string(chr) + " comes before an earlier chromosome of file 0 in file " + std::to_string(k));
+            last[k] = at[k]->run + 1;
+            if (out && count < cap) out[count] = pgt_seg{at[k]->off, run_len[k][at[k]->run]};
+            ++count;
+        }
+    }
+    *n_out = count;
+    if (out && count > cap) return fail(PGT_ECAP, "pgt_align_segments: output capacity too small");
     return PGT_OK;
 }

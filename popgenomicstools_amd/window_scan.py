@@ -22,7 +22,7 @@ import numpy as np
 from . import _lib
 from ._lib import (DXY_ROW_DTYPE, DXY_TOTAL_DTYPE, EXT_ROW_DTYPE, FST_ROW_DTYPE, HET_ROW_DTYPE, PGT_EXT_IHS,
                    PGT_EXT_XP_MAX, PGT_EXT_XP_MIN, PGT_STAT_DXY, PGT_STAT_EXT, PGT_STAT_FST, PGT_STAT_HET,
-                   SHARD_DTYPE, WIN_DTYPE, PgtError, check)
+                   SEG_DTYPE, SHARD_DTYPE, WIN_DTYPE, PgtError, check)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -105,6 +105,51 @@ def table_hints(win: np.ndarray):
 # raw device memory handed out by the library (pgt_rowbuf_*): quacks like the uint8 tensors the
 # *_dev wrappers take (data_ptr / numel), so it can be passed as `out=`
 # ---------------------------------------------------------------------------------------------
+def _runs_of(chr_ids):
+    """(ids, lengths) of the runs of equal adjacent chromosome ids of one file."""
+    c = _host_col(chr_ids, np.uint32)
+    rl = run_lengths(c)
+    starts = np.concatenate(([0], np.cumsum(rl)[:-1])).astype(np.int64) if rl.size else np.zeros(0, np.int64)
+    return np.ascontiguousarray(c[starts], dtype=np.uint32), rl
+
+
+def align_segments_runs(run_chr_list, run_len_list):
+    """pgt_align_segments over run tables (per file: the chromosome id and the length of every run) -> (segs, chr):
+    segs[m, k] (SEG_DTYPE) = the rows of matched chromosome m in file k, chr[m] = its id; file 0's order.  PgtError
+    (PGT_EDOMAIN) when a file lists an id in two runs or the matched chromosomes come in different orders.  No GPU."""
+    k = len(run_chr_list)
+    if len(run_len_list) != k or not 2 <= k <= 8:
+        raise PgtError(_lib.PGT_EARG, "align_segments: 2 ... 8 files, one run table each")
+    ids = [np.ascontiguousarray(c, dtype=np.uint32) for c in run_chr_list]
+    lens = [np.ascontiguousarray(r, dtype=np.uint64) for r in run_len_list]
+    for f in range(k):
+        if ids[f].ndim != 1 or ids[f].shape != lens[f].shape:
+            raise PgtError(_lib.PGT_EARG, f"align_segments: file {f}: {ids[f].size} chromosome ids for {lens[f].size} run lengths")
+    lib = _lib.load()
+    pc = (C.c_void_p * k)(*[a.ctypes.data for a in ids])
+    pl = (C.c_void_p * k)(*[a.ctypes.data for a in lens])
+    nr = (C.c_size_t * k)(*[a.size for a in ids])
+    n_out = C.c_size_t(0)
+    check(lib.pgt_align_segments(pc, pl, nr, k, None, 0, C.byref(n_out)))
+    segs = np.zeros(n_out.value, dtype=SEG_DTYPE)
+    check(lib.pgt_align_segments(pc, pl, nr, k, segs.ctypes.data, segs.size, C.byref(n_out)))
+    segs = segs.reshape(-1, k)
+    # the matched chromosomes: file 0's ids that every file has (ids are unique per file, or the call above has refused)
+    others = [set(a.tolist()) for a in ids[1:]]
+    chr_of = np.array([c for c in ids[0].tolist() if all(c in o for o in others)], dtype=np.uint32)
+    assert chr_of.size == segs.shape[0]
+    return segs, chr_of
+
+
+def align_segments(chr_ids_per_file):
+    """The segment plan of Context.sites_align from per-SITE chromosome ids (one array per file, as the chr_ids of
+    dxy_window; equal names must carry equal ids in every file) -> (segs[n_chr, n_files], chr[n_chr])."""
+    if not 2 <= len(chr_ids_per_file) <= 8:
+        raise PgtError(_lib.PGT_EARG, "align_segments: 2 ... 8 files, one chromosome-id column each")
+    runs = [_runs_of(c) for c in chr_ids_per_file]
+    return align_segments_runs([r[0] for r in runs], [r[1] for r in runs])
+
+
 class RowBuffer:
     def __init__(self, ptr: int, nbytes: int, owner=None):
         self._ptr, self._nbytes, self._owner = int(ptr), int(nbytes), owner  # owner keeps the mapping alive
@@ -663,6 +708,76 @@ class Context:
             self._dev(tree, torch.uint8, "tree"), tree.numel(), self._stream(stream)))
         return out, tree
 
+    # ---- the sites common to K files (pgt_sites_align, pgt_gather_dev) -------------------------
+    @staticmethod
+    def align_workspace_bytes(n_files: int, n_rows_file0: int) -> int:
+        return int(_lib.load().pgt_align_workspace_bytes(int(n_files), int(n_rows_file0)))
+
+    def sites_align(self, pos_list, segs, cap=None, idx=None, work=None, stream=None):
+        """The sites (chromosome, position) present in ALL of len(pos_list) files.  pos_list: int32 CUDA tensors (the u32
+        position columns, strictly increasing inside a chromosome); segs: align_segments' plan.  Returns (idx, counts,
+        n_common): idx[k] an int32 CUDA tensor, idx[k][m] = the row of common site m in file k; counts[c] = common sites of
+        matched chromosome c (numpy u64).  cap: room per index column (default: the most the plan admits); a cap too small
+        raises PgtError(PGT_ECAP) carrying .n_common and .counts.  Synchronous."""
+        import torch
+        k = len(pos_list)
+        if not 2 <= k <= 8:
+            raise PgtError(_lib.PGT_EARG, "sites_align: 2 ... 8 position columns")
+        segs = np.ascontiguousarray(segs, dtype=SEG_DTYPE).reshape(-1, k) if np.size(segs) else np.zeros((0, k), SEG_DTYPE)
+        n_rows = [int(p.numel()) for p in pos_list]
+        for f in range(k):
+            if segs.shape[0] and int((segs["off"][:, f] + segs["len"][:, f]).max()) > n_rows[f]:
+                raise PgtError(_lib.PGT_EARG, f"sites_align: a segment of file {f} runs beyond its {n_rows[f]} rows")
+        most = int(segs["len"].min(axis=1).sum()) if segs.shape[0] else 0
+        if cap is None:
+            cap = most if idx is None else min(int(t.numel()) for t in idx)
+        cap = int(cap)
+        dev = torch.device("cuda", self.device)
+        if idx is None:
+            idx = [torch.empty(cap, dtype=torch.int32, device=dev) for _ in range(k)]
+        if len(idx) != k:
+            raise PgtError(_lib.PGT_EARG, "sites_align: one index column per file")
+        for f, t in enumerate(idx):
+            if t.numel() < cap:
+                raise PgtError(_lib.PGT_EARG, f"sites_align: idx[{f}] holds {t.numel()} rows, cap is {cap}")
+        wb = self.align_workspace_bytes(k, n_rows[0])
+        if work is None:
+            work = torch.empty(wb, dtype=torch.uint8, device=dev)
+        self._room("sites_align: work", work, wb)
+        pp = (C.c_void_p * k)(*[self._dev(t, torch.int32, f"pos_list[{f}]") for f, t in enumerate(pos_list)])
+        pi = (C.c_void_p * k)(*[self._dev(t, torch.int32, f"idx[{f}]") for f, t in enumerate(idx)])
+        nr = (C.c_uint64 * k)(*n_rows)
+        counts = np.zeros(segs.shape[0], dtype=np.uint64)
+        n_common = C.c_uint64(0)
+        rc = self._lib.pgt_sites_align(self._ctx, pp, nr, k, segs.ctypes.data if segs.size else None, segs.size, pi, cap,
+                                       counts.ctypes.data if counts.size else None, C.byref(n_common),
+                                       self._dev(work, torch.uint8, "work"), work.numel(), self._stream(stream))
+        if rc == _lib.PGT_ECAP:
+            e = PgtError(rc, _lib.last_error(self._ctx))
+            e.n_common, e.counts = int(n_common.value), counts
+            raise e
+        self._check(rc)
+        n = int(n_common.value)
+        return [t[:n] for t in idx], counts, n
+
+    def gather_dev(self, src, idx, out=None, stream=None):
+        """out[m] = src[idx[m]] (pgt_gather_dev): src a CUDA tensor of 4- or 8-byte elements, idx an int32 CUDA tensor of
+        rows of src.  Returns out (same dtype as src, idx.numel() elements).  Asynchronous on `stream`."""
+        import torch
+        if not isinstance(src, (torch.Tensor, DeviceColumn)):
+            raise PgtError(_lib.PGT_EARG, "gather_dev: src: expected a contiguous CUDA tensor")
+        elem = torch.empty(0, dtype=src.dtype).element_size()
+        if elem not in (4, 8):
+            raise PgtError(_lib.PGT_EARG, f"gather_dev: src: elements of 4 or 8 bytes, not {src.dtype}")
+        n = idx.numel()
+        if out is None:
+            out = torch.empty(n, dtype=src.dtype, device=torch.device("cuda", self.device))
+        if out.dtype != src.dtype or out.numel() < n:
+            raise PgtError(_lib.PGT_EARG, f"gather_dev: out: {n} elements of {src.dtype} needed")
+        self._check(self._lib.pgt_gather_dev(self._ctx, self._dev(out, src.dtype, "out"), self._dev(src, src.dtype, "src"),
+                                             self._dev(idx, torch.int32, "idx"), n, elem, self._stream(stream)))
+        return out
+
     def set_max_window(self, sites: int):
         """Performance hint for the *_dev calls: no window is longer than `sites` (0 = unknown)."""
         self._check(self._lib.pgt_set_max_window(self._ctx, int(sites)))
@@ -790,6 +905,60 @@ def dxy_window(chr_ids, pos, p1, p2, n1, n2, W: int = 0, S: int = 0, minind: int
     return WindowResult(win, rows, tot)
 
 
+def _host_col(x, dtype):
+    """numpy view of a column given as numpy / list / torch tensor (a CUDA tensor is downloaded; int32 tensors stand for
+    u32 columns bit for bit)."""
+    if hasattr(x, "detach") and hasattr(x, "cpu"):
+        x = x.detach().cpu().numpy()
+        if x.dtype == np.int32 and np.dtype(dtype) == np.uint32:
+            x = x.view(np.uint32)
+    return np.ascontiguousarray(x, dtype=dtype)
+
+
+def align_sites(chr_ids_list, pos_list, columns_list, ctx: Context | None = None):
+    """K files' columns brought onto the sites all K share.  Per file: chr_ids (per-site chromosome ids on the host, equal
+    names = equal ids in every file), pos (u32 positions: numpy, or an int32 CUDA tensor) and a list of further columns
+    (CUDA tensors or numpy arrays of 4- or 8-byte elements).  The alignment runs on the device (sites_align + gather_dev).
+    Returns (chr_ids, pos, aligned_columns_list) as CUDA tensors (chr_ids and pos int32, standing for u32): what
+    dxy_window_pops and Context.dxy_pops_reduce_dev take, with freqs = [cols[0] for cols in aligned_columns_list] etc."""
+    k = len(pos_list)
+    if not 2 <= k <= 8 or len(chr_ids_list) != k or len(columns_list) != k:
+        raise PgtError(_lib.PGT_EARG, "align_sites: 2 ... 8 files, each with chromosome ids, positions and a list of columns")
+    n_rows = [int(p.numel()) if hasattr(p, "numel") else int(np.size(p)) for p in pos_list]
+    for f in range(k):
+        nc = int(c.numel()) if hasattr((c := chr_ids_list[f]), "numel") else int(np.size(c))
+        if nc != n_rows[f]:
+            raise PgtError(_lib.PGT_EARG, f"align_sites: file {f}: {nc} chromosome ids for {n_rows[f]} positions")
+        for j, col in enumerate(columns_list[f]):
+            m = int(col.numel()) if hasattr(col, "numel") else int(np.size(col))
+            if m != n_rows[f]:
+                raise PgtError(_lib.PGT_EARG, f"align_sites: file {f}: column {j} has {m} rows, the positions {n_rows[f]}")
+            size = col.element_size() if hasattr(col, "element_size") else np.asarray(col).dtype.itemsize
+            if size not in (4, 8):
+                raise PgtError(_lib.PGT_EARG, f"align_sites: file {f}: column {j}: elements of 4 or 8 bytes, not {size}")
+    segs, chr_of = align_segments(chr_ids_list)
+    import torch
+    ctx, own = _own_ctx(ctx)
+    try:
+        dev = torch.device("cuda", ctx.device)
+
+        def on_device(x, u32=False):
+            if isinstance(x, torch.Tensor):
+                return x.to(dev)
+            a = np.ascontiguousarray(x, dtype=np.uint32).view(np.int32) if u32 else np.ascontiguousarray(x)
+            return torch.from_numpy(a.copy()).to(dev)
+        pos_d = [on_device(p, u32=True) for p in pos_list]
+        idx, counts, n = ctx.sites_align(pos_d, segs)
+        pos = ctx.gather_dev(pos_d[0], idx[0])
+        cols = [[ctx.gather_dev(on_device(c), idx[f]) for c in columns_list[f]] for f in range(k)]
+        chr_ids = torch.from_numpy(np.repeat(chr_of, counts.astype(np.int64)).view(np.int32).copy()).to(dev)
+        torch.cuda.synchronize(dev)
+    finally:
+        if own:
+            ctx.close()
+    return chr_ids, pos, cols
+
+
 def pair_order(n_pops: int):
     """The pairs (i, j), i < j, in the order the all-pairs entry points (fst_af_reduce_dev, dxy_pops_reduce*) lay their
     rows out: (0,1),(0,2),..,(0,n_pops-1),(1,2),.."""
@@ -800,7 +969,8 @@ def dxy_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: 
                     chr_len=None, skip_missing: int = 0, ctx: Context | None = None) -> dict:
     """dxy_window for ALL pairs of len(freqs) already synchronised populations in one pass: {(i, j): WindowResult}.
     Arguments and errors are those of dxy_window; -skip_missing drops a pair's rows without counted sites from that pair's
-    result only."""
+    result only.  Columns may be CUDA tensors (align_sites' result): this host-table form downloads them; stay on the device
+    with Context.dxy_pops_reduce_dev."""
     if minind <= 0:
         raise PgtError(_lib.PGT_EARG, "-minind must be at least 1")  # dxyWindow.cpp:105-108
     if W > 0 and S < 1:
@@ -811,6 +981,8 @@ def dxy_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: 
         raise PgtError(_lib.PGT_EDOMAIN, "-winsize 0 needs -fixedsite 1 (the reference crashes here, SURVEY Q10)")
     if len(ninds) != len(freqs) or not 2 <= len(freqs) <= 8:
         raise PgtError(_lib.PGT_EARG, "dxy_window_pops: 2 ... 8 populations, one frequency and one count column each")
+    chr_ids, pos = _host_col(chr_ids, None), _host_col(pos, np.uint32)
+    freqs, ninds = [_host_col(f, np.float64) for f in freqs], [_host_col(c, np.int32) for c in ninds]
     rl = run_lengths(chr_ids)
     if W == 0:
         win = np.zeros(0, dtype=WIN_DTYPE)
