@@ -18,15 +18,15 @@
 // (448 B/site for 28 pairs) of precomputed component columns.
 //
 // Cross-lane cost: V sums per leaf node would be V six-step butterflies; instead a
-// REDUCE-SCATTER halves the live values at every exchange step (18+9+5+3+2+1 = 38 exchanges for
+// REDUCE-SCATTER (pgt_pops_common.h) halves the live values at every exchange step (18+9+5+3+2+1 = 38 exchanges for
 // V = 36), leaving each total in exactly one lane, which stores it and keeps the level-2 running sum.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
 #include <type_traits>
 
 #include "pgt_device.h"
 #include "pgt_internal.h"
+#include "pgt_pops_common.h"
 
 namespace pgt {
 namespace {
@@ -48,7 +48,7 @@ constexpr int kAfRadix1 = kRadix / kAfPieces;    // level-1 nodes per level-2 no
 
 template <int NP>
 struct Shape {
-    static constexpr int kPairs = NP * (NP - 1) / 2;
+    static constexpr int kPairs = pair_count(NP);
     static constexpr int kVals = NP + kPairs;  // A_0..A_{NP-1}, then D_ij in lexicographic (i<j) order
 };
 
@@ -56,90 +56,6 @@ struct AfCols {
     const double *f[kAfMaxPops];
     double nsamp[kAfMaxPops];
 };
-
-// ---- reduce-scatter across the wave ----------------------------------------------------------------
-// Step order: the steps with the MOST exchanges (18 and 9 of the 38 at 8 populations) pair lanes across the wave halves and
-// across 16-lane rows, where gfx950 has an instruction made for exactly this exchange: v_permlane32_swap / v_permlane16_swap
-// swap the upper lanes of one register with the lower lanes of another, so that "keep one half of my values, receive the
-// other half of my partner's" is two swaps (low and high dword) and ONE addition — no select, no LDS crossbar.  Until round
-// 6 these two steps came last (xor 16 by ds_swizzle, xor 32 by ds_bpermute) and the 27 busiest exchanges cost 4 v_cndmask +
-// 2 DPP moves + 1 add each (profiles/r06/af8_issue_stall.md: 29 % of the wave cycles were instruction-issue waits, the
-// kernel ran 2 waves per SIMD at 228 VGPRs).  The remaining steps (5 + 3 + 2 + 1 exchanges) stay on DPP / ds_swizzle.
-constexpr int kRsMask[6] = {32, 16, 1, 2, 8, 4};
-template <int STEP>
-__device__ __forceinline__ double xchg(double v) {
-    static_assert(STEP >= 2, "steps 0 and 1 are swaps (rs_swap)");
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    if constexpr (STEP == 2) {         // xor 1: quad_perm [1,0,3,2]
-        lo = __builtin_amdgcn_update_dpp(lo, lo, 0xB1, 0xF, 0xF, false);
-        hi = __builtin_amdgcn_update_dpp(hi, hi, 0xB1, 0xF, 0xF, false);
-    } else if constexpr (STEP == 3) {  // xor 2: quad_perm [2,3,0,1]
-        lo = __builtin_amdgcn_update_dpp(lo, lo, 0x4E, 0xF, 0xF, false);
-        hi = __builtin_amdgcn_update_dpp(hi, hi, 0x4E, 0xF, 0xF, false);
-    } else if constexpr (STEP == 4) {  // xor 8: row_ror:8 inside the 16-lane row
-        lo = __builtin_amdgcn_update_dpp(lo, lo, 0x128, 0xF, 0xF, false);
-        hi = __builtin_amdgcn_update_dpp(hi, hi, 0x128, 0xF, 0xF, false);
-    } else {                           // xor 4: ds_swizzle bit mode (and 0x1f, or 0, xor 4)
-        lo = __builtin_amdgcn_ds_swizzle(lo, 0x101F);
-        hi = __builtin_amdgcn_ds_swizzle(hi, 0x101F);
-    }
-    return __hiloint2double(hi, lo);
-}
-
-// lower lanes (mask bit clear) keep `a` and receive the partner's `a`; upper lanes keep `b` and receive the partner's `b`:
-// after the swaps register A holds {own a | partner's b} and B {partner's a | own b}, so A + B is the exchange's result
-// in every lane (an addition is commutative bit for bit: own + received = received + own).
-template <int STEP>
-__device__ __forceinline__ double rs_swap(double a, double b) {
-    const int alo = __double2loint(a), ahi = __double2hiint(a), blo = __double2loint(b), bhi = __double2hiint(b);
-    if constexpr (STEP == 0) {
-        const auto l = __builtin_amdgcn_permlane32_swap(alo, blo, false, false);
-        const auto h = __builtin_amdgcn_permlane32_swap(ahi, bhi, false, false);
-        return __hiloint2double(h[0], l[0]) + __hiloint2double(h[1], l[1]);
-    } else {
-        const auto l = __builtin_amdgcn_permlane16_swap(alo, blo, false, false);
-        const auto h = __builtin_amdgcn_permlane16_swap(ahi, bhi, false, false);
-        return __hiloint2double(h[0], l[0]) + __hiloint2double(h[1], l[1]);
-    }
-}
-
-// One reduce-scatter step: C live values -> (C+1)/2.  A lane whose mask bit is set keeps the upper
-// half and sends the lower half, its partner does the opposite; an odd C is padded with 0.
-template <int C, int STEP>
-__device__ __forceinline__ void rs_steps(double *v, int lane) {
-    if constexpr (STEP < 6) {
-        constexpr int H = (C + 1) / 2;
-        if constexpr (STEP < 2) {
-#pragma unroll
-            for (int k = 0; k < H; ++k) v[k] = rs_swap<STEP>(v[k], (k + H < C) ? v[k + H] : 0.0);
-        } else {
-            const bool up = (lane & kRsMask[STEP]) != 0;
-#pragma unroll
-            for (int k = 0; k < H; ++k) {
-                const double lo_v = v[k];
-                const double hi_v = (k + H < C) ? v[k + H] : 0.0;
-                const double keep = up ? hi_v : lo_v;
-                const double send = up ? lo_v : hi_v;
-                v[k] = keep + xchg<STEP>(send);
-            }
-        }
-        rs_steps<H, STEP + 1>(v, lane);
-    }
-}
-
-// Which of the V values ends up in this lane (-1: a padding slot)
-template <int V>
-__device__ __forceinline__ int rs_my_index(int lane) {
-    int base = 0, real = V, c = V;
-#pragma unroll
-    for (int s = 0; s < 6; ++s) {
-        const int H = (c + 1) / 2;
-        if (lane & kRsMask[s]) { base += H; real = real > H ? real - H : 0; }
-        else real = real < H ? real : H;
-        c = H;
-    }
-    return real >= 1 ? base : -1;
-}
 
 // ---- per-site contributions ----------------------------------------------------------------------
 // FIRST: the leaf's first site STARTS the sums — x*y is bit for bit fma(x, y, +0.0) (one rounding either way; a product that
@@ -204,8 +120,8 @@ __device__ __forceinline__ void af_build_body(const AfCols &cols, uint64_t n, ui
         // WAVES START THEIR TILES AT DIFFERENT PIECES (round 5; pgt_kernels.hip: tile_rotation): the waves run in lockstep, and
         // without this all of them are at the same offset of their tiles at any moment.  Even, a multiple of the burst; the
         // partial last tile is walked from its start (its guarded loads stop at n).
-        static_assert(kAfPieces == 2 || kAfPieces == 4 || kAfPieces == 8, "the walks below take a leaf's pieces two at a time, in bursts of 4");
-        const int rot = full ? (int)(((wave0 * 0x9E3779B1ull) >> 13) & (uint64_t)(kRadix - (kAfPieces > 4 ? kAfPieces : 4))) : 0;
+        static_assert(kAfPieces == 4, "the walks below take a leaf as two pairs of pieces, or as one burst of 4");
+        const int rot = full ? (int)(((wave0 * 0x9E3779B1ull) >> 13) & (uint64_t)(kRadix - kAfPieces)) : 0;
         double l2acc = 0.0;
         double vals[V];
         auto load_full = [&](double2 *dst, int j) {  // piece j of a FULL tile: one 16-byte nt load per lane and column
@@ -267,11 +183,7 @@ __device__ __forceinline__ void af_build_body(const AfCols &cols, uint64_t n, ui
                     reduce_piece(std::false_type{}, pb);
                 };
                 pair(std::true_type{}, 0);
-                if constexpr (kAfPieces == 4) pair(std::false_type{}, 2);
-                if constexpr (kAfPieces > 4) {
-#pragma unroll 1
-                    for (int h = 2; h < kAfPieces; h += 2) pair(std::false_type{}, h);  // (unrolled, a whole leaf's loads are hoisted: 408 registers at 8 pieces)
-                }
+                pair(std::false_type{}, 2);
                 rs_steps<V, 0>(vals, lane);  // the leaf is complete: one reduce-scatter per leaf
                 if (my >= 0) stage[(j / kAfPieces) * V + my] = vals[0];  // node j/kAfPieces of the wave's LDS stage: V consecutive doubles (conflict-free)
             }
@@ -304,18 +216,7 @@ __device__ __forceinline__ void af_build_body(const AfCols &cols, uint64_t n, ui
         }
         // the tile's 64 level-1 nodes = ONE contiguous block of 512*V bytes, written as 1-KiB wave stores
         // (the stage belongs to this wave alone, LDS operations of a wave complete in order: no barrier)
-        {
-            constexpr int kNodes = kAfRadix1;
-            double2 *dst = reinterpret_cast<double2 *>(af_node<V>(tv, 0, 0, t * kNodes));
-            const double2 *src = reinterpret_cast<const double2 *>(stage);
-            constexpr int kVec = V * kNodes / 2;  // double2 elements of the block
-#pragma unroll 4
-            for (int e = lane; e < kVec; e += kWave) {
-                const double2 w = src[e];
-                __builtin_nontemporal_store(w.x, &dst[e].x);
-                __builtin_nontemporal_store(w.y, &dst[e].y);
-            }
-        }
+        flush_stage<V * kAfRadix1>(af_node<V>(tv, 0, 0, t * kAfRadix1), stage, lane);
     }
 }
 
@@ -334,10 +235,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 }
 // from how many populations on the one-wave-per-SIMD build is taken (PGT_AF_ONE_WAVE_FROM: a measuring knob; 9 = never)
 inline int af_one_wave_from() {
-    static const int v = [] {
-        const char *e = std::getenv("PGT_AF_ONE_WAVE_FROM");
-        return e ? std::atoi(e) : 4;
-    }();
+    static const int v = env_int("PGT_AF_ONE_WAVE_FROM", 4);
     return v;
 }
 
@@ -365,7 +263,7 @@ __global__ __launch_bounds__(256, 2) void af_query_kernel(AfCols cols, const uin
     constexpr int V = Shape<NP>::kVals;
     constexpr int P = Shape<NP>::kPairs;
     const int lane = threadIdx.x & (kWave - 1);
-    const uint64_t wave0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint64_t wave0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;  // (no readfirstlane as in dxy_pops_query_kernel: the difference is unmeasured)
     const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
 
     for (uint64_t w = wave0; w < n_win; w += n_waves) {
@@ -421,6 +319,8 @@ __global__ __launch_bounds__(256, 2) void af_query_kernel(AfCols cols, const uin
                 for (int v = 0; v < V; ++v) acc[v] += *af_node<V>(tv, level - 1, v, i);
             }
         };
+        // the range descent: the same loop as in dxy_pops_query_kernel (as ONE shared function it compiled to other code in both
+        // kernels, with other register counts, so each keeps its copy: a change to one belongs in the other too)
         uint64_t clo = lo, chi = hi;
         for (int k = 0;; ++k) {
             const bool top = k == tv.n_levels;
@@ -484,20 +384,11 @@ __global__ __launch_bounds__(256, 2) void af_query_kernel(AfCols cols, const uin
     }
 }
 
-inline int hip_fail(hipError_t e, const char *what, std::string *err) {
-    if (e == hipSuccess) return PGT_OK;
-    if (err) *err = std::string(what) + ": " + hipGetErrorString(e);
-    return PGT_EDEVICE;
-}
-
 template <int NP>
 int launch_af_np(const AfCols &cols, const uint32_t *pos, uint64_t n, const pgt_win *win, uint64_t n_win,
                  pgt_fst_row *out, const AfTree &tv, const TreeLayout &tl, hipStream_t s, void *ev_b0, void *ev_b1,
                  void *ev_q1, std::string *err) {
-    auto rec = [&](void *ev) {
-        return ev ? hip_fail(hipEventRecord(static_cast<hipEvent_t>(ev), s), "hipEventRecord", err) : PGT_OK;
-    };
-    if (int rc = rec(ev_b0)) return rc;
+    if (int rc = record_event(ev_b0, s, err)) return rc;
     if (n > 0) {
         // Balanced grid-stride over the level-2 tiles: r = ceil(tiles / (4 cap)) rounds, ceil(tiles / r) waves,
         // so every wave does r tiles.  Measured at 10^8 sites, 8 populations (profiles/r02/af_caps.txt): the
@@ -507,6 +398,7 @@ int launch_af_np(const AfCols &cols, const uint32_t *pos, uint64_t n, const pgt_
         // workgroups run in GENERATIONS that end together — and a last generation that is nearly empty idles the chip for a
         // whole generation (3e8 sites, 8 populations: 1832 workgroups = 7.15 generations of 256, 76 % of the peak where 10^8
         // sites reach 81 %).  Among the next few round counts the one whose last generation is fullest is taken.
+        // (launch_dxy_pops keeps a static balanced grid instead, for its per-wave partials; deliberate)
         const uint64_t cap = NP == 2 ? 512 : 2048;
         const bool w1 = NP >= af_one_wave_from();
         const uint64_t resident = w1 ? 256 : 512, max_waves = cap * 4;
@@ -527,22 +419,14 @@ int launch_af_np(const AfCols &cols, const uint32_t *pos, uint64_t n, const pgt_
         else
             hipLaunchKernelGGL((af_build_kernel<NP, (NP == 2 ? 4 : 0)>), dim3((unsigned)blocks), dim3(256), kStage, s, cols, n, tl.count[1], tv);
         if (int rc = hip_fail(hipGetLastError(), "af_build_kernel", err)) return rc;
-        for (int k = 2; k < tv.n_levels; ++k) {
-            uint64_t b = (tl.count[k] + 3) / 4;
-            if (b > 65536) b = 65536;
-            hipLaunchKernelGGL(af_up_kernel, dim3((unsigned)b, Shape<NP>::kVals), dim3(256), 0, s, tv, k - 1,
-                               tl.count[k - 1], tl.count[k]);
-            if (int rc = hip_fail(hipGetLastError(), "af_up_kernel", err)) return rc;
-        }
+        if (int rc = launch_upper_levels(af_up_kernel, "af_up_kernel", Shape<NP>::kVals, tv, tl, s, err)) return rc;
     }
-    if (int rc = rec(ev_b1)) return rc;
+    if (int rc = record_event(ev_b1, s, err)) return rc;
     if (n_win > 0) {
-        uint64_t b = (n_win + 3) / 4;
-        if (b > 65536) b = 65536;
-        hipLaunchKernelGGL((af_query_kernel<NP>), dim3((unsigned)b), dim3(256), 0, s, cols, pos, tv, win, n_win, out, n);
+        hipLaunchKernelGGL((af_query_kernel<NP>), dim3(wave_grid(n_win)), dim3(256), 0, s, cols, pos, tv, win, n_win, out, n);
         if (int rc = hip_fail(hipGetLastError(), "af_query_kernel", err)) return rc;
     }
-    return rec(ev_q1);
+    return record_event(ev_q1, s, err);
 }
 
 }  // namespace
@@ -565,23 +449,18 @@ int launch_fst_af(const uint32_t *pos, const double *const *freq, const double *
                   const pgt_win *win, uint64_t n_win, pgt_fst_row *out, void *tree, void *stream, void *ev_build0,
                   void *ev_build1, void *ev_query1, std::string *err, const Hints &hints) {
     hipStream_t s = static_cast<hipStream_t>(stream);
+    if (n_pops < 2 || n_pops > (uint32_t)kAfMaxPops) {
+        if (err) *err = "pgt_fst_af_reduce: 2 <= n_pops <= 8";
+        return PGT_EARG;
+    }
     const TreeLayout tl = tree_layout(PGT_STAT_FST, n);
     const int n_vals = (int)(n_pops + n_pops * (n_pops - 1) / 2);
     const AfTree tv = af_tree_view(tl, n_vals, tree, useful_levels(tl, PGT_STAT_FST, hints.max_window));
     AfCols cols{};
     for (uint32_t k = 0; k < n_pops; ++k) { cols.f[k] = freq[k]; cols.nsamp[k] = nsamp[k]; }
-    switch (n_pops) {
-        case 2: return launch_af_np<2>(cols, pos, n, win, n_win, out, tv, tl, s, ev_build0, ev_build1, ev_query1, err);
-        case 3: return launch_af_np<3>(cols, pos, n, win, n_win, out, tv, tl, s, ev_build0, ev_build1, ev_query1, err);
-        case 4: return launch_af_np<4>(cols, pos, n, win, n_win, out, tv, tl, s, ev_build0, ev_build1, ev_query1, err);
-        case 5: return launch_af_np<5>(cols, pos, n, win, n_win, out, tv, tl, s, ev_build0, ev_build1, ev_query1, err);
-        case 6: return launch_af_np<6>(cols, pos, n, win, n_win, out, tv, tl, s, ev_build0, ev_build1, ev_query1, err);
-        case 7: return launch_af_np<7>(cols, pos, n, win, n_win, out, tv, tl, s, ev_build0, ev_build1, ev_query1, err);
-        case 8: return launch_af_np<8>(cols, pos, n, win, n_win, out, tv, tl, s, ev_build0, ev_build1, ev_query1, err);
-        default:
-            if (err) *err = "pgt_fst_af_reduce: 2 <= n_pops <= 8";
-            return PGT_EARG;
-    }
+    return dispatch_n_pops(n_pops, [&](auto np) {
+        return launch_af_np<decltype(np)::value>(cols, pos, n, win, n_win, out, tv, tl, s, ev_build0, ev_build1, ev_query1, err);
+    });
 }
 
 }  // namespace pgt

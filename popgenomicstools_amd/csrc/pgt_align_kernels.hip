@@ -25,6 +25,7 @@
 
 #include "pgt_device.h"
 #include "pgt_internal.h"
+#include "pgt_pops_common.h"  // hip_fail
 
 namespace pgt {
 namespace {
@@ -34,12 +35,6 @@ constexpr int kLaneRows = 4;
 constexpr uint32_t kTile = kThreads * kLaneRows;  // pivot rows per workgroup
 constexpr uint32_t kStage = 8192;                 // rows of another file a workgroup stages in LDS (32 KiB: five workgroups per CU)
 constexpr uint32_t kNone = 0xFFFFFFFFu;           // "not in every file" (rows per file stay below 2^32 - 1)
-
-int hip_fail(hipError_t e, const char *what, std::string *err) {
-    if (e == hipSuccess) return PGT_OK;
-    if (err) *err = std::string(what) + ": " + hipGetErrorString(e);
-    return PGT_EDEVICE;
-}
 
 struct AlignArgs {
     const uint32_t *pos[kAlignMaxFiles];

@@ -25,10 +25,9 @@
 // pgt_set_window_step is ignored by this entry point: every table is answered by the one-wave-per-window query.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "pgt_device.h"
 #include "pgt_internal.h"
+#include "pgt_pops_common.h"
 
 namespace pgt {
 namespace {
@@ -42,7 +41,7 @@ static_assert(kPieces == 4, "the build walks a leaf as two pairs of pieces");
 
 template <int NP>
 struct Shape {
-    static constexpr int kPairs = NP * (NP - 1) / 2;  // lexicographic (i < j): (0,1),(0,2),..,(0,NP-1),(1,2),..
+    static constexpr int kPairs = pair_count(NP);  // lexicographic (i < j): (0,1),(0,2),..,(0,NP-1),(1,2),..
 };
 
 struct PopCols {
@@ -50,76 +49,7 @@ struct PopCols {
     const int32_t *c[kDxyPopsMaxPops];
 };
 
-// ---- reduce-scatter across the wave (restated from pgt_af_kernels.hip, where it is explained and measured) ----------
-// C live values -> (C+1)/2 per step; the two busiest steps pair lanes across the wave halves and the 16-lane rows by
-// v_permlane32_swap / v_permlane16_swap, the others use DPP / ds_swizzle.  After six steps every total lives in one lane.
-constexpr int kRsMask[6] = {32, 16, 1, 2, 8, 4};
-template <int STEP>
-__device__ __forceinline__ double xchg(double v) {
-    static_assert(STEP >= 2, "steps 0 and 1 are swaps (rs_swap)");
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    if constexpr (STEP == 2) {         // xor 1: quad_perm [1,0,3,2]
-        lo = __builtin_amdgcn_update_dpp(lo, lo, 0xB1, 0xF, 0xF, false);
-        hi = __builtin_amdgcn_update_dpp(hi, hi, 0xB1, 0xF, 0xF, false);
-    } else if constexpr (STEP == 3) {  // xor 2: quad_perm [2,3,0,1]
-        lo = __builtin_amdgcn_update_dpp(lo, lo, 0x4E, 0xF, 0xF, false);
-        hi = __builtin_amdgcn_update_dpp(hi, hi, 0x4E, 0xF, 0xF, false);
-    } else if constexpr (STEP == 4) {  // xor 8: row_ror:8 inside the 16-lane row
-        lo = __builtin_amdgcn_update_dpp(lo, lo, 0x128, 0xF, 0xF, false);
-        hi = __builtin_amdgcn_update_dpp(hi, hi, 0x128, 0xF, 0xF, false);
-    } else {                           // xor 4: ds_swizzle bit mode (and 0x1f, or 0, xor 4)
-        lo = __builtin_amdgcn_ds_swizzle(lo, 0x101F);
-        hi = __builtin_amdgcn_ds_swizzle(hi, 0x101F);
-    }
-    return __hiloint2double(hi, lo);
-}
-template <int STEP>
-__device__ __forceinline__ double rs_swap(double a, double b) {
-    const int alo = __double2loint(a), ahi = __double2hiint(a), blo = __double2loint(b), bhi = __double2hiint(b);
-    if constexpr (STEP == 0) {
-        const auto l = __builtin_amdgcn_permlane32_swap(alo, blo, false, false);
-        const auto h = __builtin_amdgcn_permlane32_swap(ahi, bhi, false, false);
-        return __hiloint2double(h[0], l[0]) + __hiloint2double(h[1], l[1]);
-    } else {
-        const auto l = __builtin_amdgcn_permlane16_swap(alo, blo, false, false);
-        const auto h = __builtin_amdgcn_permlane16_swap(ahi, bhi, false, false);
-        return __hiloint2double(h[0], l[0]) + __hiloint2double(h[1], l[1]);
-    }
-}
-template <int C, int STEP>
-__device__ __forceinline__ void rs_steps(double *v, int lane) {
-    if constexpr (STEP < 6) {
-        constexpr int H = (C + 1) / 2;
-        if constexpr (STEP < 2) {
-#pragma unroll
-            for (int k = 0; k < H; ++k) v[k] = rs_swap<STEP>(v[k], (k + H < C) ? v[k + H] : 0.0);
-        } else {
-            const bool up = (lane & kRsMask[STEP]) != 0;
-#pragma unroll
-            for (int k = 0; k < H; ++k) {
-                const double lo_v = v[k];
-                const double hi_v = (k + H < C) ? v[k + H] : 0.0;
-                const double keep = up ? hi_v : lo_v;
-                const double send = up ? lo_v : hi_v;
-                v[k] = keep + xchg<STEP>(send);
-            }
-        }
-        rs_steps<H, STEP + 1>(v, lane);
-    }
-}
-// Which of the V values ends up in this lane (-1: a padding slot)
-template <int V>
-__device__ __forceinline__ int rs_my_index(int lane) {
-    int base = 0, real = V, c = V;
-#pragma unroll
-    for (int s = 0; s < 6; ++s) {
-        const int H = (c + 1) / 2;
-        if (lane & kRsMask[s]) { base += H; real = real > H ? real - H : 0; }
-        else real = real < H ? real : H;
-        c = H;
-    }
-    return real >= 1 ? base : -1;
-}
+// (the reduce-scatter of a leaf's P sums across the wave: rs_steps / rs_my_index of pgt_pops_common.h)
 
 // ---- per-site contribution ---------------------------------------------------------------------------------------------
 // One site of this lane into the lane's P running sums and the wave's P counters.  okbits: bit 4k = population k has at
@@ -304,16 +234,8 @@ __device__ __forceinline__ void dxy_pops_build_body(const PopCols &cols, int min
             tot_c += c2;
         }
         // the tile's 16 level-1 nodes: one contiguous block of 128 P bytes of sums and one of 64 P bytes of counts
+        flush_stage<P * kRadix1>(sum_node<NP>(tv, 0, t * kRadix1), stage_s, lane);
         {
-            double2 *dst = reinterpret_cast<double2 *>(sum_node<NP>(tv, 0, t * kRadix1));
-            const double2 *src = reinterpret_cast<const double2 *>(stage_s);
-            constexpr int kVec = P * kRadix1 / 2;
-#pragma unroll 4
-            for (int e = lane; e < kVec; e += kWave) {
-                const double2 w = src[e];
-                __builtin_nontemporal_store(w.x, &dst[e].x);
-                __builtin_nontemporal_store(w.y, &dst[e].y);
-            }
             uint4 *cdst = reinterpret_cast<uint4 *>(cnt_node<NP>(tv, 0, t * kRadix1));
             const uint4 *csrc = reinterpret_cast<const uint4 *>(stage_c);
             constexpr int kCVec = P * kRadix1 / 4;
@@ -469,6 +391,8 @@ __global__ __launch_bounds__(256, (NP >= 7 ? 1 : 2)) void dxy_pops_query_kernel(
         auto sum_nodes = [&](int level, uint64_t from, uint64_t to) {
             for (uint64_t i = from + lane; i < to; i += kWave) add_node(level - 1, i);
         };
+        // the range descent: the same loop as in af_query_kernel, where its rule is explained (each kernel keeps its copy: as one
+        // shared function the compiler gave both kernels other code; a change to one belongs in the other too)
         uint64_t clo = lo, chi = hi;
         for (int k = 0;; ++k) {
             const bool top = k == tv.n_levels;
@@ -513,21 +437,11 @@ __global__ __launch_bounds__(256, (NP >= 7 ? 1 : 2)) void dxy_pops_query_kernel(
     }
 }
 
-inline int hip_fail(hipError_t e, const char *what, std::string *err) {
-    if (e == hipSuccess) return PGT_OK;
-    if (err) *err = std::string(what) + ": " + hipGetErrorString(e);
-    return PGT_EDEVICE;
-}
-
 // populations from which the one-wave-per-SIMD build is taken (PGT_DXY_POPS_ONE_WAVE_FROM: a measuring knob, clamped to
 // what fits the registers: 2 .. kOneWaveFrom)
 inline int one_wave_from() {
-    static const int v = [] {
-        const char *e = std::getenv("PGT_DXY_POPS_ONE_WAVE_FROM");
-        const int x = e ? std::atoi(e) : kOneWaveFrom;
-        return x < 2 ? 2 : (x > kOneWaveFrom ? kOneWaveFrom : x);
-    }();
-    return v;
+    static const int v = env_int("PGT_DXY_POPS_ONE_WAVE_FROM", kOneWaveFrom);
+    return v < 2 ? 2 : (v > kOneWaveFrom ? kOneWaveFrom : v);
 }
 
 template <int NP>
@@ -537,14 +451,13 @@ template <int NP>
 int launch_np(const PopCols &cols, const uint32_t *pos, uint64_t n, int minind, const pgt_win *win, uint64_t n_win,
               pgt_dxy_row *out, pgt_dxy_total *tot, DxyPopsTree tv, const TreeLayout &tl, hipStream_t s, void *ev_b0,
               void *ev_b1, void *ev_q1, std::string *err) {
-    auto rec = [&](void *ev) {
-        return ev ? hip_fail(hipEventRecord(static_cast<hipEvent_t>(ev), s), "hipEventRecord", err) : PGT_OK;
-    };
-    if (int rc = rec(ev_b0)) return rc;
+    if (int rc = record_event(ev_b0, s, err)) return rc;
     tv.n_partials = 0;
     if (n > 0) {
         // a static balanced grid of what is resident at once (one wave per SIMD: 256 workgroups of 4 waves; two: 512): every
         // wave walks `rounds` tiles, all waves run in near lockstep and flush their node blocks at about the same times
+        // (launch_af_np picks its round count by how full the last generation is; that choice is unmeasured here, and the
+        // per-wave partials want a grid that depends on n alone)
         const bool w1 = NP >= one_wave_from();
         const uint64_t max_waves = w1 ? 1024 : (uint64_t)kMaxBuildWaves;
         const uint64_t rounds = (tl.count[1] + max_waves - 1) / max_waves;
@@ -560,21 +473,14 @@ int launch_np(const PopCols &cols, const uint32_t *pos, uint64_t n, int minind, 
             hipLaunchKernelGGL((dxy_pops_build_kernel_w1<NP>), dim3((unsigned)blocks), dim3(256), stage_bytes<NP>(), s, cols, minind, n, tl.count[1], tv);
         }
         if (int rc = hip_fail(hipGetLastError(), "dxy_pops_build_kernel", err)) return rc;
-        for (int k = 2; k < tv.n_levels; ++k) {
-            uint64_t b = (tl.count[k] + 3) / 4;
-            if (b > 65536) b = 65536;
-            hipLaunchKernelGGL(dxy_pops_up_kernel, dim3((unsigned)b, Shape<NP>::kPairs), dim3(256), 0, s, tv, k - 1, tl.count[k - 1], tl.count[k]);
-            if (int rc = hip_fail(hipGetLastError(), "dxy_pops_up_kernel", err)) return rc;
-        }
+        if (int rc = launch_upper_levels(dxy_pops_up_kernel, "dxy_pops_up_kernel", Shape<NP>::kPairs, tv, tl, s, err)) return rc;
     }
-    if (int rc = rec(ev_b1)) return rc;
+    if (int rc = record_event(ev_b1, s, err)) return rc;
     if (n_win > 0 || tot) {
-        uint64_t b = (n_win + (tot ? 1 : 0) + 3) / 4;
-        if (b > 65536) b = 65536;
-        hipLaunchKernelGGL((dxy_pops_query_kernel<NP>), dim3((unsigned)b), dim3(256), 0, s, cols, minind, pos, tv, win, n_win, out, tot, n);
+        hipLaunchKernelGGL((dxy_pops_query_kernel<NP>), dim3(wave_grid(n_win + (tot ? 1 : 0))), dim3(256), 0, s, cols, minind, pos, tv, win, n_win, out, tot, n);
         if (int rc = hip_fail(hipGetLastError(), "dxy_pops_query_kernel", err)) return rc;
     }
-    return rec(ev_q1);
+    return record_event(ev_q1, s, err);
 }
 
 template <int NP>
@@ -604,15 +510,9 @@ int launch_dxy_pops(const uint32_t *pos, const double *const *freq, const int32_
     const DxyPopsTree tv = dxy_pops_tree_view(tl, (int)(n_pops * (n_pops - 1) / 2), tree, useful_levels(tl, PGT_STAT_FST, hints.max_window));
     PopCols cols{};
     for (uint32_t k = 0; k < n_pops; ++k) { cols.f[k] = freq[k]; cols.c[k] = nind[k]; }
-    switch (n_pops) {
-        case 2: return launch_np<2>(cols, pos, n, minind, win, n_win, out, tot, tv, tl, s, ev_build0, ev_build1, ev_query1, err);
-        case 3: return launch_np<3>(cols, pos, n, minind, win, n_win, out, tot, tv, tl, s, ev_build0, ev_build1, ev_query1, err);
-        case 4: return launch_np<4>(cols, pos, n, minind, win, n_win, out, tot, tv, tl, s, ev_build0, ev_build1, ev_query1, err);
-        case 5: return launch_np<5>(cols, pos, n, minind, win, n_win, out, tot, tv, tl, s, ev_build0, ev_build1, ev_query1, err);
-        case 6: return launch_np<6>(cols, pos, n, minind, win, n_win, out, tot, tv, tl, s, ev_build0, ev_build1, ev_query1, err);
-        case 7: return launch_np<7>(cols, pos, n, minind, win, n_win, out, tot, tv, tl, s, ev_build0, ev_build1, ev_query1, err);
-        default: return launch_np<8>(cols, pos, n, minind, win, n_win, out, tot, tv, tl, s, ev_build0, ev_build1, ev_query1, err);
-    }
+    return dispatch_n_pops(n_pops, [&](auto np) {
+        return launch_np<decltype(np)::value>(cols, pos, n, minind, win, n_win, out, tot, tv, tl, s, ev_build0, ev_build1, ev_query1, err);
+    });
 }
 
 }  // namespace pgt

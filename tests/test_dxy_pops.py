@@ -280,7 +280,7 @@ def _exact_table(pgt, d, W):
     return np.concatenate(parts)
 
 
-@pytest.mark.parametrize("n,k", [(1, 2), (513, 3), (8193, 8), (65_537, 5), (300_017, 4), (1_600_001, 8)])
+@pytest.mark.parametrize("n,k", [(1, 2), (513, 3), (513, 6), (8193, 7), (8193, 8), (65_537, 5), (300_017, 4), (1_600_001, 8)])
 def test_exact_rows_under_every_hint_poison_and_guard(pgt, ctx, n, k):
     """Rows and totals of every pair equal the integer prefix sums BITWISE: under the hints 0 / W / 4 W, with the tree
     workspace poisoned three ways before every call, tree / out / tot between seeded guards, and the columns as views into

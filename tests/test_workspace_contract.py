@@ -483,9 +483,9 @@ def test_fused_dxy_het_rows_are_exact(pgt, ctx, n):
         torch.cuda.synchronize()
 
 
-@pytest.mark.parametrize("n_pops,n", [(2, 1), (2, 511), (2, 500_003), (3, 513), (3, 65_537), (8, 8193), (8, 1_600_001)])
+@pytest.mark.parametrize("n_pops,n", [(2, 1), (2, 511), (2, 500_003), (3, 513), (3, 65_537), (4, 513), (5, 8193), (6, 65_537), (7, 8193), (8, 8193), (8, 1_600_001)])
 def test_af_front_end_rows_are_exact(pgt, ctx, n_pops, n):
-    """fst_af_reduce_dev with NP = 2, 3, 8: exact frequency columns make the window sums exact, so every strategy, hint and
+    """fst_af_reduce_dev with every NP in 2 ... 8 (each is its own instantiation of the reduce-scatter): exact frequency columns make the window sums exact, so every strategy, hint and
     poison gives the same bytes — those of the kernel's closing formula on the exact sums, and within a few ulp of the
     component's scale of WCFst evaluated in rationals."""
     d, other_d = data(8, n), data(9, n)

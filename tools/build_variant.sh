@@ -10,7 +10,7 @@ OBJ=$ROOT/tools/_ab/obj
 mkdir -p "$OBJ"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -I$ROOT/include -I$CSRC $*"
 objs=()
-for src in pgt_kernels.hip pgt_af_kernels.hip pgt_ingest.hip pgt_api.cpp pgt_windows.cpp; do
+for src in pgt_kernels.hip pgt_af_kernels.hip pgt_dxy_pops_kernels.hip pgt_align_kernels.hip pgt_ingest.hip pgt_api.cpp pgt_windows.cpp; do
   key=$( (echo "$FLAGS"; cat "$CSRC/$src" "$CSRC"/*.h "$ROOT/include/pgtwin.h") | sha256sum | cut -c1-16)
   o=$OBJ/${src%.*}.$key.o
   if [ ! -f "$o" ]; then hipcc $FLAGS -x hip -c "$CSRC/$src" -o "$o" & fi

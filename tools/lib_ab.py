@@ -117,6 +117,10 @@ def main():
     nsamp = [10.0 + k for k in range(8)]
     af_tree = torch.empty(int(_lib.load().pgt_af_tree_bytes(8, n)), dtype=torch.uint8, device=dev) if fr else None
     af_out = torch.empty(28 * 40 * (win.numel() // 32), dtype=torch.uint8, device=dev) if fr else None
+    ni = [((n1, n2)[k % 2] + k) % 21 for k in range(8)] if fr else None  # individual counts of the 8 populations (int32, 0 ... 20)
+    dp_tree = torch.empty(ctx_b.dxy_pops_tree_bytes(8, n), dtype=torch.uint8, device=dev) if fr else None
+    dp_out = torch.empty(28 * 24 * (win.numel() // 32), dtype=torch.uint8, device=dev) if fr else None
+    dp_tot = torch.empty(28 * 24, dtype=torch.uint8, device=dev) if fr else None
     configs = [
         ("fstWindow", 16, lambda c: c.fst_reduce_dev(pos, a, b, win, out=out, tree=tree)),
         ("dxyWindow (with the genome-wide line)", 24, lambda c: c.dxy_reduce_dev(pos, p1, p2, n1, n2, 5, win, out=out, tree=tree)),
@@ -127,6 +131,8 @@ def main():
     if fr:
         configs.append(("AF front end, 8 populations", 64, lambda c: c.fst_af_reduce_dev(pos, fr, nsamp, win, out=af_out, tree=af_tree)))
         configs.append(("AF front end, 2 populations", 16, lambda c: c.fst_af_reduce_dev(pos, fr[:2], nsamp[:2], win, out=af_out, tree=af_tree)))
+        configs.append(("dxy of all pairs, 8 populations", 96, lambda c: c.dxy_pops_reduce_dev(pos, fr, ni, 5, win, out=dp_out, tot=dp_tot, tree=dp_tree)))
+        configs.append(("dxy of all pairs, 2 populations", 24, lambda c: c.dxy_pops_reduce_dev(pos, fr[:2], ni[:2], 5, win, out=dp_out, tot=dp_tot, tree=dp_tree)))
     print(f"A = {os.path.relpath(old, ROOT)}, B = {b_name}; {n:.0e} sites, W = {W}, S = {S}, {rounds} rounds of A B B A, {BURST} call(s) per measurement\n")
     print("| config | A build ms | B build ms | B - A paired (median) | A % of 8 TB/s | B % | A step ms | B step ms | step B - A paired | rows A = B |")
     print("|---|---|---|---|---|---|---|---|---|---|")
@@ -142,7 +148,11 @@ def main():
         def rows(c):
             r = fn(c)
             torch.cuda.synchronize()
-            return [t.clone() for t in r[:-1] if t is not None]
+            kept = [t.clone() for t in r[:-1] if t is not None]
+            for t in r[:-1]:  # the builds share their output buffers: cleared, so that the other build's rows are its own
+                if t is not None:
+                    t.zero_()
+            return kept
         ra_, rb_ = rows(ctx_a), rows(ctx_b)
         same = all(torch.equal(x, y) for x, y in zip(ra_, rb_))
         if not same:  # say WHICH tensor differs and by how much (a 24-byte tensor is the genome-wide dxy line: f64 sum, two u64 counts)
