@@ -23,7 +23,7 @@ all: $(LIB) $(addprefix $(BIN)/,$(TOOLS))
 $(LIB): $(LIBSRC) $(LIBHDR)
 	$(HIPCC) $(LIBFLAGS) -Iinclude -I$(CSRC) -o $@ $(LIBSRC)
 
-$(BIN)/%: $(HOST)/%_main.cpp $(HOST)/host_common.h $(HOST)/extreme_common.h include/pgtwin.h $(LIB)
+$(BIN)/%: $(HOST)/%_main.cpp $(HOST)/host_common.h $(HOST)/extreme_common.h $(HOST)/site_common.h $(HOST)/dxy_common.h include/pgtwin.h $(LIB)
 	@mkdir -p $(BIN)
 	$(HIPCC) -O2 -std=c++17 -Iinclude -I$(HOST) $< -o $@ -L$(PKG) -lpgtwin -lz -lpthread -Wl,-rpath,'$$ORIGIN/..'
 

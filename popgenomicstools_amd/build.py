@@ -100,7 +100,7 @@ def build_hosts(force: bool = False) -> list[str]:
     """The retained C++ hosts: same argv and TSV as the reference tools, reduction in libpgtwin."""
     os.makedirs(BIN, exist_ok=True)
     out = []
-    common = [os.path.join(HOST, "host_common.h"), os.path.join(HOST, "extreme_common.h"), os.path.join(ROOT, "include", "pgtwin.h"), LIB]
+    common = [os.path.join(HOST, h) for h in ("host_common.h", "extreme_common.h", "site_common.h", "dxy_common.h")] + [os.path.join(ROOT, "include", "pgtwin.h"), LIB]
     for tool in HOST_TOOLS:
         src = os.path.join(HOST, tool + "_main.cpp")
         if not os.path.exists(src):

@@ -14,9 +14,7 @@
 // Limits: one GPU (the first of PGT_DEVICES); no passes mode — the K parsed files and the aligned columns must fit the
 // card (and PGT_MAX_RESIDENT_SITES, where set) or the run is refused; PGT_DXY_SYNC=reference is not offered (the
 // reference's catch-up loops are defined for two files only).
-#include <map>
-
-#include "host_common.h"
+#include "dxy_common.h"
 
 using namespace pgthost;
 
@@ -50,33 +48,12 @@ static void help(unsigned W, unsigned S, int minind, int fixedsite, int skip_mis
 }
 
 // one parsed file: columns on the device (pos / freq / nind), chromosome runs on the host
-struct Maf {
-    Runs runs;
+struct Maf : MafTable {
     DeviceTable dev;  // set when the file was parsed on the GPU: pos / freq / nind are tokens 1 / 5 / 6 there
-    Column<uint32_t> pos;  // the host parser's columns (uploaded, then unused)
-    Column<double> freq;
-    Column<int32_t> nind;
-    size_t n = 0;
-    const uint32_t *d_pos = nullptr;
+    const uint32_t *d_pos = nullptr;  // (the host parser's columns are uploaded, then unused)
     const double *d_freq = nullptr;
     const int32_t *d_nind = nullptr;
-    void alloc(size_t rows) { pos.alloc(rows); freq.alloc(rows); nind.alloc(rows); }
-    // chr pos major minor ref freq nind — only chr, pos, freq, nind are used (dxyWindow.cpp:141-153)
-    bool parse_line(Cursor &c, size_t i, Runs &r) {
-        const Tok chr = c.token();
-        long long k;
-        bool ok = to_u32(c.token(), pos[i]);
-        c.token(); c.token(); c.token();  // major minor ref
-        ok = ok && to_f64(c.token(), freq[i]) && to_i64(c.token(), k);
-        if (!ok || !(freq[i] >= 0.0 && freq[i] <= 1.0)) return false;  // as the dxyWindow host: dxy must not become negative
-        nind[i] = (int32_t)std::max<long long>(std::min<long long>(k, INT32_MAX), INT32_MIN);
-        r.add(chr.first, chr.second);
-        return true;
-    }
 };
-
-static const char *const kMafWhat = "dxyWindow: cannot parse MAF line (chr pos major minor ref freq nind, freq in [0,1])";
-static const uint8_t kMafSpec[] = {PGT_TOK_CHR, PGT_TOK_U32, PGT_TOK_SKIP, PGT_TOK_SKIP, PGT_TOK_SKIP, PGT_TOK_FREQ, PGT_TOK_I32};
 
 template <class T>
 static T *dev_alloc(pgt_ctx *ctx, size_t elems) {
@@ -86,53 +63,29 @@ static T *dev_alloc(pgt_ctx *ctx, size_t elems) {
 }
 
 int main(int argc, char **argv) {
-    uint32_t W = 0, S = 0;  // dxyWindow.cpp:529-534
-    int minind = 1, fixedsite = 0, skip_missing = 0;
-    const char *sizefile = nullptr, *prefix = nullptr;
+    DxyOptions opt;
+    const char *prefix = nullptr;
     if (argc < 2) {
-        help(W, S, minind, fixedsite, skip_missing);
+        help(opt.W, opt.S, opt.minind, opt.fixedsite, opt.skip_missing);
         return 0;
     }
     // option/value pairs first; what follows the last pair are the MAF files
     int i = 1;
     for (; i < argc && argv[i][0] == '-' && argv[i][1] != '\0'; i += 2) {
-        const char *opt = argv[i];
-        if (i + 1 >= argc) die(std::string("Missing value for ") + opt);
-        const char *val = argv[i + 1];
-        if (!std::strcmp(opt, "-winsize")) W = (uint32_t)std::atoi(val);
-        else if (!std::strcmp(opt, "-stepsize")) S = (uint32_t)std::atoi(val);
-        else if (!std::strcmp(opt, "-minind")) {
-            minind = std::atoi(val);
-            if (minind <= 0) die("-minind must be at least 1");
-        } else if (!std::strcmp(opt, "-sizefile")) sizefile = val;
-        else if (!std::strcmp(opt, "-fixedsite")) fixedsite = std::atoi(val);
-        else if (!std::strcmp(opt, "-skip_missing")) skip_missing = std::atoi(val);
-        else if (!std::strcmp(opt, "-out")) prefix = val;
-        else die(std::string("Unknown command: ") + opt);
+        const char *o = argv[i];
+        if (i + 1 >= argc) die(std::string("Missing value for ") + o);
+        if (!std::strcmp(o, "-out")) prefix = argv[i + 1];
+        else if (!dxy_option(opt, o, argv[i + 1])) unknown_dxy_option(o);
     }
     const int K = argc - i;
     char **paths = argv + i;
     if (K < 2 || K > 8) die("dxyWindowPops: between 2 and 8 MAF files are needed (" + std::to_string(std::max(K, 0)) + " given)");
     if (!prefix || !*prefix) die("Must supply -out PREFIX");
-    if (W > 0 && S < 1) die("Must specify a -stepsize > 0 when -winsize is > 0");
-    if (!fixedsite && !sizefile) die("Must supply size file unless -fixedsite 1");
-    if (W > 0 && S > W) die("-stepsize must not exceed -winsize");                      // reference: crash (Q9)
-    if (W == 0 && !fixedsite) die("-winsize 0 (global dxy) requires -fixedsite 1");      // reference: crash (Q10)
-
-    std::map<std::string, uint32_t> chrsize;  // dxyWindow.cpp:155-170
-    if (!fixedsite) {
-        Text text;
-        if (!text.open(sizefile)) die(std::string("Unable to open sizefile: ") + sizefile);
-        Cursor c{text.begin(), text.end()};
-        while (c.p < c.end) {
-            auto name = c.token();
-            uint32_t len = 0;
-            if (name.first == name.second || !to_u32(c.token(), len) || len == 0)
-                die("Unable to correctly parse chromosome size file");
-            chrsize.insert({std::string(name.first, name.second), len});
-            c.next_line();
-        }
-    }
+    check_dxy_options(opt);
+    const uint32_t W = opt.W, S = opt.S;
+    const int minind = opt.minind, fixedsite = opt.fixedsite, skip_missing = opt.skip_missing;
+    std::map<std::string, uint32_t> chrsize;
+    if (!fixedsite) chrsize = read_sizefile(opt.sizefile);
 
     PhaseTimer timer;
     DeviceOpener device(std::vector<int>{devices_from_env()[0]});  // one GPU; HIP start-up runs beside the opening of the files
@@ -302,24 +255,14 @@ int main(int argc, char **argv) {
 
     std::vector<pgt_win> win;
     if (W > 0) {
-        size_t n_win = 0;
         if (fixedsite) {
-            check(pgt_build_windows_sites(runs.len.data(), runs.len.size(), W, S, nullptr, 0, &n_win), nullptr);
-            win.resize(n_win);
-            if (n_win) check(pgt_build_windows_sites(runs.len.data(), runs.len.size(), W, S, win.data(), win.size(), &n_win), nullptr);
+            win = site_windows(runs, W, S);
         } else {
-            std::vector<uint32_t> chr_len(runs.name.size());
-            for (size_t r = 0; r < runs.name.size(); ++r) {
-                auto it = chrsize.find(runs.name[r]);
-                if (it == chrsize.end()) die("Unable to determine size for " + runs.name[r]);  // dxyWindow.cpp:340-343
-                chr_len[r] = it->second;
-            }
+            const std::vector<uint32_t> chr_len = chr_lengths(runs, chrsize);
             Column<uint32_t> pos;  // the bp table is built from the aligned positions: 4 B per site, one download
             pos.alloc(n_sites);
             check(pgt_rowbuf_read(ctx, pos.data(), a_pos, n_sites * sizeof(uint32_t), nullptr), ctx);
-            check(pgt_build_windows_bp(pos.data(), runs.len.data(), chr_len.data(), runs.len.size(), W, S, nullptr, 0, &n_win), nullptr);
-            win.resize(n_win);
-            if (n_win) check(pgt_build_windows_bp(pos.data(), runs.len.data(), chr_len.data(), runs.len.size(), W, S, win.data(), win.size(), &n_win), nullptr);
+            win = bp_windows(pos.data(), runs, chr_len, W, S);
         }
     }
     timer.lap("window table");
@@ -357,12 +300,7 @@ int main(int argc, char **argv) {
             if (W > 0) {
                 const std::string path = std::string(prefix) + ".pop" + std::to_string(a + 1) + "_pop" + std::to_string(b + 1) + ".dxy";
                 FILE *f = open_out(path);
-                const pgt_dxy_row *r = rows.data() + p * n_win;
-                // chr start end dxy neffective nskip, unless -skip_missing drops the row (dxyWindow.cpp:189-191)
-                write_rows(n_win, longest_name(runs) + 80, [&](size_t w, char *o) -> size_t {
-                    if (!(r[w].neff > 0 || !skip_missing)) return 0;
-                    return put_row(o, runs.name[win[w].label_run], {r[w].start, r[w].end}, r[w].sum, {r[w].neff, r[w].nskip});
-                }, f);
+                write_dxy_rows(rows.data() + p * n_win, n_win, runs, [&](size_t w) { return win[w].label_run; }, skip_missing, f);
                 close_out(f, path);
             }
             std::fprintf(global, "%d\t%d\t%g\t%llu\t%llu\n", a + 1, b + 1, tot[p].sum, (unsigned long long)tot[p].neff, (unsigned long long)tot[p].nskip);

@@ -10,12 +10,10 @@
 // computes the intersection of the two files by (chromosome run, position), which is what the
 // reference produces on that domain, and is defined outside it as well.
 // PGT_DXY_SYNC=reference (an environment switch, the CLI surface is unchanged) replays those loops
-// instead — pair_as_the_reference() below — so that inputs on which the reference terminates
+// instead — dxy_common.h: pair_as_the_reference() — so that inputs on which the reference terminates
 // normally but oddly (a position coincidence across chromosomes, an extra Pop2 site at a
 // chromosome end, no shared site) print the reference's bytes: INTEGRATION.md §3a.
-#include <map>
-
-#include "host_common.h"
+#include "dxy_common.h"
 
 using namespace pgthost;
 
@@ -42,15 +40,10 @@ static void help(unsigned W, unsigned S, int minind, int fixedsite, int skip_mis
                 "-sizefile", "FILE", "-skip_missing", "INT", skip_missing);
 }
 
-struct Maf {
-    Runs runs;
+struct Maf : MafTable {
     DeviceTable dev;  // set when the file was parsed on the GPU: pos / freq / nind are then tokens 1 / 5 / 6 there
     pgt_ctx *ctx = nullptr;  // ... the context of that GPU
     bool on_device = false;
-    Column<uint32_t> pos;
-    Column<double> freq;
-    Column<int32_t> nind;
-    size_t n = 0;
     void reset() {  // back to empty: the host parser fills it from scratch
         if (dev.ing) pgt_ingest_free(dev.ing);
         dev.ing = nullptr;
@@ -59,25 +52,7 @@ struct Maf {
         runs = Runs{};
         n = 0;
     }
-    void alloc(size_t rows) { pos.alloc(rows); freq.alloc(rows); nind.alloc(rows); }
-    // chr pos major minor ref freq nind — only chr, pos, freq, nind are used (dxyWindow.cpp:141-153)
-    bool parse_line(Cursor &c, size_t i, Runs &r) {
-        const Tok chr = c.token();
-        long long k;
-        bool ok = to_u32(c.token(), pos[i]);
-        c.token(); c.token(); c.token();  // major minor ref
-        ok = ok && to_f64(c.token(), freq[i]) && to_i64(c.token(), k);
-        // a frequency outside [0,1] would make dxy negative, which the reference neither counts nor
-        // skips (dxyWindow.cpp:180-185): refuse it
-        if (!ok || !(freq[i] >= 0.0 && freq[i] <= 1.0)) return false;
-        nind[i] = (int32_t)std::max<long long>(std::min<long long>(k, INT32_MAX), INT32_MIN);
-        r.add(chr.first, chr.second);
-        return true;
-    }
 };
-
-static const char *const kMafWhat = "dxyWindow: cannot parse MAF line (chr pos major minor ref freq nind, freq in [0,1])";
-static const uint8_t kMafSpec[] = {PGT_TOK_CHR, PGT_TOK_U32, PGT_TOK_SKIP, PGT_TOK_SKIP, PGT_TOK_SKIP, PGT_TOK_FREQ, PGT_TOK_I32};
 
 // the device path of read_maf (plain or gzipped text of at least 8 MiB, no column cache): only the position
 // column comes back to the host (site synchronisation and the bp-window table work on it)
@@ -129,69 +104,6 @@ static void read_maf(const char *path, const char *which, Maf &m, ColumnCache &c
         cols[0].data = m.pos.data(); cols[1].data = m.freq.data(); cols[2].data = m.nind.data();
         cache.store(m.n, m.runs, cols);
     }
-}
-
-// ---- PGT_DXY_SYNC=reference: dxyWindow.cpp:315-331 replayed over the two parsed site lists ----------------------------
-// The reference keeps one current line per file and, when chromosome or position differ, advances ONE of them:
-//   Pop1 (`:317-323`) when the names agree and Pop1's position is smaller, or the names differ and Pop2's name is not the
-//        chromosome of the last processed site — until the POSITIONS are equal (names are not looked at), or Pop1 ends;
-//   Pop2 (`:324-330`) otherwise — while its position is SMALLER — and gives the whole run up unless the positions then agree.
-// What it then processes is Pop1's line with Pop2's frequency and count beside it, under Pop1's chromosome name (`:332`).  A
-// give-up ends the main loop exactly as the end of a file does (`:323,329` break to `:406`), so the reference's output is that
-// of its window machine on the pairs processed so far: the list this function returns.  "getline fails" is "no further
-// parsed line" here (both parsers stop at the first empty line as `while (!maf1line.empty())` does, `:313`).
-// -> the pairs (index in file 1, index in file 2); `last_chr`: the chromosome the closing code (`:407-426`) works on —
-// the last pair's, or the first line's when nothing was paired.
-static std::vector<std::pair<size_t, size_t>> pair_as_the_reference(const Maf &m1, const Maf &m2, std::string &last_chr) {
-    auto run_of = [](const Runs &r) {  // site index -> run index, by a cursor that only moves forward
-        return [&r, run = (size_t)0, end = (size_t)(r.len.empty() ? 0 : r.len[0])](size_t i) mutable {
-            while (i >= end && run + 1 < r.len.size()) end += r.len[++run];
-            return run;
-        };
-    };
-    auto r1 = run_of(m1.runs), r2 = run_of(m2.runs);
-    std::vector<std::pair<size_t, size_t>> pairs;
-    size_t i = 0, j = 0;
-    std::string chr = m1.runs.name[0];
-    for (;;) {
-        const std::string &c1 = m1.runs.name[r1(i)], &c2 = m2.runs.name[r2(j)];
-        if (m1.pos[i] != m2.pos[j] || c1 != c2) {  // :316
-            if ((c1 == c2 && m1.pos[i] < m2.pos[j]) || (c1 != c2 && c2 != chr)) {  // :317
-                while (m1.pos[i] != m2.pos[j] && i + 1 < m1.n) ++i;  // :319-322
-                if (m1.pos[i] != m2.pos[j]) break;                     // :323
-            } else {
-                while (m2.pos[j] < m1.pos[i] && j + 1 < m2.n) ++j;    // :326-329
-                if (m1.pos[i] != m2.pos[j]) break;                     // :330
-            }
-        }
-        chr = m1.runs.name[r1(i)];  // :332
-        pairs.emplace_back(i, j);
-        if (i + 1 >= m1.n) break;   // :399
-        ++i;
-        if (j + 1 >= m2.n) break;   // :402
-        ++j;
-    }
-    last_chr = chr;
-    return pairs;
-}
-
-// The reference's closing code on a chromosome of `len` base pairs of which NO site was processed (`:407-426` with nsites = 0,
-// positer = 1): every slot is a placeholder, every window `chr start end 0 0 0` (case H10 of tests/golden/dxy_hand_walked.json).
-static void print_placeholder_chromosome(const std::string &chr, uint64_t len, uint64_t W, uint64_t S, int skip_missing) {
-    if (skip_missing) return;  // neffective == 0: the row is dropped (`:189`)
-    uint64_t first = 1, n = 0, p = 1;
-    while (p <= len) {
-        if (n == W) {  // `:413`: the buffer is full before the next slot goes in
-            std::printf("%s\t%llu\t%llu\t0\t0\t0\n", chr.c_str(), (unsigned long long)first, (unsigned long long)(first + W - 1));
-            first += S;
-            n = W - S;
-        }
-        const uint64_t take = std::min<uint64_t>(W - n, len - p + 1);
-        n += take;
-        p += take;
-    }
-    if (n > W - S && n <= W)  // `:424`
-        std::printf("%s\t%llu\t%llu\t0\t0\t0\n", chr.c_str(), (unsigned long long)first, (unsigned long long)(first + n - 1));
 }
 
 // ---- several GPUs (PGT_DEVICES=0,1,...) ------------------------------------------------------------------------
@@ -317,9 +229,10 @@ static void reduce_dxy_on_devices(DeviceOpener &device, const std::vector<pgt_wi
 // before the first window is known: one extra pass over file 1 that keeps only its position column (4 B per site on the
 // host).  Then per block: the text of its rows of both files -> device parser -> reduce -> its rows printed; the genome-wide
 // line from the blocks' 65536-site rows, in order, as on several GPUs.
-static bool dxy_in_passes(DeviceOpener &device, const Text &t1, const Text &t2, const char *path1, const char *path2, uint32_t W, uint32_t S,
-                          int minind, int fixedsite, int skip_missing, const std::map<std::string, uint32_t> &chrsize,
-                          uint64_t max_resident, PhaseTimer &timer) {
+static bool dxy_in_passes(DeviceOpener &device, const Text &t1, const Text &t2, const char *path1, const char *path2, const DxyOptions &opt,
+                          const std::map<std::string, uint32_t> &chrsize, uint64_t max_resident, PhaseTimer &timer) {
+    const uint32_t W = opt.W, S = opt.S;
+    const int minind = opt.minind;
     struct File { const char *b, *e, *end; Runs runs; std::vector<const char *> mark; std::vector<uint64_t> pos_digest; size_t n; const char *path; } f[2];
     const Text *texts[2] = {&t1, &t2};
     const char *paths[2] = {path1, path2};
@@ -363,11 +276,8 @@ static bool dxy_in_passes(DeviceOpener &device, const Text &t1, const Text &t2, 
     std::vector<uint32_t> pos_all;  // base-pair windows only
     std::vector<pgt_win> win;
     if (W > 0) {
-        size_t n_win = 0;
-        if (fixedsite) {
-            check(pgt_build_windows_sites(runs.len.data(), runs.len.size(), W, S, nullptr, 0, &n_win), nullptr);
-            win.resize(n_win);
-            if (n_win) check(pgt_build_windows_sites(runs.len.data(), runs.len.size(), W, S, win.data(), win.size(), &n_win), nullptr);
+        if (opt.fixedsite) {
+            win = site_windows(runs, W, S);
         } else {
             pos_all.resize(n);
             for (uint64_t row0 = 0; row0 < n; row0 += per_pass) {
@@ -377,15 +287,7 @@ static bool dxy_in_passes(DeviceOpener &device, const Text &t1, const Text &t2, 
                 else std::memcpy(pos_all.data() + row0, pc.m.pos.data(), pc.rows * sizeof(uint32_t));
             }
             timer.lap("positions");
-            std::vector<uint32_t> chr_len(runs.name.size());
-            for (size_t r = 0; r < runs.name.size(); ++r) {
-                auto it = chrsize.find(runs.name[r]);
-                if (it == chrsize.end()) die("Unable to determine size for " + runs.name[r]);  // dxyWindow.cpp:340-343
-                chr_len[r] = it->second;
-            }
-            check(pgt_build_windows_bp(pos_all.data(), runs.len.data(), chr_len.data(), runs.len.size(), W, S, nullptr, 0, &n_win), nullptr);
-            win.resize(n_win);
-            if (n_win) check(pgt_build_windows_bp(pos_all.data(), runs.len.data(), chr_len.data(), runs.len.size(), W, S, win.data(), win.size(), &n_win), nullptr);
+            win = bp_windows(pos_all.data(), runs, chr_lengths(runs, chrsize), W, S);
         }
     }
     const size_t passes = (size_t)std::min<uint64_t>((n + per_pass - 1) / per_pass + (win.empty() ? 0 : 1), 1u << 20);
@@ -424,58 +326,28 @@ static bool dxy_in_passes(DeviceOpener &device, const Text &t1, const Text &t2, 
         }, out, n_own);
         if (!any) continue;
         const pgt_win *gw = win.data() + pl.shard[k].win_begin;
-        // chr start end dxy neffective nskip, unless -skip_missing drops the row (dxyWindow.cpp:189-191)
-        write_rows(n_own, longest_name(runs) + 80, [&](size_t i, char *o) -> size_t {
-            if (!(out[i].neff > 0 || !skip_missing)) return 0;
-            return put_row(o, runs.name[gw[i].label_run], {out[i].start, out[i].end}, out[i].sum, {out[i].neff, out[i].nskip});
-        });
+        write_dxy_rows(out.data(), n_own, runs, [&](size_t i) { return gw[i].label_run; }, opt.skip_missing);
         add_block_rows(tot, out.data() + n_own, out.size() - n_own);
     }
     timer.lap("passes");
-    std::fprintf(W == 0 ? stdout : stderr, "%g\t%llu\t%llu\n", tot.sum, (unsigned long long)tot.neff, (unsigned long long)tot.nskip);
+    print_dxy_total(tot, W);
     return true;
 }
 
 int main(int argc, char **argv) {
-    uint32_t W = 0, S = 0;  // dxyWindow.cpp:529-534
-    int minind = 1, fixedsite = 0, skip_missing = 0;
-    const char *sizefile = nullptr;
+    DxyOptions opt;
     if (argc < 3) {
-        help(W, S, minind, fixedsite, skip_missing);
+        help(opt.W, opt.S, opt.minind, opt.fixedsite, opt.skip_missing);
         return 0;
     }
     // the last two arguments are the MAF files; option/value pairs precede them (dxyWindow.cpp:97-126)
-    for (int i = 1; i < argc - 2; i += 2) {
-        const char *opt = argv[i], *val = argv[i + 1];
-        if (!std::strcmp(opt, "-winsize")) W = (uint32_t)std::atoi(val);
-        else if (!std::strcmp(opt, "-stepsize")) S = (uint32_t)std::atoi(val);
-        else if (!std::strcmp(opt, "-minind")) {
-            minind = std::atoi(val);
-            if (minind <= 0) die("-minind must be at least 1");
-        } else if (!std::strcmp(opt, "-sizefile")) sizefile = val;
-        else if (!std::strcmp(opt, "-fixedsite")) fixedsite = std::atoi(val);
-        else if (!std::strcmp(opt, "-skip_missing")) skip_missing = std::atoi(val);
-        else die(std::string("Unknown command: ") + opt);
-    }
-    if (W > 0 && S < 1) die("Must specify a -stepsize > 0 when -winsize is > 0");
-    if (!fixedsite && !sizefile) die("Must supply size file unless -fixedsite 1");
-    if (W > 0 && S > W) die("-stepsize must not exceed -winsize");                      // reference: crash (Q9)
-    if (W == 0 && !fixedsite) die("-winsize 0 (global dxy) requires -fixedsite 1");      // reference: crash (Q10)
-
-    std::map<std::string, uint32_t> chrsize;  // dxyWindow.cpp:155-170
-    if (!fixedsite) {
-        Text text;
-        if (!text.open(sizefile)) die(std::string("Unable to open sizefile: ") + sizefile);
-        Cursor c{text.begin(), text.end()};
-        while (c.p < c.end) {
-            auto name = c.token();
-            uint32_t len = 0;
-            if (name.first == name.second || !to_u32(c.token(), len) || len == 0)
-                die("Unable to correctly parse chromosome size file");
-            chrsize.insert({std::string(name.first, name.second), len});
-            c.next_line();
-        }
-    }
+    for (int i = 1; i < argc - 2; i += 2)
+        if (!dxy_option(opt, argv[i], argv[i + 1])) unknown_dxy_option(argv[i]);
+    check_dxy_options(opt);
+    const uint32_t W = opt.W, S = opt.S;
+    const int minind = opt.minind, fixedsite = opt.fixedsite, skip_missing = opt.skip_missing;
+    std::map<std::string, uint32_t> chrsize;
+    if (!fixedsite) chrsize = read_sizefile(opt.sizefile);
 
     PhaseTimer timer;
     DeviceOpener device;  // HIP start-up runs beside the parse; PGT_DEVICES=0,1,..: one context and host thread per GPU
@@ -496,7 +368,7 @@ int main(int argc, char **argv) {
         // inputs larger than the GPU (or PGT_MAX_RESIDENT_SITES): block by block — unless the site lists differ
         if (open1 && open2)
             if (const uint64_t resident = resident_limit(t1.begin(), t1.end(), 2 * (4 + 8 + 4), [&] { return device.get(); }, 2))
-                if (dxy_in_passes(device, t1, t2, argv[argc - 2], argv[argc - 1], W, S, minind, fixedsite, skip_missing, chrsize, resident, timer))
+                if (dxy_in_passes(device, t1, t2, argv[argc - 2], argv[argc - 1], opt, chrsize, resident, timer))
                     finish(timer);
         // large inputs: parse both files on the GPU, one after the other (one context, one thread); a file that
         // cannot be opened is left to the host path below, which reports Pop1's problems first
@@ -534,10 +406,8 @@ int main(int argc, char **argv) {
 
     // The sites common to both files, by (run, position).  Usual case first: both files list exactly the
     // same sites (ANGSD run on one site list) -> the parsed columns are used as they are, nothing is copied.
-    Runs runs;
-    std::vector<uint32_t> pos_v;
-    std::vector<double> p1_v, p2_v;
-    std::vector<int32_t> n1_v, n2_v;
+    DxySites synced;  // ... filled only where they do not
+    const Runs *runs_p = &synced.runs;
     const uint32_t *pos = nullptr;
     const double *p1 = nullptr, *p2 = nullptr;
     const int32_t *n1 = nullptr, *n2 = nullptr;
@@ -551,84 +421,38 @@ int main(int argc, char **argv) {
     const bool on_device = same_sites && m1.on_device && m2.on_device;  // frequencies and counts stay on the GPU
     if (same_sites) {
         if (!on_device) { fetch_columns(m1); fetch_columns(m2); }
-        runs = m1.runs;
+        runs_p = &m1.runs;
         pos = m1.pos.data(); p1 = m1.freq.data(); p2 = m2.freq.data(); n1 = m1.nind.data(); n2 = m2.nind.data();
         n_sites = m1.n;
-    } else if (sync_as_reference) {
-        fetch_columns(m1);
-        fetch_columns(m2);
-        std::string last_chr;
-        const auto pairs = pair_as_the_reference(m1, m2, last_chr);
-        if (pairs.empty()) {  // no site processed at all: the closing code alone (`:407-433`)
-            if (W > 0 && !fixedsite) {
-                auto it = chrsize.find(last_chr);
-                if (it == chrsize.end()) die("Unable to determine size for " + last_chr);  // dxyWindow.cpp:410-413
-                print_placeholder_chromosome(last_chr, it->second, W, S, skip_missing);
-            }
-            std::fprintf(W == 0 ? stdout : stderr, "0\t0\t0\n");
-            finish(timer);
-        }
-        size_t run1 = 0, end1 = m1.runs.len[0];
-        for (const auto &pr : pairs) {  // Pop1's line, Pop2's frequency and count beside it, under Pop1's chromosome name
-            while (pr.first >= end1) end1 += m1.runs.len[++run1];
-            const std::string &chr1 = m1.runs.name[run1];
-            pos_v.push_back(m1.pos[pr.first]);
-            p1_v.push_back(m1.freq[pr.first]); p2_v.push_back(m2.freq[pr.second]);
-            n1_v.push_back(m1.nind[pr.first]); n2_v.push_back(m2.nind[pr.second]);
-            runs.add(chr1.data(), chr1.data() + chr1.size());
-        }
-        pos = pos_v.data(); p1 = p1_v.data(); p2 = p2_v.data(); n1 = n1_v.data(); n2 = n2_v.data();
-        n_sites = pos_v.size();
     } else {
         fetch_columns(m1);
         fetch_columns(m2);
-        size_t r1 = 0, r2 = 0, o1 = 0, o2 = 0;
-        while (r1 < m1.runs.name.size() && r2 < m2.runs.name.size()) {
-            const std::string &chr1 = m1.runs.name[r1], &chr2 = m2.runs.name[r2];
-            if (chr1 != chr2) {  // skip the run that the other file does not have next
-                bool later_in_1 = false;
-                for (size_t k = r1 + 1; k < m1.runs.name.size() && !later_in_1; ++k) later_in_1 = m1.runs.name[k] == chr2;
-                if (later_in_1) { o1 += m1.runs.len[r1]; ++r1; } else { o2 += m2.runs.len[r2]; ++r2; }
-                continue;
-            }
-            size_t i = o1, j = o2;
-            const size_t e1 = o1 + m1.runs.len[r1], e2 = o2 + m2.runs.len[r2];
-            const size_t before = pos_v.size();
-            while (i < e1 && j < e2) {
-                if (m1.pos[i] < m2.pos[j]) ++i;
-                else if (m2.pos[j] < m1.pos[i]) ++j;
-                else {
-                    pos_v.push_back(m1.pos[i]);
-                    p1_v.push_back(m1.freq[i]); p2_v.push_back(m2.freq[j]);
-                    n1_v.push_back(m1.nind[i]); n2_v.push_back(m2.nind[j]);
-                    ++i; ++j;
+        if (sync_as_reference) {
+            std::string last_chr;
+            const auto pairs = pair_as_the_reference(m1, m2, last_chr);
+            if (pairs.empty()) {  // no site processed at all: the closing code alone (`:407-433`)
+                if (W > 0 && !fixedsite) {
+                    auto it = chrsize.find(last_chr);
+                    if (it == chrsize.end()) die("Unable to determine size for " + last_chr);  // dxyWindow.cpp:410-413
+                    print_placeholder_chromosome(last_chr, it->second, W, S, skip_missing);
                 }
+                print_dxy_total(pgt_dxy_total{}, W);
+                finish(timer);
             }
-            if (pos_v.size() > before) runs.add(chr1.data(), chr1.data() + chr1.size(), pos_v.size() - before);
-            o1 = e1; o2 = e2; ++r1; ++r2;
-        }
-        pos = pos_v.data(); p1 = p1_v.data(); p2 = p2_v.data(); n1 = n1_v.data(); n2 = n2_v.data();
-        n_sites = pos_v.size();
+            sites_of_pairs(m1, m2, pairs, synced);
+        } else
+            intersect_sites(m1, m2, synced);
+        pos = synced.pos.data(); p1 = synced.p1.data(); p2 = synced.p2.data(); n1 = synced.n1.data(); n2 = synced.n2.data();
+        n_sites = synced.pos.size();
     }
     if (n_sites == 0) die("dxyWindow: the two MAF files share no site");
+    const Runs &runs = *runs_p;
 
     SiteWindows sw;  // fixed-site windows: on the host, or on the device when there are very many (-stepsize 1)
     std::vector<pgt_win> &win = sw.win;
     if (W > 0) {
-        size_t n_win = 0;
-        if (fixedsite) {
-            sw.build(runs, W, S, [&] { return device.get(); }, &timer, multi);  // several GPUs shard a host table
-        } else {
-            std::vector<uint32_t> chr_len(runs.name.size());
-            for (size_t r = 0; r < runs.name.size(); ++r) {
-                auto it = chrsize.find(runs.name[r]);
-                if (it == chrsize.end()) die("Unable to determine size for " + runs.name[r]);  // dxyWindow.cpp:340-343
-                chr_len[r] = it->second;
-            }
-            check(pgt_build_windows_bp(pos, runs.len.data(), chr_len.data(), runs.len.size(), W, S, nullptr, 0, &n_win), nullptr);
-            win.resize(n_win);
-            check(pgt_build_windows_bp(pos, runs.len.data(), chr_len.data(), runs.len.size(), W, S, win.data(), win.size(), &n_win), nullptr);
-        }
+        if (fixedsite) sw.build(runs, W, S, [&] { return device.get(); }, &timer, multi);  // several GPUs shard a host table
+        else win = bp_windows(pos, runs, chr_lengths(runs, chrsize), W, S);
     }
 
     timer.lap("sync + table");
@@ -652,14 +476,7 @@ int main(int argc, char **argv) {
         check(pgt_dxy_reduce(ctx, pos, p1, p2, n1, n2, n_sites, minind, win.data(), win.size(), rows.data(), &tot), ctx);
     timer.lap("gpu reduce");
 
-    // chr start end dxy neffective nskip, unless -skip_missing drops the row (dxyWindow.cpp:189-191)
-    write_rows(n_rows, longest_name(runs) + 80, [&](size_t i, char *o) -> size_t {
-        if (!(rows[i].neff > 0 || !skip_missing)) return 0;
-        return put_row(o, runs.name[sw.tab ? sw.label(i) : win[i].label_run], {rows[i].start, rows[i].end}, rows[i].sum,
-                       {rows[i].neff, rows[i].nskip});
-    });
-    // genome-wide line: stdout for the global run, stderr beside windows (dxyWindow.cpp:429-433)
-    std::fprintf(W == 0 ? stdout : stderr, "%g\t%llu\t%llu\n", tot.sum, (unsigned long long)tot.neff,
-                 (unsigned long long)tot.nskip);
+    write_dxy_rows(rows.data(), n_rows, runs, [&](size_t i) { return sw.tab ? sw.label(i) : win[i].label_run; }, skip_missing);
+    print_dxy_total(tot, W);
     finish(timer);
 }

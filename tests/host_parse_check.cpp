@@ -13,20 +13,27 @@
 //   6. scan_runs_and_marks (first scan of the passes mode): rows, runs, end of the data, the byte marks, the position digests;
 //   6b. ScoreTable / read_chrlen (ihsWindow / xpehhWindow: locus-id prefix, score field, errors with line numbers);
 //   7. HostBuf (huge-page mappings for columns, rows and inflated text): alignment, size, every byte writable;
-//   8. resident_limit_for: which inputs are reduced in passes, and of how many sites.
+//   8. resident_limit_for: which inputs are reduced in passes, and of how many sites;
+//   9. dxy_common.h (dxyWindow / dxyWindowPops): the MAF row parser (columns bit for bit, refusals with their line numbers, the
+//      int32 clamp); intersect_sites against a brute-force model; pair_as_the_reference on identical and nested lists;
+//      print_placeholder_chromosome against a literal slot-by-slot loop; the options, their refusals (in a forked child:
+//      `die` exits the process) and the size file.
 #include <dirent.h>
+#include <sys/wait.h>
 
 #include <cinttypes>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <random>
 #include <string>
 #include <vector>
 
 #include "host_common.h"
 #include "extreme_common.h"
+#include "dxy_common.h"
 
 using namespace pgthost;
 
@@ -76,6 +83,85 @@ static void put_file(const std::string &path, const std::string &bytes) {
 static bool text_is(const std::string &path, const std::string &want) {
     Text t;
     return t.open(path.c_str()) && t.size() == want.size() && std::memcmp(t.begin(), want.data(), want.size()) == 0;
+}
+
+// f() in a forked child (`die` ends the process): what it wrote to `fd` (1 or 2), and its exit status
+template <class F>
+static std::string in_child(int fd, F f, int *status = nullptr) {
+    int pipefd[2];
+    if (pipe(pipefd) != 0) return "pipe failed";
+    std::fflush(stdout);
+    std::fflush(stderr);
+    const pid_t pid = fork();
+    if (pid == 0) {
+        close(pipefd[0]);
+        dup2(pipefd[1], fd);
+        f();
+        std::fflush(stdout);
+        _exit(0);
+    }
+    close(pipefd[1]);
+    std::string got;
+    char buf[4096];
+    for (ssize_t k; (k = read(pipefd[0], buf, sizeof buf)) > 0;) got.append(buf, (size_t)k);
+    close(pipefd[0]);
+    int st = 0;
+    waitpid(pid, &st, 0);
+    if (status) *status = WIFEXITED(st) ? WEXITSTATUS(st) : -1;
+    return got;
+}
+
+// a parsed MAF file from (chromosome, positions) lists; frequencies and counts tell the file and the row
+using SiteLists = std::vector<std::pair<std::string, std::vector<uint32_t>>>;
+static void fill_maf(MafTable &m, const SiteLists &lists, int file) {
+    size_t n = 0;
+    for (const auto &l : lists) n += l.second.size();
+    m.alloc(n);
+    m.n = n;
+    size_t i = 0;
+    for (const auto &l : lists)
+        for (uint32_t p : l.second) {
+            m.pos[i] = p;
+            m.freq[i] = (double)(i % 1000) / 1000.0 + (file == 1 ? 0.0 : 0.0005);
+            m.nind[i] = (int32_t)(file * 1000000 + (int)i);
+            m.runs.add(l.first.data(), l.first.data() + l.first.size());
+            ++i;
+        }
+}
+// the model of intersect_sites: one map (chromosome name, position) -> row per file; every key of both, in file 1's order
+struct ModelSites { std::vector<std::pair<size_t, size_t>> pairs; Runs runs; };
+static ModelSites model_intersection(const SiteLists &l1, const SiteLists &l2) {
+    std::map<std::pair<std::string, uint32_t>, size_t> in2;
+    size_t j = 0;
+    for (const auto &l : l2)
+        for (uint32_t p : l.second) in2[{l.first, p}] = j++;
+    ModelSites out;
+    size_t i = 0;
+    for (const auto &l : l1)
+        for (uint32_t p : l.second) {
+            auto it = in2.find({l.first, p});
+            if (it != in2.end()) {
+                out.pairs.emplace_back(i, it->second);
+                out.runs.add(l.first.data(), l.first.data() + l.first.size());
+            }
+            ++i;
+        }
+    return out;
+}
+static void check_intersection(const SiteLists &l1, const SiteLists &l2, size_t want_sites = ~(size_t)0) {
+    MafTable m1, m2;
+    fill_maf(m1, l1, 1);
+    fill_maf(m2, l2, 2);
+    DxySites s;
+    intersect_sites(m1, m2, s);
+    const ModelSites want = model_intersection(l1, l2);
+    if (want_sites != ~(size_t)0) CHECK(want.pairs.size() == want_sites);
+    CHECK(s.pos.size() == want.pairs.size() && s.p1.size() == s.pos.size() && s.p2.size() == s.pos.size() && s.n1.size() == s.pos.size() && s.n2.size() == s.pos.size());
+    CHECK(s.runs.name == want.runs.name && s.runs.len == want.runs.len);
+    for (size_t k = 0; k < want.pairs.size() && k < s.pos.size(); ++k) {
+        const size_t i = want.pairs[k].first, j = want.pairs[k].second;
+        CHECK(s.pos[k] == m1.pos[i] && s.p1[k] == m1.freq[i] && s.p2[k] == m2.freq[j] && s.n1[k] == m1.nind[i] && s.n2[k] == m2.nind[j]);
+    }
 }
 
 int main(int argc, char **argv) {
@@ -482,6 +568,197 @@ int main(int argc, char **argv) {
         CHECK(resident_limit_for((size_t)105e9, 35.0, 32, free_b, 2) > 0);           // an all-sites MAF pair of a 3-Gb genome
         CHECK(resident_limit_for((size_t)35e9, 35.0, 32, free_b, 2) == 0);
         CHECK(resident_limit_for((size_t)1 << 40, 8.0, 20, (size_t)1 << 20, 1) >= 1);  // never 0 when passes are needed
+    }
+    {   // 9a. the MAF row parser: chr pos major minor ref freq nind; one chunk and several (long alleles make 3000 lines > 1 MiB)
+        const size_t rows_m = 3000;
+        std::string maf;
+        std::vector<uint32_t> want_pos(rows_m);
+        std::vector<double> want_freq(rows_m);
+        std::vector<int32_t> want_nind(rows_m);
+        const std::string allele(120, 'A');
+        for (size_t i = 0; i < rows_m; ++i) {
+            char num[64];
+            want_pos[i] = (uint32_t)(i % 1000 * 4000000 + rng() % 4000000);
+            std::snprintf(num, sizeof num, "%.6f", (double)(rng() % 1000001) / 1e6);
+            want_freq[i] = std::strtod(num, nullptr);
+            want_nind[i] = (int32_t)(rng() % 4000) - 2000;
+            maf += "chr" + std::to_string(i / 1000 + 1) + "\t" + std::to_string(want_pos[i]) + "\t" + allele + "\t" + allele + "C\t" + allele + "\t" + num +
+                   "\t" + std::to_string(want_nind[i]) + "\n";
+        }
+        CHECK(maf.size() > (1u << 20));
+        for (int threads : {1, 5}) {
+            setenv("PGT_HOST_THREADS", std::to_string(threads).c_str(), 1);
+            MafTable m;
+            m.n = parse_table(maf.data(), maf.data() + maf.size(), m, m.runs, kMafWhat, "mem", 2);
+            CHECK(m.n == rows_m && m.runs.name == std::vector<std::string>({"chr1", "chr2", "chr3"}) && m.runs.len == std::vector<uint64_t>({1000, 1000, 1000}));
+            if (m.n == rows_m) {
+                CHECK(std::memcmp(m.pos.data(), want_pos.data(), rows_m * 4) == 0);
+                CHECK(std::memcmp(m.freq.data(), want_freq.data(), rows_m * 8) == 0);
+                CHECK(std::memcmp(m.nind.data(), want_nind.data(), rows_m * 4) == 0);
+            }
+        }
+        {   // a bad line in the second half of that table, parsed in several chunks: its line number counts the chunks before it
+            const size_t bad_row = 2345;
+            size_t at = 0;
+            for (size_t i = 0; i < bad_row; ++i) at = maf.find('\n', at) + 1;
+            std::string hurt = maf;
+            hurt.replace(hurt.find('\t', at) + 1, 1, "x");  // the first digit of the position
+            for (int threads : {1, 5}) {
+                setenv("PGT_HOST_THREADS", std::to_string(threads).c_str(), 1);
+                MafTable m;
+                std::string error;
+                (void)parse_table(hurt.data(), hurt.data() + hurt.size(), m, m.runs, kMafWhat, "mem", 2, &error);
+                CHECK(error == std::string(kMafWhat) + " on line " + std::to_string(bad_row + 2) + " of mem");
+            }
+        }
+        unsetenv("PGT_HOST_THREADS");
+        // refusals carry the line number (the table follows a header line: the first row is line 2); counts clamp to int32
+        std::vector<std::string> line(50);
+        for (size_t i = 0; i < line.size(); ++i) line[i] = "chr1\t" + std::to_string(i + 1) + "\tA\tC\tA\t0.25\t7\n";
+        auto parse_with = [&](size_t at, const std::string &bad, MafTable &m) {
+            std::string t, error;
+            for (size_t i = 0; i < line.size(); ++i) t += i == at ? bad : line[i];
+            m.n = parse_table(t.data(), t.data() + t.size(), m, m.runs, kMafWhat, "mem", 2, &error);
+            return error;
+        };
+        for (const char *bad : {"chr1\t37\tA\tC\tA\t-0.1\t7\n", "chr1\t37\tA\tC\tA\t1.0000001\t7\n", "chr1\t37\tA\tC\tA\tnan\t7\n", "chr1\t37\tA\tC\tA\t0.25\n",
+                                "chr1\tx37\tA\tC\tA\t0.25\t7\n"}) {
+            MafTable m;
+            CHECK(parse_with(36, bad, m) == std::string(kMafWhat) + " on line 38 of mem");
+        }
+        {
+            MafTable m;
+            CHECK(parse_with(0, "chr1\t1\tA\tC\tA\t0\t99999999999\n", m).empty() && m.n == 50 && m.nind[0] == INT32_MAX && m.freq[0] == 0.0);
+            MafTable m2;
+            CHECK(parse_with(49, "chr1\t50\tA\tC\tA\t1\t-99999999999\n", m2).empty() && m2.n == 50 && m2.nind[49] == INT32_MIN && m2.freq[49] == 1.0);
+        }
+    }
+    {   // 9b. intersect_sites against the brute-force model
+        const std::vector<uint32_t> a = {1, 5, 9, 12, 40}, inner = {5, 12}, odd = {2, 6, 10}, b = {100, 200, 300}, c = {7, 8, 9, 10};
+        check_intersection({{"A", a}, {"B", b}}, {{"A", a}, {"B", b}}, 8);                      // identical
+        check_intersection({{"A", a}, {"B", b}}, {{"A", inner}, {"B", {200}}}, 3);              // nested, either way round
+        check_intersection({{"A", inner}, {"B", {200}}}, {{"A", a}, {"B", b}}, 3);
+        check_intersection({{"A", a}}, {{"A", odd}}, 0);                                        // disjoint: empty
+        check_intersection({{"X", c}, {"A", a}, {"B", b}}, {{"A", a}, {"B", b}}, 8);            // a chromosome of one file only: front
+        check_intersection({{"A", a}, {"B", b}}, {{"X", c}, {"A", a}, {"B", b}}, 8);
+        check_intersection({{"A", a}, {"X", c}, {"B", b}}, {{"A", a}, {"B", b}}, 8);            // ... middle
+        check_intersection({{"A", a}, {"B", b}}, {{"A", a}, {"X", c}, {"B", b}}, 8);
+        check_intersection({{"A", a}, {"B", b}, {"X", c}}, {{"A", a}, {"B", b}}, 8);            // ... end
+        check_intersection({{"A", a}, {"B", b}}, {{"A", a}, {"B", b}, {"X", c}}, 8);
+        check_intersection({{"A", a}, {"B", b}, {"C", c}}, {{"A", inner}, {"B", {150}}, {"C", c}}, 6);  // B keeps no common site: no run
+        {
+            MafTable m1, m2;
+            fill_maf(m1, {{"A", a}, {"B", b}, {"C", c}}, 1);
+            fill_maf(m2, {{"A", inner}, {"B", {150}}, {"C", c}}, 2);
+            DxySites s;
+            intersect_sites(m1, m2, s);
+            CHECK(s.runs.name == std::vector<std::string>({"A", "C"}) && s.runs.len == std::vector<uint64_t>({2, 4}));
+        }
+        for (int trial = 0; trial < 60; ++trial) {  // random subsets of one universe of 1 ... 5 chromosomes
+            SiteLists l[2];
+            const int n_chr = 1 + (int)(rng() % 5);
+            for (int ch = 0; ch < n_chr; ++ch) {
+                std::vector<uint32_t> p[2];
+                const int keep[2] = {(int)(rng() % 4), (int)(rng() % 4)};  // 0: the chromosome is missing in that file
+                for (uint32_t pos = 1 + rng() % 3; pos < 600; pos += 1 + rng() % 3)
+                    for (int f = 0; f < 2; ++f)
+                        if (keep[f] && rng() % 4 < (uint64_t)keep[f] + 1) p[f].push_back(pos);
+                for (int f = 0; f < 2; ++f)
+                    if (!p[f].empty()) l[f].push_back({"scaffold_" + std::to_string(ch), p[f]});
+            }
+            check_intersection(l[0], l[1]);
+        }
+    }
+    {   // 9c. pair_as_the_reference where the reference is well defined: identical and nested lists (no position
+        //     twice in a file, every chromosome's first site in both files) — the pairs are the intersection's
+        for (int trial = 0; trial < 40; ++trial) {
+            SiteLists full, part;
+            const int n_chr = 1 + (int)(rng() % 5);
+            for (int ch = 0; ch < n_chr; ++ch) {
+                std::vector<uint32_t> p, q;
+                for (uint32_t pos = (uint32_t)ch * 100000 + 1 + rng() % 5; p.size() < 5 + rng() % 200; pos += 1 + rng() % 9) {
+                    if (p.empty() || trial % 3 == 0 || rng() % 3) q.push_back(pos);
+                    p.push_back(pos);
+                }
+                full.push_back({"chr" + std::to_string(ch + 1), p});
+                part.push_back({"chr" + std::to_string(ch + 1), q});
+            }
+            for (int way = 0; way < 2; ++way) {
+                const SiteLists &l1 = way ? part : full, &l2 = way ? full : part;
+                MafTable m1, m2;
+                fill_maf(m1, l1, 1);
+                fill_maf(m2, l2, 2);
+                std::string last_chr;
+                const auto pairs = pair_as_the_reference(m1, m2, last_chr);
+                const ModelSites want = model_intersection(l1, l2);
+                CHECK(pairs == want.pairs);
+                CHECK(!want.runs.name.empty() && last_chr == want.runs.name.back());
+                DxySites s, t;
+                sites_of_pairs(m1, m2, pairs, s);
+                intersect_sites(m1, m2, t);
+                CHECK(s.runs.name == t.runs.name && s.runs.len == t.runs.len && s.pos == t.pos && s.p1 == t.p1 && s.p2 == t.p2 && s.n1 == t.n1 && s.n2 == t.n2);
+            }
+        }
+    }
+    {   // 9d. print_placeholder_chromosome against the reference's closing loop taken literally: one position at a time goes into a
+        //     buffer of W slots, a full buffer is printed and S slots leave it
+        for (uint64_t W : {2, 4, 10})
+            for (uint64_t S : {(uint64_t)1, W / 2, W})
+                for (uint64_t len : {(uint64_t)1, W - 1, W, W + 1, 3 * W + 2})
+                    for (int skip_missing : {0, 1}) {
+                        std::string want;
+                        auto row = [&](uint64_t first, uint64_t last) { want += "chrP\t" + std::to_string(first) + "\t" + std::to_string(last) + "\t0\t0\t0\n"; };
+                        uint64_t first = 1, held = 0;
+                        for (uint64_t p = 1; p <= len; ++p) {
+                            if (held == W) { row(first, first + W - 1); first += S; held -= S; }
+                            ++held;
+                        }
+                        if (held > W - S && held <= W) row(first, first + held - 1);
+                        if (skip_missing) want.clear();
+                        int status = -1;
+                        const std::string got = in_child(1, [&] { print_placeholder_chromosome("chrP", len, W, S, skip_missing); }, &status);
+                        CHECK(status == 0 && got == want);
+                    }
+    }
+    {   // 9e. the options: an accepted list, and every refusal with its text (in a child: die() exits with 255)
+        DxyOptions o;
+        CHECK(o.W == 0 && o.S == 0 && o.minind == 1 && o.fixedsite == 0 && o.skip_missing == 0 && o.sizefile == nullptr);
+        const char *list[] = {"-winsize", "5000", "-stepsize", "1000", "-minind", "3", "-fixedsite", "1", "-sizefile", "sizes.tsv", "-skip_missing", "1"};
+        for (int k = 0; k < 12; k += 2) CHECK(dxy_option(o, list[k], list[k + 1]));
+        CHECK(o.W == 5000 && o.S == 1000 && o.minind == 3 && o.fixedsite == 1 && o.skip_missing == 1 && std::string(o.sizefile) == "sizes.tsv");
+        CHECK(!dxy_option(o, "-out", "x") && !dxy_option(o, "-winsizes", "1") && !dxy_option(o, "winsize", "1"));
+        CHECK(o.W == 5000 && o.S == 1000);
+        int status = 0;
+        CHECK(in_child(2, [&] { check_dxy_options(o); }, &status).empty() && status == 0);
+        auto refused = [&](auto set, const char *text) {
+            DxyOptions bad;
+            bad.fixedsite = 1;
+            set(bad);
+            int st = 0;
+            const std::string got = in_child(2, [&] { check_dxy_options(bad); }, &st);
+            CHECK(st == 255 && got == std::string(text) + "\n");
+        };
+        refused([](DxyOptions &b) { b.W = 10; }, "Must specify a -stepsize > 0 when -winsize is > 0");
+        refused([](DxyOptions &b) { b.fixedsite = 0; }, "Must supply size file unless -fixedsite 1");
+        refused([](DxyOptions &b) { b.W = 10; b.S = 11; }, "-stepsize must not exceed -winsize");
+        refused([](DxyOptions &b) { b.fixedsite = 0; b.sizefile = "s"; }, "-winsize 0 (global dxy) requires -fixedsite 1");
+        refused([](DxyOptions &b) { b.W = 10; b.fixedsite = 0; }, "Must specify a -stepsize > 0 when -winsize is > 0");  // the first of two
+        CHECK(in_child(2, [&] { DxyOptions b; dxy_option(b, "-minind", "0"); }, &status) == "-minind must be at least 1\n" && status == 255);
+        CHECK(in_child(2, [&] { unknown_dxy_option("-windowsize"); }, &status) == "Unknown command: -windowsize\n" && status == 255);
+        // the size file keeps a name's first entry; a chromosome without a size is refused by name
+        const std::string dirs = argc > 3 ? argv[3] : "/tmp";
+        put_file(dirs + "/sizes.tsv", "chr1\t1000\nchr2 2500\nchr1\t7\n");
+        const auto sizes = read_sizefile((dirs + "/sizes.tsv").c_str());
+        CHECK(sizes.size() == 2 && sizes.at("chr1") == 1000 && sizes.at("chr2") == 2500);
+        put_file(dirs + "/sizes.tsv", "chr1\t1000\nchr2\t0\n");
+        CHECK(in_child(2, [&] { (void)read_sizefile((dirs + "/sizes.tsv").c_str()); }, &status) == "Unable to correctly parse chromosome size file\n" && status == 255);
+        CHECK(in_child(2, [&] { (void)read_sizefile((dirs + "/no_such_sizes.tsv").c_str()); }, &status) == "Unable to open sizefile: " + dirs + "/no_such_sizes.tsv\n" && status == 255);
+        std::remove((dirs + "/sizes.tsv").c_str());
+        Runs r;
+        for (const char *nm : {"chr2", "chr1"}) r.add(nm, nm + 4, 3);
+        CHECK(chr_lengths(r, sizes) == std::vector<uint32_t>({2500, 1000}));
+        r.add("chrUn", "chrUn" + 5);
+        CHECK(in_child(2, [&] { (void)chr_lengths(r, sizes); }, &status) == "Unable to determine size for chrUn\n" && status == 255);
     }
     std::printf(fails ? "host_parse_check: %d FAILURES\n" : "host_parse_check: all equal (%d)\n", fails);
     return fails ? 1 : 0;
