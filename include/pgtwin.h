@@ -39,7 +39,8 @@ extern "C" {
 /* 6 (round 6): pgt_prepare_host_io added; the host-buffer entry points stage their uploads through a per-context pinned
  * ring and keep a per-context workspace (no argument list changed).
  * Still 6: pgt_dxy_pops_tree_bytes / pgt_dxy_pops_reduce_dev / pgt_dxy_pops_reduce added (additive: nothing that existed changed).
- * Still 6: pgt_align_segments / pgt_align_workspace_bytes / pgt_sites_align / pgt_gather_dev added (additive as well). */
+ * Still 6: pgt_align_segments / pgt_align_workspace_bytes / pgt_sites_align / pgt_gather_dev added (additive as well).
+ * Still 6: pgt_fst_total, pgt_fst_pops_tree_bytes / pgt_fst_pops_reduce_dev / pgt_fst_pops_reduce added (additive as well). */
 #define PGT_ABI_VERSION 6
 
 enum {
@@ -86,6 +87,11 @@ typedef struct { /* dxyWindow.cpp:429-433 genome-wide line */
     double sum;
     uint64_t neff, nskip;
 } pgt_dxy_total;
+
+typedef struct { /* genomeFst (betaAFOutlier.R:440-446) of one pair over its counted sites: fst = asum / bsum */
+    double asum, bsum;
+    uint64_t neff, nskip;
+} pgt_fst_total;
 
 /* ---- context ------------------------------------------------------------------------- */
 /* device: HIP ordinal, or -1 for the current device.  Fails (NULL, message via
@@ -218,6 +224,36 @@ int pgt_dxy_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *con
 int pgt_dxy_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq,
                         const int32_t *const *nind, uint32_t n_pops, uint64_t n, int minind,
                         const pgt_win *win, uint64_t n_win, pgt_dxy_row *out, pgt_dxy_total *tot);
+
+/* ---- FST of all population pairs from per-population MAF columns ------------------------------ */
+/* fstWindow's window rows for ALL pairs i<j of n_pops populations from each population's own (freq, nInd) columns — what K
+ * ANGSD .mafs files hold — over ONE position column and ONE window table, in one pass (12 B/site/population).  Unlike
+ * pgt_fst_af_reduce_dev (one scalar sample size per population) the sample sizes are the PER-SITE nInd, and a site counts
+ * for a pair only when both populations have at least minind individuals there:
+ *   counting   nind_i[s] >= minind && nind_j[s] >= minind (dxyWindow.cpp:381, as pgt_dxy_pops_reduce_dev); minind >= 1 is
+ *              required (PGT_EARG otherwise): it makes npool >= 2 and n1 n2 > 0 at every counted site
+ *   per site   the two columns of WCFst() (betaAFOutlier.R:405-417) with n1 = nind_i[s], n2 = nind_j[s], f1 = freq_i[s],
+ *              f2 = freq_j[s]: npool = n1+n2; alpha_k = 2 f_k (1-f_k); b = (n1 alpha1 + n2 alpha2)/(npool-1);
+ *              a = (4 n1 (f1-fpool)^2 + 4 n2 (f2-fpool)^2 - b)/(4 n1 n2/npool), evaluated as (f1-f2)^2 - b npool/(4 n1 n2)
+ *   row        asum = Σa, bsum = Σ(a+b) over the window's counted sites, n = their number (nskip = (hi - lo) - n),
+ *              fst = bsum != 0 ? asum/bsum : 0 (fstWindow.cpp:85); start / end / mid as pgt_fst_reduce_dev fills them
+ *   tot        DEVICE array of n_pairs genome-wide lines (genomeFst, betaAFOutlier.R:440-446, over the counted sites), or
+ *              NULL; n_win == 0 with tot: the global-only form
+ *   tree       pgt_fst_pops_tree_bytes(n_pops, n) bytes (0 for n_pops outside 2 ... 8).    2 <= n_pops <= 8, n < 2^32.
+ * Arguments, alignment, the order of the pairs and of the rows, graph capture and the hints: those of
+ * pgt_dxy_pops_reduce_dev.  Rows of a pair do not depend, bit for bit, on the other populations' columns or on the other
+ * rows of the table.  Sums are added in a fixed order (bitwise reproducible); against an exact evaluation of the lines
+ * above they stay within 1e-9 relative + 1e-12.  Parity note: the reference side is an R function with no runnable
+ * oracle here (parity unpinned, as for pgt_fst_af_reduce_dev); the rows are held to an exact-rational evaluation.
+ * Host-buffer form: columns (host arrays of n_pops HOST pointers), table, rows and the n_pairs totals in host memory. */
+size_t pgt_fst_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites);
+int pgt_fst_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq,
+                            const int32_t *const *nind, uint32_t n_pops, uint64_t n, int minind,
+                            const pgt_win *win, uint64_t n_win, pgt_fst_row *out, size_t out_bytes,
+                            pgt_fst_total *tot, void *tree, size_t tree_bytes, void *stream);
+int pgt_fst_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq,
+                        const int32_t *const *nind, uint32_t n_pops, uint64_t n, int minind,
+                        const pgt_win *win, uint64_t n_win, pgt_fst_row *out, pgt_fst_total *tot);
 
 /* ---- the sites common to K files, aligned on the device ------------------------------------------ */
 /* Replaces the two-file synchronisation of dxyWindow.cpp:315-331 (one current line per file; the file that is behind reads

@@ -29,6 +29,7 @@ HET_ROW_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("mid", "<u4"), ("no
 DXY_ROW_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("neff", "<u4"), ("nskip", "<u4"),
                           ("sum", "<f8")])
 DXY_TOTAL_DTYPE = np.dtype([("sum", "<f8"), ("neff", "<u8"), ("nskip", "<u8")])
+FST_TOTAL_DTYPE = np.dtype([("asum", "<f8"), ("bsum", "<f8"), ("neff", "<u8"), ("nskip", "<u8")])
 EXT_ROW_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("nsites", "<u4"), ("nbig", "<u4"),
                           ("position", "<u4"), ("pad_", "<u4"), ("value", "<f8")])
 SHARD_DTYPE = np.dtype([("win_begin", "<u8"), ("win_end", "<u8"), ("site_lo", "<u8"), ("site_hi", "<u8")])
@@ -37,7 +38,7 @@ SEG_DTYPE = np.dtype([("off", "<u8"), ("len", "<u8")])  # pgt_seg: the rows of o
 assert WIN_DTYPE.itemsize == 32 and FST_ROW_DTYPE.itemsize == 40 and HET_ROW_DTYPE.itemsize == 32
 assert EXT_ROW_DTYPE.itemsize == 32
 assert DXY_ROW_DTYPE.itemsize == 24 and DXY_TOTAL_DTYPE.itemsize == 24 and SHARD_DTYPE.itemsize == 32
-assert SEG_DTYPE.itemsize == 16
+assert SEG_DTYPE.itemsize == 16 and FST_TOTAL_DTYPE.itemsize == 32
 
 # every symbol include/pgtwin.h declares (tests/test_abi.py checks the list against the header)
 SYMBOLS = [
@@ -54,6 +55,7 @@ SYMBOLS = [
     "pgt_fst_reduce_tab", "pgt_het_reduce_tab", "pgt_dxy_reduce_tab",
     "pgt_dxy_pops_tree_bytes", "pgt_dxy_pops_reduce_dev", "pgt_dxy_pops_reduce",
     "pgt_align_segments", "pgt_align_workspace_bytes", "pgt_sites_align", "pgt_gather_dev",
+    "pgt_fst_pops_tree_bytes", "pgt_fst_pops_reduce_dev", "pgt_fst_pops_reduce",
 ]
 PGT_TOK_CHR, PGT_TOK_SKIP, PGT_TOK_U32, PGT_TOK_F64, PGT_TOK_I8, PGT_TOK_I32, PGT_TOK_FREQ, PGT_TOK_CHR_PREFIX = range(8)
 
@@ -128,6 +130,10 @@ def load() -> C.CDLL:
     lib.pgt_dxy_pops_tree_bytes.argtypes = [u32, u64]
     lib.pgt_dxy_pops_reduce_dev.argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, u64, vp, sz, vp, vp, sz, vp]
     lib.pgt_dxy_pops_reduce.argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, u64, vp, vp]
+    lib.pgt_fst_pops_tree_bytes.restype = sz
+    lib.pgt_fst_pops_tree_bytes.argtypes = [u32, u64]
+    lib.pgt_fst_pops_reduce_dev.argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, u64, vp, sz, vp, vp, sz, vp]
+    lib.pgt_fst_pops_reduce.argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, u64, vp, vp]
     lib.pgt_align_segments.argtypes = [vp, vp, vp, u32, vp, sz, C.POINTER(sz)]
     lib.pgt_align_workspace_bytes.restype = sz
     lib.pgt_align_workspace_bytes.argtypes = [u32, u64]

@@ -19,8 +19,8 @@ BIN = os.path.join(PKG, "bin")
 LIB = os.path.join(PKG, "libpgtwin.so")
 FLAGS = os.path.join(PKG, "libpgtwin.flags")
 
-LIB_SOURCES = ["pgt_kernels.hip", "pgt_af_kernels.hip", "pgt_dxy_pops_kernels.hip", "pgt_align_kernels.hip", "pgt_ingest.hip", "pgt_api.cpp", "pgt_windows.cpp"]
-HOST_TOOLS = ["fstWindow", "hetWindow", "dxyWindow", "dxyWindowPops", "ihsWindow", "xpehhWindow"]
+LIB_SOURCES = ["pgt_kernels.hip", "pgt_af_kernels.hip", "pgt_dxy_pops_kernels.hip", "pgt_fst_pops_kernels.hip", "pgt_align_kernels.hip", "pgt_ingest.hip", "pgt_api.cpp", "pgt_windows.cpp"]
+HOST_TOOLS = ["fstWindow", "hetWindow", "dxyWindow", "dxyWindowPops", "fstWindowPops", "ihsWindow", "xpehhWindow"]
 
 
 def _hipcc() -> str:
@@ -100,7 +100,7 @@ def build_hosts(force: bool = False) -> list[str]:
     """The retained C++ hosts: same argv and TSV as the reference tools, reduction in libpgtwin."""
     os.makedirs(BIN, exist_ok=True)
     out = []
-    common = [os.path.join(HOST, h) for h in ("host_common.h", "extreme_common.h", "site_common.h", "dxy_common.h")] + [os.path.join(ROOT, "include", "pgtwin.h"), LIB]
+    common = [os.path.join(HOST, h) for h in ("host_common.h", "extreme_common.h", "site_common.h", "dxy_common.h", "pops_common.h")] + [os.path.join(ROOT, "include", "pgtwin.h"), LIB]
     for tool in HOST_TOOLS:
         src = os.path.join(HOST, tool + "_main.cpp")
         if not os.path.exists(src):

@@ -371,7 +371,8 @@ pgt_ctx *pgt_open(int device) {
         ~Restore() { if (dev >= 0 && dev != ctx_dev) (void)hipSetDevice(dev); }
     } restore{caller_device, device};
     std::string init_err;
-    if (init_kernels(&init_err) != PGT_OK || init_af_kernels(&init_err) != PGT_OK || init_dxy_pops_kernels(&init_err) != PGT_OK) {
+    if (init_kernels(&init_err) != PGT_OK || init_af_kernels(&init_err) != PGT_OK || init_dxy_pops_kernels(&init_err) != PGT_OK ||
+        init_fst_pops_kernels(&init_err) != PGT_OK) {
         set_global_error("pgt_open: " + init_err);
         return nullptr;
     }
@@ -618,6 +619,43 @@ int pgt_dxy_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *con
                            ctx->hints);
 }
 
+size_t pgt_fst_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites) {
+    if (n_pops < 2 || n_pops > (uint32_t)kFstPopsMaxPops) return 0;
+    return fst_pops_tree_view(tree_layout(PGT_STAT_FST, n_sites), (int)(n_pops * (n_pops - 1) / 2), nullptr, 0).bytes;
+}
+
+int pgt_fst_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind,
+                            uint32_t n_pops, uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_fst_row *out,
+                            size_t out_bytes, pgt_fst_total *tot, void *tree, size_t tree_bytes, void *stream) {
+    PGT_USE_DEVICE(ctx);
+    if (n_pops < 2 || n_pops > (uint32_t)kFstPopsMaxPops) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: n_pops must be 2 ... 8");
+    if (minind < 1) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: minind must be at least 1");  // npool >= 2, n1 n2 > 0 at every counted site
+    if (n == 0 && n_win == 0 && !tot) return PGT_OK;
+    if (!freq) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: freq is NULL");
+    if (!nind) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: nind is NULL");
+    if (!tree) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: tree is NULL");
+    if (n_win && !win) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: win is NULL");
+    if (n_win && !out) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: out is NULL");
+    if (n_win && n && !pos) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: pos is NULL");  // windows without PGT_WIN_COORDS read pos[lo], pos[hi-1]
+    for (uint32_t k = 0; k < n_pops; ++k) {
+        if (!freq[k]) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: freq[" + std::to_string(k) + "] is NULL");
+        if (!nind[k]) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: nind[" + std::to_string(k) + "] is NULL");
+        if (!aligned16(freq[k])) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: freq[" + std::to_string(k) + "] is not 16-byte aligned");
+        if (!aligned16(nind[k])) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: nind[" + std::to_string(k) + "] is not 16-byte aligned");
+    }
+    if (n >= (1ull << 32)) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: n: at most 2^32-1 sites per call");
+    if (!aligned16(tree)) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: tree is not 16-byte aligned");
+    if (tree_bytes < pgt_fst_pops_tree_bytes(n_pops, n))
+        return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: tree_bytes too small (" + std::to_string(tree_bytes) + " bytes, " +
+                                           std::to_string(pgt_fst_pops_tree_bytes(n_pops, n)) + " needed)");
+    const uint64_t n_pairs = (uint64_t)n_pops * (n_pops - 1) / 2;
+    if (n_win > UINT64_MAX / n_pairs) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: n_pairs * n_win overflows");
+    if (int rc = room_check(ctx, "pgt_fst_pops_reduce: out_bytes", n_pairs * n_win, sizeof(pgt_fst_row), out_bytes)) return rc;
+    const EvSet e = events_for(ctx);
+    return launch_fst_pops(pos, freq, nind, n_pops, n, minind, win, n_win, out, tot, tree, stream, e.b0, e.b1, e.q1, &ctx->error,
+                           ctx->hints);
+}
+
 size_t pgt_align_workspace_bytes(uint32_t n_files, uint64_t n_rows_file0) {
     if (n_files < 2 || n_files > (uint32_t)kAlignMaxFiles) return 0;
     return align_layout(n_files, n_rows_file0).bytes;
@@ -822,9 +860,9 @@ namespace {
 // What every *_cols entry point does around its device call: window table up (cached workspace), rows and tree from the
 // cached workspace, kernels, rows down.  `run` gets (device windows, device rows, tree, tree bytes, device total or NULL).
 // `tables` row tables of n_win rows each (pair-major) and as many totals where `tot` is given; tb = the tree's bytes.
-template <class Row, class Run>
+template <class Row, class Tot, class Run>
 int reduce_tables_with_workspace(pgt_ctx *ctx, const char *who, size_t tb, uint64_t tables, uint64_t n, const pgt_win *win, uint64_t n_win,
-                                 Row *out, size_t out_bytes, pgt_dxy_total *tot, Run run) {
+                                 Row *out, size_t out_bytes, Tot *tot, Run run) {
     ApiTrace trace(who);
     if (n_win > UINT64_MAX / tables) return ctx_fail(ctx, PGT_EARG, std::string(who) + ": the number of rows overflows");
     const uint64_t n_rows = tables * n_win;
@@ -836,18 +874,18 @@ int reduce_tables_with_workspace(pgt_ctx *ctx, const char *who, size_t tb, uint6
     if (int rc = workspace(ctx, HostIo::kRows, n_rows * sizeof(Row), &dout)) return rc;
     if (int rc = workspace(ctx, HostIo::kTree, tb, &dtree)) return rc;
     if (tot)
-        if (int rc = workspace(ctx, HostIo::kTot, tables * sizeof(pgt_dxy_total), &dtot)) return rc;
+        if (int rc = workspace(ctx, HostIo::kTot, tables * sizeof(Tot), &dtot)) return rc;
     trace.lap("workspace");
     if (n_win)
         if (int rc = hip_check(ctx, hipMemcpy(dwin, win, n_win * sizeof(pgt_win), hipMemcpyHostToDevice), "upload windows")) return rc;
     trace.lap("upload windows", n_win * sizeof(pgt_win));
-    if (int rc = run(static_cast<const pgt_win *>(dwin), static_cast<Row *>(dout), dtree, tb, static_cast<pgt_dxy_total *>(dtot))) return rc;
+    if (int rc = run(static_cast<const pgt_win *>(dwin), static_cast<Row *>(dout), dtree, tb, static_cast<Tot *>(dtot))) return rc;
     if (int rc = hip_check(ctx, hipStreamSynchronize(nullptr), "kernels")) return rc;
     trace.lap("kernels");
     if (n_win)
         if (int rc = hip_check(ctx, hipMemcpy(out, dout, n_rows * sizeof(Row), hipMemcpyDeviceToHost), "download rows")) return rc;
     if (tot)
-        if (int rc = hip_check(ctx, hipMemcpy(tot, dtot, tables * sizeof(pgt_dxy_total), hipMemcpyDeviceToHost), "download total")) return rc;
+        if (int rc = hip_check(ctx, hipMemcpy(tot, dtot, tables * sizeof(Tot), hipMemcpyDeviceToHost), "download total")) return rc;
     trace.lap("download rows", n_rows * sizeof(Row));
     return PGT_OK;
 }
@@ -989,6 +1027,38 @@ int pgt_dxy_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *
         [&](const pgt_win *dw, pgt_dxy_row *dr, void *tree, size_t tb, pgt_dxy_total *dtot) {
             return pgt_dxy_pops_reduce_dev(ctx, static_cast<uint32_t *>(dpos.p), pf, pn, n_pops, n, minind, dw, n_win, dr,
                                            (size_t)(n_pairs * n_win) * sizeof(pgt_dxy_row), dtot, tree, tb, nullptr);
+        });
+}
+
+/* FST of all pairs from per-population (freq, nInd) columns: the host-buffer form, as pgt_dxy_pops_reduce */
+int pgt_fst_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
+                        uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_fst_row *out, pgt_fst_total *tot) {
+    PGT_USE_DEVICE(ctx);
+    if (n_pops < 2 || n_pops > (uint32_t)kFstPopsMaxPops) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: n_pops must be 2 ... 8");
+    if (minind < 1) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: minind must be at least 1");
+    if (!freq || !nind || (n && !pos) || (n_win && (!win || !out))) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: NULL argument");
+    for (uint32_t k = 0; k < n_pops; ++k)
+        if (n && (!freq[k] || !nind[k])) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: NULL column");
+    ApiTrace trace("pgt_fst_pops_reduce");
+    const uint64_t n_pairs = (uint64_t)n_pops * (n_pops - 1) / 2;
+    if (n_win > UINT64_MAX / n_pairs / sizeof(pgt_fst_row)) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: n_pairs * n_win overflows");
+    DevBuf dpos, df[kFstPopsMaxPops], dn[kFstPopsMaxPops];
+    UploadJob jobs[1 + 2 * kFstPopsMaxPops];
+    int n_jobs = 0;
+    jobs[n_jobs++] = {&dpos, pos, n * sizeof(uint32_t), "upload pos"};
+    for (uint32_t k = 0; k < n_pops; ++k) {
+        jobs[n_jobs++] = {&df[k], freq[k], n * sizeof(double), "upload freq"};
+        jobs[n_jobs++] = {&dn[k], nind[k], n * sizeof(int32_t), "upload nind"};
+    }
+    if (int rc = upload_columns(ctx, jobs, n_jobs, trace)) return rc;
+    const double *pf[kFstPopsMaxPops];
+    const int32_t *pn[kFstPopsMaxPops];
+    for (uint32_t k = 0; k < n_pops; ++k) { pf[k] = static_cast<double *>(df[k].p); pn[k] = static_cast<int32_t *>(dn[k].p); }
+    return reduce_tables_with_workspace<pgt_fst_row>(ctx, "pgt_fst_pops_reduce", pgt_fst_pops_tree_bytes(n_pops, n), n_pairs, n, win, n_win, out,
+        (size_t)(n_pairs * n_win) * sizeof(pgt_fst_row), tot,
+        [&](const pgt_win *dw, pgt_fst_row *dr, void *tree, size_t tb, pgt_fst_total *dtot) {
+            return pgt_fst_pops_reduce_dev(ctx, static_cast<uint32_t *>(dpos.p), pf, pn, n_pops, n, minind, dw, n_win, dr,
+                                           (size_t)(n_pairs * n_win) * sizeof(pgt_fst_row), dtot, tree, tb, nullptr);
         });
 }
 

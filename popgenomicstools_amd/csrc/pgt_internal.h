@@ -167,6 +167,43 @@ inline DxyPopsTree dxy_pops_tree_view(const TreeLayout &t, int n_pairs, void *tr
     return v;
 }
 
+// ---- FST of all population pairs from per-population (freq, nInd) columns (pgt_fst_pops_kernels.hip) ----------------------
+// The shape of DxyPopsTree with two sums per pair: a node is 2 P doubles (Σa of pair 0 .. P-1, then Σ(a+b) of pair 0 .. P-1)
+// and P u32 (neff); a level holds the two arrays node-major.  Behind the levels one {Σa, Σ(a+b), neff} per pair and build wave.
+constexpr int kFstPopsMaxPops = 8;
+constexpr int kFstPopsLeafPieces = 4;  // 128-site pieces per level-1 node
+struct FstPopsTree {
+    char *base;
+    size_t sum_off[kMaxLevels];  // byte offset of level slot k: 2 P doubles per node
+    size_t cnt_off[kMaxLevels];  // ... P u32 per node
+    size_t part_sum, part_cnt;   // [build wave][2 P] doubles / [build wave][P] u32
+    size_t bytes;
+    int n_levels;
+    int n_pairs;
+    uint32_t n_partials;         // build waves that left a partial (0: no sites)
+};
+inline FstPopsTree fst_pops_tree_view(const TreeLayout &t, int n_pairs, void *tree, int levels) {
+    FstPopsTree v{};
+    v.base = static_cast<char *>(tree);
+    v.n_levels = levels;
+    v.n_pairs = n_pairs;
+    auto pad = [](size_t b) { return ((b + 255) / 256) * 256; };
+    size_t off = 0;
+    for (int k = 0; k < t.n_levels; ++k) {
+        const uint64_t nodes = k == 0 ? t.count[0] / kFstPopsLeafPieces : t.count[k];
+        v.sum_off[k] = off;
+        off += pad(nodes * (size_t)n_pairs * 16);
+        v.cnt_off[k] = off;
+        off += pad(nodes * (size_t)n_pairs * 4);
+    }
+    v.part_sum = off;
+    off += pad((size_t)kMaxBuildWaves * n_pairs * 16);
+    v.part_cnt = off;
+    off += pad((size_t)kMaxBuildWaves * n_pairs * 4);
+    v.bytes = off;
+    return v;
+}
+
 // Speed-only hints of a context (pgt_set_max_window, pgt_set_window_step); 0 = unknown.
 struct Hints {
     uint64_t max_window = 0;   // longest window in sites: tree levels with larger nodes are not built
@@ -230,6 +267,12 @@ int launch_dxy_pops(const uint32_t *pos, const double *const *freq, const int32_
                     void *tree, void *stream, void *ev_build0, void *ev_build1, void *ev_query1, std::string *err,
                     const Hints &hints);
 
+// pgt_fst_pops_kernels.hip: tot = n_pairs device totals or NULL; minind >= 1 (checked by the caller)
+int launch_fst_pops(const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
+                    uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_fst_row *out, pgt_fst_total *tot,
+                    void *tree, void *stream, void *ev_build0, void *ev_build1, void *ev_query1, std::string *err,
+                    const Hints &hints);
+
 // pgt_align_kernels.hip: the sites common to K position columns (pgt_sites_align) and the gather behind it.
 // The workspace, every part 256-byte aligned: the plan (segments as u32 pairs, first tile per chromosome), the first output
 // row per chromosome, per tile of 1024 pivot rows its count and first output row, and per file k >= 1 the row found for
@@ -274,6 +317,7 @@ size_t ingest_column_bytes(const pgt_ingest *ing, int token);  // rows * element
 int init_kernels(std::string *err);     // pgt_kernels.hip: one-time kernel attributes (called by pgt_open)
 int init_af_kernels(std::string *err);  // pgt_af_kernels.hip
 int init_dxy_pops_kernels(std::string *err);  // pgt_dxy_pops_kernels.hip
+int init_fst_pops_kernels(std::string *err);  // pgt_fst_pops_kernels.hip
 
 // thread-local message for the ctx-less entry points
 void set_global_error(const std::string &msg);

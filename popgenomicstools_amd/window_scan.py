@@ -20,7 +20,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import (DXY_ROW_DTYPE, DXY_TOTAL_DTYPE, EXT_ROW_DTYPE, FST_ROW_DTYPE, HET_ROW_DTYPE, PGT_EXT_IHS,
+from ._lib import (DXY_ROW_DTYPE, DXY_TOTAL_DTYPE, EXT_ROW_DTYPE, FST_ROW_DTYPE, FST_TOTAL_DTYPE, HET_ROW_DTYPE, PGT_EXT_IHS,
                    PGT_EXT_XP_MAX, PGT_EXT_XP_MIN, PGT_STAT_DXY, PGT_STAT_EXT, PGT_STAT_FST, PGT_STAT_HET,
                    SEG_DTYPE, SHARD_DTYPE, WIN_DTYPE, PgtError, check)
 
@@ -370,6 +370,27 @@ class Context:
                                                   win.ctypes.data, win.size, out.ctypes.data, tot.ctypes.data))
         return out, tot
 
+    def fst_pops_reduce(self, pos, freqs, ninds, minind, win):
+        """FST rows of ALL pairs i<j of len(freqs) populations (pair_order) from per-population numpy (freq, nInd) columns, one
+        pass: -> (rows[n_pairs, n_win], totals[n_pairs]) (pgt_fst_pops_reduce).  A row's n is the number of counted sites."""
+        pos = np.ascontiguousarray(pos, dtype=np.uint32)
+        freqs = [np.ascontiguousarray(f, dtype=np.float64) for f in freqs]
+        ninds = [np.ascontiguousarray(k, dtype=np.int32) for k in ninds]
+        win = np.ascontiguousarray(win, dtype=WIN_DTYPE)
+        n_pops = len(freqs)
+        if len(ninds) != n_pops or not 2 <= n_pops <= 8:
+            raise PgtError(_lib.PGT_EARG, "fst_pops_reduce: 2 ... 8 populations, one frequency and one count column each")
+        if any(c.size != pos.size for c in freqs + ninds):
+            raise PgtError(_lib.PGT_EARG, "fst_pops_reduce: column lengths differ")
+        n_pairs = n_pops * (n_pops - 1) // 2
+        out = np.zeros((n_pairs, win.size), dtype=FST_ROW_DTYPE)
+        tot = np.zeros(n_pairs, dtype=FST_TOTAL_DTYPE)
+        pf = (C.c_void_p * n_pops)(*[f.ctypes.data for f in freqs])
+        pn = (C.c_void_p * n_pops)(*[k.ctypes.data for k in ninds])
+        self._check(self._lib.pgt_fst_pops_reduce(self._ctx, pos.ctypes.data, pf, pn, n_pops, pos.size, int(minind),
+                                                  win.ctypes.data, win.size, out.ctypes.data, tot.ctypes.data))
+        return out, tot
+
     # ---- device-resident columns (torch CUDA tensors) -------------------------------------
     @staticmethod
     def _stream(stream):
@@ -689,6 +710,47 @@ class Context:
             self._dev(tree, torch.uint8, "tree"), tree.numel(), self._stream(stream)))
         return out, tot, tree
 
+    @staticmethod
+    def fst_pops_tree_bytes(n_pops: int, n_sites: int) -> int:
+        return int(_lib.load().pgt_fst_pops_tree_bytes(int(n_pops), int(n_sites)))
+
+    def fst_pops_reduce_dev(self, pos, freqs, ninds, minind, win, out=None, tot=None, tree=None, stream=None):
+        """FST rows of ALL pairs i<j of len(freqs) populations (pair-major, pair_order) in one pass over the populations' own
+        (freq, nInd) columns, with per-site sample sizes and the -minind predicate.  freqs: float64 CUDA tensors, ninds: int32
+        CUDA tensors.  tot: None = a fresh buffer of n_pairs totals is allocated and filled; False = no genome-wide lines.
+        Returns (out, tot, tree).  Asynchronous on `stream`."""
+        import torch
+        n_pops = len(freqs)
+        if len(ninds) != n_pops or not 2 <= n_pops <= 8:
+            raise PgtError(_lib.PGT_EARG, "fst_pops_reduce_dev: 2 ... 8 populations, one frequency and one count column each")
+        n = freqs[0].numel()
+        n_pairs = n_pops * (n_pops - 1) // 2
+        n_win = win.numel() // WIN_DTYPE.itemsize
+        tb = self.fst_pops_tree_bytes(n_pops, n)
+        dev = pos.device
+        if tree is None:
+            tree = torch.empty(tb, dtype=torch.uint8, device=dev)
+        if out is None:
+            out = torch.empty(n_pairs * n_win * FST_ROW_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        if tot is None:
+            tot = torch.empty(n_pairs * FST_TOTAL_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        elif tot is False:
+            tot = None
+        self._same_len("fst_pops_reduce_dev", n, pos, *freqs, *ninds)
+        self._room("fst_pops_reduce_dev: out", out, n_pairs * n_win * FST_ROW_DTYPE.itemsize)
+        self._room("fst_pops_reduce_dev: tree", tree, tb)
+        if tot is not None:
+            self._room("fst_pops_reduce_dev: tot", tot, n_pairs * FST_TOTAL_DTYPE.itemsize)
+        pf = (C.c_void_p * n_pops)(*[self._col(t, torch.float64, f"freqs[{k}]") for k, t in enumerate(freqs)])
+        pn = (C.c_void_p * n_pops)(*[self._col(t, torch.int32, f"ninds[{k}]") for k, t in enumerate(ninds)])
+        self._check(self._lib.pgt_fst_pops_reduce_dev(
+            self._ctx, self._dev(pos, torch.int32, "pos"), pf, pn, n_pops, n, int(minind),
+            self._dev(win, torch.uint8, "win") if n_win else None, n_win,
+            self._dev(out, torch.uint8, "out") if n_win else None, out.numel(),
+            self._dev(tot, torch.uint8, "tot") if tot is not None else None,
+            self._dev(tree, torch.uint8, "tree"), tree.numel(), self._stream(stream)))
+        return out, tot, tree
+
     def extreme_reduce_dev(self, pos, score, mode, cutoff, win, out=None, tree=None, stream=None):
         """ihsWindow / xpehhWindow rows from a device-resident score column (mode: PGT_EXT_*)."""
         import torch
@@ -1001,6 +1063,47 @@ def dxy_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: 
         w, r = win, rows[p]
         if skip_missing:
             keep = r["neff"] > 0
+            w, r = w[keep], r[keep]
+        res[ij] = WindowResult(w, r, tot[p])
+    return res
+
+
+def fst_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: int = 1, fixedsite: int = 0,
+                    chr_len=None, skip_missing: int = 0, ctx: Context | None = None) -> dict:
+    """Windowed FST for ALL pairs of len(freqs) already synchronised populations in one pass: {(i, j): WindowResult} with
+    fstWindow's rows (n = counted sites of the pair; the skipped ones are (hi - lo) - n) and the genome-wide line as total.
+    Window arguments and their errors are those of dxy_window_pops; -skip_missing drops a pair's rows without counted
+    sites from that pair's result only."""
+    if minind <= 0:
+        raise PgtError(_lib.PGT_EARG, "-minind must be at least 1")
+    if W > 0 and S < 1:
+        raise PgtError(_lib.PGT_EARG, "Must specify a -stepsize > 0 when -winsize is > 0")
+    if not fixedsite and chr_len is None:
+        raise PgtError(_lib.PGT_EARG, "Must supply size file unless -fixedsite 1")
+    if W == 0 and not fixedsite:
+        raise PgtError(_lib.PGT_EDOMAIN, "-winsize 0 needs -fixedsite 1 (the reference crashes here, SURVEY Q10)")
+    if len(ninds) != len(freqs) or not 2 <= len(freqs) <= 8:
+        raise PgtError(_lib.PGT_EARG, "fst_window_pops: 2 ... 8 populations, one frequency and one count column each")
+    chr_ids, pos = _host_col(chr_ids, None), _host_col(pos, np.uint32)
+    freqs, ninds = [_host_col(f, np.float64) for f in freqs], [_host_col(c, np.int32) for c in ninds]
+    rl = run_lengths(chr_ids)
+    if W == 0:
+        win = np.zeros(0, dtype=WIN_DTYPE)
+    elif fixedsite:
+        win = build_windows_sites(rl, W, S)
+    else:
+        win = build_windows_bp(pos, rl, chr_len, W, S)
+    ctx, own = _own_ctx(ctx)
+    try:
+        rows, tot = ctx.fst_pops_reduce(pos, freqs, ninds, minind, win)
+    finally:
+        if own:
+            ctx.close()
+    res = {}
+    for p, ij in enumerate(pair_order(len(freqs))):
+        w, r = win, rows[p]
+        if skip_missing:
+            keep = r["n"] > 0
             w, r = w[keep], r[keep]
         res[ij] = WindowResult(w, r, tot[p])
     return res

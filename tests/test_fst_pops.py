@@ -1,0 +1,387 @@
+"""GPU: FST of all population pairs from per-population (freq, nInd) columns (pgt_fst_pops_reduce_dev / pgt_fst_pops_reduce).
+
+The yardsticks are the float64 NumPy model of the spec (tests/fst_pops_model.py), the exact-rational fixture
+(tests/golden/wcfst_nind_exact.json), the allele-frequency front end on constant sample sizes and pgt_dxy_pops_reduce_dev's
+counts — never the code under test.  Tolerance: counts, coordinates and mid exact; asum, bsum, fst within
+|x - y| <= 1e-9 |y| + 1e-12 (helpers.REL / helpers.ABS)."""
+import ctypes as C
+import sys
+
+import numpy as np
+import pytest
+
+import fst_pops_model
+import helpers
+import synth
+from helpers import GuardedBuffers, padded_column, poison_tree, rows_equal
+from popgenomicstools_amd import _lib
+from popgenomicstools_amd._lib import DXY_ROW_DTYPE, DXY_TOTAL_DTYPE, FST_ROW_DTYPE, FST_TOTAL_DTYPE, WIN_DTYPE
+from popgenomicstools_amd.window_scan import pair_order, rows_from_device, run_lengths, windows_to_device
+
+pytestmark = pytest.mark.gpu
+
+MININD = 5
+SIZES = [1, 511, 512, 513, 8191, 8192, 8193, 2 * 8192 + 700]
+SITE_TABLES = [(1, 1), (7, 3), (512, 512), (5000, 1000)]
+
+
+def _dev():
+    import torch
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _t(x):
+    import torch
+    x = np.ascontiguousarray(x)
+    if x.dtype == np.uint32:
+        x = x.view(np.int32)
+    return torch.from_numpy(x).to(_dev())
+
+
+def random_pops(rng, n, k):
+    """the project's inputs: 6-decimal frequencies, nInd uniform in 0 .. 20; the LAST population is the first shifted by
+    about 1e-3, so that a of pair (0, k-1) is negative throughout"""
+    f = [np.round(rng.uniform(0, 1, n), 6) for _ in range(k)]
+    f[0] = np.round(rng.uniform(0.05, 0.95, n), 6)
+    f[k - 1] = np.round(f[0] + rng.uniform(0.0008, 0.0012, n), 6)
+    return f, [rng.integers(0, 21, n, dtype=np.int32) for _ in range(k)]
+
+
+def pops_dev(ctx, tp, tf, tn, minind, win, **kw):
+    """-> (rows[n_pairs, n_win], totals[n_pairs] or None) of one fst_pops_reduce_dev call"""
+    wd = windows_to_device(win, _dev())
+    out, tot, _ = ctx.fst_pops_reduce_dev(tp, tf, tn, minind, wd, **kw)
+    n_pairs = len(tf) * (len(tf) - 1) // 2
+    rows = rows_from_device(out, FST_ROW_DTYPE)[: n_pairs * win.size].reshape(n_pairs, win.size)
+    return rows, (rows_from_device(tot, FST_TOTAL_DTYPE)[:n_pairs] if tot is not None else None)
+
+
+def excess(x, y):
+    """max of |x - y| - (REL |y| + ABS): <= 0 when every entry is within the bound"""
+    x, y = np.atleast_1d(np.asarray(x, np.float64)), np.atleast_1d(np.asarray(y, np.float64))
+    return -1.0 if x.size == 0 else float(np.max(np.abs(x - y) - (helpers.REL * np.abs(y) + helpers.ABS)))
+
+
+def assert_rows(got, want, what):
+    assert got.size == want.size, what
+    for fld in ("start", "end", "mid", "n"):
+        assert np.array_equal(got[fld], want[fld]), (what, fld)
+    for fld in ("asum", "bsum", "fst"):
+        e = excess(got[fld], want[fld])
+        print(f"{what} {fld}: excess over the bound {e:.3e}")
+        assert e <= 0.0, (what, fld, e)
+
+
+def assert_totals(got, want, what):
+    for fld in ("neff", "nskip"):
+        assert np.array_equal(got[fld], want[fld]), (what, fld)
+    for fld in ("asum", "bsum"):
+        assert excess(got[fld], want[fld]) <= 0.0, (what, fld, got[fld], want[fld])
+
+
+def tables_for(pgt, pos, rl):
+    ends = np.cumsum(rl).astype(np.int64)
+    chr_len = (pos[ends - 1].astype(np.int64) + 17).astype(np.uint32)
+    t = [(f"site W={W} S={S}", pgt.build_windows_sites(rl, W, S)) for W, S in SITE_TABLES]
+    return t + [("bp W=2000 S=500", pgt.build_windows_bp(pos, rl, chr_len, 2000, 500))]
+
+
+# ---- 1: rows and genome-wide lines against the model and the exact fixture --------------------------------------------------
+@pytest.mark.parametrize("k", [2, 3, 5, 8])
+def test_rows_and_totals_against_the_numpy_model(pgt, ctx, k):
+    for si, n in enumerate(SIZES):
+        rng = np.random.default_rng(1000 * k + si)
+        chr_ids, pos = synth.chromosomes(rng, n, min(1 + (si + k) % 3, n), equal=False)
+        f, c = random_pops(rng, n, k)
+        tp, tf, tn = _t(pos), [_t(x) for x in f], [_t(x) for x in c]
+        for name, win in tables_for(pgt, pos, run_lengths(chr_ids)):
+            rows, tot = pops_dev(ctx, tp, tf, tn, MININD, win)
+            want, want_t = fst_pops_model.model(pos, f, c, MININD, win)
+            for p, ij in enumerate(pair_order(k)):
+                assert_rows(rows[p], want[p], f"K={k} n={n} {name} pair {ij}")
+            assert_totals(tot, want_t, f"K={k} n={n} {name} totals")
+            if k > 2 and n >= 511:  # the close pair: a negative at every counted site
+                one = rows[k - 2][rows[k - 2]["n"] > 0]
+                assert name != "site W=1 S=1" or np.all(one["asum"] < 0)
+
+
+def test_level3_nodes_are_built_and_used(pgt, ctx):
+    n, W, k = 600_001, 550_000, 3
+    rng = np.random.default_rng(31)
+    chr_ids, pos = synth.chromosomes(rng, n, 1)
+    f, c = random_pops(rng, n, k)
+    win = pgt.build_windows_sites(run_lengths(chr_ids), W, 10_000)
+    lo, hi = win["lo"].astype(np.int64), win["hi"].astype(np.int64)
+    assert np.any(-(-lo // (8192 * 64)) < hi // (8192 * 64)), "a window must contain a level-3 node"
+    tp, tf, tn = _t(pos), [_t(x) for x in f], [_t(x) for x in c]
+    want, want_t = fst_pops_model.model(pos, f, c, MININD, win)
+    for hint in (0, W):
+        with ctx.hints(hint, 0, 0):
+            rows, tot = pops_dev(ctx, tp, tf, tn, MININD, win)
+        for p, ij in enumerate(pair_order(k)):
+            assert_rows(rows[p], want[p], f"level 3, hint {hint}, pair {ij}")
+        assert_totals(tot, want_t, f"level 3, hint {hint}")
+
+
+def test_rows_against_the_exact_rational_fixture(pgt, ctx):
+    sys.path.insert(0, helpers.GOLDEN)
+    import make_wcfst_nind_exact as gen
+    k = helpers.load_golden("wcfst_nind_exact.json")
+    pos = np.array(k["pos"], dtype=np.uint32)
+    f = [np.array(x, dtype=np.float64) for x in k["freq"]]
+    c = [np.array(x, dtype=np.int32) for x in k["nind"]]
+    tp, tf, tn = _t(pos), [_t(x) for x in f], [_t(x) for x in c]
+    fixed = np.zeros(len(k["windows"]), dtype=WIN_DTYPE)
+    fixed["lo"], fixed["hi"] = [w[0] for w in k["windows"]], [w[1] for w in k["windows"]]
+    rl = np.array([pos.size], dtype=np.uint64)
+    for case in k["cases"]:
+        rows, tot = pops_dev(ctx, tp, tf, tn, case["minind"], fixed)
+        whole = k["windows"].index([0, int(pos.size)])
+        for p, pr in enumerate(case["pairs"]):
+            what = f"fixture minind={case['minind']} pair {pr['pair']}"
+            assert np.array_equal(rows[p]["n"], np.array(pr["n"], dtype=np.uint32)), what
+            assert excess(rows[p]["asum"], pr["asum"]) <= 0 and excess(rows[p]["bsum"], pr["bsum"]) <= 0, what
+            fst = [fst_pops_model.fst_of(a, b) for a, b in zip(pr["asum"], pr["bsum"])]
+            assert excess(rows[p]["fst"], fst) <= 0, what
+            assert int(tot[p]["neff"]) == pr["n"][whole] and int(tot[p]["nskip"]) == pos.size - pr["n"][whole]
+            assert excess(tot[p]["asum"], pr["asum"][whole]) <= 0 and excess(tot[p]["bsum"], pr["bsum"][whole]) <= 0, what
+        # the tools' site tables on the fixture's columns, the exact sums from the generator's own functions
+        for W, S in SITE_TABLES:
+            win = pgt.build_windows_sites(rl, W, S)
+            rows, _ = pops_dev(ctx, tp, tf, tn, case["minind"], win)
+            for p, (i, j) in enumerate(pair_order(3)):
+                sites = gen.exact_sites(f, c, i, j, case["minind"])
+                ex = [gen.exact_window(sites, int(w["lo"]), int(w["hi"])) for w in win]
+                what = f"fixture W={W} S={S} minind={case['minind']} pair {(i, j)}"
+                assert [int(x) for x in rows[p]["n"]] == [e[2] for e in ex], what
+                assert excess(rows[p]["asum"], [float(e[0]) for e in ex]) <= 0, what
+                assert excess(rows[p]["bsum"], [float(e[1]) for e in ex]) <= 0, what
+
+
+# ---- 2: constant sample sizes = the allele-frequency front end -------------------------------------------------------------
+@pytest.mark.parametrize("k", [2, 3, 5, 8])
+def test_constant_nind_equals_the_allele_frequency_front_end(pgt, ctx, k):
+    n, const = 2 * 8192 + 700, 7
+    rng = np.random.default_rng(200 + k)
+    chr_ids, pos = synth.chromosomes(rng, n, 2, equal=False)
+    f, _ = random_pops(rng, n, k)
+    c = [np.full(n, const, dtype=np.int32) for _ in range(k)]
+    tp, tf, tn = _t(pos), [_t(x) for x in f], [_t(x) for x in c]
+    for name, win in tables_for(pgt, pos, run_lengths(chr_ids)):
+        wd = windows_to_device(win, _dev())
+        out, _ = ctx.fst_af_reduce_dev(tp, tf, [float(const)] * k, wd)
+        want = rows_from_device(out, FST_ROW_DTYPE)[: len(pair_order(k)) * win.size].reshape(-1, win.size)
+        for minind in (1, const):
+            rows, _ = pops_dev(ctx, tp, tf, tn, minind, win)
+            for p, ij in enumerate(pair_order(k)):
+                assert_rows(rows[p], want[p], f"K={k} {name} minind={minind} pair {ij} against fst_af")
+
+
+# ---- 3: counts = dxy pops' counts ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("k", [2, 3, 5, 8])
+def test_counts_equal_dxy_pops(pgt, ctx, k):
+    n = 2 * 8192 + 700
+    rng = np.random.default_rng(300 + k)
+    chr_ids, pos = synth.chromosomes(rng, n, 2, equal=False)
+    f, c = random_pops(rng, n, k)
+    tp, tf, tn = _t(pos), [_t(x) for x in f], [_t(x) for x in c]
+    for name, win in tables_for(pgt, pos, run_lengths(chr_ids)):
+        wd = windows_to_device(win, _dev())
+        rows, tot = pops_dev(ctx, tp, tf, tn, MININD, win)
+        out, dtot, _ = ctx.dxy_pops_reduce_dev(tp, tf, tn, MININD, wd)
+        n_pairs = len(pair_order(k))
+        d = rows_from_device(out, DXY_ROW_DTYPE)[: n_pairs * win.size].reshape(n_pairs, win.size)
+        dt = rows_from_device(dtot, DXY_TOTAL_DTYPE)[:n_pairs]
+        for p in range(n_pairs):
+            assert np.array_equal(rows[p]["n"], d[p]["neff"]), (k, name, p)
+            assert np.array_equal((win["hi"] - win["lo"]).astype(np.uint32) - rows[p]["n"], d[p]["nskip"]), (k, name, p)
+        assert np.array_equal(tot["neff"], dt["neff"]) and np.array_equal(tot["nskip"], dt["nskip"])
+
+
+# ---- 4: pair isolation -----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("k", [3, 5, 8])
+def test_pairs_do_not_see_the_other_populations(pgt, ctx, k):
+    n = 2 * 8192 + 700
+    rng = np.random.default_rng(400 + k)
+    chr_ids, pos = synth.chromosomes(rng, n, 2, equal=False)
+    f, c = random_pops(rng, n, k)
+    f2, c2 = random_pops(rng, n, k)
+    win = np.concatenate([pgt.build_windows_sites(run_lengths(chr_ids), W, S) for W, S in ((7, 3), (5000, 1000))])
+    tp = _t(pos)
+    rows, tot = pops_dev(ctx, tp, [_t(x) for x in f], [_t(x) for x in c], MININD, win)
+    for r in (0, k // 2, k - 1):  # population r replaced: every pair without it keeps its bits
+        fr, cr = list(f), list(c)
+        fr[r], cr[r] = f2[r], c2[r]
+        got, got_t = pops_dev(ctx, tp, [_t(x) for x in fr], [_t(x) for x in cr], MININD, win)
+        for p, (i, j) in enumerate(pair_order(k)):
+            if r not in (i, j):
+                rows_equal(got[p], rows[p], f"K={k}, population {r} replaced, pair {(i, j)}")
+                assert got_t[p].tobytes() == tot[p].tobytes()
+    for p, (i, j) in enumerate(pair_order(k)):  # a pair's table from the K-population call = the two-population call's
+        two, two_t = pops_dev(ctx, tp, [_t(f[i]), _t(f[j])], [_t(c[i]), _t(c[j])], MININD, win)
+        assert_rows(rows[p], two[0], f"K={k} pair {(i, j)} against the two-population call")
+        assert_totals(tot[p:p + 1], two_t, f"K={k} pair {(i, j)} totals")
+
+
+# ---- 5: workspace contract -------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n,k", [(513, 3), (8193, 8), (600_001, 4)])
+def test_rows_under_every_hint_poison_and_guard(pgt, ctx, n, k):
+    W = 550_000 if n > 100_000 else 5000
+    rng = np.random.default_rng(500 + k)
+    chr_ids, pos = synth.chromosomes(rng, n, 1)
+    f, c = random_pops(rng, n, k)
+    fb, cb = random_pops(rng, n, k)
+    win = np.concatenate([pgt.build_windows_sites(run_lengths(chr_ids), min(W, n), max(1, min(W, n) // 4)),
+                          pgt.build_windows_sites(run_lengths(chr_ids), min(1000, n), min(333, n))])
+    want, want_t = fst_pops_model.model(pos, f, c, MININD, win)
+    dev = _dev()
+    tf, tn = [padded_column(x, float("nan"), dev) for x in f], [padded_column(x, 1000, dev) for x in c]
+    tp, wd = _t(pos), windows_to_device(win, dev)
+    n_pairs = k * (k - 1) // 2
+    tb = ctx.fst_pops_tree_bytes(k, n)
+    _, _, foreign = ctx.fst_pops_reduce_dev(tp, [_t(x) for x in fb], [_t(x) for x in cb], MININD, wd)
+    g = GuardedBuffers([tb, n_pairs * win.size * FST_ROW_DTYPE.itemsize, n_pairs * FST_TOTAL_DTYPE.itemsize], 31 + k, dev)
+    tree, out, tot = g.bufs
+    for hint in (0, W, 4 * W):
+        first = None
+        with ctx.hints(hint, 0, 0):
+            for kind in (0, 1, 2):
+                poison_tree(tree, kind, other=foreign)
+                out.fill_(0xFF)
+                tot.fill_(0xFF)
+                ctx.fst_pops_reduce_dev(tp, tf, tn, MININD, wd, out=out, tot=tot, tree=tree)
+                what = f"n={n} K={k} hint={hint} poison={kind}"
+                g.check(what)
+                got = rows_from_device(out, FST_ROW_DTYPE).reshape(n_pairs, win.size).copy()
+                got_t = rows_from_device(tot, FST_TOTAL_DTYPE).copy()
+                if first is None:
+                    first = (got, got_t)
+                    for p in range(n_pairs):
+                        assert_rows(got[p], want[p], what + f" pair {p}")
+                    assert_totals(got_t, want_t, what)
+                else:  # identical under one hint, whatever the workspace held
+                    assert got.tobytes() == first[0].tobytes() and got_t.tobytes() == first[1].tobytes(), what
+
+
+# ---- 6: graph capture ------------------------------------------------------------------------------------------------------
+def test_graph_replay_rebuilds_from_new_columns(pgt, ctx):
+    import torch
+    n, k = 2 * 8192 + 700, 4
+    rng = np.random.default_rng(600)
+    chr_ids, pos = synth.chromosomes(rng, n, 2, equal=False)
+    A, B = random_pops(rng, n, k), random_pops(rng, n, k)
+    win = pgt.build_windows_sites(run_lengths(chr_ids), 5000, 100)
+    dev = _dev()
+    wd, tp = windows_to_device(win, dev), _t(pos)
+    tf, tn = [_t(x) for x in A[0]], [_t(x) for x in A[1]]
+    n_pairs = k * (k - 1) // 2
+    g = GuardedBuffers([ctx.fst_pops_tree_bytes(k, n), n_pairs * win.size * FST_ROW_DTYPE.itemsize, n_pairs * FST_TOTAL_DTYPE.itemsize], 3, dev)
+    tree, out, tot = g.bufs
+    with ctx.hints(5000, 100, 0):
+        ctx.fst_pops_reduce_dev(tp, tf, tn, MININD, wd, out=out, tot=tot, tree=tree)  # warm-up outside the capture
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            ctx.fst_pops_reduce_dev(tp, tf, tn, MININD, wd, out=out, tot=tot, tree=tree)
+    for name, src in (("B", B), ("A", A)):
+        for t, x in zip(tf + tn, src[0] + src[1]):
+            t.copy_(torch.from_numpy(x))
+        for buf in (tree, out, tot):
+            buf.fill_(0xFF)
+        graph.replay()
+        g.check("fst_pops graph replay")
+        want, want_t = fst_pops_model.model(pos, src[0], src[1], MININD, win)
+        got = rows_from_device(out, FST_ROW_DTYPE).reshape(n_pairs, win.size)
+        for p in range(n_pairs):
+            assert_rows(got[p], want[p], f"replay {name} pair {p}")
+        assert_totals(rows_from_device(tot, FST_TOTAL_DTYPE), want_t, f"replay {name}")
+
+
+# ---- 7: refusals -----------------------------------------------------------------------------------------------------------
+def test_refusals_name_the_argument_and_launch_nothing(pgt, ctx):
+    import torch
+    n, k = 10_000, 3
+    rng = np.random.default_rng(700)
+    chr_ids, pos = synth.chromosomes(rng, n, 1)
+    f, c = random_pops(rng, n, k)
+    win = pgt.build_windows_sites(run_lengths(chr_ids), 1000, 500)
+    wd = windows_to_device(win, _dev())
+    n_pairs = 3
+    tb = ctx.fst_pops_tree_bytes(k, n)
+    g = GuardedBuffers([tb, n_pairs * win.size * FST_ROW_DTYPE.itemsize, n_pairs * FST_TOTAL_DTYPE.itemsize], 5, _dev())
+    tree, out, tot = g.bufs
+    tp, tf, tn = _t(pos), [_t(x) for x in f], [_t(x) for x in c]
+    lib, h = ctx._lib, ctx._ctx
+    before = [b.clone() for b in g.bufs]
+
+    def call(freq=None, nind=None, n_pops=k, minind=MININD, win_p=wd.data_ptr(), out_p=out.data_ptr(), out_bytes=out.numel(),
+             tree_p=tree.data_ptr(), tree_bytes=tree.numel(), freq_null=False, nind_null=False, pos_p=tp.data_ptr()):
+        fp = [t.data_ptr() for t in tf] if freq is None else freq
+        npn = [t.data_ptr() for t in tn] if nind is None else nind
+        pf = (C.c_void_p * 8)(*(fp + [None] * (8 - len(fp))))
+        pn = (C.c_void_p * 8)(*(npn + [None] * (8 - len(npn))))
+        return lib.pgt_fst_pops_reduce_dev(h, pos_p, None if freq_null else pf, None if nind_null else pn, n_pops, n, minind, win_p, win.size,
+                                           out_p, out_bytes, tot.data_ptr(), tree_p, tree_bytes, None)
+
+    f_ptrs, n_ptrs = [t.data_ptr() for t in tf], [t.data_ptr() for t in tn]
+    refusals = [
+        (dict(minind=0), "minind"), (dict(minind=-3), "minind"),
+        (dict(pos_p=None), "pos"), (dict(freq_null=True), "freq"), (dict(nind_null=True), "nind"), (dict(tree_p=None), "tree"), (dict(win_p=None), "win"),
+        (dict(out_p=None), "out"), (dict(n_pops=1), "n_pops"), (dict(n_pops=9), "n_pops"),
+        (dict(freq=[f_ptrs[0], None, f_ptrs[2]]), "freq[1]"), (dict(nind=[n_ptrs[0], n_ptrs[1], None]), "nind[2]"),
+        (dict(freq=[f_ptrs[0], f_ptrs[1] + 8, f_ptrs[2]]), "freq[1]"), (dict(nind=[n_ptrs[0], n_ptrs[1], n_ptrs[2] + 8]), "nind[2]"),
+        (dict(nind=[n_ptrs[0] + 4, n_ptrs[1], n_ptrs[2]]), "nind[0]"),
+        (dict(out_bytes=out.numel() - 1), "out_bytes"), (dict(tree_bytes=tb - 1), "tree_bytes"),
+    ]
+    for kw, name in refusals:
+        rc = call(**kw)
+        msg = _lib.last_error(h)
+        assert rc == _lib.PGT_EARG and name in msg, (kw, rc, msg)
+    g.check("refused calls")
+    for b, was in zip(g.bufs, before):
+        assert torch.equal(b, was), "a refused call wrote to a buffer"
+    assert call() == _lib.PGT_OK  # the same arguments, unharmed, are accepted
+    torch.cuda.synchronize()
+    want, _ = fst_pops_model.model(pos, f, c, MININD, win)
+    got = rows_from_device(out, FST_ROW_DTYPE).reshape(n_pairs, win.size)
+    for p in range(n_pairs):
+        assert_rows(got[p], want[p], f"accepted call, pair {p}")
+
+    # the Python wrapper refuses misaligned views and differing lengths by name
+    m = 1000
+    fcols = [torch.zeros(m + 4, dtype=torch.float64, device=_dev()) for _ in range(3)]
+    ccols = [torch.ones(m + 4, dtype=torch.int32, device=_dev()) for _ in range(3)]
+    posm = torch.arange(1, m + 1, dtype=torch.int32, device=_dev())
+    w1 = windows_to_device(pgt.build_windows_sites(np.array([m], np.uint64), 100, 100), _dev())
+    good_f, good_c = [t[4:4 + m] for t in fcols], [t[4:4 + m] for t in ccols]
+    ctx.fst_pops_reduce_dev(posm, good_f, good_c, 1, w1)
+    with pytest.raises(_lib.PgtError, match=r"freqs\[1\]"):
+        ctx.fst_pops_reduce_dev(posm, [good_f[0], fcols[1][1:1 + m], good_f[2]], good_c, 1, w1)
+    with pytest.raises(_lib.PgtError, match=r"ninds\[2\]"):
+        ctx.fst_pops_reduce_dev(posm, good_f, [good_c[0], good_c[1], ccols[2][2:2 + m]], 1, w1)
+    with pytest.raises(_lib.PgtError, match="column lengths differ"):
+        ctx.fst_pops_reduce_dev(posm, [good_f[0], good_f[1][:-4], good_f[2]], good_c, 1, w1)
+    with pytest.raises(_lib.PgtError, match="minind"):
+        ctx.fst_pops_reduce_dev(posm, good_f, good_c, 0, w1)
+    torch.cuda.synchronize()
+
+
+# ---- 8: host-buffer form ---------------------------------------------------------------------------------------------------
+def test_host_buffer_form_equals_the_device_form_twice_in_a_row(pgt, ctx):
+    n, k = 2 * 8192 + 700, 4
+    for seed in (61, 62):  # different data through the one context: nothing of the cached workspace may survive
+        rng = np.random.default_rng(seed)
+        chr_ids, pos = synth.chromosomes(rng, n, 3, equal=False)
+        f, c = random_pops(rng, n, k)
+        win = pgt.build_windows_sites(run_lengths(chr_ids), 5000, 1000)
+        rows, tot = ctx.fst_pops_reduce(pos, f, c, MININD, win)
+        hints = pgt.window_scan.table_hints(win)
+        with ctx.hints(hints[0], 0, 0):  # the host-buffer form derives the longest-window hint from the table
+            want, want_t = pops_dev(ctx, _t(pos), [_t(x) for x in f], [_t(x) for x in c], MININD, win)
+        assert rows.shape == want.shape
+        for p in range(rows.shape[0]):
+            rows_equal(np.ascontiguousarray(rows[p]), want[p], f"seed {seed} pair {p}")
+        assert tot.tobytes() == want_t.tobytes()
+    res = pgt.fst_window_pops(chr_ids, pos, f, c, 5000, 1000, MININD, 1, ctx=ctx)
+    assert list(res) == pair_order(k)
+    rows_equal(np.ascontiguousarray(res[(0, 1)].rows), want[0], "fst_window_pops pair (0, 1)")
