@@ -22,6 +22,17 @@
  *     entry points, 64 MiB + about 1 % of the largest input seen; pgt_close frees them);
  *   - one pgt_ctx per GPU and per thread (one process per GPU); a ctx is not thread-safe;
  *   - there is NO CPU fallback: without a usable gfx950 device pgt_open fails.
+ *
+ * Values the columns admit (tests/test_special_values.py)
+ *   - a, b (fst) and score (ihs / xpehh): ANY f64, NaN and +-inf included.  Sums and the one division per row follow IEEE 754
+ *     as the reference's own `+=` and `/` do (fstWindow.cpp:76-85): a NaN or an infinity reaches exactly the rows of the windows
+ *     that hold it, a sum starts at +0.0 (never -0.0), fst is ONE correctly rounded division, denormals included.  The sign and
+ *     payload of a COMPUTED NaN are unspecified.  For the score see pgt_ext_row below.
+ *   - allele frequencies (p1, p2, freq[k]): in [0, 1] at every COUNTED site (both populations have at least minind individuals
+ *     there); at a site that is not counted the frequency is never used and may hold anything, NaN included.  pgt_fst_af_reduce_dev
+ *     has no counts: every site is counted; a NaN there stays in the rows of the pairs with that population.
+ *   - genotypes: any int8 (non-missing is g >= 0, heterozygous g == 1, hetWindow.cpp:78-80); counts (n1, n2, nind[k]) and minind:
+ *     any int32, compared as signed integers (dxyWindow.cpp:381).
  */
 #ifndef PGTWIN_H
 #define PGTWIN_H
@@ -303,8 +314,13 @@ enum {
 typedef struct { /* ihsWindow.cpp:101-110 row: chr start end score position proportion nsites */
     uint32_t start, end, nsites, nbig;
     uint32_t position, pad_; /* position of the extreme score; 0 when nsites == 0 (the tool prints NA) */
-    double value;            /* the extreme score (signed) */
+    double value;            /* the extreme score (signed): a copy of the input, bit for bit; 0.0 when nsites == 0 */
 } pgt_ext_row;
+/* NaN scores, as the reference's loop treats them (ihsWindow.cpp:194-205): the window's FIRST site is the running extreme
+ * unconditionally and a later site replaces it only when its key is strictly greater.  So a window whose first score is NaN
+ * reports that site (value = that NaN, with its position) whatever follows; a NaN at a later site never wins; a NaN is never
+ * beyond the cutoff (nbig).  +-inf are ordinary keys (ties: the first occurrence).  The rule depends on the window alone:
+ * rows do not depend on the query strategy or on the sharding. */
 /* The tools' window rules applied site by site on the host (they are history dependent: a site at
  * pos >= window end opens the next window, ihsWindow.cpp:176-190): fixed bp windows [1,W],[W+1,2W],..
  * per chromosome, clamped to chr_len[r] where given (0 = not given; chr_len may be NULL), empty

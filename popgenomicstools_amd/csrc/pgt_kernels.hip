@@ -839,9 +839,17 @@ struct ExtTraits {
         r.nsites = (uint32_t)(hi - lo);
         r.nbig = t.count;
         r.pad_ = 0;
-        const bool any = hi > lo && t.idx != 0xFFFFFFFFu;
-        r.position = any ? pos[t.idx] : 0u;   // maxihs[2], ihsWindow.cpp:98
-        r.value = any ? c.s[t.idx] : 0.0;     // maxihs[1]: the signed score itself
+        // The reference takes the window's FIRST site as the running extreme unconditionally and replaces it only by a
+        // strict `>` (ihsWindow.cpp:194-201): a NaN key there is never replaced, a NaN key later never wins.  The tree
+        // drops NaN keys everywhere, so the rule is applied here, on the window alone: first key NaN -> the row is that site.
+        uint64_t at = t.idx;
+        bool any = hi > lo && t.idx != 0xFFFFFFFFu;
+        if (hi > lo) {
+            const double k0 = key_of(c.s[lo], c.mode);
+            if (k0 != k0) { at = lo; any = true; }
+        }
+        r.position = any ? pos[at] : 0u;   // maxihs[2], ihsWindow.cpp:98
+        r.value = any ? c.s[at] : 0.0;     // maxihs[1]: the signed score itself
         *out = r;
     }
     static __device__ __forceinline__ void store_total(pgt_dxy_total *, const Node &) {}

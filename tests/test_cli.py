@@ -1130,3 +1130,32 @@ def test_cli_device_window_table_equals_host_table(hosts, tmp_path, oracle):
     a = run([hosts["hetWindow"], str(h), "40", "1"], env=dict(os.environ, PGT_HOST_TIMING="1"))
     b = run([hosts["hetWindow"], str(h), "40", "1"], env=off)
     assert a.returncode == b.returncode == 0 and a.stdout == b.stdout and len(a.stdout.splitlines()) > n - 5 * 40
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ingest", ["0", "1"])
+def test_cli_nan_and_inf_tokens_print_the_pinned_tsv(hosts, hosts_ext, tmp_path, ingest):
+    """`nan`, `-nan`, `inf`, `-inf` in a value column are the IEEE values and the rows are what the reference's arithmetic gives
+    on them (tests/golden/special_tokens.json, `expected`: the oracle's text front end) — with the host
+    parser and with the device parser.  ihsWindow / xpehhWindow print a SELECTED score: byte for byte, the sign of a NaN
+    included.  fstWindow prints a computed ratio: the sign of a computed NaN is not part of the contract, so `-nan` and `nan`
+    are one value in its float column."""
+    cases = helpers.load_golden("special_tokens.json")["cases"]
+    assert len(cases) >= 10
+    bins = dict(hosts, **hosts_ext)
+    env = dict(os.environ, PGT_GPU_INGEST=ingest)
+    jobs = []
+    for i, c in enumerate(cases):
+        jobs.append((_extreme_argv(bins, c, tmp_path, i), env))
+
+    def unsigned_nan(tsv):
+        rows = helpers.parse_tsv(tsv)
+        for r in rows:
+            r[4] = "nan" if r[4] == "-nan" else r[4]
+        return rows
+    for c, r in zip(cases, run_all(jobs)):
+        assert r.returncode == 0, (c["tool"], c["args"], r.stderr)
+        if c["tool"] == "fstWindow":
+            assert unsigned_nan(r.stdout) == unsigned_nan(c["expected"]), (c["args"], c["note"], r.stdout)
+        else:
+            assert r.stdout == c["expected"], (c["tool"], c["args"], c["note"], r.stdout)
