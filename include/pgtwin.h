@@ -51,7 +51,8 @@ extern "C" {
  * ring and keep a per-context workspace (no argument list changed).
  * Still 6: pgt_dxy_pops_tree_bytes / pgt_dxy_pops_reduce_dev / pgt_dxy_pops_reduce added (additive: nothing that existed changed).
  * Still 6: pgt_align_segments / pgt_align_workspace_bytes / pgt_sites_align / pgt_gather_dev added (additive as well).
- * Still 6: pgt_fst_total, pgt_fst_pops_tree_bytes / pgt_fst_pops_reduce_dev / pgt_fst_pops_reduce added (additive as well). */
+ * Still 6: pgt_fst_total, pgt_fst_pops_tree_bytes / pgt_fst_pops_reduce_dev / pgt_fst_pops_reduce added (additive as well).
+ * Still 6: pgt_pi_pops_tree_bytes / pgt_pi_pops_reduce_dev / pgt_pi_pops_reduce added (additive as well). */
 #define PGT_ABI_VERSION 6
 
 enum {
@@ -265,6 +266,45 @@ int pgt_fst_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *con
 int pgt_fst_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq,
                         const int32_t *const *nind, uint32_t n_pops, uint64_t n, int minind,
                         const pgt_win *win, uint64_t n_win, pgt_fst_row *out, pgt_fst_total *tot);
+
+/* ---- nucleotide diversity (pi) per population from per-population MAF columns --------------------- */
+/* Windowed within-population nucleotide diversity of each of n_pops populations from its own (freq, nInd) columns — the
+ * columns pgt_dxy_pops_reduce_dev and pgt_fst_pops_reduce_dev read — over ONE position column and ONE window table, in one
+ * pass (12 B/site/population).  The statistic dxy and FST scans are read against: net divergence is dxy - (pi_1 + pi_2)/2.
+ * It has NO counterpart in the reference (none of its tools computes pi): the definition below is the contract.
+ *   counting   nind[s] >= minind, compared as signed int32; minind >= 1 is required (PGT_EARG otherwise, the rule of
+ *              pgt_fst_pops_reduce_dev): it makes 2 nind - 1 >= 1 at every counted site
+ *   per site   with p = freq[s], dn = (double)nind[s] (exact), every operation rounded on its own:
+ *                  c = (2.0*dn) / (2.0*dn - 1.0)      one correctly rounded IEEE division: the finite-sample factor
+ *                  h = (2.0*p) * (1.0 - p)
+ *                  pi = h * c
+ *              a site that is not counted is selected away, never multiplied: its frequency may be NaN
+ *   row        pgt_dxy_row: sum = Σ pi over the window's counted sites, starting from +0.0 (like dxyWindow.cpp:190 the row
+ *              carries the SUM: divide by neff or by the window length); neff = the counted sites; nskip = (hi - lo) - neff;
+ *              start / end as pgt_dxy_reduce_dev fills them (PGT_WIN_COORDS honoured).  A one-site window has exactly the bits
+ *              of `pi` above
+ *   out        n_pops * n_win rows, population-major
+ *   tot        DEVICE array of n_pops genome-wide lines (pgt_dxy_total: exact counts; the sum added from one partial per
+ *              build wave, in wave order, as for pgt_dxy_reduce_dev), or NULL; n_win == 0 with tot: the global-only form
+ *   tree       pgt_pi_pops_tree_bytes(n_pops, n) bytes (0 for n_pops outside 1 ... 8).    1 <= n_pops <= 8, n < 2^32.
+ * Arguments, alignment (freq[k], nind[k] 16-byte aligned), refusals (each names its argument; nothing is launched) and graph
+ * capture (the pointer arrays are read before the call returns) are those of pgt_dxy_pops_reduce_dev.  Unlike the all-pairs
+ * calls, a population's predicate is its own, so the generic range tree answers the windows: pgt_set_max_window,
+ * pgt_set_window_step and pgt_set_typical_window are ALL honoured, with the strategies of pgt_dxy_reduce_dev (one wave per
+ * window, the sliding query, the group query).  A population's rows do not depend, bit for bit, on the other populations
+ * in the call (n_pops = 1 gives the same bits), and a row does not depend on the other rows of the table under one set of
+ * hints.  Sums are added in a fixed order (bitwise reproducible); against an exact evaluation of the lines above they stay
+ * within 1e-9 relative + 1e-12.  Parity: to this definition and to an exact-rational fixture (tests/golden/pi_exact.json).
+ * Host-buffer form: columns (host arrays of n_pops HOST pointers), table, rows and the n_pops totals in host memory; hints
+ * that are not set are derived from the table, as in the other host-buffer calls. */
+size_t pgt_pi_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites);
+int pgt_pi_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq,
+                           const int32_t *const *nind, uint32_t n_pops, uint64_t n, int minind,
+                           const pgt_win *win, uint64_t n_win, pgt_dxy_row *out, size_t out_bytes,
+                           pgt_dxy_total *tot, void *tree, size_t tree_bytes, void *stream);
+int pgt_pi_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq,
+                       const int32_t *const *nind, uint32_t n_pops, uint64_t n, int minind,
+                       const pgt_win *win, uint64_t n_win, pgt_dxy_row *out, pgt_dxy_total *tot);
 
 /* ---- the sites common to K files, aligned on the device ------------------------------------------ */
 /* Replaces the two-file synchronisation of dxyWindow.cpp:315-331 (one current line per file; the file that is behind reads

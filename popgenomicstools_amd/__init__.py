@@ -20,6 +20,7 @@ from .window_scan import (  # noqa: F401
     dxy_window_pops,
     fst_window,
     fst_window_pops,
+    pi_window_pops,
     het_window,
     ihs_window,
     pair_order,
@@ -29,4 +30,4 @@ from .window_scan import (  # noqa: F401
 )
 
 __all__ = ["Context", "build_windows_sites", "build_windows_bp", "fst_window", "het_window",
-           "dxy_window", "dxy_window_pops", "fst_window_pops", "pair_order", "align_segments", "align_segments_runs", "align_sites", "ihs_window", "xpehh_window", "build_windows_extreme", "plan_shards", "run_lengths"]
+           "dxy_window", "dxy_window_pops", "fst_window_pops", "pi_window_pops", "pair_order", "align_segments", "align_segments_runs", "align_sites", "ihs_window", "xpehh_window", "build_windows_extreme", "plan_shards", "run_lengths"]

@@ -56,6 +56,7 @@ SYMBOLS = [
     "pgt_dxy_pops_tree_bytes", "pgt_dxy_pops_reduce_dev", "pgt_dxy_pops_reduce",
     "pgt_align_segments", "pgt_align_workspace_bytes", "pgt_sites_align", "pgt_gather_dev",
     "pgt_fst_pops_tree_bytes", "pgt_fst_pops_reduce_dev", "pgt_fst_pops_reduce",
+    "pgt_pi_pops_tree_bytes", "pgt_pi_pops_reduce_dev", "pgt_pi_pops_reduce",
 ]
 PGT_TOK_CHR, PGT_TOK_SKIP, PGT_TOK_U32, PGT_TOK_F64, PGT_TOK_I8, PGT_TOK_I32, PGT_TOK_FREQ, PGT_TOK_CHR_PREFIX = range(8)
 
@@ -134,6 +135,10 @@ def load() -> C.CDLL:
     lib.pgt_fst_pops_tree_bytes.argtypes = [u32, u64]
     lib.pgt_fst_pops_reduce_dev.argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, u64, vp, sz, vp, vp, sz, vp]
     lib.pgt_fst_pops_reduce.argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, u64, vp, vp]
+    lib.pgt_pi_pops_tree_bytes.restype = sz
+    lib.pgt_pi_pops_tree_bytes.argtypes = [u32, u64]
+    lib.pgt_pi_pops_reduce_dev.argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, u64, vp, sz, vp, vp, sz, vp]
+    lib.pgt_pi_pops_reduce.argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, u64, vp, vp]
     lib.pgt_align_segments.argtypes = [vp, vp, vp, u32, vp, sz, C.POINTER(sz)]
     lib.pgt_align_workspace_bytes.restype = sz
     lib.pgt_align_workspace_bytes.argtypes = [u32, u64]

@@ -656,6 +656,42 @@ int pgt_fst_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *con
                            ctx->hints);
 }
 
+size_t pgt_pi_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites) {
+    if (n_pops < 1 || n_pops > (uint32_t)kPiPopsMaxPops) return 0;
+    return (size_t)n_pops * tree_layout(PGT_STAT_DXY, n_sites).bytes;  // one tree of the two-population dxy layout per population
+}
+
+int pgt_pi_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind,
+                           uint32_t n_pops, uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_dxy_row *out,
+                           size_t out_bytes, pgt_dxy_total *tot, void *tree, size_t tree_bytes, void *stream) {
+    PGT_USE_DEVICE(ctx);
+    if (n_pops < 1 || n_pops > (uint32_t)kPiPopsMaxPops) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: n_pops must be 1 ... 8");
+    if (minind < 1) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: minind must be at least 1");  // 2 nind - 1 >= 1 at every counted site
+    if (n == 0 && n_win == 0 && !tot) return PGT_OK;
+    if (!freq) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: freq is NULL");
+    if (!nind) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: nind is NULL");
+    if (!tree) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: tree is NULL");
+    if (n_win && !win) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: win is NULL");
+    if (n_win && !out) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: out is NULL");
+    if (n_win && n && !pos) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: pos is NULL");  // windows without PGT_WIN_COORDS read pos[lo], pos[hi-1]
+    for (uint32_t k = 0; k < n_pops; ++k) {
+        if (!freq[k]) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: freq[" + std::to_string(k) + "] is NULL");
+        if (!nind[k]) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: nind[" + std::to_string(k) + "] is NULL");
+        if (!aligned16(freq[k])) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: freq[" + std::to_string(k) + "] is not 16-byte aligned");
+        if (!aligned16(nind[k])) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: nind[" + std::to_string(k) + "] is not 16-byte aligned");
+    }
+    if (n >= (1ull << 32)) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: n: at most 2^32-1 sites per call");
+    if (!aligned16(tree)) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: tree is not 16-byte aligned");
+    if (tree_bytes < pgt_pi_pops_tree_bytes(n_pops, n))
+        return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: tree_bytes too small (" + std::to_string(tree_bytes) + " bytes, " +
+                                           std::to_string(pgt_pi_pops_tree_bytes(n_pops, n)) + " needed)");
+    if (n_win > UINT64_MAX / n_pops) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: n_pops * n_win overflows");
+    if (int rc = room_check(ctx, "pgt_pi_pops_reduce: out_bytes", (uint64_t)n_pops * n_win, sizeof(pgt_dxy_row), out_bytes)) return rc;
+    const EvSet e = events_for(ctx);
+    return launch_pi_pops(pos, freq, nind, n_pops, n, minind, win, n_win, out, tot, tree, stream, e.b0, e.b1, e.q1, &ctx->error,
+                          ctx->hints);
+}
+
 size_t pgt_align_workspace_bytes(uint32_t n_files, uint64_t n_rows_file0) {
     if (n_files < 2 || n_files > (uint32_t)kAlignMaxFiles) return 0;
     return align_layout(n_files, n_rows_file0).bytes;
@@ -1059,6 +1095,37 @@ int pgt_fst_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *
         [&](const pgt_win *dw, pgt_fst_row *dr, void *tree, size_t tb, pgt_fst_total *dtot) {
             return pgt_fst_pops_reduce_dev(ctx, static_cast<uint32_t *>(dpos.p), pf, pn, n_pops, n, minind, dw, n_win, dr,
                                            (size_t)(n_pairs * n_win) * sizeof(pgt_fst_row), dtot, tree, tb, nullptr);
+        });
+}
+
+/* pi per population from (freq, nInd) columns: the host-buffer form, as pgt_dxy_pops_reduce with one table per population */
+int pgt_pi_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
+                       uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_dxy_row *out, pgt_dxy_total *tot) {
+    PGT_USE_DEVICE(ctx);
+    if (n_pops < 1 || n_pops > (uint32_t)kPiPopsMaxPops) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: n_pops must be 1 ... 8");
+    if (minind < 1) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: minind must be at least 1");
+    if (!freq || !nind || (n && !pos) || (n_win && (!win || !out))) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: NULL argument");
+    for (uint32_t k = 0; k < n_pops; ++k)
+        if (n && (!freq[k] || !nind[k])) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: NULL column");
+    ApiTrace trace("pgt_pi_pops_reduce");
+    if (n_win > UINT64_MAX / n_pops / sizeof(pgt_dxy_row)) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: n_pops * n_win overflows");
+    DevBuf dpos, df[kPiPopsMaxPops], dn[kPiPopsMaxPops];
+    UploadJob jobs[1 + 2 * kPiPopsMaxPops];
+    int n_jobs = 0;
+    jobs[n_jobs++] = {&dpos, pos, n * sizeof(uint32_t), "upload pos"};
+    for (uint32_t k = 0; k < n_pops; ++k) {
+        jobs[n_jobs++] = {&df[k], freq[k], n * sizeof(double), "upload freq"};
+        jobs[n_jobs++] = {&dn[k], nind[k], n * sizeof(int32_t), "upload nind"};
+    }
+    if (int rc = upload_columns(ctx, jobs, n_jobs, trace)) return rc;
+    const double *pf[kPiPopsMaxPops];
+    const int32_t *pn[kPiPopsMaxPops];
+    for (uint32_t k = 0; k < n_pops; ++k) { pf[k] = static_cast<double *>(df[k].p); pn[k] = static_cast<int32_t *>(dn[k].p); }
+    const size_t row_bytes = (size_t)((uint64_t)n_pops * n_win) * sizeof(pgt_dxy_row);
+    return reduce_tables_with_workspace<pgt_dxy_row>(ctx, "pgt_pi_pops_reduce", pgt_pi_pops_tree_bytes(n_pops, n), n_pops, n, win, n_win, out,
+        row_bytes, tot, [&](const pgt_win *dw, pgt_dxy_row *dr, void *tree, size_t tb, pgt_dxy_total *dtot) {
+            return pgt_pi_pops_reduce_dev(ctx, static_cast<uint32_t *>(dpos.p), pf, pn, n_pops, n, minind, dw, n_win, dr, row_bytes, dtot,
+                                          tree, tb, nullptr);
         });
 }
 

@@ -171,6 +171,7 @@ inline DxyPopsTree dxy_pops_tree_view(const TreeLayout &t, int n_pairs, void *tr
 // The shape of DxyPopsTree with two sums per pair: a node is 2 P doubles (Σa of pair 0 .. P-1, then Σ(a+b) of pair 0 .. P-1)
 // and P u32 (neff); a level holds the two arrays node-major.  Behind the levels one {Σa, Σ(a+b), neff} per pair and build wave.
 constexpr int kFstPopsMaxPops = 8;
+constexpr int kPiPopsMaxPops = 8;  // pi per population (pgt_kernels.hip: pi_build_kernel, PiTraits): 1 ... 8 trees of the dxy layout
 constexpr int kFstPopsLeafPieces = 4;  // 128-site pieces per level-1 node
 struct FstPopsTree {
     char *base;
@@ -272,6 +273,13 @@ int launch_fst_pops(const uint32_t *pos, const double *const *freq, const int32_
                     uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_fst_row *out, pgt_fst_total *tot,
                     void *tree, void *stream, void *ev_build0, void *ev_build1, void *ev_query1, std::string *err,
                     const Hints &hints);
+
+// pgt_kernels.hip: pi per population, 1 <= n_pops <= 8 and minind >= 1 (checked by the caller); out = n_pops tables of
+// n_win rows, tot = n_pops device totals or NULL; tree = n_pops trees of tree_layout(PGT_STAT_DXY, n).bytes each
+int launch_pi_pops(const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
+                   uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_dxy_row *out, pgt_dxy_total *tot,
+                   void *tree, void *stream, void *ev_build0, void *ev_build1, void *ev_query1, std::string *err,
+                   const Hints &hints);
 
 // pgt_align_kernels.hip: the sites common to K position columns (pgt_sites_align) and the gather behind it.
 // The workspace, every part 256-byte aligned: the plan (segments as u32 pairs, first tile per chromosome), the first output

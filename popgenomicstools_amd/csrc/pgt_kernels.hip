@@ -461,6 +461,122 @@ __global__ __launch_bounds__(256) void dxy_build_kernel(const double *p1, const 
     dxy_build_body<>(p1, p2, n1, n2, n, minind, n_l2, tv, lds_stage);
 }
 
+// ------------------------------------------------------------------------------------------
+// BUILD, pi (within-population nucleotide diversity; no counterpart in the reference): per site of ONE population
+//     counted = nind >= minind;  c = (2 nind) / (2 nind - 1);  h = (2 p) (1 - p);  pi = h c
+// every operation rounded on its own (include/pgtwin.h, pgt_pi_pops_reduce_dev), an uncounted site selected away, then
+// level-1 {Σpi, neff, nskip} per 128 sites.  grid.y = population: a y-slice streams one population's freq (f64) and
+// nind (i32), 12 B/site, into that population's own tree (pair_stride apart), so a population's nodes do not depend on
+// which others are in the launch.
+// The count is needed as a VALUE here (dxy needs only its predicate, see count_pair_pred), so a lane owns FOUR CONSECUTIVE
+// sites of a PAIR of leaf tiles j, j+1 (j even): one 16-byte load of nind and two of freq per lane, lane L = sites
+// 4L .. 4L+3 of the pair's 256.  Lanes 0-31 hold leaf tile j, lanes 32-63 leaf tile j+1: the sums are five butterfly
+// steps inside each half, the counts four ballots.  The schedule is the dxy build's: batches of four leaf tiles, freq's four
+// kibibytes requested and awaited before nind's two, the walk rotated per wave, node rows deferred through the LDS stage,
+// the static balanced grid, one partial sum per wave for the genome-wide line.  The ACCESS PATTERN is not: a lane's two freq
+// loads are 32 bytes apart, so one wave instruction touches every other 16 bytes of 2 KiB and needs its twin to use the
+// whole cache lines (every other build issues one contiguous KiB per instruction).  Measured once, interleaved with the dxy
+// build in one process (profiles/r10/pi_pops.md, 10^8 sites): 0.667 / 0.694 / 0.698 of the HBM peak on 12 K B/site at
+// K = 1 / 4 / 8 against the dxy build's 0.813 on 24 B/site — that pattern is the likely cause, the IEEE division per site
+// (about 20 instructions on 12 bytes) the second candidate; no A/B has separated them and nothing was tuned.
+// ------------------------------------------------------------------------------------------
+struct PopCols {
+    const double *f[kPiPopsMaxPops];
+    const int32_t *n[kPiPopsMaxPops];
+};
+__device__ __forceinline__ double pi_site(double p, int n) {
+    const double two_n = __dmul_rn(2.0, (double)n);
+    const double c = __ddiv_rn(two_n, __dsub_rn(two_n, 1.0));  // 2n - 1 is odd: never 0
+    return __dmul_rn(__dmul_rn(__dmul_rn(2.0, p), __dsub_rn(1.0, p)), c);
+}
+__device__ __forceinline__ void pi_acc(NodeDxy &acc, double p, int n, int minind) {
+    const double v = pi_site(p, n);
+    if (n >= minind) { acc.s += v; acc.neff += 1; }  // a select: the value of an uncounted site (NaN, say) is never used
+    else acc.nskip += 1;
+}
+__device__ __forceinline__ double half_wave_sum(double v) {  // lanes 0-31 and lanes 32-63 each among themselves
+    v += dpp_f64<kDppQuadXor1>(v);
+    v += dpp_f64<kDppQuadXor2>(v);
+    v += dpp_f64<kDppRowHalfMirror>(v);
+    v += dpp_f64<kDppRowMirror>(v);
+    v += __shfl_xor(v, 16, kWave);
+    return v;
+}
+template <int SRC>
+__device__ __forceinline__ double readlane_f64(double v) {  // wave-uniform
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), SRC), __builtin_amdgcn_readlane(__double2loint(v), SRC));
+}
+
+template <int U = 4>  // leaf tiles per batch (even)
+__global__ __launch_bounds__(256) void pi_build_kernel(PopCols cols, uint64_t n, int minind, uint64_t n_l2, TreeView tv) {
+    static_assert(U % 2 == 0, "the columns are read per PAIR of leaf tiles");
+    extern __shared__ __attribute__((aligned(16))) char lds_stage[];
+    const int lane = threadIdx.x & (kWave - 1);
+    const uint64_t wave0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    const double *__restrict__ f = cols.f[blockIdx.y];
+    const int32_t *__restrict__ ni = cols.n[blockIdx.y];
+    char *tree = tv.base + (size_t)blockIdx.y * tv.pair_stride;
+    NodeDxy *__restrict__ l1 = reinterpret_cast<NodeDxy *>(tree + tv.off[0]);
+    NodeDxy *__restrict__ l2 = reinterpret_cast<NodeDxy *>(tree + tv.off[1]);
+    constexpr uint64_t kTile2 = (uint64_t)kLeafF64 * kRadix;
+    NodeStage<NodeDxy, kFstStage, true> stage(lds_stage, threadIdx.x >> 6, lane, l1, l2, n_waves);  // deferred node stores
+
+    for (uint64_t t = wave0; t < n_l2; t += n_waves) {
+        const uint64_t base = t * kTile2;
+        NodeDxy keep{0.0, 0u, 0u};
+        if (base + kTile2 <= n) {
+            const double2 *__restrict__ q = reinterpret_cast<const double2 *>(f + base);
+            const int4 *__restrict__ m = reinterpret_cast<const int4 *>(ni + base);  // base is a multiple of 8192: 16-byte aligned
+            const int rot = tile_rotation<U>(wave0);  // see fst_column_sums
+#pragma unroll 1
+            for (int j0 = 0; j0 < kRadix; j0 += U) {
+                const int j = (j0 + rot) & (kRadix - 1);
+                double2 x[U];  // x[2u], x[2u+1]: sites 4L, 4L+1 and 4L+2, 4L+3 of the pair of leaf tiles j+2u, j+2u+1
+                int4 k[U / 2];
+#pragma unroll
+                for (int u = 0; u < U; ++u) x[u] = load16<true>(q + (j + (u & ~1)) * kWave + 2 * lane + (u & 1));
+                load_fence(x[U - 1].y);
+#pragma unroll
+                for (int u = 0; u < U / 2; ++u) k[u] = load16_nt(m + (j / 2 + u) * kWave + lane);
+#pragma unroll
+                for (int u = 0; u < U / 2; ++u) {
+                    // the lane's four sites in site order, an uncounted one selected away; the counts come from the ballots below
+                    double part = 0.0;
+                    part += k[u].x >= minind ? pi_site(x[2 * u].x, k[u].x) : 0.0;
+                    part += k[u].y >= minind ? pi_site(x[2 * u].y, k[u].y) : 0.0;
+                    part += k[u].z >= minind ? pi_site(x[2 * u + 1].x, k[u].z) : 0.0;
+                    part += k[u].w >= minind ? pi_site(x[2 * u + 1].y, k[u].w) : 0.0;
+                    const unsigned long long c0 = __ballot(k[u].x >= minind), c1 = __ballot(k[u].y >= minind),
+                                             c2 = __ballot(k[u].z >= minind), c3 = __ballot(k[u].w >= minind);
+                    const uint32_t neff0 = (uint32_t)(__popc((uint32_t)c0) + __popc((uint32_t)c1) + __popc((uint32_t)c2) + __popc((uint32_t)c3));
+                    const uint32_t neff1 = (uint32_t)(__popc((uint32_t)(c0 >> 32)) + __popc((uint32_t)(c1 >> 32)) +
+                                                      __popc((uint32_t)(c2 >> 32)) + __popc((uint32_t)(c3 >> 32)));
+                    const double s = half_wave_sum(part);
+                    const double s0 = readlane_f64<0>(s), s1 = readlane_f64<32>(s);
+                    if (lane == j + 2 * u) keep = NodeDxy{s0, neff0, (uint32_t)kLeafF64 - neff0};
+                    if (lane == j + 2 * u + 1) keep = NodeDxy{s1, neff1, (uint32_t)kLeafF64 - neff1};
+                }
+            }
+        } else {  // the last, partial tile: site by site, sites beyond n count as nothing
+            for (int j = 0; j < kRadix; ++j) {
+                const uint64_t tile0 = base + (uint64_t)j * kLeafF64;
+                if (tile0 >= n) break;  // wave-uniform
+                NodeDxy acc{0.0, 0u, 0u};
+                for (int q = 0; q < 2; ++q) {
+                    const uint64_t i = tile0 + 2 * lane + q;
+                    if (i < n) pi_acc(acc, f[i], ni[i], minind);
+                }
+                acc = node_wave_sum(acc);
+                if (lane == j) keep = acc;
+            }
+        }
+        stage.put(t, keep);
+    }
+    stage.flush();
+    if (lane == 0) reinterpret_cast<NodeDxy *>(tree + tv.partials)[wave0] = stage.sum;  // the genome-wide line: see dxy_build_body
+}
+
 // BASELINE config 3: dxyWindow + hetWindow (two genotype columns) over one position column and one
 // window table — ONE stream of 26 B/site (p1,p2 f64 + n1,n2 i32 + g1,g2 i8).  The wave that owns level-2
 // tile t of the dxy tree (8192 sites) also owns the SAME 8192 sites of both genotype columns: that is
@@ -813,6 +929,44 @@ struct DxyTraits {
     }
 };
 
+// pi per population: the batch index of the generic queries (blockIdx.y) is the population
+struct PiTraits {
+    using Node = NodeDxy;
+    using Row = pgt_dxy_row;
+    static constexpr int kLeaf = kLeafF64;
+    struct Args { PopCols cols; int minind; };
+    struct Cols { const double *f; const int32_t *n; int minind; };
+    static __device__ __forceinline__ Cols cols(const Args &g, int pop) { return {g.cols.f[pop], g.cols.n[pop], g.minind}; }
+    static __device__ __forceinline__ Node leaf(const Cols &c, uint64_t i) {
+        Node v{0.0, 0u, 0u};
+        pi_acc(v, c.f[i], c.n[i], c.minind);
+        return v;
+    }
+    static __device__ __forceinline__ void leaf_pair(const Cols &c, uint64_t i0, Node &v0, Node &v1) {  // i0 even
+        const double2 x = *reinterpret_cast<const double2 *>(c.f + i0);
+        const int2 k = *reinterpret_cast<const int2 *>(c.n + i0);
+        v0 = Node{0.0, 0u, 0u};
+        v1 = Node{0.0, 0u, 0u};
+        pi_acc(v0, x.x, k.x, c.minind);
+        pi_acc(v1, x.y, k.y, c.minind);
+    }
+    static __device__ __forceinline__ void sum_sites(Node &acc, const Cols &c, uint64_t from, uint64_t to, int lane,
+                                                     uint64_t) {
+        for (uint64_t i = from + lane; i < to; i += kWave) node_add(acc, leaf(c, i));
+    }
+    static __device__ __forceinline__ void finish(Row *out, const Node &t, uint32_t start, uint32_t end,
+                                                  uint64_t, uint64_t, const Cols &, const uint32_t *) {
+        Row r;
+        r.start = start;
+        r.end = end;
+        r.neff = t.neff;
+        r.nskip = t.nskip;
+        r.sum = t.s + 0.0;
+        *out = r;
+    }
+    static __device__ __forceinline__ void store_total(pgt_dxy_total *tot, const Node &t) { DxyTraits::store_total(tot, t); }
+};
+
 struct ExtTraits {
     using Node = NodeExt;
     using Row = pgt_ext_row;
@@ -1157,7 +1311,7 @@ __device__ __forceinline__ void query_body(const typename Tr::Args &args, const 
         }
         if (is_total) {  // wave-uniform
             const typename Tr::Node acc = node_wave_sum(total_partial<Tr>(tree, tv, lane));
-            if (lane == 0) Tr::store_total(tot, acc);
+            if (lane == 0) Tr::store_total(tot + pair, acc);  // one line per batch entry (pair is 0 wherever a total is asked for, but for pi)
             continue;
         }
         // clamp to the columns so that a corrupt table can never fault the GPU
@@ -1294,7 +1448,7 @@ __device__ __forceinline__ void query_slide_body(const typename Tr::Args &args, 
     for (uint64_t task = wave0; task < n_tasks; task += n_waves) {
         if (task == n_groups) {  // the genome-wide total (dxy)
             const Node acc = node_wave_sum(total_partial<Tr>(tree, tv, lane));
-            if (lane == 0) Tr::store_total(tot, acc);
+            if (lane == 0) Tr::store_total(tot + pair, acc);  // one line per batch entry (pair is 0 wherever a total is asked for, but for pi)
             continue;
         }
         const uint64_t w = task * group + (uint64_t)lane;
@@ -1440,7 +1594,7 @@ __device__ __forceinline__ void query_group_body(const typename Tr::Args &args, 
     for (uint64_t task = wave0; task < n_tasks; task += n_waves) {
         if (task == n_groups) {  // the genome-wide total (dxy)
             const Node acc = node_wave_sum(total_partial<Tr>(tree, tv, lane));
-            if (lane == 0) Tr::store_total(tot, acc);
+            if (lane == 0) Tr::store_total(tot + pair, acc);  // one line per batch entry (pair is 0 wherever a total is asked for, but for pi)
             continue;
         }
         const uint64_t w = task * group + (uint64_t)lane;
@@ -1803,7 +1957,7 @@ int launch_windows_from_plan(const RunPlan *d_plan, uint64_t n_runs, uint64_t n_
 // attribute call can fall inside a caller's stream capture.
 int init_kernels(std::string *err) {  // per pgt_open, i.e. per device: function attributes are per device
     const void *staged[] = {reinterpret_cast<const void *>(fst_build_kernel<>),
-                            reinterpret_cast<const void *>(dxy_build_kernel),
+                            reinterpret_cast<const void *>(dxy_build_kernel), reinterpret_cast<const void *>(pi_build_kernel<>),
                             reinterpret_cast<const void *>(ext_build_kernel<>), reinterpret_cast<const void *>(ext_build_kernel<kExtStageSmall, 2, true>)};
     for (const void *k : staged)
         if (int rc = hip_fail(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFstStageBytes),
@@ -1946,6 +2100,43 @@ int launch_dxy(const uint32_t *pos, const double *p1, const double *p2, const in
             hipLaunchKernelGGL(query_kernel<DxyTraits>, dim3(query_grid(n_win + 1)), dim3(256), 0, s, args, pos, tv,
                                win, n_win, out, n, tot);
         if (int rc = hip_fail(hipGetLastError(), "query_kernel<dxy>", err)) return rc;
+    }
+    return record(ev_query1, s, err);
+}
+
+// pi of n_pops populations (1 ... 8, checked by the caller): one build launch with grid.y = population, one tree of the
+// two-population dxy layout per population (tl.bytes apart), then the query strategy launch_dxy would choose, batched over
+// the populations; out: n_pops tables of n_win rows, tot: n_pops lines or NULL
+int launch_pi_pops(const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops, uint64_t n,
+                   int minind, const pgt_win *win, uint64_t n_win, pgt_dxy_row *out, pgt_dxy_total *tot, void *tree, void *stream,
+                   void *ev_build0, void *ev_build1, void *ev_query1, std::string *err, const Hints &hints) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const TreeLayout tl = tree_layout(PGT_STAT_DXY, n);
+    TreeView tv = make_view(tl, tree, tl.bytes, useful_levels(tl, PGT_STAT_DXY, hints.max_window));
+    PiTraits::Args args{};
+    for (uint32_t k = 0; k < n_pops; ++k) { args.cols.f[k] = freq[k]; args.cols.n[k] = nind[k]; }
+    args.minind = minind;
+    if (int rc = record(ev_build0, s, err)) return rc;
+    if (n > 0) {
+        const dim3 grid(build_grid(tl.count[1], kFstBuildBlocks), n_pops);
+        tv.n_partials = grid.x * 4;  // see launch_dxy
+        hipLaunchKernelGGL(pi_build_kernel<>, grid, dim3(256), kFstStageBytes, s, args.cols, n, minind, tl.count[1], tv);
+        if (int rc = hip_fail(hipGetLastError(), "pi_build_kernel", err)) return rc;
+        if (int rc = launch_upper<NodeDxy>(tl, tv, n_pops, s, err)) return rc;
+    }
+    if (int rc = record(ev_build1, s, err)) return rc;
+    if (n_win > 0 || tot) {
+        if (group_query(hints, kLeafF64)) {
+            const uint32_t g = group_size(n_win);
+            hipLaunchKernelGGL(query_group_kernel<PiTraits>, dim3(query_grid((n_win + g - 1) / g + 1), n_pops), dim3(256),
+                               kGroupLdsBytes, s, args, pos, tv, win, n_win, out, n, tot, g, group_edge_scans(hints));
+        } else if (const uint32_t group = slide_group(hints.window_step); group > 1)
+            hipLaunchKernelGGL(query_slide_kernel<PiTraits>, dim3(query_grid((n_win + group - 1) / group + 1), n_pops), dim3(256),
+                               kSlideLdsBytes, s, args, pos, tv, win, n_win, out, n, tot, group);
+        else
+            hipLaunchKernelGGL(query_kernel<PiTraits>, dim3(query_grid(n_win + 1), n_pops), dim3(256), 0, s, args, pos, tv, win,
+                               n_win, out, n, tot);
+        if (int rc = hip_fail(hipGetLastError(), "query_kernel<pi>", err)) return rc;
     }
     return record(ev_query1, s, err);
 }

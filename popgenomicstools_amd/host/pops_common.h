@@ -1,10 +1,12 @@
-// pops_common.h — the K-file front end the all-pairs hosts (dxyWindowPops, fstWindowPops) share: the command line
-// (dxyWindow's options, -out PREFIX, 2 ... 8 MAF files), and from the opened files to the aligned columns and the window
+// pops_common.h — the K-file front end the all-pairs hosts (dxyWindowPops, fstWindowPops) and piWindowPops share: the command
+// line (dxyWindow's options, -out PREFIX, 2 ... 8 MAF files; piWindowPops admits one), and from the opened files to the aligned columns and the window
 // table on the device — open, parse on the host or the device, the resident-size refusals, chromosome ids,
 // pgt_align_segments, upload, pgt_sites_align, pgt_gather_dev, the runs of the common sites, the window table.
 // The K-file form of the reference's site synchronisation (dxyWindow.cpp:315-331): the sites (chromosome, position) that
-// ALL files list are found on the GPU.  Messages carry the tool's name.
+// ALL files list are found on the GPU (a single file is its own site list: nothing to align).  Messages carry the tool's name.
 #pragma once
+
+#include <memory>
 
 #include "dxy_common.h"
 
@@ -33,9 +35,10 @@ struct PopsArgs {
     char **paths = nullptr;
     std::map<std::string, uint32_t> chrsize;
 };
-// option/value pairs first; what follows the last pair are the MAF files.  help(opt) prints the tool's usage (no argument: exit 0)
+// option/value pairs first; what follows the last pair are the MAF files (min_files ... 8 of them).  help(opt) prints the tool's
+// usage (no argument: exit 0)
 template <class Help>
-inline PopsArgs parse_pops_args(const std::string &tool, int argc, char **argv, Help help) {
+inline PopsArgs parse_pops_args(const std::string &tool, int argc, char **argv, Help help, int min_files = 2) {
     PopsArgs a;
     if (argc < 2) {
         help(a.opt);
@@ -50,7 +53,8 @@ inline PopsArgs parse_pops_args(const std::string &tool, int argc, char **argv, 
     }
     a.K = argc - i;
     a.paths = argv + i;
-    if (a.K < 2 || a.K > 8) die(tool + ": between 2 and 8 MAF files are needed (" + std::to_string(std::max(a.K, 0)) + " given)");
+    if (a.K < min_files || a.K > 8)
+        die(tool + ": between " + std::to_string(min_files) + " and 8 MAF files are needed (" + std::to_string(std::max(a.K, 0)) + " given)");
     if (!a.prefix || !*a.prefix) die("Must supply -out PREFIX");
     check_dxy_options(a.opt);
     if (!a.opt.fixedsite) a.chrsize = read_sizefile(a.opt.sizefile);
@@ -63,12 +67,13 @@ inline PopsArgs parse_pops_args(const std::string &tool, int argc, char **argv, 
 struct PopsSites {
     pgt_ctx *ctx = nullptr;
     uint64_t n_sites = 0;
-    uint32_t *a_pos = nullptr;
+    const uint32_t *a_pos = nullptr;
     std::vector<const double *> a_freq;
     std::vector<const int32_t *> a_nind;
     Runs runs;
     std::vector<pgt_win> win;
     pgt_win *d_win = nullptr;
+    std::shared_ptr<std::vector<PopsMaf>> single;  // ONE file: the parsed file, owner of the device columns above (else empty)
 };
 
 inline PopsSites load_pops(const std::string &tool, const PopsArgs &args, PhaseTimer &timer, DeviceOpener &device) {
@@ -101,10 +106,14 @@ inline PopsSites load_pops(const std::string &tool, const PopsArgs &args, PhaseT
         smallest = std::min(smallest, text[(size_t)k]->size());
         if (text[(size_t)k]->size() > text[largest_k]->size()) largest_k = (size_t)k;
     }
-    if (!resident_env && resident_limit(text[largest_k]->begin(), text[largest_k]->end(), (size_t)K * 40, [&] { return device.get(); }, K))
-        die(tool + ": the MAF files and their aligned columns do not fit the GPU; this tool has no passes mode");
+    // ONE file is not aligned: only its parsed columns (16 B per site) live on the card.
+    const size_t site_bytes = K == 1 ? (size_t)16 : (size_t)K * 40;
+    if (!resident_env && resident_limit(text[largest_k]->begin(), text[largest_k]->end(), site_bytes, [&] { return device.get(); }, K))
+        die(tool + (K == 1 ? ": the MAF file does not fit the GPU; this tool has no passes mode"
+                           : ": the MAF files and their aligned columns do not fit the GPU; this tool has no passes mode"));
 
-    std::vector<Maf> maf((size_t)K);
+    auto files = std::make_shared<std::vector<Maf>>((size_t)K);
+    std::vector<Maf> &maf = *files;
     pgt_ctx *ctx = nullptr;
     const bool on_gpu = gpu_ingest_wanted(smallest);
     if (on_gpu) {
@@ -139,48 +148,53 @@ inline PopsSites load_pops(const std::string &tool, const PopsArgs &args, PhaseT
     for (int k = 1; k < K; ++k)
         if (maf[(size_t)k].runs.name[0] != maf[0].runs.name[0]) die("Chromosomes in MAF files differ");  // dxyWindow.cpp:295-298
 
-    // chromosome names -> ids (equal names, equal ids), then the segments of the chromosomes every file has
-    std::map<std::string, uint32_t> id_of;
-    std::vector<std::string> name_of;
-    std::vector<std::vector<uint32_t>> run_chr((size_t)K);
-    std::vector<const uint32_t *> p_chr((size_t)K);
-    std::vector<const uint64_t *> p_len((size_t)K);
-    std::vector<size_t> n_runs((size_t)K);
-    for (int k = 0; k < K; ++k) {
-        const Runs &r = maf[(size_t)k].runs;
-        for (const std::string &nm : r.name) {
-            auto it = id_of.insert({nm, (uint32_t)name_of.size()});
-            if (it.second) name_of.push_back(nm);
-            run_chr[(size_t)k].push_back(it.first->second);
-        }
-        p_chr[(size_t)k] = run_chr[(size_t)k].data();
-        p_len[(size_t)k] = r.len.data();
-        n_runs[(size_t)k] = r.len.size();
-    }
-    size_t n_seg = 0;
-    int rc = pgt_align_segments(p_chr.data(), p_len.data(), n_runs.data(), (uint32_t)K, nullptr, 0, &n_seg);
-    std::vector<pgt_seg> seg(n_seg);
-    if (rc == PGT_OK && n_seg) rc = pgt_align_segments(p_chr.data(), p_len.data(), n_runs.data(), (uint32_t)K, seg.data(), seg.size(), &n_seg);
-    if (rc == PGT_EDOMAIN) {  // the library names the id; the user knows the name
-        const std::string msg = pgt_last_error(nullptr);
-        const char *tag = "chromosome id ";
-        const size_t at = msg.find(tag);
-        const size_t id = at == std::string::npos ? name_of.size() : (size_t)std::strtoull(msg.c_str() + at + std::strlen(tag), nullptr, 10);
-        if (id >= name_of.size()) die(tool + ": " + msg);
-        die(tool + ": chromosome " + name_of[id] + (msg.find("two runs") != std::string::npos
-                ? " appears in two separate blocks of a MAF file"
-                : " is not in the same order in all MAF files") + " (all MAF files need the same chromosomes in the same order)");
-    }
-    check(rc, nullptr);
-    const size_t n_chr = n_seg / (size_t)K;
+    // K >= 2: the sites all files share are found on the GPU (pgt_sites_align is defined for 2 ... 8 files); ONE file is its own
+    // site list: its columns and runs are used as they are
+    std::vector<pgt_seg> seg;
+    size_t n_seg = 0, n_chr = 0;
     uint64_t cap = 0;  // no chromosome has more common sites than its shortest list
-    for (size_t m = 0; m < n_chr; ++m) {
-        uint64_t least = UINT64_MAX;
-        for (int k = 0; k < K; ++k) least = std::min(least, seg[m * (size_t)K + (size_t)k].len);
-        cap += least;
+    if (K > 1) {
+        // chromosome names -> ids (equal names, equal ids), then the segments of the chromosomes every file has
+        std::map<std::string, uint32_t> id_of;
+        std::vector<std::string> name_of;
+        std::vector<std::vector<uint32_t>> run_chr((size_t)K);
+        std::vector<const uint32_t *> p_chr((size_t)K);
+        std::vector<const uint64_t *> p_len((size_t)K);
+        std::vector<size_t> n_runs((size_t)K);
+        for (int k = 0; k < K; ++k) {
+            const Runs &r = maf[(size_t)k].runs;
+            for (const std::string &nm : r.name) {
+                auto it = id_of.insert({nm, (uint32_t)name_of.size()});
+                if (it.second) name_of.push_back(nm);
+                run_chr[(size_t)k].push_back(it.first->second);
+            }
+            p_chr[(size_t)k] = run_chr[(size_t)k].data();
+            p_len[(size_t)k] = r.len.data();
+            n_runs[(size_t)k] = r.len.size();
+        }
+        int rc = pgt_align_segments(p_chr.data(), p_len.data(), n_runs.data(), (uint32_t)K, nullptr, 0, &n_seg);
+        seg.resize(n_seg);
+        if (rc == PGT_OK && n_seg) rc = pgt_align_segments(p_chr.data(), p_len.data(), n_runs.data(), (uint32_t)K, seg.data(), seg.size(), &n_seg);
+        if (rc == PGT_EDOMAIN) {  // the library names the id; the user knows the name
+            const std::string msg = pgt_last_error(nullptr);
+            const char *tag = "chromosome id ";
+            const size_t at = msg.find(tag);
+            const size_t id = at == std::string::npos ? name_of.size() : (size_t)std::strtoull(msg.c_str() + at + std::strlen(tag), nullptr, 10);
+            if (id >= name_of.size()) die(tool + ": " + msg);
+            die(tool + ": chromosome " + name_of[id] + (msg.find("two runs") != std::string::npos
+                    ? " appears in two separate blocks of a MAF file"
+                    : " is not in the same order in all MAF files") + " (all MAF files need the same chromosomes in the same order)");
+        }
+        check(rc, nullptr);
+        n_chr = n_seg / (size_t)K;
+        for (size_t m = 0; m < n_chr; ++m) {
+            uint64_t least = UINT64_MAX;
+            for (int k = 0; k < K; ++k) least = std::min(least, seg[m * (size_t)K + (size_t)k].len);
+            cap += least;
+        }
+        if (cap == 0) die(tool + ": the MAF files share no site");
+        timer.lap("segments");
     }
-    if (cap == 0) die(tool + ": the MAF files share no site");
-    timer.lap("segments");
 
     if (!ctx) {
         ctx = device.get();
@@ -199,46 +213,57 @@ inline PopsSites load_pops(const std::string &tool, const PopsArgs &args, PhaseT
     }
     if (!on_gpu) timer.lap("upload");
 
-    // the common sites: one index column per file, then every column gathered onto them
-    std::vector<const uint32_t *> d_pos((size_t)K);
-    std::vector<uint64_t> rows_of((size_t)K);
-    std::vector<uint32_t *> d_idx((size_t)K);
-    for (int k = 0; k < K; ++k) {
-        d_pos[(size_t)k] = maf[(size_t)k].d_pos;
-        rows_of[(size_t)k] = maf[(size_t)k].n;
-        d_idx[(size_t)k] = pops_dev_alloc<uint32_t>(ctx, cap);
-    }
-    const size_t work_bytes = pgt_align_workspace_bytes((uint32_t)K, rows_of[0]);
-    void *work = nullptr;
-    check(pgt_dev_alloc(ctx, work_bytes, &work), ctx);
-    std::vector<uint64_t> seg_count(n_chr, 0);
     uint64_t n_sites = 0;
-    check(pgt_sites_align(ctx, d_pos.data(), rows_of.data(), (uint32_t)K, seg.data(), n_seg, d_idx.data(), cap, seg_count.data(), &n_sites,
-                          work, work_bytes, nullptr), ctx);
-    check(pgt_dev_free(ctx, work), ctx);
-    if (n_sites == 0) die(tool + ": the MAF files share no site");
-    uint32_t *a_pos = pops_dev_alloc<uint32_t>(ctx, n_sites);
+    const uint32_t *a_pos = nullptr;
     std::vector<const double *> a_freq((size_t)K);
     std::vector<const int32_t *> a_nind((size_t)K);
-    check(pgt_gather_dev(ctx, a_pos, d_pos[0], d_idx[0], n_sites, 4, nullptr), ctx);
-    for (int k = 0; k < K; ++k) {
-        double *f = pops_dev_alloc<double>(ctx, n_sites);
-        int32_t *c = pops_dev_alloc<int32_t>(ctx, n_sites);
-        check(pgt_gather_dev(ctx, f, maf[(size_t)k].d_freq, d_idx[(size_t)k], n_sites, 8, nullptr), ctx);
-        check(pgt_gather_dev(ctx, c, maf[(size_t)k].d_nind, d_idx[(size_t)k], n_sites, 4, nullptr), ctx);
-        a_freq[(size_t)k] = f;
-        a_nind[(size_t)k] = c;
-    }
-    Runs runs;  // chromosomes left with no common site are dropped (as the dxyWindow host does)
-    for (size_t m = 0; m < n_chr; ++m) {
-        if (!seg_count[m]) continue;
-        // the matched chromosome's name: file 0's run that starts at its segment
-        const Runs &r0 = maf[0].runs;
-        uint64_t off = 0;
-        size_t r = 0;
-        while (off != seg[m * (size_t)K].off || r0.len[r] != seg[m * (size_t)K].len) off += r0.len[r++];
-        runs.name.push_back(r0.name[r]);
-        runs.len.push_back(seg_count[m]);
+    std::vector<uint32_t *> d_idx;
+    Runs runs;
+    if (K == 1) {
+        n_sites = maf[0].n;
+        a_pos = maf[0].d_pos;
+        a_freq[0] = maf[0].d_freq;
+        a_nind[0] = maf[0].d_nind;
+        runs = maf[0].runs;
+    } else {
+        // the common sites: one index column per file, then every column gathered onto them
+        std::vector<const uint32_t *> d_pos((size_t)K);
+        std::vector<uint64_t> rows_of((size_t)K);
+        d_idx.resize((size_t)K);
+        for (int k = 0; k < K; ++k) {
+            d_pos[(size_t)k] = maf[(size_t)k].d_pos;
+            rows_of[(size_t)k] = maf[(size_t)k].n;
+            d_idx[(size_t)k] = pops_dev_alloc<uint32_t>(ctx, cap);
+        }
+        const size_t work_bytes = pgt_align_workspace_bytes((uint32_t)K, rows_of[0]);
+        void *work = nullptr;
+        check(pgt_dev_alloc(ctx, work_bytes, &work), ctx);
+        std::vector<uint64_t> seg_count(n_chr, 0);
+        check(pgt_sites_align(ctx, d_pos.data(), rows_of.data(), (uint32_t)K, seg.data(), n_seg, d_idx.data(), cap, seg_count.data(), &n_sites,
+                              work, work_bytes, nullptr), ctx);
+        check(pgt_dev_free(ctx, work), ctx);
+        if (n_sites == 0) die(tool + ": the MAF files share no site");
+        uint32_t *g_pos = pops_dev_alloc<uint32_t>(ctx, n_sites);
+        a_pos = g_pos;
+        check(pgt_gather_dev(ctx, g_pos, d_pos[0], d_idx[0], n_sites, 4, nullptr), ctx);
+        for (int k = 0; k < K; ++k) {
+            double *f = pops_dev_alloc<double>(ctx, n_sites);
+            int32_t *c = pops_dev_alloc<int32_t>(ctx, n_sites);
+            check(pgt_gather_dev(ctx, f, maf[(size_t)k].d_freq, d_idx[(size_t)k], n_sites, 8, nullptr), ctx);
+            check(pgt_gather_dev(ctx, c, maf[(size_t)k].d_nind, d_idx[(size_t)k], n_sites, 4, nullptr), ctx);
+            a_freq[(size_t)k] = f;
+            a_nind[(size_t)k] = c;
+        }
+        for (size_t m = 0; m < n_chr; ++m) {  // chromosomes left with no common site are dropped (as the dxyWindow host does)
+            if (!seg_count[m]) continue;
+            // the matched chromosome's name: file 0's run that starts at its segment
+            const Runs &r0 = maf[0].runs;
+            uint64_t off = 0;
+            size_t r = 0;
+            while (off != seg[m * (size_t)K].off || r0.len[r] != seg[m * (size_t)K].len) off += r0.len[r++];
+            runs.name.push_back(r0.name[r]);
+            runs.len.push_back(seg_count[m]);
+        }
     }
     timer.lap("align");
 
@@ -257,7 +282,7 @@ inline PopsSites load_pops(const std::string &tool, const PopsArgs &args, PhaseT
     timer.lap("window table");
 
     const size_t n_win = win.size();
-    for (int k = 0; k < K; ++k) check(pgt_dev_free(ctx, d_idx[(size_t)k]), ctx);
+    for (uint32_t *idx : d_idx) check(pgt_dev_free(ctx, idx), ctx);
     pgt_win *d_win = pops_dev_alloc<pgt_win>(ctx, n_win);
     check(pgt_dev_upload(ctx, d_win, win.data(), n_win * sizeof(pgt_win)), ctx);
     PopsSites r;
@@ -269,6 +294,7 @@ inline PopsSites load_pops(const std::string &tool, const PopsArgs &args, PhaseT
     r.runs = std::move(runs);
     r.win = std::move(win);
     r.d_win = d_win;
+    if (K == 1) r.single = std::move(files);  // a_pos / a_freq / a_nind are that file's own columns: it lives as long as they are used
     return r;
 }
 

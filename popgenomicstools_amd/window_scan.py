@@ -391,6 +391,27 @@ class Context:
                                                   win.ctypes.data, win.size, out.ctypes.data, tot.ctypes.data))
         return out, tot
 
+    def pi_pops_reduce(self, pos, freqs, ninds, minind, win):
+        """Nucleotide-diversity (pi) rows of EACH of len(freqs) populations (1 ... 8) from per-population numpy (freq, nInd)
+        columns, one pass: -> (rows[n_pops, n_win], totals[n_pops]) (pgt_pi_pops_reduce).  A row's sum is Σ 2p(1-p) 2n/(2n-1) over
+        its counted sites (nInd >= minind); divide by neff or by the window length."""
+        pos = np.ascontiguousarray(pos, dtype=np.uint32)
+        freqs = [np.ascontiguousarray(f, dtype=np.float64) for f in freqs]
+        ninds = [np.ascontiguousarray(k, dtype=np.int32) for k in ninds]
+        win = np.ascontiguousarray(win, dtype=WIN_DTYPE)
+        n_pops = len(freqs)
+        if len(ninds) != n_pops or not 1 <= n_pops <= 8:
+            raise PgtError(_lib.PGT_EARG, "pi_pops_reduce: 1 ... 8 populations, one frequency and one count column each")
+        if any(c.size != pos.size for c in freqs + ninds):
+            raise PgtError(_lib.PGT_EARG, "pi_pops_reduce: column lengths differ")
+        out = np.zeros((n_pops, win.size), dtype=DXY_ROW_DTYPE)
+        tot = np.zeros(n_pops, dtype=DXY_TOTAL_DTYPE)
+        pf = (C.c_void_p * n_pops)(*[f.ctypes.data for f in freqs])
+        pn = (C.c_void_p * n_pops)(*[k.ctypes.data for k in ninds])
+        self._check(self._lib.pgt_pi_pops_reduce(self._ctx, pos.ctypes.data, pf, pn, n_pops, pos.size, int(minind),
+                                                 win.ctypes.data, win.size, out.ctypes.data, tot.ctypes.data))
+        return out, tot
+
     # ---- device-resident columns (torch CUDA tensors) -------------------------------------
     @staticmethod
     def _stream(stream):
@@ -744,6 +765,46 @@ class Context:
         pf = (C.c_void_p * n_pops)(*[self._col(t, torch.float64, f"freqs[{k}]") for k, t in enumerate(freqs)])
         pn = (C.c_void_p * n_pops)(*[self._col(t, torch.int32, f"ninds[{k}]") for k, t in enumerate(ninds)])
         self._check(self._lib.pgt_fst_pops_reduce_dev(
+            self._ctx, self._dev(pos, torch.int32, "pos"), pf, pn, n_pops, n, int(minind),
+            self._dev(win, torch.uint8, "win") if n_win else None, n_win,
+            self._dev(out, torch.uint8, "out") if n_win else None, out.numel(),
+            self._dev(tot, torch.uint8, "tot") if tot is not None else None,
+            self._dev(tree, torch.uint8, "tree"), tree.numel(), self._stream(stream)))
+        return out, tot, tree
+
+    @staticmethod
+    def pi_pops_tree_bytes(n_pops: int, n_sites: int) -> int:
+        return int(_lib.load().pgt_pi_pops_tree_bytes(int(n_pops), int(n_sites)))
+
+    def pi_pops_reduce_dev(self, pos, freqs, ninds, minind, win, out=None, tot=None, tree=None, stream=None):
+        """Nucleotide-diversity (pi) rows of EACH of len(freqs) populations (1 ... 8; population-major) in one pass over the
+        populations' own (freq, nInd) columns.  freqs: float64 CUDA tensors, ninds: int32 CUDA tensors.  tot: None = a fresh
+        buffer of n_pops totals is allocated and filled; False = no genome-wide lines.  All three hints of the context are
+        honoured (the query strategies of dxy_reduce_dev).  Returns (out, tot, tree).  Asynchronous on `stream`."""
+        import torch
+        n_pops = len(freqs)
+        if len(ninds) != n_pops or not 1 <= n_pops <= 8:
+            raise PgtError(_lib.PGT_EARG, "pi_pops_reduce_dev: 1 ... 8 populations, one frequency and one count column each")
+        n = freqs[0].numel()
+        n_win = win.numel() // WIN_DTYPE.itemsize
+        tb = self.pi_pops_tree_bytes(n_pops, n)
+        dev = pos.device
+        if tree is None:
+            tree = torch.empty(tb, dtype=torch.uint8, device=dev)
+        if out is None:
+            out = torch.empty(n_pops * n_win * DXY_ROW_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        if tot is None:
+            tot = torch.empty(n_pops * DXY_TOTAL_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        elif tot is False:
+            tot = None
+        self._same_len("pi_pops_reduce_dev", n, pos, *freqs, *ninds)
+        self._room("pi_pops_reduce_dev: out", out, n_pops * n_win * DXY_ROW_DTYPE.itemsize)
+        self._room("pi_pops_reduce_dev: tree", tree, tb)
+        if tot is not None:
+            self._room("pi_pops_reduce_dev: tot", tot, n_pops * DXY_TOTAL_DTYPE.itemsize)
+        pf = (C.c_void_p * n_pops)(*[self._col(t, torch.float64, f"freqs[{k}]") for k, t in enumerate(freqs)])
+        pn = (C.c_void_p * n_pops)(*[self._col(t, torch.int32, f"ninds[{k}]") for k, t in enumerate(ninds)])
+        self._check(self._lib.pgt_pi_pops_reduce_dev(
             self._ctx, self._dev(pos, torch.int32, "pos"), pf, pn, n_pops, n, int(minind),
             self._dev(win, torch.uint8, "win") if n_win else None, n_win,
             self._dev(out, torch.uint8, "out") if n_win else None, out.numel(),
@@ -1107,6 +1168,40 @@ def fst_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: 
             w, r = w[keep], r[keep]
         res[ij] = WindowResult(w, r, tot[p])
     return res
+
+
+def pi_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: int = 1, fixedsite: int = 0,
+                   chr_len=None, ctx: Context | None = None) -> list:
+    """Windowed nucleotide diversity (pi) of EACH of len(freqs) populations (1 ... 8; already synchronised when there are
+    several) in one pass: a list of WindowResult, one per population, with dxyWindow's rows (sum = Σ pi over the counted
+    sites, neff, nskip) and the genome-wide line as total.  Window arguments and their errors are those of dxy_window_pops.
+    The reference has no counterpart; the per-site definition is pgt_pi_pops_reduce_dev's (include/pgtwin.h)."""
+    if minind <= 0:
+        raise PgtError(_lib.PGT_EARG, "-minind must be at least 1")
+    if W > 0 and S < 1:
+        raise PgtError(_lib.PGT_EARG, "Must specify a -stepsize > 0 when -winsize is > 0")
+    if not fixedsite and chr_len is None:
+        raise PgtError(_lib.PGT_EARG, "Must supply size file unless -fixedsite 1")
+    if W == 0 and not fixedsite:
+        raise PgtError(_lib.PGT_EDOMAIN, "-winsize 0 needs -fixedsite 1 (the reference crashes here, SURVEY Q10)")
+    if len(ninds) != len(freqs) or not 1 <= len(freqs) <= 8:
+        raise PgtError(_lib.PGT_EARG, "pi_window_pops: 1 ... 8 populations, one frequency and one count column each")
+    chr_ids, pos = _host_col(chr_ids, None), _host_col(pos, np.uint32)
+    freqs, ninds = [_host_col(f, np.float64) for f in freqs], [_host_col(c, np.int32) for c in ninds]
+    rl = run_lengths(chr_ids)
+    if W == 0:
+        win = np.zeros(0, dtype=WIN_DTYPE)
+    elif fixedsite:
+        win = build_windows_sites(rl, W, S)
+    else:
+        win = build_windows_bp(pos, rl, chr_len, W, S)
+    ctx, own = _own_ctx(ctx)
+    try:
+        rows, tot = ctx.pi_pops_reduce(pos, freqs, ninds, minind, win)
+    finally:
+        if own:
+            ctx.close()
+    return [WindowResult(win, rows[k], tot[k]) for k in range(len(freqs))]
 
 
 def ihs_window(chr_ids, pos, score, W: int = 100000, cutoff: float = 2.0, chr_len=None,
