@@ -127,18 +127,11 @@ def load() -> C.CDLL:
     lib.pgt_af_tree_bytes.restype = sz
     lib.pgt_af_tree_bytes.argtypes = [u32, u64]
     lib.pgt_fst_af_reduce_dev.argtypes = [vp, vp, vp, vp, u32, u64, vp, u64, vp, sz, vp, sz, vp]
-    lib.pgt_dxy_pops_tree_bytes.restype = sz
-    lib.pgt_dxy_pops_tree_bytes.argtypes = [u32, u64]
-    lib.pgt_dxy_pops_reduce_dev.argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, u64, vp, sz, vp, vp, sz, vp]
-    lib.pgt_dxy_pops_reduce.argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, u64, vp, vp]
-    lib.pgt_fst_pops_tree_bytes.restype = sz
-    lib.pgt_fst_pops_tree_bytes.argtypes = [u32, u64]
-    lib.pgt_fst_pops_reduce_dev.argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, u64, vp, sz, vp, vp, sz, vp]
-    lib.pgt_fst_pops_reduce.argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, u64, vp, vp]
-    lib.pgt_pi_pops_tree_bytes.restype = sz
-    lib.pgt_pi_pops_tree_bytes.argtypes = [u32, u64]
-    lib.pgt_pi_pops_reduce_dev.argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, u64, vp, sz, vp, vp, sz, vp]
-    lib.pgt_pi_pops_reduce.argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, u64, vp, vp]
+    for stat in ("dxy", "fst", "pi"):  # the K-population statistics over (freq, nInd) columns: one argument list each form
+        getattr(lib, f"pgt_{stat}_pops_tree_bytes").restype = sz
+        getattr(lib, f"pgt_{stat}_pops_tree_bytes").argtypes = [u32, u64]
+        getattr(lib, f"pgt_{stat}_pops_reduce_dev").argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, u64, vp, sz, vp, vp, sz, vp]
+        getattr(lib, f"pgt_{stat}_pops_reduce").argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, u64, vp, vp]
     lib.pgt_align_segments.argtypes = [vp, vp, vp, u32, vp, sz, C.POINTER(sz)]
     lib.pgt_align_workspace_bytes.restype = sz
     lib.pgt_align_workspace_bytes.argtypes = [u32, u64]

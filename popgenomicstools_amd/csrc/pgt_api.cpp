@@ -328,6 +328,61 @@ struct DeviceScope {
     DeviceScope device_scope; \
     if (int rc_ = device_scope.enter(ctx)) return rc_
 
+// What is particular to one statistic of the (freq, nInd) front ends (pgt_{dxy,fst,pi}_pops_reduce and _dev); the rest of
+// their argument checks is one text for all three: pops_check_range, pops_check_dev, pops_reduce_host.
+struct PopsStat {
+    const char *who;                                          // the prefix of every message
+    uint32_t min_pops;                                        // min_pops <= n_pops <= kPopsMaxPops
+    bool minind_from_1;                                       // minind < 1 is refused (dxy takes it as it comes)
+    uint64_t (*tables)(uint32_t n_pops);                      // row tables, and totals, of one call
+    const char *tables_word;                                  // ... and the word for them in the overflow message
+    size_t row_bytes;
+    size_t (*tree_bytes)(uint32_t n_pops, uint64_t n_sites);
+};
+uint64_t pops_pairs(uint32_t n_pops) { return (uint64_t)n_pops * (n_pops - 1) / 2; }
+uint64_t pops_each(uint32_t n_pops) { return n_pops; }
+
+// first in both forms, and before the device form's early PGT_OK
+int pops_check_range(pgt_ctx *ctx, const PopsStat &st, uint32_t n_pops, int minind) {
+    if (n_pops < st.min_pops || n_pops > (uint32_t)kPopsMaxPops)
+        return ctx_fail(ctx, PGT_EARG, std::string(st.who) + ": n_pops must be " + std::to_string(st.min_pops) + " ... " + std::to_string(kPopsMaxPops));
+    if (st.minind_from_1 && minind < 1) return ctx_fail(ctx, PGT_EARG, std::string(st.who) + ": minind must be at least 1");
+    return PGT_OK;
+}
+
+// Every check of a *_pops_reduce_dev entry point.  *launch = false with PGT_OK: a shard without sites, windows and total.
+int pops_check_dev(pgt_ctx *ctx, const PopsStat &st, const uint32_t *pos, const double *const *freq, const int32_t *const *nind,
+                   uint32_t n_pops, uint64_t n, int minind, const pgt_win *win, uint64_t n_win, const void *out, size_t out_bytes,
+                   const void *tot, const void *tree, size_t tree_bytes, bool *launch) {
+    *launch = false;
+    if (int rc = pops_check_range(ctx, st, n_pops, minind)) return rc;
+    if (n == 0 && n_win == 0 && !tot) return PGT_OK;
+    const std::string who = std::string(st.who) + ": ";
+    if (!freq) return ctx_fail(ctx, PGT_EARG, who + "freq is NULL");
+    if (!nind) return ctx_fail(ctx, PGT_EARG, who + "nind is NULL");
+    if (!tree) return ctx_fail(ctx, PGT_EARG, who + "tree is NULL");
+    if (n_win && !win) return ctx_fail(ctx, PGT_EARG, who + "win is NULL");
+    if (n_win && !out) return ctx_fail(ctx, PGT_EARG, who + "out is NULL");
+    if (n_win && n && !pos) return ctx_fail(ctx, PGT_EARG, who + "pos is NULL");  // windows without PGT_WIN_COORDS read pos[lo], pos[hi-1]
+    for (uint32_t k = 0; k < n_pops; ++k) {
+        const std::string at = "[" + std::to_string(k) + "]";
+        if (!freq[k]) return ctx_fail(ctx, PGT_EARG, who + "freq" + at + " is NULL");
+        if (!nind[k]) return ctx_fail(ctx, PGT_EARG, who + "nind" + at + " is NULL");
+        if (!aligned16(freq[k])) return ctx_fail(ctx, PGT_EARG, who + "freq" + at + " is not 16-byte aligned");
+        if (!aligned16(nind[k])) return ctx_fail(ctx, PGT_EARG, who + "nind" + at + " is not 16-byte aligned");
+    }
+    if (n >= (1ull << 32)) return ctx_fail(ctx, PGT_EARG, who + "n: at most 2^32-1 sites per call");
+    if (!aligned16(tree)) return ctx_fail(ctx, PGT_EARG, who + "tree is not 16-byte aligned");
+    if (tree_bytes < st.tree_bytes(n_pops, n))
+        return ctx_fail(ctx, PGT_EARG, who + "tree_bytes too small (" + std::to_string(tree_bytes) + " bytes, " +
+                                           std::to_string(st.tree_bytes(n_pops, n)) + " needed)");
+    const uint64_t tables = st.tables(n_pops);
+    if (n_win > UINT64_MAX / tables) return ctx_fail(ctx, PGT_EARG, who + st.tables_word + " * n_win overflows");
+    if (int rc = room_check(ctx, (who + "out_bytes").c_str(), tables * n_win, st.row_bytes, out_bytes)) return rc;
+    *launch = true;
+    return PGT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -584,109 +639,56 @@ int pgt_fst_af_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const
 }
 
 size_t pgt_dxy_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites) {
-    if (n_pops < 2 || n_pops > (uint32_t)kDxyPopsMaxPops) return 0;
+    if (n_pops < 2 || n_pops > (uint32_t)kPopsMaxPops) return 0;
     return dxy_pops_tree_view(tree_layout(PGT_STAT_FST, n_sites), (int)(n_pops * (n_pops - 1) / 2), nullptr, 0).bytes;
 }
+static const PopsStat kDxyPops = {"pgt_dxy_pops_reduce", 2, false, pops_pairs, "n_pairs", sizeof(pgt_dxy_row), pgt_dxy_pops_tree_bytes};
 
 int pgt_dxy_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind,
                             uint32_t n_pops, uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_dxy_row *out,
                             size_t out_bytes, pgt_dxy_total *tot, void *tree, size_t tree_bytes, void *stream) {
     PGT_USE_DEVICE(ctx);
-    if (n_pops < 2 || n_pops > (uint32_t)kDxyPopsMaxPops) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: n_pops must be 2 ... 8");
-    if (n == 0 && n_win == 0 && !tot) return PGT_OK;
-    if (!freq) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: freq is NULL");
-    if (!nind) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: nind is NULL");
-    if (!tree) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: tree is NULL");
-    if (n_win && !win) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: win is NULL");
-    if (n_win && !out) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: out is NULL");
-    if (n_win && n && !pos) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: pos is NULL");  // windows without PGT_WIN_COORDS read pos[lo], pos[hi-1]
-    for (uint32_t k = 0; k < n_pops; ++k) {
-        if (!freq[k]) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: freq[" + std::to_string(k) + "] is NULL");
-        if (!nind[k]) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: nind[" + std::to_string(k) + "] is NULL");
-        if (!aligned16(freq[k])) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: freq[" + std::to_string(k) + "] is not 16-byte aligned");
-        if (!aligned16(nind[k])) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: nind[" + std::to_string(k) + "] is not 16-byte aligned");
-    }
-    if (n >= (1ull << 32)) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: n: at most 2^32-1 sites per call");
-    if (!aligned16(tree)) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: tree is not 16-byte aligned");
-    if (tree_bytes < pgt_dxy_pops_tree_bytes(n_pops, n))
-        return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: tree_bytes too small (" + std::to_string(tree_bytes) + " bytes, " +
-                                           std::to_string(pgt_dxy_pops_tree_bytes(n_pops, n)) + " needed)");
-    const uint64_t n_pairs = (uint64_t)n_pops * (n_pops - 1) / 2;
-    if (n_win > UINT64_MAX / n_pairs) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: n_pairs * n_win overflows");
-    if (int rc = room_check(ctx, "pgt_dxy_pops_reduce: out_bytes", n_pairs * n_win, sizeof(pgt_dxy_row), out_bytes)) return rc;
+    bool launch;
+    if (int rc = pops_check_dev(ctx, kDxyPops, pos, freq, nind, n_pops, n, minind, win, n_win, out, out_bytes, tot, tree, tree_bytes, &launch)) return rc;
+    if (!launch) return PGT_OK;
     const EvSet e = events_for(ctx);
     return launch_dxy_pops(pos, freq, nind, n_pops, n, minind, win, n_win, out, tot, tree, stream, e.b0, e.b1, e.q1, &ctx->error,
                            ctx->hints);
 }
 
 size_t pgt_fst_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites) {
-    if (n_pops < 2 || n_pops > (uint32_t)kFstPopsMaxPops) return 0;
+    if (n_pops < 2 || n_pops > (uint32_t)kPopsMaxPops) return 0;
     return fst_pops_tree_view(tree_layout(PGT_STAT_FST, n_sites), (int)(n_pops * (n_pops - 1) / 2), nullptr, 0).bytes;
 }
+// minind >= 1: npool >= 2 and n1, n2 > 0 at every counted site
+static const PopsStat kFstPops = {"pgt_fst_pops_reduce", 2, true, pops_pairs, "n_pairs", sizeof(pgt_fst_row), pgt_fst_pops_tree_bytes};
 
 int pgt_fst_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind,
                             uint32_t n_pops, uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_fst_row *out,
                             size_t out_bytes, pgt_fst_total *tot, void *tree, size_t tree_bytes, void *stream) {
     PGT_USE_DEVICE(ctx);
-    if (n_pops < 2 || n_pops > (uint32_t)kFstPopsMaxPops) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: n_pops must be 2 ... 8");
-    if (minind < 1) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: minind must be at least 1");  // npool >= 2, n1 n2 > 0 at every counted site
-    if (n == 0 && n_win == 0 && !tot) return PGT_OK;
-    if (!freq) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: freq is NULL");
-    if (!nind) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: nind is NULL");
-    if (!tree) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: tree is NULL");
-    if (n_win && !win) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: win is NULL");
-    if (n_win && !out) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: out is NULL");
-    if (n_win && n && !pos) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: pos is NULL");  // windows without PGT_WIN_COORDS read pos[lo], pos[hi-1]
-    for (uint32_t k = 0; k < n_pops; ++k) {
-        if (!freq[k]) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: freq[" + std::to_string(k) + "] is NULL");
-        if (!nind[k]) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: nind[" + std::to_string(k) + "] is NULL");
-        if (!aligned16(freq[k])) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: freq[" + std::to_string(k) + "] is not 16-byte aligned");
-        if (!aligned16(nind[k])) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: nind[" + std::to_string(k) + "] is not 16-byte aligned");
-    }
-    if (n >= (1ull << 32)) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: n: at most 2^32-1 sites per call");
-    if (!aligned16(tree)) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: tree is not 16-byte aligned");
-    if (tree_bytes < pgt_fst_pops_tree_bytes(n_pops, n))
-        return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: tree_bytes too small (" + std::to_string(tree_bytes) + " bytes, " +
-                                           std::to_string(pgt_fst_pops_tree_bytes(n_pops, n)) + " needed)");
-    const uint64_t n_pairs = (uint64_t)n_pops * (n_pops - 1) / 2;
-    if (n_win > UINT64_MAX / n_pairs) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: n_pairs * n_win overflows");
-    if (int rc = room_check(ctx, "pgt_fst_pops_reduce: out_bytes", n_pairs * n_win, sizeof(pgt_fst_row), out_bytes)) return rc;
+    bool launch;
+    if (int rc = pops_check_dev(ctx, kFstPops, pos, freq, nind, n_pops, n, minind, win, n_win, out, out_bytes, tot, tree, tree_bytes, &launch)) return rc;
+    if (!launch) return PGT_OK;
     const EvSet e = events_for(ctx);
     return launch_fst_pops(pos, freq, nind, n_pops, n, minind, win, n_win, out, tot, tree, stream, e.b0, e.b1, e.q1, &ctx->error,
                            ctx->hints);
 }
 
 size_t pgt_pi_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites) {
-    if (n_pops < 1 || n_pops > (uint32_t)kPiPopsMaxPops) return 0;
+    if (n_pops < 1 || n_pops > (uint32_t)kPopsMaxPops) return 0;
     return (size_t)n_pops * tree_layout(PGT_STAT_DXY, n_sites).bytes;  // one tree of the two-population dxy layout per population
 }
+// one table per population; minind >= 1: 2 nind - 1 >= 1 at every counted site
+static const PopsStat kPiPops = {"pgt_pi_pops_reduce", 1, true, pops_each, "n_pops", sizeof(pgt_dxy_row), pgt_pi_pops_tree_bytes};
 
 int pgt_pi_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind,
                            uint32_t n_pops, uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_dxy_row *out,
                            size_t out_bytes, pgt_dxy_total *tot, void *tree, size_t tree_bytes, void *stream) {
     PGT_USE_DEVICE(ctx);
-    if (n_pops < 1 || n_pops > (uint32_t)kPiPopsMaxPops) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: n_pops must be 1 ... 8");
-    if (minind < 1) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: minind must be at least 1");  // 2 nind - 1 >= 1 at every counted site
-    if (n == 0 && n_win == 0 && !tot) return PGT_OK;
-    if (!freq) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: freq is NULL");
-    if (!nind) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: nind is NULL");
-    if (!tree) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: tree is NULL");
-    if (n_win && !win) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: win is NULL");
-    if (n_win && !out) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: out is NULL");
-    if (n_win && n && !pos) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: pos is NULL");  // windows without PGT_WIN_COORDS read pos[lo], pos[hi-1]
-    for (uint32_t k = 0; k < n_pops; ++k) {
-        if (!freq[k]) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: freq[" + std::to_string(k) + "] is NULL");
-        if (!nind[k]) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: nind[" + std::to_string(k) + "] is NULL");
-        if (!aligned16(freq[k])) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: freq[" + std::to_string(k) + "] is not 16-byte aligned");
-        if (!aligned16(nind[k])) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: nind[" + std::to_string(k) + "] is not 16-byte aligned");
-    }
-    if (n >= (1ull << 32)) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: n: at most 2^32-1 sites per call");
-    if (!aligned16(tree)) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: tree is not 16-byte aligned");
-    if (tree_bytes < pgt_pi_pops_tree_bytes(n_pops, n))
-        return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: tree_bytes too small (" + std::to_string(tree_bytes) + " bytes, " +
-                                           std::to_string(pgt_pi_pops_tree_bytes(n_pops, n)) + " needed)");
-    if (n_win > UINT64_MAX / n_pops) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: n_pops * n_win overflows");
-    if (int rc = room_check(ctx, "pgt_pi_pops_reduce: out_bytes", (uint64_t)n_pops * n_win, sizeof(pgt_dxy_row), out_bytes)) return rc;
+    bool launch;
+    if (int rc = pops_check_dev(ctx, kPiPops, pos, freq, nind, n_pops, n, minind, win, n_win, out, out_bytes, tot, tree, tree_bytes, &launch)) return rc;
+    if (!launch) return PGT_OK;
     const EvSet e = events_for(ctx);
     return launch_pi_pops(pos, freq, nind, n_pops, n, minind, win, n_win, out, tot, tree, stream, e.b0, e.b1, e.q1, &ctx->error,
                           ctx->hints);
@@ -926,6 +928,42 @@ int reduce_tables_with_workspace(pgt_ctx *ctx, const char *who, size_t tb, uint6
     return PGT_OK;
 }
 
+// The host-buffer form of a (freq, nInd) front end: checks, pos and n_pops x (freq, nind) up, the statistic's _dev entry point
+// `dev` between reduce_tables_with_workspace's copies.  Rows and totals are written by every call (the query stores every row
+// of every table, the build every tree level the query reads): nothing of the cached workspace survives.
+template <class Row, class Tot>
+int pops_reduce_host(pgt_ctx *ctx, const PopsStat &st,
+                     int (*dev)(pgt_ctx *, const uint32_t *, const double *const *, const int32_t *const *, uint32_t, uint64_t, int,
+                                const pgt_win *, uint64_t, Row *, size_t, Tot *, void *, size_t, void *),
+                     const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops, uint64_t n, int minind,
+                     const pgt_win *win, uint64_t n_win, Row *out, Tot *tot) {
+    if (int rc = pops_check_range(ctx, st, n_pops, minind)) return rc;
+    const std::string who = st.who;
+    if (!freq || !nind || (n && !pos) || (n_win && (!win || !out))) return ctx_fail(ctx, PGT_EARG, who + ": NULL argument");
+    for (uint32_t k = 0; k < n_pops; ++k)
+        if (n && (!freq[k] || !nind[k])) return ctx_fail(ctx, PGT_EARG, who + ": NULL column");
+    ApiTrace trace(st.who);
+    const uint64_t tables = st.tables(n_pops);
+    if (n_win > UINT64_MAX / tables / sizeof(Row)) return ctx_fail(ctx, PGT_EARG, who + ": " + st.tables_word + " * n_win overflows");
+    DevBuf dpos, df[kPopsMaxPops], dn[kPopsMaxPops];
+    UploadJob jobs[1 + 2 * kPopsMaxPops];
+    int n_jobs = 0;
+    jobs[n_jobs++] = {&dpos, pos, n * sizeof(uint32_t), "upload pos"};
+    for (uint32_t k = 0; k < n_pops; ++k) {
+        jobs[n_jobs++] = {&df[k], freq[k], n * sizeof(double), "upload freq"};
+        jobs[n_jobs++] = {&dn[k], nind[k], n * sizeof(int32_t), "upload nind"};
+    }
+    if (int rc = upload_columns(ctx, jobs, n_jobs, trace)) return rc;
+    const double *pf[kPopsMaxPops];
+    const int32_t *pn[kPopsMaxPops];
+    for (uint32_t k = 0; k < n_pops; ++k) { pf[k] = static_cast<double *>(df[k].p); pn[k] = static_cast<int32_t *>(dn[k].p); }
+    const size_t row_bytes = (size_t)(tables * n_win) * sizeof(Row);
+    return reduce_tables_with_workspace<Row>(ctx, st.who, st.tree_bytes(n_pops, n), tables, n, win, n_win, out, row_bytes, tot,
+        [&](const pgt_win *dw, Row *dr, void *tree, size_t tb, Tot *dtot) {
+            return dev(ctx, static_cast<uint32_t *>(dpos.p), pf, pn, n_pops, n, minind, dw, n_win, dr, row_bytes, dtot, tree, tb, nullptr);
+        });
+}
+
 template <class Row, class Run>
 int reduce_with_workspace(pgt_ctx *ctx, const char *who, int stat, uint64_t n, const pgt_win *win, uint64_t n_win, Row *out, size_t out_bytes,
                           pgt_dxy_total *tot, Run run) {
@@ -1034,99 +1072,25 @@ int pgt_dxy_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *p1, const do
                                n_win * sizeof(pgt_dxy_row), tot);
 }
 
-/* all pairs of n_pops populations: columns, table and rows in HOST memory.  Rows and totals are written by every call (the
- * query stores every row of every pair, the build every tree level the query reads): nothing of the cached workspace survives */
+/* all pairs of n_pops populations: columns, table and rows in HOST memory (pops_reduce_host) */
 int pgt_dxy_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
                         uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_dxy_row *out, pgt_dxy_total *tot) {
     PGT_USE_DEVICE(ctx);
-    if (n_pops < 2 || n_pops > (uint32_t)kDxyPopsMaxPops) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: n_pops must be 2 ... 8");
-    if (!freq || !nind || (n && !pos) || (n_win && (!win || !out))) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: NULL argument");
-    for (uint32_t k = 0; k < n_pops; ++k)
-        if (n && (!freq[k] || !nind[k])) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: NULL column");
-    ApiTrace trace("pgt_dxy_pops_reduce");
-    const uint64_t n_pairs = (uint64_t)n_pops * (n_pops - 1) / 2;
-    if (n_win > UINT64_MAX / n_pairs / sizeof(pgt_dxy_row)) return ctx_fail(ctx, PGT_EARG, "pgt_dxy_pops_reduce: n_pairs * n_win overflows");
-    DevBuf dpos, df[kDxyPopsMaxPops], dn[kDxyPopsMaxPops];
-    UploadJob jobs[1 + 2 * kDxyPopsMaxPops];
-    int n_jobs = 0;
-    jobs[n_jobs++] = {&dpos, pos, n * sizeof(uint32_t), "upload pos"};
-    for (uint32_t k = 0; k < n_pops; ++k) {
-        jobs[n_jobs++] = {&df[k], freq[k], n * sizeof(double), "upload freq"};
-        jobs[n_jobs++] = {&dn[k], nind[k], n * sizeof(int32_t), "upload nind"};
-    }
-    if (int rc = upload_columns(ctx, jobs, n_jobs, trace)) return rc;
-    const double *pf[kDxyPopsMaxPops];
-    const int32_t *pn[kDxyPopsMaxPops];
-    for (uint32_t k = 0; k < n_pops; ++k) { pf[k] = static_cast<double *>(df[k].p); pn[k] = static_cast<int32_t *>(dn[k].p); }
-    return reduce_tables_with_workspace<pgt_dxy_row>(ctx, "pgt_dxy_pops_reduce", pgt_dxy_pops_tree_bytes(n_pops, n), n_pairs, n, win, n_win, out,
-        (size_t)(n_pairs * n_win) * sizeof(pgt_dxy_row), tot,
-        [&](const pgt_win *dw, pgt_dxy_row *dr, void *tree, size_t tb, pgt_dxy_total *dtot) {
-            return pgt_dxy_pops_reduce_dev(ctx, static_cast<uint32_t *>(dpos.p), pf, pn, n_pops, n, minind, dw, n_win, dr,
-                                           (size_t)(n_pairs * n_win) * sizeof(pgt_dxy_row), dtot, tree, tb, nullptr);
-        });
+    return pops_reduce_host(ctx, kDxyPops, pgt_dxy_pops_reduce_dev, pos, freq, nind, n_pops, n, minind, win, n_win, out, tot);
 }
 
 /* FST of all pairs from per-population (freq, nInd) columns: the host-buffer form, as pgt_dxy_pops_reduce */
 int pgt_fst_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
                         uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_fst_row *out, pgt_fst_total *tot) {
     PGT_USE_DEVICE(ctx);
-    if (n_pops < 2 || n_pops > (uint32_t)kFstPopsMaxPops) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: n_pops must be 2 ... 8");
-    if (minind < 1) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: minind must be at least 1");
-    if (!freq || !nind || (n && !pos) || (n_win && (!win || !out))) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: NULL argument");
-    for (uint32_t k = 0; k < n_pops; ++k)
-        if (n && (!freq[k] || !nind[k])) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: NULL column");
-    ApiTrace trace("pgt_fst_pops_reduce");
-    const uint64_t n_pairs = (uint64_t)n_pops * (n_pops - 1) / 2;
-    if (n_win > UINT64_MAX / n_pairs / sizeof(pgt_fst_row)) return ctx_fail(ctx, PGT_EARG, "pgt_fst_pops_reduce: n_pairs * n_win overflows");
-    DevBuf dpos, df[kFstPopsMaxPops], dn[kFstPopsMaxPops];
-    UploadJob jobs[1 + 2 * kFstPopsMaxPops];
-    int n_jobs = 0;
-    jobs[n_jobs++] = {&dpos, pos, n * sizeof(uint32_t), "upload pos"};
-    for (uint32_t k = 0; k < n_pops; ++k) {
-        jobs[n_jobs++] = {&df[k], freq[k], n * sizeof(double), "upload freq"};
-        jobs[n_jobs++] = {&dn[k], nind[k], n * sizeof(int32_t), "upload nind"};
-    }
-    if (int rc = upload_columns(ctx, jobs, n_jobs, trace)) return rc;
-    const double *pf[kFstPopsMaxPops];
-    const int32_t *pn[kFstPopsMaxPops];
-    for (uint32_t k = 0; k < n_pops; ++k) { pf[k] = static_cast<double *>(df[k].p); pn[k] = static_cast<int32_t *>(dn[k].p); }
-    return reduce_tables_with_workspace<pgt_fst_row>(ctx, "pgt_fst_pops_reduce", pgt_fst_pops_tree_bytes(n_pops, n), n_pairs, n, win, n_win, out,
-        (size_t)(n_pairs * n_win) * sizeof(pgt_fst_row), tot,
-        [&](const pgt_win *dw, pgt_fst_row *dr, void *tree, size_t tb, pgt_fst_total *dtot) {
-            return pgt_fst_pops_reduce_dev(ctx, static_cast<uint32_t *>(dpos.p), pf, pn, n_pops, n, minind, dw, n_win, dr,
-                                           (size_t)(n_pairs * n_win) * sizeof(pgt_fst_row), dtot, tree, tb, nullptr);
-        });
+    return pops_reduce_host(ctx, kFstPops, pgt_fst_pops_reduce_dev, pos, freq, nind, n_pops, n, minind, win, n_win, out, tot);
 }
 
 /* pi per population from (freq, nInd) columns: the host-buffer form, as pgt_dxy_pops_reduce with one table per population */
 int pgt_pi_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
                        uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_dxy_row *out, pgt_dxy_total *tot) {
     PGT_USE_DEVICE(ctx);
-    if (n_pops < 1 || n_pops > (uint32_t)kPiPopsMaxPops) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: n_pops must be 1 ... 8");
-    if (minind < 1) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: minind must be at least 1");
-    if (!freq || !nind || (n && !pos) || (n_win && (!win || !out))) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: NULL argument");
-    for (uint32_t k = 0; k < n_pops; ++k)
-        if (n && (!freq[k] || !nind[k])) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: NULL column");
-    ApiTrace trace("pgt_pi_pops_reduce");
-    if (n_win > UINT64_MAX / n_pops / sizeof(pgt_dxy_row)) return ctx_fail(ctx, PGT_EARG, "pgt_pi_pops_reduce: n_pops * n_win overflows");
-    DevBuf dpos, df[kPiPopsMaxPops], dn[kPiPopsMaxPops];
-    UploadJob jobs[1 + 2 * kPiPopsMaxPops];
-    int n_jobs = 0;
-    jobs[n_jobs++] = {&dpos, pos, n * sizeof(uint32_t), "upload pos"};
-    for (uint32_t k = 0; k < n_pops; ++k) {
-        jobs[n_jobs++] = {&df[k], freq[k], n * sizeof(double), "upload freq"};
-        jobs[n_jobs++] = {&dn[k], nind[k], n * sizeof(int32_t), "upload nind"};
-    }
-    if (int rc = upload_columns(ctx, jobs, n_jobs, trace)) return rc;
-    const double *pf[kPiPopsMaxPops];
-    const int32_t *pn[kPiPopsMaxPops];
-    for (uint32_t k = 0; k < n_pops; ++k) { pf[k] = static_cast<double *>(df[k].p); pn[k] = static_cast<int32_t *>(dn[k].p); }
-    const size_t row_bytes = (size_t)((uint64_t)n_pops * n_win) * sizeof(pgt_dxy_row);
-    return reduce_tables_with_workspace<pgt_dxy_row>(ctx, "pgt_pi_pops_reduce", pgt_pi_pops_tree_bytes(n_pops, n), n_pops, n, win, n_win, out,
-        row_bytes, tot, [&](const pgt_win *dw, pgt_dxy_row *dr, void *tree, size_t tb, pgt_dxy_total *dtot) {
-            return pgt_pi_pops_reduce_dev(ctx, static_cast<uint32_t *>(dpos.p), pf, pn, n_pops, n, minind, dw, n_win, dr, row_bytes, dtot,
-                                          tree, tb, nullptr);
-        });
+    return pops_reduce_host(ctx, kPiPops, pgt_pi_pops_reduce_dev, pos, freq, nind, n_pops, n, minind, win, n_win, out, tot);
 }
 
 /* ---------------- window tables built on the device ---------------- */

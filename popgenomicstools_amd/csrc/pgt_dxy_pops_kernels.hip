@@ -34,7 +34,7 @@ namespace {
 
 using namespace dev;
 
-constexpr int kPieces = kDxyPopsLeafPieces;   // 128-site pieces per level-1 node
+constexpr int kPieces = kPopsLeafPieces;   // 128-site pieces per level-1 node
 constexpr int kLeaf = kPieces * kLeafF64;     // sites per level-1 node (512: the level-1 bytes written are 12 P / 512 per site, 0.7 % of the bytes read at 8 populations; see pgt_af_kernels.hip on what node stores cost)
 constexpr int kRadix1 = kRadix / kPieces;     // level-1 nodes per level-2 node
 static_assert(kPieces == 4, "the build walks a leaf as two pairs of pieces");
@@ -45,8 +45,8 @@ struct Shape {
 };
 
 struct PopCols {
-    const double *f[kDxyPopsMaxPops];
-    const int32_t *c[kDxyPopsMaxPops];
+    const double *f[kPopsMaxPops];
+    const int32_t *c[kPopsMaxPops];
 };
 
 // (the reduce-scatter of a leaf's P sums across the wave: rs_steps / rs_my_index of pgt_pops_common.h)
@@ -454,23 +454,16 @@ int launch_np(const PopCols &cols, const uint32_t *pos, uint64_t n, int minind, 
     if (int rc = record_event(ev_b0, s, err)) return rc;
     tv.n_partials = 0;
     if (n > 0) {
-        // a static balanced grid of what is resident at once (one wave per SIMD: 256 workgroups of 4 waves; two: 512): every
-        // wave walks `rounds` tiles, all waves run in near lockstep and flush their node blocks at about the same times
-        // (launch_af_np picks its round count by how full the last generation is; that choice is unmeasured here, and the
-        // per-wave partials want a grid that depends on n alone)
         const bool w1 = NP >= one_wave_from();
-        const uint64_t max_waves = w1 ? 1024 : (uint64_t)kMaxBuildWaves;
-        const uint64_t rounds = (tl.count[1] + max_waves - 1) / max_waves;
-        const uint64_t waves = (tl.count[1] + rounds - 1) / rounds;
-        const uint64_t blocks = (waves + 3) / 4;
-        tv.n_partials = (uint32_t)(blocks * 4);  // <= kMaxBuildWaves: what the workspace reserves
+        const auto [blocks, n_partials] = pops_build_grid(tl.count[1], w1);
+        tv.n_partials = n_partials;
         if constexpr (NP < kOneWaveFrom) {
             if (w1)
-                hipLaunchKernelGGL((dxy_pops_build_kernel_w1<NP>), dim3((unsigned)blocks), dim3(256), stage_bytes<NP>(), s, cols, minind, n, tl.count[1], tv);
+                hipLaunchKernelGGL((dxy_pops_build_kernel_w1<NP>), dim3(blocks), dim3(256), stage_bytes<NP>(), s, cols, minind, n, tl.count[1], tv);
             else
-                hipLaunchKernelGGL((dxy_pops_build_kernel<NP>), dim3((unsigned)blocks), dim3(256), stage_bytes<NP>(), s, cols, minind, n, tl.count[1], tv);
+                hipLaunchKernelGGL((dxy_pops_build_kernel<NP>), dim3(blocks), dim3(256), stage_bytes<NP>(), s, cols, minind, n, tl.count[1], tv);
         } else {  // (one_wave_from() <= kOneWaveFrom: always the one-wave form here)
-            hipLaunchKernelGGL((dxy_pops_build_kernel_w1<NP>), dim3((unsigned)blocks), dim3(256), stage_bytes<NP>(), s, cols, minind, n, tl.count[1], tv);
+            hipLaunchKernelGGL((dxy_pops_build_kernel_w1<NP>), dim3(blocks), dim3(256), stage_bytes<NP>(), s, cols, minind, n, tl.count[1], tv);
         }
         if (int rc = hip_fail(hipGetLastError(), "dxy_pops_build_kernel", err)) return rc;
         if (int rc = launch_upper_levels(dxy_pops_up_kernel, "dxy_pops_up_kernel", Shape<NP>::kPairs, tv, tl, s, err)) return rc;
@@ -502,10 +495,7 @@ int launch_dxy_pops(const uint32_t *pos, const double *const *freq, const int32_
                     int minind, const pgt_win *win, uint64_t n_win, pgt_dxy_row *out, pgt_dxy_total *tot, void *tree,
                     void *stream, void *ev_build0, void *ev_build1, void *ev_query1, std::string *err, const Hints &hints) {
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (n_pops < 2 || n_pops > (uint32_t)kDxyPopsMaxPops) {
-        if (err) *err = "pgt_dxy_pops_reduce: 2 <= n_pops <= 8";
-        return PGT_EARG;
-    }
+    // 2 <= n_pops <= 8: checked by the caller
     const TreeLayout tl = tree_layout(PGT_STAT_FST, n);  // node counts of the f64 layout (levels 2 and up; level 1: a quarter)
     const DxyPopsTree tv = dxy_pops_tree_view(tl, (int)(n_pops * (n_pops - 1) / 2), tree, useful_levels(tl, PGT_STAT_FST, hints.max_window));
     PopCols cols{};

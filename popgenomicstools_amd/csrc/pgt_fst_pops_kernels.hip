@@ -38,7 +38,7 @@ namespace {
 
 using namespace dev;
 
-constexpr int kPieces = kFstPopsLeafPieces;   // 128-site pieces per level-1 node
+constexpr int kPieces = kPopsLeafPieces;   // 128-site pieces per level-1 node
 constexpr int kLeaf = kPieces * kLeafF64;     // sites per level-1 node
 constexpr int kRadix1 = kRadix / kPieces;     // level-1 nodes per level-2 node
 static_assert(kPieces == 4, "the build walks a leaf as two pairs of pieces");
@@ -50,8 +50,8 @@ struct Shape {
 };
 
 struct PopCols {
-    const double *f[kFstPopsMaxPops];
-    const int32_t *c[kFstPopsMaxPops];
+    const double *f[kPopsMaxPops];
+    const int32_t *c[kPopsMaxPops];
 };
 
 // 1/d for d >= 1 (finite): the hardware estimate and two Newton steps
@@ -480,18 +480,13 @@ int launch_np(const PopCols &cols, const uint32_t *pos, uint64_t n, int minind, 
     if (int rc = record_event(ev_b0, s, err)) return rc;
     tv.n_partials = 0;
     if (n > 0) {
-        // the static balanced grid of launch_np in pgt_dxy_pops_kernels.hip: what is resident at once (one wave per SIMD: 256
-        // workgroups of 4 waves; two: 512), every wave walks `rounds` tiles; a function of n alone (the per-wave partials)
         constexpr bool w1 = NP >= kOneWaveFrom;
-        const uint64_t max_waves = w1 ? 1024 : (uint64_t)kMaxBuildWaves;
-        const uint64_t rounds = (tl.count[1] + max_waves - 1) / max_waves;
-        const uint64_t waves = (tl.count[1] + rounds - 1) / rounds;
-        const uint64_t blocks = (waves + 3) / 4;
-        tv.n_partials = (uint32_t)(blocks * 4);  // <= kMaxBuildWaves: what the workspace reserves
+        const auto [blocks, n_partials] = pops_build_grid(tl.count[1], w1);
+        tv.n_partials = n_partials;
         if constexpr (w1)
-            hipLaunchKernelGGL((fst_pops_build_kernel_w1<NP>), dim3((unsigned)blocks), dim3(256), stage_bytes<NP>(), s, cols, minind, n, tl.count[1], tv);
+            hipLaunchKernelGGL((fst_pops_build_kernel_w1<NP>), dim3(blocks), dim3(256), stage_bytes<NP>(), s, cols, minind, n, tl.count[1], tv);
         else
-            hipLaunchKernelGGL((fst_pops_build_kernel<NP>), dim3((unsigned)blocks), dim3(256), stage_bytes<NP>(), s, cols, minind, n, tl.count[1], tv);
+            hipLaunchKernelGGL((fst_pops_build_kernel<NP>), dim3(blocks), dim3(256), stage_bytes<NP>(), s, cols, minind, n, tl.count[1], tv);
         if (int rc = hip_fail(hipGetLastError(), "fst_pops_build_kernel", err)) return rc;
         if (int rc = launch_upper_levels(fst_pops_up_kernel, "fst_pops_up_kernel", Shape<NP>::kSums, tv, tl, s, err)) return rc;
     }
@@ -523,14 +518,7 @@ int launch_fst_pops(const uint32_t *pos, const double *const *freq, const int32_
                     int minind, const pgt_win *win, uint64_t n_win, pgt_fst_row *out, pgt_fst_total *tot, void *tree,
                     void *stream, void *ev_build0, void *ev_build1, void *ev_query1, std::string *err, const Hints &hints) {
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (n_pops < 2 || n_pops > (uint32_t)kFstPopsMaxPops) {
-        if (err) *err = "pgt_fst_pops_reduce: 2 <= n_pops <= 8";
-        return PGT_EARG;
-    }
-    if (minind < 1) {
-        if (err) *err = "pgt_fst_pops_reduce: minind must be at least 1";
-        return PGT_EARG;
-    }
+    // 2 <= n_pops <= 8 and minind >= 1: checked by the caller
     const TreeLayout tl = tree_layout(PGT_STAT_FST, n);  // node counts of the f64 layout (levels 2 and up; level 1: a quarter)
     const FstPopsTree tv = fst_pops_tree_view(tl, (int)(n_pops * (n_pops - 1) / 2), tree, useful_levels(tl, PGT_STAT_FST, hints.max_window));
     PopCols cols{};

@@ -128,13 +128,15 @@ inline AfTree af_tree_view(const TreeLayout &t, int n_vals, void *tree, int leve
     return v;
 }
 
+// ---- the (freq, nInd) front ends: dxy and FST of all population pairs, pi per population ------
+constexpr int kPopsMaxPops = 8;     // populations per call of pgt_{dxy,fst,pi}_pops_reduce*: sizes their pointer arrays
+constexpr int kPopsLeafPieces = 4;  // 128-site pieces per level-1 node of the two all-pairs trees below
+
 // ---- dxy of all population pairs (pgt_dxy_pops_kernels.hip): nodes of P = NP(NP-1)/2 {Σd, neff}, node-major ------
 // A level holds two arrays: P doubles per node (the pairs' Σd) and P u32 per node (their neff); nskip is not stored
 // (every site of a range is a data site: nskip = sites - neff).  Level 1: 512-site nodes, 16 per level-2 node; levels 2
 // and up are those of the f64 layout (8192 sites, x64 per level).  Behind the levels one {Σd, neff} per pair and build
 // wave: the genome-wide lines are their sums in wave order (as TreeLayout::partials for the two-population tree).
-constexpr int kDxyPopsMaxPops = 8;
-constexpr int kDxyPopsLeafPieces = 4;  // 128-site pieces per level-1 node
 struct DxyPopsTree {
     char *base;
     size_t sum_off[kMaxLevels];  // byte offset of level slot k: P doubles per node
@@ -145,34 +147,10 @@ struct DxyPopsTree {
     int n_pairs;
     uint32_t n_partials;         // build waves that left a partial (0: no sites)
 };
-inline DxyPopsTree dxy_pops_tree_view(const TreeLayout &t, int n_pairs, void *tree, int levels) {
-    DxyPopsTree v{};
-    v.base = static_cast<char *>(tree);
-    v.n_levels = levels;
-    v.n_pairs = n_pairs;
-    auto pad = [](size_t b) { return ((b + 255) / 256) * 256; };
-    size_t off = 0;
-    for (int k = 0; k < t.n_levels; ++k) {
-        const uint64_t nodes = k == 0 ? t.count[0] / kDxyPopsLeafPieces : t.count[k];
-        v.sum_off[k] = off;
-        off += pad(nodes * (size_t)n_pairs * 8);
-        v.cnt_off[k] = off;
-        off += pad(nodes * (size_t)n_pairs * 4);
-    }
-    v.part_sum = off;
-    off += pad((size_t)kMaxBuildWaves * n_pairs * 8);
-    v.part_cnt = off;
-    off += pad((size_t)kMaxBuildWaves * n_pairs * 4);
-    v.bytes = off;
-    return v;
-}
 
 // ---- FST of all population pairs from per-population (freq, nInd) columns (pgt_fst_pops_kernels.hip) ----------------------
 // The shape of DxyPopsTree with two sums per pair: a node is 2 P doubles (Σa of pair 0 .. P-1, then Σ(a+b) of pair 0 .. P-1)
 // and P u32 (neff); a level holds the two arrays node-major.  Behind the levels one {Σa, Σ(a+b), neff} per pair and build wave.
-constexpr int kFstPopsMaxPops = 8;
-constexpr int kPiPopsMaxPops = 8;  // pi per population (pgt_kernels.hip: pi_build_kernel, PiTraits): 1 ... 8 trees of the dxy layout
-constexpr int kFstPopsLeafPieces = 4;  // 128-site pieces per level-1 node
 struct FstPopsTree {
     char *base;
     size_t sum_off[kMaxLevels];  // byte offset of level slot k: 2 P doubles per node
@@ -183,26 +161,36 @@ struct FstPopsTree {
     int n_pairs;
     uint32_t n_partials;         // build waves that left a partial (0: no sites)
 };
-inline FstPopsTree fst_pops_tree_view(const TreeLayout &t, int n_pairs, void *tree, int levels) {
-    FstPopsTree v{};
+
+// The one layout behind both (two kernel-argument types, one shape): per level and behind the levels an array of `sum_bytes`
+// of sums per pair and node (8: Σd; 16: Σa and Σ(a+b)) and an array of one u32 per pair and node, each padded to 256 bytes.
+template <class Tree>
+inline Tree pops_tree_view(const TreeLayout &t, int n_pairs, size_t sum_bytes, void *tree, int levels) {
+    Tree v{};
     v.base = static_cast<char *>(tree);
     v.n_levels = levels;
     v.n_pairs = n_pairs;
     auto pad = [](size_t b) { return ((b + 255) / 256) * 256; };
     size_t off = 0;
     for (int k = 0; k < t.n_levels; ++k) {
-        const uint64_t nodes = k == 0 ? t.count[0] / kFstPopsLeafPieces : t.count[k];
+        const uint64_t nodes = k == 0 ? t.count[0] / kPopsLeafPieces : t.count[k];
         v.sum_off[k] = off;
-        off += pad(nodes * (size_t)n_pairs * 16);
+        off += pad(nodes * (size_t)n_pairs * sum_bytes);
         v.cnt_off[k] = off;
         off += pad(nodes * (size_t)n_pairs * 4);
     }
     v.part_sum = off;
-    off += pad((size_t)kMaxBuildWaves * n_pairs * 16);
+    off += pad((size_t)kMaxBuildWaves * n_pairs * sum_bytes);
     v.part_cnt = off;
     off += pad((size_t)kMaxBuildWaves * n_pairs * 4);
     v.bytes = off;
     return v;
+}
+inline DxyPopsTree dxy_pops_tree_view(const TreeLayout &t, int n_pairs, void *tree, int levels) {
+    return pops_tree_view<DxyPopsTree>(t, n_pairs, 8, tree, levels);
+}
+inline FstPopsTree fst_pops_tree_view(const TreeLayout &t, int n_pairs, void *tree, int levels) {
+    return pops_tree_view<FstPopsTree>(t, n_pairs, 16, tree, levels);
 }
 
 // Speed-only hints of a context (pgt_set_max_window, pgt_set_window_step); 0 = unknown.
@@ -262,13 +250,13 @@ int launch_fst_af(const uint32_t *pos, const double *const *freq, const double *
                   uint64_t n, const pgt_win *win, uint64_t n_win, pgt_fst_row *out, void *tree, void *stream,
                   void *ev_build0, void *ev_build1, void *ev_query1, std::string *err, const Hints &hints);
 
-// pgt_dxy_pops_kernels.hip: tot = n_pairs device totals or NULL
+// pgt_dxy_pops_kernels.hip: tot = n_pairs device totals or NULL; 2 <= n_pops <= 8 (checked by the caller)
 int launch_dxy_pops(const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
                     uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_dxy_row *out, pgt_dxy_total *tot,
                     void *tree, void *stream, void *ev_build0, void *ev_build1, void *ev_query1, std::string *err,
                     const Hints &hints);
 
-// pgt_fst_pops_kernels.hip: tot = n_pairs device totals or NULL; minind >= 1 (checked by the caller)
+// pgt_fst_pops_kernels.hip: tot = n_pairs device totals or NULL; 2 <= n_pops <= 8 and minind >= 1 (checked by the caller)
 int launch_fst_pops(const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
                     uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_fst_row *out, pgt_fst_total *tot,
                     void *tree, void *stream, void *ev_build0, void *ev_build1, void *ev_query1, std::string *err,

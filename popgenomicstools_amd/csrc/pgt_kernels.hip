@@ -481,8 +481,8 @@ __global__ __launch_bounds__(256) void dxy_build_kernel(const double *p1, const 
 // (about 20 instructions on 12 bytes) the second candidate; no A/B has separated them and nothing was tuned.
 // ------------------------------------------------------------------------------------------
 struct PopCols {
-    const double *f[kPiPopsMaxPops];
-    const int32_t *n[kPiPopsMaxPops];
+    const double *f[kPopsMaxPops];
+    const int32_t *n[kPopsMaxPops];
 };
 __device__ __forceinline__ double pi_site(double p, int n) {
     const double two_n = __dmul_rn(2.0, (double)n);
@@ -1889,6 +1889,28 @@ inline int record(void *ev, hipStream_t s, std::string *err) {
     return hip_fail(hipEventRecord(static_cast<hipEvent_t>(ev), s), "hipEventRecord", err);
 }
 
+// The query launch of one statistic, `tables` row tables at once (grid.y): the group query, the sliding query or one wave per
+// window, as the hints say (group_query / slide_group, pgt_internal.h).  with_total: one extra work item carries the
+// genome-wide line (written where `tot` is not NULL); edge_scans: the group query is told group_edge_scans(hints), else 0.
+// `what` names the statistic in the error.  (The fused dxy_het queries are other kernels with a plan of their own.)
+template <class Tr>
+int launch_query(hipStream_t s, const Hints &hints, uint64_t leaf, unsigned tables, bool with_total, bool edge_scans,
+                 const typename Tr::Args &args, const uint32_t *pos, const TreeView &tv, const pgt_win *win, uint64_t n_win,
+                 typename Tr::Row *out, uint64_t n, pgt_dxy_total *tot, const char *what, std::string *err) {
+    const uint64_t extra = with_total ? 1 : 0;
+    if (group_query(hints, leaf)) {
+        const uint32_t g = group_size(n_win);
+        hipLaunchKernelGGL(query_group_kernel<Tr>, dim3(query_grid((n_win + g - 1) / g + extra), tables), dim3(256), kGroupLdsBytes, s,
+                           args, pos, tv, win, n_win, out, n, tot, g, edge_scans ? group_edge_scans(hints) : 0);
+    } else if (const uint32_t group = slide_group(hints.window_step); group > 1)
+        hipLaunchKernelGGL(query_slide_kernel<Tr>, dim3(query_grid((n_win + group - 1) / group + extra), tables), dim3(256),
+                           kSlideLdsBytes, s, args, pos, tv, win, n_win, out, n, tot, group);
+    else
+        hipLaunchKernelGGL(query_kernel<Tr>, dim3(query_grid(n_win + extra), tables), dim3(256), 0, s, args, pos, tv, win, n_win, out,
+                           n, tot);
+    return hip_fail(hipGetLastError(), what, err);
+}
+
 // ------------------------------------------------------------------------------------------
 // The site-window table written on the device from the per-run plan (pgt_windows.cpp: plan_entry_windows /
 // for_each_window are the host form of exactly this): thread i finds its run by bisection over the runs'
@@ -2001,22 +2023,10 @@ int launch_fst_with(BuildFn build, const uint32_t *pos, const double *const *a, 
             if (int rc = launch_upper<NodeFst>(tl, tv, np, s, err)) return rc;
         }
         if (p0 + np >= n_pairs) if (int rc = record(ev_build1, s, err)) return rc;
-        if (n_win > 0) {
-            FstTraits::Args args{cols};
-            if (group_query(hints, kLeafF64)) {
-                const uint32_t g = group_size(n_win);
-                hipLaunchKernelGGL(query_group_kernel<FstTraits>, dim3(query_grid((n_win + g - 1) / g), np), dim3(256),
-                                   kGroupLdsBytes, s, args, pos, tv, win, n_win, out + (uint64_t)p0 * n_win, n,
-                                   (pgt_dxy_total *)nullptr, g, group_edge_scans(hints));
-            } else if (const uint32_t group = slide_group(hints.window_step); group > 1)
-                hipLaunchKernelGGL(query_slide_kernel<FstTraits>, dim3(query_grid((n_win + group - 1) / group), np), dim3(256),
-                                   kSlideLdsBytes, s, args, pos, tv, win, n_win, out + (uint64_t)p0 * n_win, n,
-                                   (pgt_dxy_total *)nullptr, group);
-            else
-                hipLaunchKernelGGL(query_kernel<FstTraits>, dim3(query_grid(n_win), np), dim3(256), 0, s, args, pos,
-                                   tv, win, n_win, out + (uint64_t)p0 * n_win, n, (pgt_dxy_total *)nullptr);
-            if (int rc = hip_fail(hipGetLastError(), "query_kernel<fst>", err)) return rc;
-        }
+        if (n_win > 0)
+            if (int rc = launch_query<FstTraits>(s, hints, kLeafF64, np, false, true, FstTraits::Args{cols}, pos, tv, win, n_win,
+                                                 out + (uint64_t)p0 * n_win, n, nullptr, "query_kernel<fst>", err))
+                return rc;
     }
     return record(ev_query1, s, err);
 }
@@ -2053,20 +2063,10 @@ int launch_het(const uint32_t *pos, const int8_t *g, uint64_t n, const pgt_win *
         if (int rc = launch_upper<NodeHet>(tl, tv, 1, s, err, 1, n_items * kHetChunk)) return rc;
     }
     if (int rc = record(ev_build1, s, err)) return rc;
-    if (n_win > 0) {
-        HetTraits::Args args{g};
-        if (group_query(hints, kLeafI8)) {
-            const uint32_t g = group_size(n_win);
-            hipLaunchKernelGGL(query_group_kernel<HetTraits>, dim3(query_grid((n_win + g - 1) / g)), dim3(256),
-                               kGroupLdsBytes, s, args, pos, tv, win, n_win, out, n, (pgt_dxy_total *)nullptr, g, 0);
-        } else if (const uint32_t group = slide_group(hints.window_step); group > 1)
-            hipLaunchKernelGGL(query_slide_kernel<HetTraits>, dim3(query_grid((n_win + group - 1) / group)), dim3(256),
-                               kSlideLdsBytes, s, args, pos, tv, win, n_win, out, n, (pgt_dxy_total *)nullptr, group);
-        else
-            hipLaunchKernelGGL(query_kernel<HetTraits>, dim3(query_grid(n_win)), dim3(256), 0, s, args, pos, tv, win,
-                               n_win, out, n, (pgt_dxy_total *)nullptr);
-        if (int rc = hip_fail(hipGetLastError(), "query_kernel<het>", err)) return rc;
-    }
+    if (n_win > 0)
+        if (int rc = launch_query<HetTraits>(s, hints, kLeafI8, 1, false, false, HetTraits::Args{g}, pos, tv, win, n_win, out, n, nullptr,
+                                             "query_kernel<het>", err))
+            return rc;
     return record(ev_query1, s, err);
 }
 
@@ -2087,20 +2087,10 @@ int launch_dxy(const uint32_t *pos, const double *p1, const double *p2, const in
         if (int rc = launch_upper<NodeDxy>(tl, tv, 1, s, err)) return rc;
     }
     if (int rc = record(ev_build1, s, err)) return rc;
-    if (n_win > 0 || tot) {
-        DxyTraits::Args args{p1, p2, n1, n2, minind};
-        if (group_query(hints, kLeafF64)) {
-            const uint32_t g = group_size(n_win);
-            hipLaunchKernelGGL(query_group_kernel<DxyTraits>, dim3(query_grid((n_win + g - 1) / g + 1)), dim3(256),
-                               kGroupLdsBytes, s, args, pos, tv, win, n_win, out, n, tot, g, group_edge_scans(hints));
-        } else if (const uint32_t group = slide_group(hints.window_step); group > 1)
-            hipLaunchKernelGGL(query_slide_kernel<DxyTraits>, dim3(query_grid((n_win + group - 1) / group + 1)), dim3(256),
-                               kSlideLdsBytes, s, args, pos, tv, win, n_win, out, n, tot, group);
-        else
-            hipLaunchKernelGGL(query_kernel<DxyTraits>, dim3(query_grid(n_win + 1)), dim3(256), 0, s, args, pos, tv,
-                               win, n_win, out, n, tot);
-        if (int rc = hip_fail(hipGetLastError(), "query_kernel<dxy>", err)) return rc;
-    }
+    if (n_win > 0 || tot)
+        if (int rc = launch_query<DxyTraits>(s, hints, kLeafF64, 1, true, true, DxyTraits::Args{p1, p2, n1, n2, minind}, pos, tv, win,
+                                             n_win, out, n, tot, "query_kernel<dxy>", err))
+            return rc;
     return record(ev_query1, s, err);
 }
 
@@ -2125,19 +2115,10 @@ int launch_pi_pops(const uint32_t *pos, const double *const *freq, const int32_t
         if (int rc = launch_upper<NodeDxy>(tl, tv, n_pops, s, err)) return rc;
     }
     if (int rc = record(ev_build1, s, err)) return rc;
-    if (n_win > 0 || tot) {
-        if (group_query(hints, kLeafF64)) {
-            const uint32_t g = group_size(n_win);
-            hipLaunchKernelGGL(query_group_kernel<PiTraits>, dim3(query_grid((n_win + g - 1) / g + 1), n_pops), dim3(256),
-                               kGroupLdsBytes, s, args, pos, tv, win, n_win, out, n, tot, g, group_edge_scans(hints));
-        } else if (const uint32_t group = slide_group(hints.window_step); group > 1)
-            hipLaunchKernelGGL(query_slide_kernel<PiTraits>, dim3(query_grid((n_win + group - 1) / group + 1), n_pops), dim3(256),
-                               kSlideLdsBytes, s, args, pos, tv, win, n_win, out, n, tot, group);
-        else
-            hipLaunchKernelGGL(query_kernel<PiTraits>, dim3(query_grid(n_win + 1), n_pops), dim3(256), 0, s, args, pos, tv, win,
-                               n_win, out, n, tot);
-        if (int rc = hip_fail(hipGetLastError(), "query_kernel<pi>", err)) return rc;
-    }
+    if (n_win > 0 || tot)
+        if (int rc = launch_query<PiTraits>(s, hints, kLeafF64, n_pops, true, true, args, pos, tv, win, n_win, out, n, tot,
+                                            "query_kernel<pi>", err))
+            return rc;
     return record(ev_query1, s, err);
 }
 

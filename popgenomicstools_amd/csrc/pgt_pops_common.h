@@ -1,8 +1,10 @@
 // pgt_pops_common.h — what the "all pairs of up to 8 populations in one pass" front ends share (pgt_af_kernels.hip: FST from
-// allele frequencies; pgt_dxy_pops_kernels.hip: dxy from the populations' own columns): the pair count, the wave
-// reduce-scatter, the flush of a build wave's LDS stage, and the host
+// allele frequencies; pgt_dxy_pops_kernels.hip, pgt_fst_pops_kernels.hip: dxy and FST from the populations' own (freq, nInd)
+// columns): the pair count, the wave reduce-scatter, the flush of a build wave's LDS stage, and the host
 // side of a launch (error mapping, event records, grids, the upper-level loop, the dispatch on the population count, the
-// measuring knobs).  pgt_kernels.hip keeps helpers of its own: it does not include this header.
+// measuring knobs).  The static balanced build grid of the two (freq, nInd) front ends is pops_build_grid below; the layout of
+// their trees is pops_tree_view in pgt_internal.h (the C ABI sizes workspaces with it).  pgt_kernels.hip keeps helpers of its
+// own: it does not include this header.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -142,6 +144,24 @@ inline int record_event(void *ev, hipStream_t s, std::string *err) {
 inline unsigned wave_grid(uint64_t items) {
     const uint64_t b = (items + 3) / 4;
     return (unsigned)(b > 65536 ? 65536 : b);
+}
+
+// The build grid of the (freq, nInd) front ends (launch_np of pgt_dxy_pops_kernels.hip and pgt_fst_pops_kernels.hip) over
+// `n_tiles` level-2 tiles (tl.count[1] > 0): a static balanced grid of what is resident at once (one wave per SIMD: 256
+// workgroups of 4 waves; two: 512): every wave walks `rounds` tiles, all waves run in near lockstep and flush their node
+// blocks at about the same times.  (launch_af_np picks its round count by how full the last generation is; that choice is
+// unmeasured here, and the per-wave partials want a grid that depends on n alone.)  n_partials = the waves of the grid, one
+// partial each: <= kMaxBuildWaves, what the workspace reserves.
+struct PopsBuildGrid {
+    unsigned blocks;
+    uint32_t n_partials;
+};
+inline PopsBuildGrid pops_build_grid(uint64_t n_tiles, bool one_wave_per_simd) {
+    const uint64_t max_waves = one_wave_per_simd ? 1024 : (uint64_t)kMaxBuildWaves;
+    const uint64_t rounds = (n_tiles + max_waves - 1) / max_waves;
+    const uint64_t waves = (n_tiles + rounds - 1) / rounds;
+    const uint64_t blocks = (waves + 3) / 4;
+    return {(unsigned)blocks, (uint32_t)(blocks * 4)};
 }
 
 // levels 3 and up, one launch each: parent = Σ of 64 children, per value of a node (blockIdx.y < n_vals)

@@ -256,6 +256,31 @@ class WindowTable:
 
 
 # ---------------------------------------------------------------------------------------------
+# the K-population statistics over per-population (freq, nInd) columns: what is particular to each.  Their wrappers
+# (Context._pops_reduce, Context._pops_reduce_dev, _window_pops) are one body per form.
+# ---------------------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class _PopsStat:
+    name: str          # pgt_<name>_pops_reduce / _reduce_dev / _tree_bytes; <name>_pops_reduce* and <name>_window_pops in messages
+    min_pops: int      # min_pops ... 8 populations
+    per_pair: bool     # one row table per pair i < j (pair_order), else one per population
+    row: np.dtype
+    total: np.dtype
+
+    def tables(self, n_pops: int) -> int:
+        return n_pops * (n_pops - 1) // 2 if self.per_pair else n_pops
+
+    def check_count(self, who: str, freqs, ninds):
+        if len(ninds) != len(freqs) or not self.min_pops <= len(freqs) <= 8:
+            raise PgtError(_lib.PGT_EARG, f"{who}: {self.min_pops} ... 8 populations, one frequency and one count column each")
+
+
+_DXY_POPS = _PopsStat("dxy", 2, True, DXY_ROW_DTYPE, DXY_TOTAL_DTYPE)
+_FST_POPS = _PopsStat("fst", 2, True, FST_ROW_DTYPE, FST_TOTAL_DTYPE)
+_PI_POPS = _PopsStat("pi", 1, False, DXY_ROW_DTYPE, DXY_TOTAL_DTYPE)
+
+
+# ---------------------------------------------------------------------------------------------
 # context
 # ---------------------------------------------------------------------------------------------
 class Context:
@@ -349,68 +374,40 @@ class Context:
                                              win.ctypes.data, win.size, out.ctypes.data, tot.ctypes.data))
         return out, tot[0]
 
-    def dxy_pops_reduce(self, pos, freqs, ninds, minind, win):
-        """dxy rows of ALL pairs i<j of len(freqs) populations (pair_order) from per-population numpy columns, one pass:
-        -> (rows[n_pairs, n_win], totals[n_pairs]) (pgt_dxy_pops_reduce)."""
+    def _pops_reduce(self, st: _PopsStat, pos, freqs, ninds, minind, win):
+        """The numpy form of a K-population statistic (pgt_<name>_pops_reduce) -> (rows[tables, n_win], totals[tables])."""
+        who = f"{st.name}_pops_reduce"
         pos = np.ascontiguousarray(pos, dtype=np.uint32)
         freqs = [np.ascontiguousarray(f, dtype=np.float64) for f in freqs]
         ninds = [np.ascontiguousarray(k, dtype=np.int32) for k in ninds]
         win = np.ascontiguousarray(win, dtype=WIN_DTYPE)
         n_pops = len(freqs)
-        if len(ninds) != n_pops or not 2 <= n_pops <= 8:
-            raise PgtError(_lib.PGT_EARG, "dxy_pops_reduce: 2 ... 8 populations, one frequency and one count column each")
+        st.check_count(who, freqs, ninds)
         if any(c.size != pos.size for c in freqs + ninds):
-            raise PgtError(_lib.PGT_EARG, "dxy_pops_reduce: column lengths differ")
-        n_pairs = n_pops * (n_pops - 1) // 2
-        out = np.zeros((n_pairs, win.size), dtype=DXY_ROW_DTYPE)
-        tot = np.zeros(n_pairs, dtype=DXY_TOTAL_DTYPE)
+            raise PgtError(_lib.PGT_EARG, f"{who}: column lengths differ")
+        out = np.zeros((st.tables(n_pops), win.size), dtype=st.row)
+        tot = np.zeros(st.tables(n_pops), dtype=st.total)
         pf = (C.c_void_p * n_pops)(*[f.ctypes.data for f in freqs])
         pn = (C.c_void_p * n_pops)(*[k.ctypes.data for k in ninds])
-        self._check(self._lib.pgt_dxy_pops_reduce(self._ctx, pos.ctypes.data, pf, pn, n_pops, pos.size, int(minind),
-                                                  win.ctypes.data, win.size, out.ctypes.data, tot.ctypes.data))
+        self._check(getattr(self._lib, f"pgt_{who}")(self._ctx, pos.ctypes.data, pf, pn, n_pops, pos.size, int(minind),
+                                                     win.ctypes.data, win.size, out.ctypes.data, tot.ctypes.data))
         return out, tot
+
+    def dxy_pops_reduce(self, pos, freqs, ninds, minind, win):
+        """dxy rows of ALL pairs i<j of len(freqs) populations (pair_order) from per-population numpy columns, one pass:
+        -> (rows[n_pairs, n_win], totals[n_pairs]) (pgt_dxy_pops_reduce)."""
+        return self._pops_reduce(_DXY_POPS, pos, freqs, ninds, minind, win)
 
     def fst_pops_reduce(self, pos, freqs, ninds, minind, win):
         """FST rows of ALL pairs i<j of len(freqs) populations (pair_order) from per-population numpy (freq, nInd) columns, one
         pass: -> (rows[n_pairs, n_win], totals[n_pairs]) (pgt_fst_pops_reduce).  A row's n is the number of counted sites."""
-        pos = np.ascontiguousarray(pos, dtype=np.uint32)
-        freqs = [np.ascontiguousarray(f, dtype=np.float64) for f in freqs]
-        ninds = [np.ascontiguousarray(k, dtype=np.int32) for k in ninds]
-        win = np.ascontiguousarray(win, dtype=WIN_DTYPE)
-        n_pops = len(freqs)
-        if len(ninds) != n_pops or not 2 <= n_pops <= 8:
-            raise PgtError(_lib.PGT_EARG, "fst_pops_reduce: 2 ... 8 populations, one frequency and one count column each")
-        if any(c.size != pos.size for c in freqs + ninds):
-            raise PgtError(_lib.PGT_EARG, "fst_pops_reduce: column lengths differ")
-        n_pairs = n_pops * (n_pops - 1) // 2
-        out = np.zeros((n_pairs, win.size), dtype=FST_ROW_DTYPE)
-        tot = np.zeros(n_pairs, dtype=FST_TOTAL_DTYPE)
-        pf = (C.c_void_p * n_pops)(*[f.ctypes.data for f in freqs])
-        pn = (C.c_void_p * n_pops)(*[k.ctypes.data for k in ninds])
-        self._check(self._lib.pgt_fst_pops_reduce(self._ctx, pos.ctypes.data, pf, pn, n_pops, pos.size, int(minind),
-                                                  win.ctypes.data, win.size, out.ctypes.data, tot.ctypes.data))
-        return out, tot
+        return self._pops_reduce(_FST_POPS, pos, freqs, ninds, minind, win)
 
     def pi_pops_reduce(self, pos, freqs, ninds, minind, win):
         """Nucleotide-diversity (pi) rows of EACH of len(freqs) populations (1 ... 8) from per-population numpy (freq, nInd)
         columns, one pass: -> (rows[n_pops, n_win], totals[n_pops]) (pgt_pi_pops_reduce).  A row's sum is Σ 2p(1-p) 2n/(2n-1) over
         its counted sites (nInd >= minind); divide by neff or by the window length."""
-        pos = np.ascontiguousarray(pos, dtype=np.uint32)
-        freqs = [np.ascontiguousarray(f, dtype=np.float64) for f in freqs]
-        ninds = [np.ascontiguousarray(k, dtype=np.int32) for k in ninds]
-        win = np.ascontiguousarray(win, dtype=WIN_DTYPE)
-        n_pops = len(freqs)
-        if len(ninds) != n_pops or not 1 <= n_pops <= 8:
-            raise PgtError(_lib.PGT_EARG, "pi_pops_reduce: 1 ... 8 populations, one frequency and one count column each")
-        if any(c.size != pos.size for c in freqs + ninds):
-            raise PgtError(_lib.PGT_EARG, "pi_pops_reduce: column lengths differ")
-        out = np.zeros((n_pops, win.size), dtype=DXY_ROW_DTYPE)
-        tot = np.zeros(n_pops, dtype=DXY_TOTAL_DTYPE)
-        pf = (C.c_void_p * n_pops)(*[f.ctypes.data for f in freqs])
-        pn = (C.c_void_p * n_pops)(*[k.ctypes.data for k in ninds])
-        self._check(self._lib.pgt_pi_pops_reduce(self._ctx, pos.ctypes.data, pf, pn, n_pops, pos.size, int(minind),
-                                                 win.ctypes.data, win.size, out.ctypes.data, tot.ctypes.data))
-        return out, tot
+        return self._pops_reduce(_PI_POPS, pos, freqs, ninds, minind, win)
 
     # ---- device-resident columns (torch CUDA tensors) -------------------------------------
     @staticmethod
@@ -691,6 +688,40 @@ class Context:
             self._stream(stream)))
         return out, tree
 
+    def _pops_reduce_dev(self, st: _PopsStat, pos, freqs, ninds, minind, win, out, tot, tree, stream):
+        """The device form of a K-population statistic (pgt_<name>_pops_reduce_dev) -> (out, tot, tree)."""
+        import torch
+        who = f"{st.name}_pops_reduce_dev"
+        n_pops = len(freqs)
+        st.check_count(who, freqs, ninds)
+        n = freqs[0].numel()
+        tables = st.tables(n_pops)
+        n_win = win.numel() // WIN_DTYPE.itemsize
+        tb = int(getattr(self._lib, f"pgt_{st.name}_pops_tree_bytes")(n_pops, n))
+        dev = pos.device
+        if tree is None:
+            tree = torch.empty(tb, dtype=torch.uint8, device=dev)
+        if out is None:
+            out = torch.empty(tables * n_win * st.row.itemsize, dtype=torch.uint8, device=dev)
+        if tot is None:
+            tot = torch.empty(tables * st.total.itemsize, dtype=torch.uint8, device=dev)
+        elif tot is False:
+            tot = None
+        self._same_len(who, n, pos, *freqs, *ninds)
+        self._room(f"{who}: out", out, tables * n_win * st.row.itemsize)
+        self._room(f"{who}: tree", tree, tb)
+        if tot is not None:
+            self._room(f"{who}: tot", tot, tables * st.total.itemsize)
+        pf = (C.c_void_p * n_pops)(*[self._col(t, torch.float64, f"freqs[{k}]") for k, t in enumerate(freqs)])
+        pn = (C.c_void_p * n_pops)(*[self._col(t, torch.int32, f"ninds[{k}]") for k, t in enumerate(ninds)])
+        self._check(getattr(self._lib, f"pgt_{who}")(
+            self._ctx, self._dev(pos, torch.int32, "pos"), pf, pn, n_pops, n, int(minind),
+            self._dev(win, torch.uint8, "win") if n_win else None, n_win,
+            self._dev(out, torch.uint8, "out") if n_win else None, out.numel(),
+            self._dev(tot, torch.uint8, "tot") if tot is not None else None,
+            self._dev(tree, torch.uint8, "tree"), tree.numel(), self._stream(stream)))
+        return out, tot, tree
+
     @staticmethod
     def dxy_pops_tree_bytes(n_pops: int, n_sites: int) -> int:
         return int(_lib.load().pgt_dxy_pops_tree_bytes(int(n_pops), int(n_sites)))
@@ -699,37 +730,7 @@ class Context:
         """dxy rows of ALL pairs i<j of len(freqs) populations (pair-major, pair_order) in one pass over the populations'
         own columns.  freqs: float64 CUDA tensors, ninds: int32 CUDA tensors.  tot: None = a fresh buffer of n_pairs totals
         is allocated and filled; False = no genome-wide lines.  Returns (out, tot, tree).  Asynchronous on `stream`."""
-        import torch
-        n_pops = len(freqs)
-        if len(ninds) != n_pops or not 2 <= n_pops <= 8:
-            raise PgtError(_lib.PGT_EARG, "dxy_pops_reduce_dev: 2 ... 8 populations, one frequency and one count column each")
-        n = freqs[0].numel()
-        n_pairs = n_pops * (n_pops - 1) // 2
-        n_win = win.numel() // WIN_DTYPE.itemsize
-        tb = self.dxy_pops_tree_bytes(n_pops, n)
-        dev = pos.device
-        if tree is None:
-            tree = torch.empty(tb, dtype=torch.uint8, device=dev)
-        if out is None:
-            out = torch.empty(n_pairs * n_win * DXY_ROW_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        if tot is None:
-            tot = torch.empty(n_pairs * DXY_TOTAL_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        elif tot is False:
-            tot = None
-        self._same_len("dxy_pops_reduce_dev", n, pos, *freqs, *ninds)
-        self._room("dxy_pops_reduce_dev: out", out, n_pairs * n_win * DXY_ROW_DTYPE.itemsize)
-        self._room("dxy_pops_reduce_dev: tree", tree, tb)
-        if tot is not None:
-            self._room("dxy_pops_reduce_dev: tot", tot, n_pairs * DXY_TOTAL_DTYPE.itemsize)
-        pf = (C.c_void_p * n_pops)(*[self._col(t, torch.float64, f"freqs[{k}]") for k, t in enumerate(freqs)])
-        pn = (C.c_void_p * n_pops)(*[self._col(t, torch.int32, f"ninds[{k}]") for k, t in enumerate(ninds)])
-        self._check(self._lib.pgt_dxy_pops_reduce_dev(
-            self._ctx, self._dev(pos, torch.int32, "pos"), pf, pn, n_pops, n, int(minind),
-            self._dev(win, torch.uint8, "win") if n_win else None, n_win,
-            self._dev(out, torch.uint8, "out") if n_win else None, out.numel(),
-            self._dev(tot, torch.uint8, "tot") if tot is not None else None,
-            self._dev(tree, torch.uint8, "tree"), tree.numel(), self._stream(stream)))
-        return out, tot, tree
+        return self._pops_reduce_dev(_DXY_POPS, pos, freqs, ninds, minind, win, out, tot, tree, stream)
 
     @staticmethod
     def fst_pops_tree_bytes(n_pops: int, n_sites: int) -> int:
@@ -740,37 +741,7 @@ class Context:
         (freq, nInd) columns, with per-site sample sizes and the -minind predicate.  freqs: float64 CUDA tensors, ninds: int32
         CUDA tensors.  tot: None = a fresh buffer of n_pairs totals is allocated and filled; False = no genome-wide lines.
         Returns (out, tot, tree).  Asynchronous on `stream`."""
-        import torch
-        n_pops = len(freqs)
-        if len(ninds) != n_pops or not 2 <= n_pops <= 8:
-            raise PgtError(_lib.PGT_EARG, "fst_pops_reduce_dev: 2 ... 8 populations, one frequency and one count column each")
-        n = freqs[0].numel()
-        n_pairs = n_pops * (n_pops - 1) // 2
-        n_win = win.numel() // WIN_DTYPE.itemsize
-        tb = self.fst_pops_tree_bytes(n_pops, n)
-        dev = pos.device
-        if tree is None:
-            tree = torch.empty(tb, dtype=torch.uint8, device=dev)
-        if out is None:
-            out = torch.empty(n_pairs * n_win * FST_ROW_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        if tot is None:
-            tot = torch.empty(n_pairs * FST_TOTAL_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        elif tot is False:
-            tot = None
-        self._same_len("fst_pops_reduce_dev", n, pos, *freqs, *ninds)
-        self._room("fst_pops_reduce_dev: out", out, n_pairs * n_win * FST_ROW_DTYPE.itemsize)
-        self._room("fst_pops_reduce_dev: tree", tree, tb)
-        if tot is not None:
-            self._room("fst_pops_reduce_dev: tot", tot, n_pairs * FST_TOTAL_DTYPE.itemsize)
-        pf = (C.c_void_p * n_pops)(*[self._col(t, torch.float64, f"freqs[{k}]") for k, t in enumerate(freqs)])
-        pn = (C.c_void_p * n_pops)(*[self._col(t, torch.int32, f"ninds[{k}]") for k, t in enumerate(ninds)])
-        self._check(self._lib.pgt_fst_pops_reduce_dev(
-            self._ctx, self._dev(pos, torch.int32, "pos"), pf, pn, n_pops, n, int(minind),
-            self._dev(win, torch.uint8, "win") if n_win else None, n_win,
-            self._dev(out, torch.uint8, "out") if n_win else None, out.numel(),
-            self._dev(tot, torch.uint8, "tot") if tot is not None else None,
-            self._dev(tree, torch.uint8, "tree"), tree.numel(), self._stream(stream)))
-        return out, tot, tree
+        return self._pops_reduce_dev(_FST_POPS, pos, freqs, ninds, minind, win, out, tot, tree, stream)
 
     @staticmethod
     def pi_pops_tree_bytes(n_pops: int, n_sites: int) -> int:
@@ -781,36 +752,7 @@ class Context:
         populations' own (freq, nInd) columns.  freqs: float64 CUDA tensors, ninds: int32 CUDA tensors.  tot: None = a fresh
         buffer of n_pops totals is allocated and filled; False = no genome-wide lines.  All three hints of the context are
         honoured (the query strategies of dxy_reduce_dev).  Returns (out, tot, tree).  Asynchronous on `stream`."""
-        import torch
-        n_pops = len(freqs)
-        if len(ninds) != n_pops or not 1 <= n_pops <= 8:
-            raise PgtError(_lib.PGT_EARG, "pi_pops_reduce_dev: 1 ... 8 populations, one frequency and one count column each")
-        n = freqs[0].numel()
-        n_win = win.numel() // WIN_DTYPE.itemsize
-        tb = self.pi_pops_tree_bytes(n_pops, n)
-        dev = pos.device
-        if tree is None:
-            tree = torch.empty(tb, dtype=torch.uint8, device=dev)
-        if out is None:
-            out = torch.empty(n_pops * n_win * DXY_ROW_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        if tot is None:
-            tot = torch.empty(n_pops * DXY_TOTAL_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        elif tot is False:
-            tot = None
-        self._same_len("pi_pops_reduce_dev", n, pos, *freqs, *ninds)
-        self._room("pi_pops_reduce_dev: out", out, n_pops * n_win * DXY_ROW_DTYPE.itemsize)
-        self._room("pi_pops_reduce_dev: tree", tree, tb)
-        if tot is not None:
-            self._room("pi_pops_reduce_dev: tot", tot, n_pops * DXY_TOTAL_DTYPE.itemsize)
-        pf = (C.c_void_p * n_pops)(*[self._col(t, torch.float64, f"freqs[{k}]") for k, t in enumerate(freqs)])
-        pn = (C.c_void_p * n_pops)(*[self._col(t, torch.int32, f"ninds[{k}]") for k, t in enumerate(ninds)])
-        self._check(self._lib.pgt_pi_pops_reduce_dev(
-            self._ctx, self._dev(pos, torch.int32, "pos"), pf, pn, n_pops, n, int(minind),
-            self._dev(win, torch.uint8, "win") if n_win else None, n_win,
-            self._dev(out, torch.uint8, "out") if n_win else None, out.numel(),
-            self._dev(tot, torch.uint8, "tot") if tot is not None else None,
-            self._dev(tree, torch.uint8, "tree"), tree.numel(), self._stream(stream)))
-        return out, tot, tree
+        return self._pops_reduce_dev(_PI_POPS, pos, freqs, ninds, minind, win, out, tot, tree, stream)
 
     def extreme_reduce_dev(self, pos, score, mode, cutoff, win, out=None, tree=None, stream=None):
         """ihsWindow / xpehhWindow rows from a device-resident score column (mode: PGT_EXT_*)."""
@@ -996,11 +938,8 @@ def het_window(chr_ids, pos, g, W: int = 1, S: int = 1, ctx: Context | None = No
             ctx.close()
 
 
-def dxy_window(chr_ids, pos, p1, p2, n1, n2, W: int = 0, S: int = 0, minind: int = 1, fixedsite: int = 0,
-               chr_len=None, skip_missing: int = 0, ctx: Context | None = None) -> WindowResult:
-    """dxyWindow.cpp:253-436 over two already synchronised populations.  chr_len[r] is the -sizefile
-    length of run r (required unless fixedsite).  Rows suppressed by -skip_missing are dropped, as
-    dxyWindow.cpp:189 does."""
+def _refuse_dxy_window_args(W, S, minind, fixedsite, chr_len):
+    """The refusals of dxyWindow's command line, raised before a context is opened (dxy_window and the *_window_pops)."""
     if minind <= 0:
         raise PgtError(_lib.PGT_EARG, "-minind must be at least 1")  # dxyWindow.cpp:105-108
     if W > 0 and S < 1:
@@ -1009,13 +948,25 @@ def dxy_window(chr_ids, pos, p1, p2, n1, n2, W: int = 0, S: int = 0, minind: int
         raise PgtError(_lib.PGT_EARG, "Must supply size file unless -fixedsite 1")  # :133-136
     if W == 0 and not fixedsite:
         raise PgtError(_lib.PGT_EDOMAIN, "-winsize 0 needs -fixedsite 1 (the reference crashes here, SURVEY Q10)")
+
+
+def _dxy_window_table(chr_ids, pos, W, S, fixedsite, chr_len) -> np.ndarray:
+    """dxyWindow's table: none (-winsize 0: the genome-wide line alone), site windows (-fixedsite 1) or base-pair slots."""
     rl = run_lengths(chr_ids)
     if W == 0:
-        win = np.zeros(0, dtype=WIN_DTYPE)
-    elif fixedsite:
-        win = build_windows_sites(rl, W, S)
-    else:
-        win = build_windows_bp(pos, rl, chr_len, W, S)
+        return np.zeros(0, dtype=WIN_DTYPE)
+    if fixedsite:
+        return build_windows_sites(rl, W, S)
+    return build_windows_bp(pos, rl, chr_len, W, S)
+
+
+def dxy_window(chr_ids, pos, p1, p2, n1, n2, W: int = 0, S: int = 0, minind: int = 1, fixedsite: int = 0,
+               chr_len=None, skip_missing: int = 0, ctx: Context | None = None) -> WindowResult:
+    """dxyWindow.cpp:253-436 over two already synchronised populations.  chr_len[r] is the -sizefile
+    length of run r (required unless fixedsite).  Rows suppressed by -skip_missing are dropped, as
+    dxyWindow.cpp:189 does."""
+    _refuse_dxy_window_args(W, S, minind, fixedsite, chr_len)
+    win = _dxy_window_table(chr_ids, pos, W, S, fixedsite, chr_len)
     ctx, own = _own_ctx(ctx)
     try:
         rows, tot = ctx.dxy_reduce(pos, p1, p2, n1, n2, minind, win)
@@ -1088,45 +1039,43 @@ def pair_order(n_pops: int):
     return [(i, j) for i in range(int(n_pops)) for j in range(i + 1, int(n_pops))]
 
 
+def _window_pops(st: _PopsStat, chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx):
+    """What the *_window_pops functions share: dxy_window's refusals, the population count, host columns, the window table and
+    one pass of the statistic's numpy form -> (win, rows[tables, n_win], totals[tables])."""
+    _refuse_dxy_window_args(W, S, minind, fixedsite, chr_len)
+    st.check_count(f"{st.name}_window_pops", freqs, ninds)
+    chr_ids, pos = _host_col(chr_ids, None), _host_col(pos, np.uint32)
+    freqs, ninds = [_host_col(f, np.float64) for f in freqs], [_host_col(c, np.int32) for c in ninds]
+    win = _dxy_window_table(chr_ids, pos, W, S, fixedsite, chr_len)
+    ctx, own = _own_ctx(ctx)
+    try:
+        rows, tot = ctx._pops_reduce(st, pos, freqs, ninds, minind, win)
+    finally:
+        if own:
+            ctx.close()
+    return win, rows, tot
+
+
+def _results_by_pair(n_pops, win, rows, tot, skip_missing, counted: str) -> dict:
+    """{(i, j): WindowResult} in pair_order; -skip_missing drops a pair's rows without counted sites (field `counted`)."""
+    res = {}
+    for p, ij in enumerate(pair_order(n_pops)):
+        w, r = win, rows[p]
+        if skip_missing:
+            keep = r[counted] > 0
+            w, r = w[keep], r[keep]
+        res[ij] = WindowResult(w, r, tot[p])
+    return res
+
+
 def dxy_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: int = 1, fixedsite: int = 0,
                     chr_len=None, skip_missing: int = 0, ctx: Context | None = None) -> dict:
     """dxy_window for ALL pairs of len(freqs) already synchronised populations in one pass: {(i, j): WindowResult}.
     Arguments and errors are those of dxy_window; -skip_missing drops a pair's rows without counted sites from that pair's
     result only.  Columns may be CUDA tensors (align_sites' result): this host-table form downloads them; stay on the device
     with Context.dxy_pops_reduce_dev."""
-    if minind <= 0:
-        raise PgtError(_lib.PGT_EARG, "-minind must be at least 1")  # dxyWindow.cpp:105-108
-    if W > 0 and S < 1:
-        raise PgtError(_lib.PGT_EARG, "Must specify a -stepsize > 0 when -winsize is > 0")  # :128-131
-    if not fixedsite and chr_len is None:
-        raise PgtError(_lib.PGT_EARG, "Must supply size file unless -fixedsite 1")  # :133-136
-    if W == 0 and not fixedsite:
-        raise PgtError(_lib.PGT_EDOMAIN, "-winsize 0 needs -fixedsite 1 (the reference crashes here, SURVEY Q10)")
-    if len(ninds) != len(freqs) or not 2 <= len(freqs) <= 8:
-        raise PgtError(_lib.PGT_EARG, "dxy_window_pops: 2 ... 8 populations, one frequency and one count column each")
-    chr_ids, pos = _host_col(chr_ids, None), _host_col(pos, np.uint32)
-    freqs, ninds = [_host_col(f, np.float64) for f in freqs], [_host_col(c, np.int32) for c in ninds]
-    rl = run_lengths(chr_ids)
-    if W == 0:
-        win = np.zeros(0, dtype=WIN_DTYPE)
-    elif fixedsite:
-        win = build_windows_sites(rl, W, S)
-    else:
-        win = build_windows_bp(pos, rl, chr_len, W, S)
-    ctx, own = _own_ctx(ctx)
-    try:
-        rows, tot = ctx.dxy_pops_reduce(pos, freqs, ninds, minind, win)
-    finally:
-        if own:
-            ctx.close()
-    res = {}
-    for p, ij in enumerate(pair_order(len(freqs))):
-        w, r = win, rows[p]
-        if skip_missing:
-            keep = r["neff"] > 0
-            w, r = w[keep], r[keep]
-        res[ij] = WindowResult(w, r, tot[p])
-    return res
+    win, rows, tot = _window_pops(_DXY_POPS, chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx)
+    return _results_by_pair(len(freqs), win, rows, tot, skip_missing, "neff")
 
 
 def fst_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: int = 1, fixedsite: int = 0,
@@ -1135,39 +1084,8 @@ def fst_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: 
     fstWindow's rows (n = counted sites of the pair; the skipped ones are (hi - lo) - n) and the genome-wide line as total.
     Window arguments and their errors are those of dxy_window_pops; -skip_missing drops a pair's rows without counted
     sites from that pair's result only."""
-    if minind <= 0:
-        raise PgtError(_lib.PGT_EARG, "-minind must be at least 1")
-    if W > 0 and S < 1:
-        raise PgtError(_lib.PGT_EARG, "Must specify a -stepsize > 0 when -winsize is > 0")
-    if not fixedsite and chr_len is None:
-        raise PgtError(_lib.PGT_EARG, "Must supply size file unless -fixedsite 1")
-    if W == 0 and not fixedsite:
-        raise PgtError(_lib.PGT_EDOMAIN, "-winsize 0 needs -fixedsite 1 (the reference crashes here, SURVEY Q10)")
-    if len(ninds) != len(freqs) or not 2 <= len(freqs) <= 8:
-        raise PgtError(_lib.PGT_EARG, "fst_window_pops: 2 ... 8 populations, one frequency and one count column each")
-    chr_ids, pos = _host_col(chr_ids, None), _host_col(pos, np.uint32)
-    freqs, ninds = [_host_col(f, np.float64) for f in freqs], [_host_col(c, np.int32) for c in ninds]
-    rl = run_lengths(chr_ids)
-    if W == 0:
-        win = np.zeros(0, dtype=WIN_DTYPE)
-    elif fixedsite:
-        win = build_windows_sites(rl, W, S)
-    else:
-        win = build_windows_bp(pos, rl, chr_len, W, S)
-    ctx, own = _own_ctx(ctx)
-    try:
-        rows, tot = ctx.fst_pops_reduce(pos, freqs, ninds, minind, win)
-    finally:
-        if own:
-            ctx.close()
-    res = {}
-    for p, ij in enumerate(pair_order(len(freqs))):
-        w, r = win, rows[p]
-        if skip_missing:
-            keep = r["n"] > 0
-            w, r = w[keep], r[keep]
-        res[ij] = WindowResult(w, r, tot[p])
-    return res
+    win, rows, tot = _window_pops(_FST_POPS, chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx)
+    return _results_by_pair(len(freqs), win, rows, tot, skip_missing, "n")
 
 
 def pi_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: int = 1, fixedsite: int = 0,
@@ -1176,31 +1094,7 @@ def pi_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: i
     several) in one pass: a list of WindowResult, one per population, with dxyWindow's rows (sum = Σ pi over the counted
     sites, neff, nskip) and the genome-wide line as total.  Window arguments and their errors are those of dxy_window_pops.
     The reference has no counterpart; the per-site definition is pgt_pi_pops_reduce_dev's (include/pgtwin.h)."""
-    if minind <= 0:
-        raise PgtError(_lib.PGT_EARG, "-minind must be at least 1")
-    if W > 0 and S < 1:
-        raise PgtError(_lib.PGT_EARG, "Must specify a -stepsize > 0 when -winsize is > 0")
-    if not fixedsite and chr_len is None:
-        raise PgtError(_lib.PGT_EARG, "Must supply size file unless -fixedsite 1")
-    if W == 0 and not fixedsite:
-        raise PgtError(_lib.PGT_EDOMAIN, "-winsize 0 needs -fixedsite 1 (the reference crashes here, SURVEY Q10)")
-    if len(ninds) != len(freqs) or not 1 <= len(freqs) <= 8:
-        raise PgtError(_lib.PGT_EARG, "pi_window_pops: 1 ... 8 populations, one frequency and one count column each")
-    chr_ids, pos = _host_col(chr_ids, None), _host_col(pos, np.uint32)
-    freqs, ninds = [_host_col(f, np.float64) for f in freqs], [_host_col(c, np.int32) for c in ninds]
-    rl = run_lengths(chr_ids)
-    if W == 0:
-        win = np.zeros(0, dtype=WIN_DTYPE)
-    elif fixedsite:
-        win = build_windows_sites(rl, W, S)
-    else:
-        win = build_windows_bp(pos, rl, chr_len, W, S)
-    ctx, own = _own_ctx(ctx)
-    try:
-        rows, tot = ctx.pi_pops_reduce(pos, freqs, ninds, minind, win)
-    finally:
-        if own:
-            ctx.close()
+    win, rows, tot = _window_pops(_PI_POPS, chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx)
     return [WindowResult(win, rows[k], tot[k]) for k in range(len(freqs))]
 
 
