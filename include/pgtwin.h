@@ -52,7 +52,8 @@ extern "C" {
  * Still 6: pgt_dxy_pops_tree_bytes / pgt_dxy_pops_reduce_dev / pgt_dxy_pops_reduce added (additive: nothing that existed changed).
  * Still 6: pgt_align_segments / pgt_align_workspace_bytes / pgt_sites_align / pgt_gather_dev added (additive as well).
  * Still 6: pgt_fst_total, pgt_fst_pops_tree_bytes / pgt_fst_pops_reduce_dev / pgt_fst_pops_reduce added (additive as well).
- * Still 6: pgt_pi_pops_tree_bytes / pgt_pi_pops_reduce_dev / pgt_pi_pops_reduce added (additive as well). */
+ * Still 6: pgt_pi_pops_tree_bytes / pgt_pi_pops_reduce_dev / pgt_pi_pops_reduce added (additive as well).
+ * Still 6: pgt_fst_hudson_pops_tree_bytes / pgt_fst_hudson_pops_reduce_dev / pgt_fst_hudson_pops_reduce added (additive as well). */
 #define PGT_ABI_VERSION 6
 
 enum {
@@ -266,6 +267,46 @@ int pgt_fst_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *con
 int pgt_fst_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq,
                         const int32_t *const *nind, uint32_t n_pops, uint64_t n, int minind,
                         const pgt_win *win, uint64_t n_win, pgt_fst_row *out, pgt_fst_total *tot);
+
+/* ---- Hudson's FST of all population pairs from per-population MAF columns ---------------------------- */
+/* The rows of pgt_fst_pops_reduce_dev with the other estimator: Hudson's FST as a RATIO OF AVERAGES (Hudson, Slatkin &
+ * Maddison 1992; Bhatia, Patterson, Sankararaman & Price 2013, eq. 10, who recommend it for populations of unequal, per-site
+ * varying sample size — what MAF files from low-coverage data hold).  Same columns, window table, pair order, row and total
+ * types as pgt_fst_pops_reduce_dev; a row's asum is the window's Σ numerator, its bsum the Σ denominator.  Per site the
+ * denominator is dxy (pgt_dxy_pops_reduce_dev's term, bit for bit) and the numerator the net divergence dxy - (pi_i + pi_j)/2
+ * with pi as pgt_pi_pops_reduce_dev defines it: (p1-p2)^2 - h1 - h2 = D - [p1(1-p1)+h1] - [p2(1-p2)+h2].
+ * It has NO counterpart in the reference (WCFst() is its only frequency-based FST): the definition below is the contract.
+ * For pair (i, j), i < j, and site s:
+ *   counting   nind_i[s] >= minind && nind_j[s] >= minind   (signed int32 compare; minind >= 1 required,
+ *              PGT_EARG otherwise: it makes 2 nind - 1 >= 1 at every counted site)
+ *   per site   p1 = freq_i[s], p2 = freq_j[s]; for k in {1, 2}, every operation rounded on its own, no contraction:
+ *                  m_k = 2.0 * (double)nind_k[s] - 1.0          haploid sample size minus one
+ *                  h_k = (p_k * (1.0 - p_k)) / m_k              ONE correctly rounded IEEE division per population and site
+ *              d   = p1 - p2
+ *              num = (d * d - h_1) - h_2                        h_1 is population i's, h_2 population j's
+ *              den = p1 * (1.0 - p2) + p2 * (1.0 - p1)          dxy_site_pred's roundings, bit for bit
+ *              a site that is not counted is selected away, never multiplied (its frequency may be NaN, its nind 0 or negative)
+ *   row        pgt_fst_row: asum = Σ num, bsum = Σ den over the window's counted sites, each from +0.0; n = their number
+ *              (nskip = (hi - lo) - n); fst = bsum != 0 ? asum / bsum : 0; start / end / mid as pgt_fst_pops_reduce_dev
+ *   tot        pgt_fst_total per pair: the same sums over all counted sites, from one partial per build wave in wave order
+ * A one-site window carries exactly the bits of `num`, `den` and `num/den` above.
+ *   tree       pgt_fst_hudson_pops_tree_bytes(n_pops, n) = pgt_fst_pops_tree_bytes(n_pops, n): one buffer may serve both
+ *              entry points in turn, never two calls in flight.    2 <= n_pops <= 8, n < 2^32.
+ * Arguments, alignment, refusals (each names its argument; nothing is launched), the order of the pairs and of the rows,
+ * graph capture and the hints: those of pgt_fst_pops_reduce_dev (pgt_set_max_window honoured, pgt_set_window_step ignored).
+ * Rows of a pair do not depend, bit for bit, on the other populations' columns or on the other rows of the table.  Sums are
+ * added in a fixed order (bitwise reproducible); against an exact evaluation of the lines above they stay within 1e-9
+ * relative + 1e-12.  Parity: none to pin; held to this definition, to an exact-rational fixture
+ * (tests/golden/hudson_exact.json) and to the dxy and pi entry points.
+ * Host-buffer form: columns (host arrays of n_pops HOST pointers), table, rows and the n_pairs totals in host memory. */
+size_t pgt_fst_hudson_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites);
+int pgt_fst_hudson_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq,
+                                   const int32_t *const *nind, uint32_t n_pops, uint64_t n, int minind,
+                                   const pgt_win *win, uint64_t n_win, pgt_fst_row *out, size_t out_bytes,
+                                   pgt_fst_total *tot, void *tree, size_t tree_bytes, void *stream);
+int pgt_fst_hudson_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq,
+                               const int32_t *const *nind, uint32_t n_pops, uint64_t n, int minind,
+                               const pgt_win *win, uint64_t n_win, pgt_fst_row *out, pgt_fst_total *tot);
 
 /* ---- nucleotide diversity (pi) per population from per-population MAF columns --------------------- */
 /* Windowed within-population nucleotide diversity of each of n_pops populations from its own (freq, nInd) columns — the

@@ -57,6 +57,7 @@ SYMBOLS = [
     "pgt_align_segments", "pgt_align_workspace_bytes", "pgt_sites_align", "pgt_gather_dev",
     "pgt_fst_pops_tree_bytes", "pgt_fst_pops_reduce_dev", "pgt_fst_pops_reduce",
     "pgt_pi_pops_tree_bytes", "pgt_pi_pops_reduce_dev", "pgt_pi_pops_reduce",
+    "pgt_fst_hudson_pops_tree_bytes", "pgt_fst_hudson_pops_reduce_dev", "pgt_fst_hudson_pops_reduce",
 ]
 PGT_TOK_CHR, PGT_TOK_SKIP, PGT_TOK_U32, PGT_TOK_F64, PGT_TOK_I8, PGT_TOK_I32, PGT_TOK_FREQ, PGT_TOK_CHR_PREFIX = range(8)
 
@@ -127,7 +128,7 @@ def load() -> C.CDLL:
     lib.pgt_af_tree_bytes.restype = sz
     lib.pgt_af_tree_bytes.argtypes = [u32, u64]
     lib.pgt_fst_af_reduce_dev.argtypes = [vp, vp, vp, vp, u32, u64, vp, u64, vp, sz, vp, sz, vp]
-    for stat in ("dxy", "fst", "pi"):  # the K-population statistics over (freq, nInd) columns: one argument list each form
+    for stat in ("dxy", "fst", "pi", "fst_hudson"):  # the K-population statistics over (freq, nInd) columns: one argument list each form
         getattr(lib, f"pgt_{stat}_pops_tree_bytes").restype = sz
         getattr(lib, f"pgt_{stat}_pops_tree_bytes").argtypes = [u32, u64]
         getattr(lib, f"pgt_{stat}_pops_reduce_dev").argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, u64, vp, sz, vp, vp, sz, vp]

@@ -672,7 +672,24 @@ int pgt_fst_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *con
     if (!launch) return PGT_OK;
     const EvSet e = events_for(ctx);
     return launch_fst_pops(pos, freq, nind, n_pops, n, minind, win, n_win, out, tot, tree, stream, e.b0, e.b1, e.q1, &ctx->error,
-                           ctx->hints);
+                           ctx->hints, FstPopsEstimator::WeirCockerham);
+}
+
+// Hudson's estimator on the same columns, tree layout and row types: one more PopsStat, the other per-site function
+size_t pgt_fst_hudson_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites) { return pgt_fst_pops_tree_bytes(n_pops, n_sites); }
+// minind >= 1: 2 nind - 1 >= 1 at every counted site
+static const PopsStat kFstHudsonPops = {"pgt_fst_hudson_pops_reduce", 2, true, pops_pairs, "n_pairs", sizeof(pgt_fst_row), pgt_fst_hudson_pops_tree_bytes};
+
+int pgt_fst_hudson_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind,
+                                   uint32_t n_pops, uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_fst_row *out,
+                                   size_t out_bytes, pgt_fst_total *tot, void *tree, size_t tree_bytes, void *stream) {
+    PGT_USE_DEVICE(ctx);
+    bool launch;
+    if (int rc = pops_check_dev(ctx, kFstHudsonPops, pos, freq, nind, n_pops, n, minind, win, n_win, out, out_bytes, tot, tree, tree_bytes, &launch)) return rc;
+    if (!launch) return PGT_OK;
+    const EvSet e = events_for(ctx);
+    return launch_fst_pops(pos, freq, nind, n_pops, n, minind, win, n_win, out, tot, tree, stream, e.b0, e.b1, e.q1, &ctx->error,
+                           ctx->hints, FstPopsEstimator::Hudson);
 }
 
 size_t pgt_pi_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites) {
@@ -1084,6 +1101,13 @@ int pgt_fst_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *
                         uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_fst_row *out, pgt_fst_total *tot) {
     PGT_USE_DEVICE(ctx);
     return pops_reduce_host(ctx, kFstPops, pgt_fst_pops_reduce_dev, pos, freq, nind, n_pops, n, minind, win, n_win, out, tot);
+}
+
+/* Hudson's FST of all pairs: the host-buffer form, as pgt_fst_pops_reduce */
+int pgt_fst_hudson_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
+                               uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_fst_row *out, pgt_fst_total *tot) {
+    PGT_USE_DEVICE(ctx);
+    return pops_reduce_host(ctx, kFstHudsonPops, pgt_fst_hudson_pops_reduce_dev, pos, freq, nind, n_pops, n, minind, win, n_win, out, tot);
 }
 
 /* pi per population from (freq, nInd) columns: the host-buffer form, as pgt_dxy_pops_reduce with one table per population */

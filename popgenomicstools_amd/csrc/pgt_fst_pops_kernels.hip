@@ -17,6 +17,9 @@
 // The per-population terms (n_k as a double, 4 n_k, n_k alpha_k) are computed once per site.  A site that is not counted may
 // have n1 n2 = 0 (q infinite, a NaN): its values are never added (a select, not a product with 0).
 //
+// A second estimator, Hudson's ratio of averages (struct Hudson below; pgt_fst_hudson_pops_reduce_dev), runs through the same
+// kernels: the estimator is a template parameter that names the per-site function, and nothing else knows about it.
+//
 // Tree, build walk, reduce-scatter, LDS-staged node block, per-wave partials and the one-wave-per-window query: those of
 // pgt_dxy_pops_kernels.hip, with two sums per pair.  The counts are needed as VALUES here, not only for the predicate: they
 // are read by 16-byte loads in the four-sites-per-lane layout (lane L: sites 4L .. 4L+3 of a pair of 128-site pieces) and the
@@ -66,37 +69,81 @@ __device__ __forceinline__ double recip(double d) {
 // One site of this lane into the lane's 2 P running sums and the wave's P counters.  f[k], c[k]: population k's frequency and
 // individual count at the site (a site outside the range carries a count of 0: never counted, minind >= 1).
 // MUST be called by all 64 lanes together (the counters are popcounts of ballots).
-template <int NP>
-__device__ __forceinline__ void fst_pops_site(double *acc, uint32_t *cnt, const double *f, const int *c, int minind) {
-    constexpr int P = Shape<NP>::kPairs;
-    double nd[NP], n4[NP], na[NP];
-    bool ok[NP];
+// The estimator is a compile-time tag with a static per-site function: the walk, the stage, the tree and the query below are
+// written once and know only that a pair keeps two sums (acc[v], acc[P + v]) and a count (cnt[v]).
+struct WeirCockerham {  // the spec at the top of this file: acc[v] += a, acc[P + v] += a + b
+    template <int NP>
+    static __device__ __forceinline__ void site(double *acc, uint32_t *cnt, const double *f, const int *c, int minind) {
+        constexpr int P = Shape<NP>::kPairs;
+        double nd[NP], n4[NP], na[NP];
+        bool ok[NP];
 #pragma unroll
-    for (int k = 0; k < NP; ++k) {
-        nd[k] = (double)c[k];
-        ok[k] = c[k] >= minind;
-        n4[k] = 4.0 * nd[k];
-        na[k] = nd[k] * ((2.0 * f[k]) * (1.0 - f[k]));  // n_k alpha_k, betaAFOutlier.R:408-410
-    }
-    int v = 0;
-#pragma unroll
-    for (int i = 0; i < NP; ++i)
-#pragma unroll
-        for (int j = i + 1; j < NP; ++j) {
-            const bool counted = ok[i] && ok[j];
-            const double npool = nd[i] + nd[j];
-            const double p4 = n4[i] * nd[j];                // 4 n1 n2
-            const double q = recip((npool - 1.0) * p4);
-            const double t = (na[i] + na[j]) * q;
-            const double b = t * p4;
-            const double d = f[i] - f[j];
-            const double a = d * d - t * npool;
-            const double ab = a + b;
-            acc[v] = acc[v] + (counted ? a : 0.0);
-            acc[P + v] = acc[P + v] + (counted ? ab : 0.0);
-            cnt[v] += (uint32_t)__popcll(__ballot(counted));
-            ++v;
+        for (int k = 0; k < NP; ++k) {
+            nd[k] = (double)c[k];
+            ok[k] = c[k] >= minind;
+            n4[k] = 4.0 * nd[k];
+            na[k] = nd[k] * ((2.0 * f[k]) * (1.0 - f[k]));  // n_k alpha_k, betaAFOutlier.R:408-410
         }
+        int v = 0;
+#pragma unroll
+        for (int i = 0; i < NP; ++i)
+#pragma unroll
+            for (int j = i + 1; j < NP; ++j) {
+                const bool counted = ok[i] && ok[j];
+                const double npool = nd[i] + nd[j];
+                const double p4 = n4[i] * nd[j];                // 4 n1 n2
+                const double q = recip((npool - 1.0) * p4);
+                const double t = (na[i] + na[j]) * q;
+                const double b = t * p4;
+                const double d = f[i] - f[j];
+                const double a = d * d - t * npool;
+                const double ab = a + b;
+                acc[v] = acc[v] + (counted ? a : 0.0);
+                acc[P + v] = acc[P + v] + (counted ? ab : 0.0);
+                cnt[v] += (uint32_t)__popcll(__ballot(counted));
+                ++v;
+            }
+    }
+};
+
+// Hudson's estimator as a ratio of averages (Hudson, Slatkin & Maddison 1992; Bhatia et al. 2013, eq. 10), the definition of
+// pgt_fst_hudson_pops_reduce_dev in include/pgtwin.h: acc[v] += (p1 - p2)^2 - h_1 - h_2 with h_k = p_k (1 - p_k) / (2 n_k - 1),
+// acc[P + v] += p1 (1 - p2) + p2 (1 - p1) — dxy_site_pred's roundings (pgt_kernels.hip), so a pair's denominator IS its dxy.
+// Every operation is rounded on its own.  The only division is per population and site (pi_site's divisor 2 n - 1: odd, never
+// 0), not per pair; an uncounted site (n_k <= 0: a negative divisor; any frequency) is selected away, never multiplied.
+struct Hudson {
+    template <int NP>
+    static __device__ __forceinline__ void site(double *acc, uint32_t *cnt, const double *f, const int *c, int minind) {
+        constexpr int P = Shape<NP>::kPairs;
+        double om[NP], h[NP];
+        bool ok[NP];
+#pragma unroll
+        for (int k = 0; k < NP; ++k) {
+            ok[k] = c[k] >= minind;
+            om[k] = __dsub_rn(1.0, f[k]);
+            const double m = __dsub_rn(__dmul_rn(2.0, (double)c[k]), 1.0);  // haploid sample size minus one
+            h[k] = __ddiv_rn(__dmul_rn(f[k], om[k]), m);
+        }
+        int v = 0;
+#pragma unroll
+        for (int i = 0; i < NP; ++i)
+#pragma unroll
+            for (int j = i + 1; j < NP; ++j) {
+                const bool counted = ok[i] && ok[j];
+                const double d = __dsub_rn(f[i], f[j]);
+                const double num = __dsub_rn(__dsub_rn(__dmul_rn(d, d), h[i]), h[j]);
+                const double den = __dadd_rn(__dmul_rn(f[i], om[j]), __dmul_rn(f[j], om[i]));
+                acc[v] = acc[v] + (counted ? num : 0.0);
+                acc[P + v] = acc[P + v] + (counted ? den : 0.0);
+                cnt[v] += (uint32_t)__popcll(__ballot(counted));
+                ++v;
+            }
+    }
+};
+
+template <int NP, class Est>
+__device__ __forceinline__ void fst_pops_site(double *acc, uint32_t *cnt, const double *f, const int *c, int minind) {
+    Est::template site<NP>(acc, cnt, f, c, minind);
 }
 
 // A pair of 128-site pieces in registers: the counts of the pair's 256 sites (lane L: sites 4L .. 4L+3 of the pair) and
@@ -107,7 +154,7 @@ struct PieceSet {
     double2 f[2][NP];
 };
 // The lane's four sites of a pair of pieces, in site order, into the running sums.
-template <int NP>
+template <int NP, class Est>
 __device__ __forceinline__ void fst_pops_accumulate(double *acc, uint32_t *cnt, const PieceSet<NP> &s, int minind, int lane) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -125,8 +172,8 @@ __device__ __forceinline__ void fst_pops_accumulate(double *acc, uint32_t *cnt, 
             px[k] = s.f[h][k].x;
             py[k] = s.f[h][k].y;
         }
-        fst_pops_site<NP>(acc, cnt, px, cx, minind);
-        fst_pops_site<NP>(acc, cnt, py, cy, minind);
+        fst_pops_site<NP, Est>(acc, cnt, px, cx, minind);
+        fst_pops_site<NP, Est>(acc, cnt, py, cy, minind);
     }
 }
 
@@ -144,7 +191,7 @@ __device__ __forceinline__ uint32_t *cnt_node(const FstPopsTree &tv, int slot, u
 // swap roles, a full tile is walked from a piece of the wave's own, the tile's level-1 nodes are staged in LDS and leave as
 // contiguous blocks of nt stores.  A leaf's sums do not depend on the wave or on where its walk started: a lane adds its 8
 // sites of the leaf in site order, the reduce-scatter is a fixed tree, and the level-2 node adds the 16 leaf nodes in leaf order.
-template <int NP>
+template <int NP, class Est>
 __device__ __forceinline__ void fst_pops_build_body(const PopCols &cols, int minind, uint64_t n, uint64_t n_l2, const FstPopsTree &tv) {
     constexpr int P = Shape<NP>::kPairs;
     constexpr int V = Shape<NP>::kSums;
@@ -203,9 +250,9 @@ __device__ __forceinline__ void fst_pops_build_body(const PopCols &cols, int min
             for (int i = 0; i < kRadix; i += kPieces) {  // one leaf per turn
                 const int j = (i + rot) & (kRadix - 1);  // rot is a multiple of the leaf's pieces: they stay together
                 load_full(b, j + 2);
-                fst_pops_accumulate<NP>(acc, cnt, a, minind, lane);
+                fst_pops_accumulate<NP, Est>(acc, cnt, a, minind, lane);
                 if (i + kPieces < kRadix) load_full(a, (j + kPieces) & (kRadix - 1));
-                fst_pops_accumulate<NP>(acc, cnt, b, minind, lane);
+                fst_pops_accumulate<NP, Est>(acc, cnt, b, minind, lane);
                 finish_leaf(j / kPieces);
             }
         } else {  // the last, partial tile (one wave, once): guarded loads; a site beyond n has a count of 0 and is never counted
@@ -232,7 +279,7 @@ __device__ __forceinline__ void fst_pops_build_body(const PopCols &cols, int min
                             s.f[h][k].y = f0 + 1 < n ? cols.f[k][f0 + 1] : 0.0;
                         }
                     }
-                    fst_pops_accumulate<NP>(acc, cnt, s, minind, lane);
+                    fst_pops_accumulate<NP, Est>(acc, cnt, s, minind, lane);
                 }
                 finish_leaf(q);
             }
@@ -276,13 +323,13 @@ __device__ __forceinline__ void fst_pops_build_body(const PopCols &cols, int min
 
 // Two occupancies of the one body (as dxy_pops_build_kernel / _w1): two waves per SIMD with 256 registers each, or one with
 // the whole file.
-template <int NP>
+template <int NP, class Est>
 __global__ __launch_bounds__(256, 2) void fst_pops_build_kernel(PopCols cols, int minind, uint64_t n, uint64_t n_l2, FstPopsTree tv) {
-    fst_pops_build_body<NP>(cols, minind, n, n_l2, tv);
+    fst_pops_build_body<NP, Est>(cols, minind, n, n_l2, tv);
 }
-template <int NP>
+template <int NP, class Est>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void fst_pops_build_kernel_w1(PopCols cols, int minind, uint64_t n, uint64_t n_l2, FstPopsTree tv) {
-    fst_pops_build_body<NP>(cols, minind, n, n_l2, tv);
+    fst_pops_build_body<NP, Est>(cols, minind, n, n_l2, tv);
 }
 constexpr int kOneWaveFrom = 5;  // populations from which the build takes one wave per SIMD (two register sets of 12 NP and 3 P running values)
 
@@ -314,7 +361,7 @@ __global__ __launch_bounds__(256) void fst_pops_up_kernel(FstPopsTree tv, int ch
 // a multiple of 4 (one 16-byte load per count column, two per frequency column); sites of the quad outside [from, to) get a
 // count of 0; the column's last quad, when n is not a multiple of 4, is read site by site.  A lane adds its items in an order
 // that depends on the window alone: left sites, right sites, then per level the left and right ragged nodes.
-template <int NP>
+template <int NP, class Est>
 __global__ __launch_bounds__(256, (NP >= 5 ? 1 : 2)) void fst_pops_query_kernel(PopCols cols, int minind, const uint32_t *__restrict__ pos, FstPopsTree tv,
                                                              const pgt_win *__restrict__ win, uint64_t n_win,
                                                              pgt_fst_row *__restrict__ out, pgt_fst_total *__restrict__ tot, uint64_t n_sites) {
@@ -398,16 +445,16 @@ __global__ __launch_bounds__(256, (NP >= 5 ? 1 : 2)) void fst_pops_query_kernel(
                 int c[NP];
 #pragma unroll
                 for (int q = 0; q < NP; ++q) { p[q] = f0[q].x; c[q] = in[0] ? k[q].x : 0; }
-                fst_pops_site<NP>(acc, scnt, p, c, minind);
+                fst_pops_site<NP, Est>(acc, scnt, p, c, minind);
 #pragma unroll
                 for (int q = 0; q < NP; ++q) { p[q] = f0[q].y; c[q] = in[1] ? k[q].y : 0; }
-                fst_pops_site<NP>(acc, scnt, p, c, minind);
+                fst_pops_site<NP, Est>(acc, scnt, p, c, minind);
 #pragma unroll
                 for (int q = 0; q < NP; ++q) { p[q] = f1[q].x; c[q] = in[2] ? k[q].z : 0; }
-                fst_pops_site<NP>(acc, scnt, p, c, minind);
+                fst_pops_site<NP, Est>(acc, scnt, p, c, minind);
 #pragma unroll
                 for (int q = 0; q < NP; ++q) { p[q] = f1[q].y; c[q] = in[3] ? k[q].w : 0; }
-                fst_pops_site<NP>(acc, scnt, p, c, minind);
+                fst_pops_site<NP, Est>(acc, scnt, p, c, minind);
             }
         };
         auto add_node = [&](int slot, uint64_t i) {
@@ -473,7 +520,7 @@ __global__ __launch_bounds__(256, (NP >= 5 ? 1 : 2)) void fst_pops_query_kernel(
 template <int NP>
 constexpr size_t stage_bytes() { return (size_t)4 * kRadix1 * Shape<NP>::kPairs * 20; }
 
-template <int NP>
+template <int NP, class Est>
 int launch_np(const PopCols &cols, const uint32_t *pos, uint64_t n, int minind, const pgt_win *win, uint64_t n_win,
               pgt_fst_row *out, pgt_fst_total *tot, FstPopsTree tv, const TreeLayout &tl, hipStream_t s, void *ev_b0,
               void *ev_b1, void *ev_q1, std::string *err) {
@@ -484,47 +531,57 @@ int launch_np(const PopCols &cols, const uint32_t *pos, uint64_t n, int minind, 
         const auto [blocks, n_partials] = pops_build_grid(tl.count[1], w1);
         tv.n_partials = n_partials;
         if constexpr (w1)
-            hipLaunchKernelGGL((fst_pops_build_kernel_w1<NP>), dim3(blocks), dim3(256), stage_bytes<NP>(), s, cols, minind, n, tl.count[1], tv);
+            hipLaunchKernelGGL((fst_pops_build_kernel_w1<NP, Est>), dim3(blocks), dim3(256), stage_bytes<NP>(), s, cols, minind, n, tl.count[1], tv);
         else
-            hipLaunchKernelGGL((fst_pops_build_kernel<NP>), dim3(blocks), dim3(256), stage_bytes<NP>(), s, cols, minind, n, tl.count[1], tv);
+            hipLaunchKernelGGL((fst_pops_build_kernel<NP, Est>), dim3(blocks), dim3(256), stage_bytes<NP>(), s, cols, minind, n, tl.count[1], tv);
         if (int rc = hip_fail(hipGetLastError(), "fst_pops_build_kernel", err)) return rc;
         if (int rc = launch_upper_levels(fst_pops_up_kernel, "fst_pops_up_kernel", Shape<NP>::kSums, tv, tl, s, err)) return rc;
     }
     if (int rc = record_event(ev_b1, s, err)) return rc;
     if (n_win > 0 || tot) {
-        hipLaunchKernelGGL((fst_pops_query_kernel<NP>), dim3(wave_grid(n_win + (tot ? 1 : 0))), dim3(256), 0, s, cols, minind, pos, tv, win, n_win, out, tot, n);
+        hipLaunchKernelGGL((fst_pops_query_kernel<NP, Est>), dim3(wave_grid(n_win + (tot ? 1 : 0))), dim3(256), 0, s, cols, minind, pos, tv, win, n_win, out, tot, n);
         if (int rc = hip_fail(hipGetLastError(), "fst_pops_query_kernel", err)) return rc;
     }
     return record_event(ev_q1, s, err);
 }
 
-template <int NP>
+template <int NP, class Est>
 void allow_lds() {
     if constexpr (NP >= kOneWaveFrom)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fst_pops_build_kernel_w1<NP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)stage_bytes<NP>());
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fst_pops_build_kernel_w1<NP, Est>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)stage_bytes<NP>());
     else
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fst_pops_build_kernel<NP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)stage_bytes<NP>());
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fst_pops_build_kernel<NP, Est>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)stage_bytes<NP>());
+}
+
+template <class Est>
+void allow_lds_all() {
+    allow_lds<2, Est>(); allow_lds<3, Est>(); allow_lds<4, Est>(); allow_lds<5, Est>(); allow_lds<6, Est>(); allow_lds<7, Est>(); allow_lds<8, Est>();
 }
 
 }  // namespace
 
 // Called once from pgt_open, so that no attribute call can fall inside a caller's stream capture.
 int init_fst_pops_kernels(std::string *err) {
-    allow_lds<2>(); allow_lds<3>(); allow_lds<4>(); allow_lds<5>(); allow_lds<6>(); allow_lds<7>(); allow_lds<8>();
+    allow_lds_all<WeirCockerham>();
+    allow_lds_all<Hudson>();
     return hip_fail(hipGetLastError(), "hipFuncSetAttribute", err);
 }
 
 int launch_fst_pops(const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops, uint64_t n,
                     int minind, const pgt_win *win, uint64_t n_win, pgt_fst_row *out, pgt_fst_total *tot, void *tree,
-                    void *stream, void *ev_build0, void *ev_build1, void *ev_query1, std::string *err, const Hints &hints) {
+                    void *stream, void *ev_build0, void *ev_build1, void *ev_query1, std::string *err, const Hints &hints,
+                    FstPopsEstimator estimator) {
     hipStream_t s = static_cast<hipStream_t>(stream);
-    // 2 <= n_pops <= 8 and minind >= 1: checked by the caller
+    // 2 <= n_pops <= 8 and minind >= 1: checked by the caller; both estimators share the tree's layout
     const TreeLayout tl = tree_layout(PGT_STAT_FST, n);  // node counts of the f64 layout (levels 2 and up; level 1: a quarter)
     const FstPopsTree tv = fst_pops_tree_view(tl, (int)(n_pops * (n_pops - 1) / 2), tree, useful_levels(tl, PGT_STAT_FST, hints.max_window));
     PopCols cols{};
     for (uint32_t k = 0; k < n_pops; ++k) { cols.f[k] = freq[k]; cols.c[k] = nind[k]; }
     return dispatch_n_pops(n_pops, [&](auto np) {
-        return launch_np<decltype(np)::value>(cols, pos, n, minind, win, n_win, out, tot, tv, tl, s, ev_build0, ev_build1, ev_query1, err);
+        constexpr int NP = decltype(np)::value;
+        if (estimator == FstPopsEstimator::Hudson)
+            return launch_np<NP, Hudson>(cols, pos, n, minind, win, n_win, out, tot, tv, tl, s, ev_build0, ev_build1, ev_query1, err);
+        return launch_np<NP, WeirCockerham>(cols, pos, n, minind, win, n_win, out, tot, tv, tl, s, ev_build0, ev_build1, ev_query1, err);
     });
 }
 

@@ -256,11 +256,14 @@ int launch_dxy_pops(const uint32_t *pos, const double *const *freq, const int32_
                     void *tree, void *stream, void *ev_build0, void *ev_build1, void *ev_query1, std::string *err,
                     const Hints &hints);
 
-// pgt_fst_pops_kernels.hip: tot = n_pairs device totals or NULL; 2 <= n_pops <= 8 and minind >= 1 (checked by the caller)
+// pgt_fst_pops_kernels.hip: tot = n_pairs device totals or NULL; 2 <= n_pops <= 8 and minind >= 1 (checked by the caller).
+// The estimator selects the per-site function the kernels are instantiated with (pgt_fst_pops_reduce_dev: WeirCockerham,
+// pgt_fst_hudson_pops_reduce_dev: Hudson); tree layout, grids and the order of all additions are the same for both.
+enum class FstPopsEstimator { WeirCockerham, Hudson };
 int launch_fst_pops(const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
                     uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_fst_row *out, pgt_fst_total *tot,
                     void *tree, void *stream, void *ev_build0, void *ev_build1, void *ev_query1, std::string *err,
-                    const Hints &hints);
+                    const Hints &hints, FstPopsEstimator estimator);
 
 // pgt_kernels.hip: pi per population, 1 <= n_pops <= 8 and minind >= 1 (checked by the caller); out = n_pops tables of
 // n_win rows, tot = n_pops device totals or NULL; tree = n_pops trees of tree_layout(PGT_STAT_DXY, n).bytes each

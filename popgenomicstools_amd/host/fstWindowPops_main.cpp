@@ -9,6 +9,8 @@
 // reduces all K(K-1)/2 pairs: per site and pair the two columns of WCFst() (betaAFOutlier.R:405-417) with the site's nInd
 // as the sample sizes, counted where both populations have at least -minind individuals (dxyWindow.cpp:381); per window
 // fstWindow's statistic Σa / Σ(a+b) (fstWindow.cpp:85).
+// -estimator hudson: pgt_fst_hudson_pops_reduce_dev instead — Hudson's ratio of averages, Σ[(p1-p2)² - h1 - h2] / Σ dxy with
+// h = p(1-p)/(2 nInd - 1) (include/pgtwin.h); files, rows and counts are laid out the same.  -estimator wc is the default.
 // Pair (i, j) of pair order (0,1),(0,2),..,(1,2),.. -> PREFIX.pop<i+1>_pop<j+1>.fst with fstWindow's row and the skipped
 // count (`chr start end mid fst neff nskip`); the genome-wide lines of all pairs (genomeFst, betaAFOutlier.R:440-446)
 // -> PREFIX.global (`i+1  j+1  fst  neff  nskip`).  stdout stays empty.
@@ -28,9 +30,11 @@ static void help(const DxyOptions &o) {
                 "%-14s%-8s(1) Use fixed number of sites from MAF input for each window (window sizes may vary) or (0) constant window size [%d]\n"
                 "%-14s%-8sTwo-column TSV file with each row having (1) chromsome name (2) chromosome size in base pairs\n"
                 "%-14s%-8sDo not print windows with zero effective sites if INT=1 [%d]\n"
+                "%-14s%-8sFST estimator: wc (Weir-Cockerham components) or hudson (Hudson's ratio of averages) [wc]\n"
                 "\nNotes:\n"
                 "* Only the sites (chromosome, position) present in ALL MAF files are analyzed\n"
                 "* FST is the ratio of the summed Reynolds / Weir-Cockerham variance components, the per-site sample sizes being the MAF files' nInd\n"
+                "* -estimator hudson: FST is sum[(p1-p2)^2 - h1 - h2] / sum[dxy] with h = p(1-p)/(2 nInd - 1): its denominator is dxy (dxyWindowPops' sum)\n"
                 "* A site counts for a pair when both populations have at least -minind individuals with data\n"
                 "* -sizefile is REQUIRED(!) with -fixedsite 0 (the default)\n"
                 "* All input MAF files need to have the same chromosomes in the same order\n"
@@ -45,12 +49,19 @@ static void help(const DxyOptions &o) {
                 "(7) number of sites in MAF input that were skipped due to too few individuals\n"
                 "PREFIX.global, one line per pair:\n(1) i\n(2) j\n(3) Fst\n(4) number of sites analyzed\n(5) number of sites skipped\n\n",
                 "-out", "STRING", "-winsize", "INT", o.W, "-stepsize", "INT", o.S, "-minind", "INT", o.minind, "-fixedsite", "INT", o.fixedsite,
-                "-sizefile", "FILE", "-skip_missing", "INT", o.skip_missing);
+                "-sizefile", "FILE", "-skip_missing", "INT", o.skip_missing, "-estimator", "STRING");
 }
 
 int main(int argc, char **argv) {
     const std::string tool = "fstWindowPops";
-    const PopsArgs args = parse_pops_args(tool, argc, argv, help);
+    bool hudson = false;
+    const PopsArgs args = parse_pops_args(tool, argc, argv, help, 2, [&](const char *o, const char *v) {
+        if (std::strcmp(o, "-estimator")) return false;
+        if (!std::strcmp(v, "hudson")) hudson = true;
+        else if (!std::strcmp(v, "wc")) hudson = false;
+        else die(std::string("-estimator must be wc or hudson (given: ") + v + ")");
+        return true;
+    });
     const int K = args.K;
     const char *prefix = args.prefix;
     const uint32_t W = args.opt.W;
@@ -68,8 +79,8 @@ int main(int argc, char **argv) {
     const size_t tree_bytes = pgt_fst_pops_tree_bytes((uint32_t)K, s.n_sites);
     void *tree = nullptr;
     check(pgt_dev_alloc(ctx, tree_bytes, &tree), ctx);
-    check(pgt_fst_pops_reduce_dev(ctx, s.a_pos, s.a_freq.data(), s.a_nind.data(), (uint32_t)K, s.n_sites, minind, n_win ? s.d_win : nullptr, n_win,
-                                  n_win ? d_rows : nullptr, n_pairs * n_win * sizeof(pgt_fst_row), d_tot, tree, tree_bytes, nullptr), ctx);
+    check((hudson ? pgt_fst_hudson_pops_reduce_dev : pgt_fst_pops_reduce_dev)(ctx, s.a_pos, s.a_freq.data(), s.a_nind.data(), (uint32_t)K, s.n_sites, minind, n_win ? s.d_win : nullptr, n_win,
+            n_win ? d_rows : nullptr, n_pairs * n_win * sizeof(pgt_fst_row), d_tot, tree, tree_bytes, nullptr), ctx);
     RowArray<pgt_fst_row> rows(n_pairs * n_win);
     std::vector<pgt_fst_total> tot(n_pairs);
     check(pgt_rowbuf_read(ctx, rows.data(), d_rows, n_pairs * n_win * sizeof(pgt_fst_row), nullptr), ctx);

@@ -36,9 +36,13 @@ struct PopsArgs {
     std::map<std::string, uint32_t> chrsize;
 };
 // option/value pairs first; what follows the last pair are the MAF files (min_files ... 8 of them).  help(opt) prints the tool's
-// usage (no argument: exit 0)
-template <class Help>
-inline PopsArgs parse_pops_args(const std::string &tool, int argc, char **argv, Help help, int min_files = 2) {
+// usage (no argument: exit 0).  own(option, value) -> true when the pair is an option of this tool alone, which it has taken
+// (or refused by die()); a tool without one keeps answering `Unknown command:` for every option that is not dxyWindow's
+struct NoOwnOption {
+    bool operator()(const char *, const char *) const { return false; }
+};
+template <class Help, class Own = NoOwnOption>
+inline PopsArgs parse_pops_args(const std::string &tool, int argc, char **argv, Help help, int min_files = 2, Own own = Own{}) {
     PopsArgs a;
     if (argc < 2) {
         help(a.opt);
@@ -49,6 +53,7 @@ inline PopsArgs parse_pops_args(const std::string &tool, int argc, char **argv, 
         const char *o = argv[i];
         if (i + 1 >= argc) die(std::string("Missing value for ") + o);
         if (!std::strcmp(o, "-out")) a.prefix = argv[i + 1];
+        else if (own(o, argv[i + 1])) continue;
         else if (!dxy_option(a.opt, o, argv[i + 1])) unknown_dxy_option(o);
     }
     a.K = argc - i;

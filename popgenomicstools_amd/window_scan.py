@@ -278,6 +278,8 @@ class _PopsStat:
 _DXY_POPS = _PopsStat("dxy", 2, True, DXY_ROW_DTYPE, DXY_TOTAL_DTYPE)
 _FST_POPS = _PopsStat("fst", 2, True, FST_ROW_DTYPE, FST_TOTAL_DTYPE)
 _PI_POPS = _PopsStat("pi", 1, False, DXY_ROW_DTYPE, DXY_TOTAL_DTYPE)
+_FST_HUDSON_POPS = _PopsStat("fst_hudson", 2, True, FST_ROW_DTYPE, FST_TOTAL_DTYPE)
+_FST_ESTIMATORS = {"wc": _FST_POPS, "hudson": _FST_HUDSON_POPS}  # fst_window_pops(estimator=...)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -402,6 +404,11 @@ class Context:
         """FST rows of ALL pairs i<j of len(freqs) populations (pair_order) from per-population numpy (freq, nInd) columns, one
         pass: -> (rows[n_pairs, n_win], totals[n_pairs]) (pgt_fst_pops_reduce).  A row's n is the number of counted sites."""
         return self._pops_reduce(_FST_POPS, pos, freqs, ninds, minind, win)
+
+    def fst_hudson_pops_reduce(self, pos, freqs, ninds, minind, win):
+        """fst_pops_reduce with Hudson's estimator as a ratio of averages (pgt_fst_hudson_pops_reduce): a row's asum is
+        Σ [(p1-p2)² - h1 - h2], h = p(1-p)/(2n-1), its bsum Σ dxy over the pair's counted sites, fst their ratio."""
+        return self._pops_reduce(_FST_HUDSON_POPS, pos, freqs, ninds, minind, win)
 
     def pi_pops_reduce(self, pos, freqs, ninds, minind, win):
         """Nucleotide-diversity (pi) rows of EACH of len(freqs) populations (1 ... 8) from per-population numpy (freq, nInd)
@@ -744,6 +751,16 @@ class Context:
         return self._pops_reduce_dev(_FST_POPS, pos, freqs, ninds, minind, win, out, tot, tree, stream)
 
     @staticmethod
+    def fst_hudson_pops_tree_bytes(n_pops: int, n_sites: int) -> int:
+        return int(_lib.load().pgt_fst_hudson_pops_tree_bytes(int(n_pops), int(n_sites)))
+
+    def fst_hudson_pops_reduce_dev(self, pos, freqs, ninds, minind, win, out=None, tot=None, tree=None, stream=None):
+        """fst_pops_reduce_dev with Hudson's estimator as a ratio of averages (pgt_fst_hudson_pops_reduce_dev): the same
+        arguments, buffers (the tree is fst_pops_tree_bytes large and may be reused between the two, one call at a time) and
+        row layout; asum = Σ [(p1-p2)² - h1 - h2], bsum = Σ dxy.  Returns (out, tot, tree).  Asynchronous on `stream`."""
+        return self._pops_reduce_dev(_FST_HUDSON_POPS, pos, freqs, ninds, minind, win, out, tot, tree, stream)
+
+    @staticmethod
     def pi_pops_tree_bytes(n_pops: int, n_sites: int) -> int:
         return int(_lib.load().pgt_pi_pops_tree_bytes(int(n_pops), int(n_sites)))
 
@@ -1079,12 +1096,16 @@ def dxy_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: 
 
 
 def fst_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: int = 1, fixedsite: int = 0,
-                    chr_len=None, skip_missing: int = 0, ctx: Context | None = None) -> dict:
+                    chr_len=None, skip_missing: int = 0, ctx: Context | None = None, estimator: str = "wc") -> dict:
     """Windowed FST for ALL pairs of len(freqs) already synchronised populations in one pass: {(i, j): WindowResult} with
     fstWindow's rows (n = counted sites of the pair; the skipped ones are (hi - lo) - n) and the genome-wide line as total.
     Window arguments and their errors are those of dxy_window_pops; -skip_missing drops a pair's rows without counted
-    sites from that pair's result only."""
-    win, rows, tot = _window_pops(_FST_POPS, chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx)
+    sites from that pair's result only.  estimator: "wc" (the Weir–Cockerham components of WCFst(), pgt_fst_pops_reduce)
+    or "hudson" (Hudson's ratio of averages, pgt_fst_hudson_pops_reduce: asum = Σ numerator, bsum = Σ dxy)."""
+    st = _FST_ESTIMATORS.get(estimator) if isinstance(estimator, str) else None
+    if st is None:
+        raise PgtError(_lib.PGT_EARG, f'fst_window_pops: estimator must be "wc" or "hudson", not {estimator!r}')
+    win, rows, tot = _window_pops(st, chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx)
     return _results_by_pair(len(freqs), win, rows, tot, skip_missing, "n")
 
 

@@ -1,0 +1,463 @@
+"""GPU: Hudson's FST of all population pairs from per-population (freq, nInd) columns (pgt_fst_hudson_pops_reduce_dev /
+pgt_fst_hudson_pops_reduce).
+
+The yardsticks are the float64 NumPy model of the definition (tests/fst_hudson_model.py), the exact-rational fixture
+(tests/golden/hudson_exact.json) and two other, independently written kernels of the library: pgt_dxy_pops_reduce_dev (the
+denominator IS dxy) and pgt_pi_pops_reduce_dev (the numerator is dxy - (pi_i + pi_j)/2) — never the code under test.
+Tolerance: counts, coordinates and mid exact; asum, bsum, fst within |x - y| <= 1e-9 |y| + 1e-12 (helpers.REL / helpers.ABS);
+one-site windows bit for bit."""
+import ctypes as C
+import sys
+
+import numpy as np
+import pytest
+
+import fst_hudson_model
+import helpers
+import synth
+from helpers import GuardedBuffers, padded_column, poison_tree, rows_equal
+from popgenomicstools_amd import _lib
+from popgenomicstools_amd._lib import DXY_ROW_DTYPE, DXY_TOTAL_DTYPE, FST_ROW_DTYPE, FST_TOTAL_DTYPE, WIN_DTYPE
+from popgenomicstools_amd.window_scan import pair_order, rows_from_device, run_lengths, windows_to_device
+from test_fst_pops import MININD, SITE_TABLES, SIZES, _dev, _t, assert_rows, assert_totals, excess, random_pops, tables_for
+
+pytestmark = pytest.mark.gpu
+
+
+def hudson_dev(ctx, tp, tf, tn, minind, win, **kw):
+    """-> (rows[n_pairs, n_win], totals[n_pairs] or None) of one fst_hudson_pops_reduce_dev call"""
+    wd = windows_to_device(win, _dev())
+    out, tot, _ = ctx.fst_hudson_pops_reduce_dev(tp, tf, tn, minind, wd, **kw)
+    n_pairs = len(tf) * (len(tf) - 1) // 2
+    rows = rows_from_device(out, FST_ROW_DTYPE)[: n_pairs * win.size].reshape(n_pairs, win.size)
+    return rows, (rows_from_device(tot, FST_TOTAL_DTYPE)[:n_pairs] if tot is not None else None)
+
+
+def dxy_dev(ctx, tp, tf, tn, minind, win):
+    out, tot, _ = ctx.dxy_pops_reduce_dev(tp, tf, tn, minind, windows_to_device(win, _dev()))
+    n_pairs = len(tf) * (len(tf) - 1) // 2
+    return (rows_from_device(out, DXY_ROW_DTYPE)[: n_pairs * win.size].reshape(n_pairs, win.size),
+            rows_from_device(tot, DXY_TOTAL_DTYPE)[:n_pairs])
+
+
+def pi_dev(ctx, tp, tf, tn, minind, win):
+    out, tot, _ = ctx.pi_pops_reduce_dev(tp, tf, tn, minind, windows_to_device(win, _dev()))
+    k = len(tf)
+    return rows_from_device(out, DXY_ROW_DTYPE)[: k * win.size].reshape(k, win.size), rows_from_device(tot, DXY_TOTAL_DTYPE)[:k]
+
+
+def bits(x):
+    return np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)
+
+
+# ---- 1: rows and genome-wide lines against the model and the exact fixture --------------------------------------------------
+@pytest.mark.parametrize("k", [2, 4, 5, 8])
+def test_rows_and_totals_against_the_numpy_model(pgt, ctx, k):
+    for si, n in enumerate(SIZES):
+        rng = np.random.default_rng(1100 * k + si)
+        chr_ids, pos = synth.chromosomes(rng, n, min(1 + (si + k) % 3, n), equal=False)
+        f, c = random_pops(rng, n, k)
+        tp, tf, tn = _t(pos), [_t(x) for x in f], [_t(x) for x in c]
+        for name, win in tables_for(pgt, pos, run_lengths(chr_ids)):
+            rows, tot = hudson_dev(ctx, tp, tf, tn, MININD, win)
+            want, want_t = fst_hudson_model.model(pos, f, c, MININD, win)
+            for p, ij in enumerate(pair_order(k)):
+                assert_rows(rows[p], want[p], f"K={k} n={n} {name} pair {ij}")
+            assert_totals(tot, want_t, f"K={k} n={n} {name} totals")
+            if k > 2 and n >= 511:  # the close pair: the numerator negative at every counted site
+                one = rows[k - 2][rows[k - 2]["n"] > 0]
+                assert name != "site W=1 S=1" or np.all(one["asum"] < 0)
+                assert float(tot[k - 2]["asum"]) < 0
+
+
+def test_level3_nodes_are_built_and_used(pgt, ctx):
+    n, W, k = 600_001, 550_000, 3
+    rng = np.random.default_rng(131)
+    chr_ids, pos = synth.chromosomes(rng, n, 1)
+    f, c = random_pops(rng, n, k)
+    win = pgt.build_windows_sites(run_lengths(chr_ids), W, 10_000)
+    lo, hi = win["lo"].astype(np.int64), win["hi"].astype(np.int64)
+    assert np.any(-(-lo // (8192 * 64)) < hi // (8192 * 64)), "a window must contain a level-3 node"
+    tp, tf, tn = _t(pos), [_t(x) for x in f], [_t(x) for x in c]
+    want, want_t = fst_hudson_model.model(pos, f, c, MININD, win)
+    for hint in (0, W):
+        with ctx.hints(hint, 0, 0):
+            rows, tot = hudson_dev(ctx, tp, tf, tn, MININD, win)
+        for p, ij in enumerate(pair_order(k)):
+            assert_rows(rows[p], want[p], f"level 3, hint {hint}, pair {ij}")
+        assert_totals(tot, want_t, f"level 3, hint {hint}")
+
+
+def test_rows_against_the_exact_rational_fixture(pgt, ctx):
+    k = helpers.load_golden("hudson_exact.json")
+    pos = np.array(k["pos"], dtype=np.uint32)
+    f = [np.array(x, dtype=np.float64) for x in k["freq"]]
+    c = [np.array(x, dtype=np.int32) for x in k["nind"]]
+    tp, tf, tn = _t(pos), [_t(x) for x in f], [_t(x) for x in c]
+    fixed = np.zeros(len(k["windows"]), dtype=WIN_DTYPE)
+    fixed["lo"], fixed["hi"] = [w[0] for w in k["windows"]], [w[1] for w in k["windows"]]
+    assert [case["minind"] for case in k["cases"]] == [1, 5]
+    for case in k["cases"]:
+        rows, tot = hudson_dev(ctx, tp, tf, tn, case["minind"], fixed)
+        whole = k["windows"].index([0, int(pos.size)])
+        for p, pr in enumerate(case["pairs"]):
+            what = f"fixture minind={case['minind']} pair {pr['pair']}"
+            assert np.array_equal(rows[p]["n"], np.array(pr["n"], dtype=np.uint32)), what
+            assert excess(rows[p]["asum"], pr["asum"]) <= 0 and excess(rows[p]["bsum"], pr["bsum"]) <= 0, what
+            fst = [fst_hudson_model.fst_of(a, b) for a, b in zip(pr["asum"], pr["bsum"])]
+            assert excess(rows[p]["fst"], fst) <= 0, what
+            assert int(tot[p]["neff"]) == pr["n"][whole] and int(tot[p]["nskip"]) == pos.size - pr["n"][whole]
+            assert excess(tot[p]["asum"], pr["asum"][whole]) <= 0 and excess(tot[p]["bsum"], pr["bsum"][whole]) <= 0, what
+
+
+# ---- 2: one-site windows hold the definition's bits --------------------------------------------------------------------------
+@pytest.mark.parametrize("k,minind", [(3, 1), (3, 5), (8, 1)])
+def test_one_site_windows_hold_the_bits_of_the_definition(pgt, ctx, k, minind):
+    n = 8193
+    rng = np.random.default_rng(1200 + k + minind)
+    chr_ids, pos = synth.chromosomes(rng, n, 2, equal=False)
+    f, c = random_pops(rng, n, k)
+    win = pgt.build_windows_sites(run_lengths(chr_ids), 1, 1)
+    assert win.size == n and np.all(win["hi"] - win["lo"] == 1)
+    tp, tf, tn = _t(pos), [_t(x) for x in f], [_t(x) for x in c]
+    rows, _ = hudson_dev(ctx, tp, tf, tn, minind, win)
+    d, _ = dxy_dev(ctx, tp, tf, tn, minind, win)
+    for p, (i, j) in enumerate(pair_order(k)):
+        site = win["lo"].astype(np.int64)
+        ok = (c[i][site] >= minind) & (c[j][site] >= minind)
+        num, den = fst_hudson_model.site_components(f[i][site], f[j][site], c[i][site], c[j][site])
+        num, den = np.where(ok, num, 0.0) + 0.0, np.where(ok, den, 0.0) + 0.0  # `+ 0.0` as the kernel's row epilogue
+        with np.errstate(all="ignore"):
+            fst = np.where(den != 0, num / den, 0.0)
+        what = f"K={k} minind={minind} pair {(i, j)}"
+        assert np.array_equal(rows[p]["n"], ok.astype(np.uint32)), what
+        assert np.array_equal(bits(rows[p]["asum"]), bits(num)), what
+        assert np.array_equal(bits(rows[p]["bsum"]), bits(den)), what
+        assert np.array_equal(bits(rows[p]["fst"]), bits(fst)), what
+        # the denominator IS dxy: the bits of pgt_dxy_pops_reduce_dev's sum at every counted site
+        assert np.array_equal(d[p]["neff"], rows[p]["n"]), what
+        assert np.array_equal(bits(rows[p]["bsum"][ok]), bits(d[p]["sum"][ok])), what
+        if minind == 1:  # nInd = 1 is counted, with m = 2 - 1 = 1: h = p (1 - p)
+            m1 = ok & ((c[i][site] == 1) | (c[j][site] == 1))
+            assert m1.sum() > 100 and np.all(rows[p]["n"][m1] == 1)
+
+
+# ---- 3: against the other kernels -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("k", [2, 3, 5, 8])
+def test_counts_and_denominator_equal_dxy_pops(pgt, ctx, k):
+    n = 2 * 8192 + 700
+    rng = np.random.default_rng(1300 + k)
+    chr_ids, pos = synth.chromosomes(rng, n, 2, equal=False)
+    f, c = random_pops(rng, n, k)
+    tp, tf, tn = _t(pos), [_t(x) for x in f], [_t(x) for x in c]
+    for name, win in tables_for(pgt, pos, run_lengths(chr_ids)):
+        rows, tot = hudson_dev(ctx, tp, tf, tn, MININD, win)
+        d, dt = dxy_dev(ctx, tp, tf, tn, MININD, win)
+        for p in range(len(pair_order(k))):
+            assert np.array_equal(rows[p]["n"], d[p]["neff"]), (k, name, p)
+            assert np.array_equal((win["hi"] - win["lo"]).astype(np.uint32) - rows[p]["n"], d[p]["nskip"]), (k, name, p)
+            assert excess(rows[p]["bsum"], d[p]["sum"]) <= 0, (k, name, p)
+        assert np.array_equal(tot["neff"], dt["neff"]) and np.array_equal(tot["nskip"], dt["nskip"])
+        assert excess(tot["bsum"], dt["sum"]) <= 0, (k, name)
+
+
+@pytest.mark.parametrize("k", [2, 3, 5, 8])
+def test_numerator_is_dxy_minus_mean_pi(pgt, ctx, k):
+    """every population has nInd >= minind at every site, so that a pair's counted sites are each population's:
+    asum(i, j) = dxy_sum(i, j) - (pi_sum_i + pi_sum_j) / 2 within the three contracts added up"""
+    n = 2 * 8192 + 700
+    rng = np.random.default_rng(1400 + k)
+    chr_ids, pos = synth.chromosomes(rng, n, 2, equal=False)
+    f, _ = random_pops(rng, n, k)
+    c = [rng.integers(MININD, 21, n, dtype=np.int32) for _ in range(k)]
+    tp, tf, tn = _t(pos), [_t(x) for x in f], [_t(x) for x in c]
+
+    def check(asum, dxy, pi_i, pi_j, what):
+        asum, dxy, pi_i, pi_j = (np.atleast_1d(np.asarray(x, np.float64)) for x in (asum, dxy, pi_i, pi_j))
+        bound = helpers.REL * (np.abs(dxy) + (np.abs(pi_i) + np.abs(pi_j)) / 2 + np.abs(asum)) + 3 * helpers.ABS
+        e = float(np.max(np.abs(asum - (dxy - (pi_i + pi_j) / 2)) - bound))
+        print(f"{what}: excess over the bound {e:.3e}")
+        assert e <= 0, (what, e)
+
+    for name, win in tables_for(pgt, pos, run_lengths(chr_ids)):
+        rows, tot = hudson_dev(ctx, tp, tf, tn, MININD, win)
+        d, dt = dxy_dev(ctx, tp, tf, tn, MININD, win)
+        pi, pt = pi_dev(ctx, tp, tf, tn, MININD, win)
+        for p, (i, j) in enumerate(pair_order(k)):
+            assert np.array_equal(rows[p]["n"], (win["hi"] - win["lo"]).astype(np.uint32))
+            check(rows[p]["asum"], d[p]["sum"], pi[i]["sum"], pi[j]["sum"], f"K={k} {name} pair {(i, j)}")
+            check(tot[p]["asum"], dt[p]["sum"], pt[i]["sum"], pt[j]["sum"], f"K={k} {name} pair {(i, j)} total")
+
+
+def test_the_estimator_is_really_switched(pgt, ctx):
+    n, k = 2 * 8192 + 700, 3
+    rng = np.random.default_rng(1500)
+    chr_ids, pos = synth.chromosomes(rng, n, 2, equal=False)
+    f, c = random_pops(rng, n, k)
+    tp, tf, tn = _t(pos), [_t(x) for x in f], [_t(x) for x in c]
+    win = pgt.build_windows_sites(run_lengths(chr_ids), 5000, 1000)
+    wd = windows_to_device(win, _dev())
+    h, ht = hudson_dev(ctx, tp, tf, tn, MININD, win)
+    out, tot, _ = ctx.fst_pops_reduce_dev(tp, tf, tn, MININD, wd)
+    w = rows_from_device(out, FST_ROW_DTYPE)[: 3 * win.size].reshape(3, win.size)
+    wt = rows_from_device(tot, FST_TOTAL_DTYPE)[:3]
+    for fld in ("start", "end", "mid", "n"):
+        assert np.array_equal(h[fld], w[fld]), fld
+    assert np.array_equal(ht["neff"], wt["neff"]) and np.array_equal(ht["nskip"], wt["nskip"])
+    assert np.all(h["n"] > 0)
+    for fld in ("asum", "bsum"):
+        assert np.all(h[fld] != w[fld]) and np.all(ht[fld] != wt[fld]), fld
+
+
+# ---- 4: pair isolation -----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("k", [3, 5, 8])
+def test_pairs_do_not_see_the_other_populations(pgt, ctx, k):
+    n = 2 * 8192 + 700
+    rng = np.random.default_rng(1600 + k)
+    chr_ids, pos = synth.chromosomes(rng, n, 2, equal=False)
+    f, c = random_pops(rng, n, k)
+    f2, c2 = random_pops(rng, n, k)
+    win = np.concatenate([pgt.build_windows_sites(run_lengths(chr_ids), W, S) for W, S in ((7, 3), (5000, 1000))])
+    tp = _t(pos)
+    rows, tot = hudson_dev(ctx, tp, [_t(x) for x in f], [_t(x) for x in c], MININD, win)
+    for r in (0, k // 2, k - 1):  # population r replaced: every pair without it keeps its bits
+        fr, cr = list(f), list(c)
+        fr[r], cr[r] = f2[r], c2[r]
+        got, got_t = hudson_dev(ctx, tp, [_t(x) for x in fr], [_t(x) for x in cr], MININD, win)
+        for p, (i, j) in enumerate(pair_order(k)):
+            if r not in (i, j):
+                rows_equal(got[p], rows[p], f"K={k}, population {r} replaced, pair {(i, j)}")
+                assert got_t[p].tobytes() == tot[p].tobytes()
+    for p, (i, j) in enumerate(pair_order(k)):  # a pair's table from the K-population call = the two-population call's
+        two, two_t = hudson_dev(ctx, tp, [_t(f[i]), _t(f[j])], [_t(c[i]), _t(c[j])], MININD, win)
+        assert_rows(rows[p], two[0], f"K={k} pair {(i, j)} against the two-population call")
+        assert_totals(tot[p:p + 1], two_t, f"K={k} pair {(i, j)} totals")
+
+
+# ---- 5: uncounted sites may hold anything ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("k", [3, 8])
+def test_uncounted_sites_may_hold_anything(pgt, ctx, k):
+    n = 2 * 8192 + 700
+    rng = np.random.default_rng(1700 + k)
+    chr_ids, pos = synth.chromosomes(rng, n, 2, equal=False)
+    f, c = random_pops(rng, n, k)
+    bad_f = np.array([np.nan, np.inf, -np.inf, 2.0])
+    bad_c = np.array([0, -1, np.iinfo(np.int32).min], dtype=np.int32)
+    wild_f, wild_c, tame_f, tame_c = [], [], [], []
+    for q in range(k):
+        low = np.flatnonzero(c[q] < MININD)
+        assert low.size > 1000
+        wf, wc, mf, mc = f[q].copy(), c[q].copy(), f[q].copy(), c[q].copy()
+        wf[low], wc[low] = bad_f[(low + q) % 4], bad_c[(low // 4 + q) % 3]
+        mf[low], mc[low] = 0.5, 0
+        wild_f.append(wf); wild_c.append(wc); tame_f.append(mf); tame_c.append(mc)
+    win = np.concatenate([pgt.build_windows_sites(run_lengths(chr_ids), W, S) for W, S in ((1, 1), (7, 3), (5000, 1000))])
+    tp = _t(pos)
+    wild, wild_t = hudson_dev(ctx, tp, [_t(x) for x in wild_f], [_t(x) for x in wild_c], MININD, win)
+    tame, tame_t = hudson_dev(ctx, tp, [_t(x) for x in tame_f], [_t(x) for x in tame_c], MININD, win)
+    for p, ij in enumerate(pair_order(k)):
+        rows_equal(wild[p], tame[p], f"K={k} pair {ij}: NaN, inf, 2.0 and nInd 0, -1, INT32_MIN below minind")
+        assert np.all(np.isfinite(wild[p]["asum"])) and np.all(np.isfinite(wild[p]["bsum"])) and np.all(np.isfinite(wild[p]["fst"]))
+    assert wild_t.tobytes() == tame_t.tobytes()
+    want, want_t = fst_hudson_model.model(pos, wild_f, wild_c, MININD, win)
+    for p, ij in enumerate(pair_order(k)):
+        assert_rows(wild[p], want[p], f"K={k} pair {ij} against the model on the wild columns")
+    assert_totals(wild_t, want_t, f"K={k} totals on the wild columns")
+
+
+# ---- 6: workspace contract -------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n,k", [(513, 3), (8193, 8), (600_001, 4)])
+def test_rows_under_every_hint_poison_and_guard(pgt, ctx, n, k):
+    W = 550_000 if n > 100_000 else 5000
+    rng = np.random.default_rng(1800 + k)
+    chr_ids, pos = synth.chromosomes(rng, n, 1)
+    f, c = random_pops(rng, n, k)
+    fb, cb = random_pops(rng, n, k)
+    win = np.concatenate([pgt.build_windows_sites(run_lengths(chr_ids), min(W, n), max(1, min(W, n) // 4)),
+                          pgt.build_windows_sites(run_lengths(chr_ids), min(1000, n), min(333, n))])
+    want, want_t = fst_hudson_model.model(pos, f, c, MININD, win)
+    dev = _dev()
+    tf, tn = [padded_column(x, float("nan"), dev) for x in f], [padded_column(x, 1000, dev) for x in c]
+    tp, wd = _t(pos), windows_to_device(win, dev)
+    n_pairs = k * (k - 1) // 2
+    tb = ctx.fst_hudson_pops_tree_bytes(k, n)
+    assert tb == ctx.fst_pops_tree_bytes(k, n)
+    # the tree of the OTHER estimator's call on other columns: the two may share a buffer in turn
+    _, _, foreign = ctx.fst_pops_reduce_dev(tp, [_t(x) for x in fb], [_t(x) for x in cb], MININD, wd)
+    g = GuardedBuffers([tb, n_pairs * win.size * FST_ROW_DTYPE.itemsize, n_pairs * FST_TOTAL_DTYPE.itemsize], 131 + k, dev)
+    tree, out, tot = g.bufs
+    for hint in (0, W, 4 * W):
+        first = None
+        with ctx.hints(hint, 0, 0):
+            for kind in (0, 1, 2):
+                poison_tree(tree, kind, other=foreign)
+                out.fill_(0xFF)
+                tot.fill_(0xFF)
+                ctx.fst_hudson_pops_reduce_dev(tp, tf, tn, MININD, wd, out=out, tot=tot, tree=tree)
+                what = f"n={n} K={k} hint={hint} poison={kind}"
+                g.check(what)
+                got = rows_from_device(out, FST_ROW_DTYPE).reshape(n_pairs, win.size).copy()
+                got_t = rows_from_device(tot, FST_TOTAL_DTYPE).copy()
+                if first is None:
+                    first = (got, got_t)
+                    for p in range(n_pairs):
+                        assert_rows(got[p], want[p], what + f" pair {p}")
+                    assert_totals(got_t, want_t, what)
+                else:  # identical under one hint, whatever the workspace held
+                    assert got.tobytes() == first[0].tobytes() and got_t.tobytes() == first[1].tobytes(), what
+
+
+# ---- 7: graph capture ------------------------------------------------------------------------------------------------------
+def test_graph_replay_rebuilds_from_new_columns(pgt, ctx):
+    import torch
+    n, k = 2 * 8192 + 700, 4
+    rng = np.random.default_rng(1900)
+    chr_ids, pos = synth.chromosomes(rng, n, 2, equal=False)
+    A, B = random_pops(rng, n, k), random_pops(rng, n, k)
+    win = pgt.build_windows_sites(run_lengths(chr_ids), 5000, 100)
+    dev = _dev()
+    wd, tp = windows_to_device(win, dev), _t(pos)
+    tf, tn = [_t(x) for x in A[0]], [_t(x) for x in A[1]]
+    n_pairs = k * (k - 1) // 2
+    g = GuardedBuffers([ctx.fst_hudson_pops_tree_bytes(k, n), n_pairs * win.size * FST_ROW_DTYPE.itemsize, n_pairs * FST_TOTAL_DTYPE.itemsize], 13, dev)
+    tree, out, tot = g.bufs
+    with ctx.hints(5000, 100, 0):
+        ctx.fst_hudson_pops_reduce_dev(tp, tf, tn, MININD, wd, out=out, tot=tot, tree=tree)  # warm-up outside the capture
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):  # one call on one stream: a chain of kernels, no parallel branches
+            ctx.fst_hudson_pops_reduce_dev(tp, tf, tn, MININD, wd, out=out, tot=tot, tree=tree)
+    for name, src in (("B", B), ("A", A)):
+        for t, x in zip(tf + tn, src[0] + src[1]):
+            t.copy_(torch.from_numpy(x))
+        for buf in (tree, out, tot):
+            buf.fill_(0xFF)
+        graph.replay()
+        g.check("fst_hudson_pops graph replay")
+        want, want_t = fst_hudson_model.model(pos, src[0], src[1], MININD, win)
+        got = rows_from_device(out, FST_ROW_DTYPE).reshape(n_pairs, win.size)
+        for p in range(n_pairs):
+            assert_rows(got[p], want[p], f"replay {name} pair {p}")
+        assert_totals(rows_from_device(tot, FST_TOTAL_DTYPE), want_t, f"replay {name}")
+
+
+# ---- 8: refusals -----------------------------------------------------------------------------------------------------------
+def test_refusals_name_the_argument_and_launch_nothing(pgt, ctx):
+    import torch
+    n, k = 10_000, 3
+    rng = np.random.default_rng(2000)
+    chr_ids, pos = synth.chromosomes(rng, n, 1)
+    f, c = random_pops(rng, n, k)
+    win = pgt.build_windows_sites(run_lengths(chr_ids), 1000, 500)
+    wd = windows_to_device(win, _dev())
+    n_pairs = 3
+    tb = ctx.fst_hudson_pops_tree_bytes(k, n)
+    g = GuardedBuffers([tb, n_pairs * win.size * FST_ROW_DTYPE.itemsize, n_pairs * FST_TOTAL_DTYPE.itemsize], 15, _dev())
+    tree, out, tot = g.bufs
+    for b in g.bufs:
+        b.fill_(0xFF)
+    tp, tf, tn = _t(pos), [_t(x) for x in f], [_t(x) for x in c]
+    lib, h = ctx._lib, ctx._ctx
+
+    def call(freq=None, nind=None, n_pops=k, minind=MININD, win_p=wd.data_ptr(), out_p=out.data_ptr(), out_bytes=out.numel(),
+             tree_p=tree.data_ptr(), tree_bytes=tree.numel(), freq_null=False, nind_null=False, pos_p=tp.data_ptr()):
+        fp = [t.data_ptr() for t in tf] if freq is None else freq
+        npn = [t.data_ptr() for t in tn] if nind is None else nind
+        pf = (C.c_void_p * 8)(*(fp + [None] * (8 - len(fp))))
+        pn = (C.c_void_p * 8)(*(npn + [None] * (8 - len(npn))))
+        return lib.pgt_fst_hudson_pops_reduce_dev(h, pos_p, None if freq_null else pf, None if nind_null else pn, n_pops, n, minind, win_p,
+                                                  win.size, out_p, out_bytes, tot.data_ptr(), tree_p, tree_bytes, None)
+
+    f_ptrs, n_ptrs = [t.data_ptr() for t in tf], [t.data_ptr() for t in tn]
+    refusals = [
+        (dict(minind=0), "minind"), (dict(minind=-3), "minind"),
+        (dict(pos_p=None), "pos"), (dict(freq_null=True), "freq"), (dict(nind_null=True), "nind"), (dict(tree_p=None), "tree"), (dict(win_p=None), "win"),
+        (dict(out_p=None), "out"), (dict(n_pops=1), "n_pops"), (dict(n_pops=9), "n_pops"),
+        (dict(freq=[f_ptrs[0], None, f_ptrs[2]]), "freq[1]"), (dict(nind=[n_ptrs[0], n_ptrs[1], None]), "nind[2]"),
+        (dict(freq=[f_ptrs[0], f_ptrs[1] + 8, f_ptrs[2]]), "freq[1]"), (dict(nind=[n_ptrs[0], n_ptrs[1], n_ptrs[2] + 8]), "nind[2]"),
+        (dict(nind=[n_ptrs[0] + 4, n_ptrs[1], n_ptrs[2]]), "nind[0]"),
+        (dict(out_bytes=out.numel() - 1), "out_bytes"), (dict(tree_bytes=tb - 1), "tree_bytes"),
+    ]
+    for kw, name in refusals:
+        rc = call(**kw)
+        msg = _lib.last_error(h)
+        assert rc == _lib.PGT_EARG and name in msg and msg.startswith("pgt_fst_hudson_pops_reduce: "), (kw, rc, msg)
+    g.check("refused calls")
+    for b in g.bufs:
+        assert bool(torch.all(b == 0xFF)), "a refused call wrote to a buffer"
+
+    # the host-buffer C form: outputs stay as they were
+    win_h = np.ascontiguousarray(win)
+    out_h = np.full(n_pairs * win.size * FST_ROW_DTYPE.itemsize, 0xFF, dtype=np.uint8)
+    tot_h = np.full(n_pairs * FST_TOTAL_DTYPE.itemsize, 0xFF, dtype=np.uint8)
+    hf = (C.c_void_p * 8)(*([x.ctypes.data for x in f] + [None] * 5))
+    hn = (C.c_void_p * 8)(*([x.ctypes.data for x in c] + [None] * 5))
+    hf_hole = (C.c_void_p * 8)(*([f[0].ctypes.data, None, f[2].ctypes.data] + [None] * 5))
+
+    def host(pf=hf, pn=hn, n_pops=k, minind=MININD, pos_p=pos.ctypes.data, win_p=win_h.ctypes.data, out_p=out_h.ctypes.data):
+        return lib.pgt_fst_hudson_pops_reduce(h, pos_p, pf, pn, n_pops, n, minind, win_p, win.size, out_p, tot_h.ctypes.data)
+
+    for kw, name in [(dict(minind=0), "minind"), (dict(n_pops=1), "n_pops"), (dict(n_pops=9), "n_pops"), (dict(pf=None), "NULL argument"),
+                     (dict(pn=None), "NULL argument"), (dict(pos_p=None), "NULL argument"), (dict(win_p=None), "NULL argument"),
+                     (dict(out_p=None), "NULL argument"), (dict(pf=hf_hole), "NULL column")]:
+        rc = host(**kw)
+        msg = _lib.last_error(h)
+        assert rc == _lib.PGT_EARG and name in msg and msg.startswith("pgt_fst_hudson_pops_reduce: "), (kw, rc, msg)
+    assert np.all(out_h == 0xFF) and np.all(tot_h == 0xFF), "a refused host-buffer call wrote to its outputs"
+
+    assert call() == _lib.PGT_OK  # the same arguments, unharmed, are accepted
+    torch.cuda.synchronize()
+    want, _ = fst_hudson_model.model(pos, f, c, MININD, win)
+    got = rows_from_device(out, FST_ROW_DTYPE).reshape(n_pairs, win.size)
+    for p in range(n_pairs):
+        assert_rows(got[p], want[p], f"accepted call, pair {p}")
+
+    # the Python wrappers refuse misaligned views, differing lengths and counts by name
+    m = 1000
+    fcols = [torch.zeros(m + 4, dtype=torch.float64, device=_dev()) for _ in range(3)]
+    ccols = [torch.ones(m + 4, dtype=torch.int32, device=_dev()) for _ in range(3)]
+    posm = torch.arange(1, m + 1, dtype=torch.int32, device=_dev())
+    w1 = windows_to_device(pgt.build_windows_sites(np.array([m], np.uint64), 100, 100), _dev())
+    good_f, good_c = [t[4:4 + m] for t in fcols], [t[4:4 + m] for t in ccols]
+    ctx.fst_hudson_pops_reduce_dev(posm, good_f, good_c, 1, w1)
+    with pytest.raises(_lib.PgtError, match=r"freqs\[1\]"):
+        ctx.fst_hudson_pops_reduce_dev(posm, [good_f[0], fcols[1][1:1 + m], good_f[2]], good_c, 1, w1)
+    with pytest.raises(_lib.PgtError, match=r"ninds\[2\]"):
+        ctx.fst_hudson_pops_reduce_dev(posm, good_f, [good_c[0], good_c[1], ccols[2][2:2 + m]], 1, w1)
+    with pytest.raises(_lib.PgtError, match="column lengths differ"):
+        ctx.fst_hudson_pops_reduce_dev(posm, [good_f[0], good_f[1][:-4], good_f[2]], good_c, 1, w1)
+    with pytest.raises(_lib.PgtError, match="minind"):
+        ctx.fst_hudson_pops_reduce_dev(posm, good_f, good_c, 0, w1)
+    with pytest.raises(_lib.PgtError, match="2 ... 8 populations"):
+        ctx.fst_hudson_pops_reduce_dev(posm, good_f[:1], good_c[:1], 1, w1)
+    with pytest.raises(_lib.PgtError, match="column lengths differ"):
+        ctx.fst_hudson_pops_reduce(pos, [f[0], f[1][:-1], f[2]], c, MININD, win)
+    with pytest.raises(_lib.PgtError, match="2 ... 8 populations"):
+        ctx.fst_hudson_pops_reduce(pos, f[:1], c[:1], MININD, win)
+    with pytest.raises(_lib.PgtError, match="minind"):
+        ctx.fst_hudson_pops_reduce(pos, f, c, 0, win)
+    torch.cuda.synchronize()
+
+
+# ---- 9: host-buffer form ---------------------------------------------------------------------------------------------------
+def test_host_buffer_form_equals_the_device_form_twice_in_a_row(pgt, ctx):
+    n, k = 2 * 8192 + 700, 4
+    for seed in (161, 162):  # different data through the one context: nothing of the cached workspace may survive
+        rng = np.random.default_rng(seed)
+        chr_ids, pos = synth.chromosomes(rng, n, 3, equal=False)
+        f, c = random_pops(rng, n, k)
+        win = pgt.build_windows_sites(run_lengths(chr_ids), 5000, 1000)
+        rows, tot = ctx.fst_hudson_pops_reduce(pos, f, c, MININD, win)
+        hints = pgt.window_scan.table_hints(win)
+        with ctx.hints(hints[0], 0, 0):  # the host-buffer form derives the longest-window hint from the table
+            want, want_t = hudson_dev(ctx, _t(pos), [_t(x) for x in f], [_t(x) for x in c], MININD, win)
+        assert rows.shape == want.shape
+        for p in range(rows.shape[0]):
+            rows_equal(np.ascontiguousarray(rows[p]), want[p], f"seed {seed} pair {p}")
+        assert tot.tobytes() == want_t.tobytes()
+    res = pgt.fst_window_pops(chr_ids, pos, f, c, 5000, 1000, MININD, 1, ctx=ctx, estimator="hudson")
+    assert list(res) == pair_order(k)
+    rows_equal(np.ascontiguousarray(res[(0, 1)].rows), want[0], "fst_window_pops(estimator='hudson') pair (0, 1)")
+    wc = pgt.fst_window_pops(chr_ids, pos, f, c, 5000, 1000, MININD, 1, ctx=ctx)
+    dflt = pgt.fst_window_pops(chr_ids, pos, f, c, 5000, 1000, MININD, 1, ctx=ctx, estimator="wc")
+    assert wc[(0, 1)].rows.tobytes() == dflt[(0, 1)].rows.tobytes() != res[(0, 1)].rows.tobytes()

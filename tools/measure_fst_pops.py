@@ -7,7 +7,12 @@
 compared with leg (a)'s (coordinates and counts exactly, sums within 1e-9 |y| + 1e-12); a mismatch exits non-zero.  Timing:
 after a warm-up of every shape, the two legs ALTERNATE, 3 repetitions each; a repetition is as many back-to-back steps as
 fill at least one second (the count is fixed after the warm-up and printed), timed by events on the launch stream; medians.
-The build kernel's own time comes from the library's events (last_kernel_ms).  One JSON line per K on stdout."""
+The build kernel's own time comes from the library's events (last_kernel_ms).  One JSON line per K on stdout.
+
+--estimators (anywhere on the command line) runs another leg instead: the two estimators of the K-population call, Weir-Cockerham
+(fst_pops_reduce_dev) and Hudson (fst_hudson_pops_reduce_dev), ALTERNATELY on the same columns, table and buffers in one
+process; counts and coordinates of the two must be equal before anything is timed; whole steps by events as above, build and
+query by the library's events, 7 alternating readings each after the warm-up; medians.  One JSON line per K."""
 import json
 import os
 import sys
@@ -36,7 +41,53 @@ def event_ms(fn, steps):
     return e0.elapsed_time(e1) / steps
 
 
+def estimator_leg(ctx, k, n, pos, f, c, minind, win, n_win, dev, card, W, S):
+    """WC and Hudson K-population calls alternately on the same columns -> one JSON line; False when their counts differ"""
+    n_pairs = len(pair_order(k))
+    calls = {"wc": ctx.fst_pops_reduce_dev, "hudson": ctx.fst_hudson_pops_reduce_dev}
+    out = {e: torch.empty(n_pairs * n_win * FST_ROW_DTYPE.itemsize, dtype=torch.uint8, device=dev) for e in calls}
+    tot = {e: torch.empty(FST_TOTAL_DTYPE.itemsize * n_pairs, dtype=torch.uint8, device=dev) for e in calls}
+    tree = torch.empty(ctx.fst_pops_tree_bytes(k, n), dtype=torch.uint8, device=dev)  # one buffer, the two in turn
+    leg = {e: (lambda e=e: calls[e](pos, f, c, minind, win, out=out[e], tot=tot[e], tree=tree)) for e in calls}
+    for e in calls:
+        leg[e]()
+    torch.cuda.synchronize()
+    rw, rh = rows_from_device(out["wc"], FST_ROW_DTYPE), rows_from_device(out["hudson"], FST_ROW_DTYPE)
+    if not all(np.array_equal(rw[fld], rh[fld]) for fld in ("start", "end", "mid", "n")):
+        print(json.dumps({"k": k, "rows_check": "FAILED: counts or coordinates of the two estimators differ"}), flush=True)
+        return False
+    for _ in range(3):  # warm-up, discarded
+        for e in calls:
+            leg[e]()
+    torch.cuda.synchronize()
+    steps = {e: max(1, int(np.ceil(1000.0 / event_ms(leg[e], 3)))) for e in calls}
+    step_ms = {e: [] for e in calls}
+    for _ in range(3):  # alternating
+        for e in calls:
+            step_ms[e].append(event_ms(leg[e], steps[e]))
+    ctx.set_profiling(True)
+    bq = {e: [] for e in calls}
+    for _ in range(7):  # alternating
+        for e in calls:
+            leg[e]()
+            bq[e].append(ctx.last_kernel_ms())
+    ctx.set_profiling(False)
+    res = {"k": k, "n_sites": n, "n_pairs": n_pairs, "n_win": int(n_win), "W": W, "S": S, "minind": minind, "rows_check": "ok",
+           "steps_per_repetition": steps, "card": card}
+    for e in calls:
+        build = float(np.median([x[0] for x in bq[e]]))
+        res[e] = {"step_ms": float(np.median(step_ms[e])), "repetitions_ms": step_ms[e], "build_ms": build,
+                  "query_ms": float(np.median([x[1] for x in bq[e]])),
+                  "build_fraction_of_hbm_peak": 12.0 * k * n / (build * 1e-3) / HBM_PEAK}
+    res["hudson_build_over_wc_build"] = res["hudson"]["build_ms"] / res["wc"]["build_ms"]
+    res["hudson_step_over_wc_step"] = res["hudson"]["step_ms"] / res["wc"]["step_ms"]
+    print(json.dumps(res), flush=True)
+    return True
+
+
 def main():
+    estimators = "--estimators" in sys.argv
+    sys.argv = [a for a in sys.argv if a != "--estimators"]
     n = int(float(sys.argv[1])) if len(sys.argv) > 1 else 100_000_000
     ks = [int(x) for x in sys.argv[2].split(",")] if len(sys.argv) > 2 else [2, 4, 8]
     dev = torch.device("cuda", 0)
@@ -61,6 +112,11 @@ def main():
     for k in ks:
         pairs = pair_order(k)
         f, c = freqs[:k], ninds[:k]
+        if estimators:
+            if not estimator_leg(ctx, k, n, pos, f, c, minind, win, n_win, dev, card, W, S):
+                rc = 1
+                break
+            continue
         out_a = torch.empty(len(pairs) * n_win * FST_ROW_DTYPE.itemsize, dtype=torch.uint8, device=dev)
         out_b = torch.empty_like(out_a)
         tot_a = torch.empty(FST_TOTAL_DTYPE.itemsize, dtype=torch.uint8, device=dev)
