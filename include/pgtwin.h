@@ -53,7 +53,8 @@ extern "C" {
  * Still 6: pgt_align_segments / pgt_align_workspace_bytes / pgt_sites_align / pgt_gather_dev added (additive as well).
  * Still 6: pgt_fst_total, pgt_fst_pops_tree_bytes / pgt_fst_pops_reduce_dev / pgt_fst_pops_reduce added (additive as well).
  * Still 6: pgt_pi_pops_tree_bytes / pgt_pi_pops_reduce_dev / pgt_pi_pops_reduce added (additive as well).
- * Still 6: pgt_fst_hudson_pops_tree_bytes / pgt_fst_hudson_pops_reduce_dev / pgt_fst_hudson_pops_reduce added (additive as well). */
+ * Still 6: pgt_fst_hudson_pops_tree_bytes / pgt_fst_hudson_pops_reduce_dev / pgt_fst_hudson_pops_reduce added (additive as well).
+ * Still 6: pgt_dstat_row, pgt_dstat_total, pgt_dstat_pops_tree_bytes / pgt_dstat_pops_reduce_dev / pgt_dstat_pops_reduce added (additive as well). */
 #define PGT_ABI_VERSION 6
 
 enum {
@@ -105,6 +106,17 @@ typedef struct { /* genomeFst (betaAFOutlier.R:440-446) of one pair over its cou
     double asum, bsum;
     uint64_t neff, nskip;
 } pgt_fst_total;
+
+typedef struct { /* ABBA-BABA window row of one trio ((i,j),k) against the outgroup: pgt_dstat_pops_reduce_dev */
+    uint32_t start, end, mid, n;
+    double d;                /* (abba + baba) != 0 ? (abba - baba) / (abba + baba) : 0   Patterson's D */
+    double bbaa, abba, baba; /* the three window sums, full precision */
+} pgt_dstat_row;
+
+typedef struct { /* the three sums of one trio over all its counted sites */
+    double bbaa, abba, baba;
+    uint64_t neff, nskip;
+} pgt_dstat_total;
 
 /* ---- context ------------------------------------------------------------------------- */
 /* device: HIP ordinal, or -1 for the current device.  Fails (NULL, message via
@@ -346,6 +358,54 @@ int pgt_pi_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *cons
 int pgt_pi_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq,
                        const int32_t *const *nind, uint32_t n_pops, uint64_t n, int minind,
                        const pgt_win *win, uint64_t n_win, pgt_dxy_row *out, pgt_dxy_total *tot);
+
+/* ---- ABBA-BABA (Patterson's D) of all ingroup trios against an outgroup, from per-population MAF columns -------------- */
+/* The window rows of an introgression scan (Green et al. 2010; Durand et al. 2011; Martin et al. 2015; what Dsuite's Dtrios /
+ * Dinvestigate compute from frequencies) for ALL trios of the ingroup populations at once, from each population's own
+ * (freq, nInd) columns — the input of pgt_fst_pops_reduce_dev — over ONE position column and ONE window table, in one pass
+ * (12 B/site/population).  It has NO counterpart in the reference: the definition below is the contract.
+ * n_pops = K populations, 4 <= K <= 7.  The LAST population (index K-1) is the outgroup o, the first K-1 are the ingroup.  A
+ * trio is (i, j, k) with i < j < k < K-1; trios are numbered in lexicographic order (0,1,2),(0,1,3),..,(0,1,K-2),(0,2,3),..;
+ * there are T = C(K-1, 3) of them: 1 / 4 / 10 / 20 at K = 4 / 5 / 6 / 7.  For trio (i, j, k) and site s:
+ *   counting   nind_i[s] >= minind && nind_j[s] >= minind && nind_k[s] >= minind && nind_o[s] >= minind   (signed int32 compare;
+ *              minind >= 1 required, PGT_EARG otherwise, as in the other *_pops calls); a site that is not counted is selected
+ *              away, never multiplied (its frequencies may be NaN, its counts 0 or negative)
+ *   per site   p_x = freq_x[s], q_x = 1.0 - p_x; every operation rounded on its own, no contraction, in exactly this grouping:
+ *                  bbaa = (p_i*p_j)*(q_k*q_o) + (q_i*q_j)*(p_k*p_o)
+ *                  abba = (q_i*p_j)*(p_k*q_o) + (p_i*q_j)*(q_k*p_o)
+ *                  baba = (p_i*q_j)*(p_k*q_o) + (q_i*p_j)*(q_k*p_o)
+ *              The second term of each line is the pattern with the roles of the two alleles swapped (Dsuite's form): the three
+ *              values do not depend on which allele the columns report, provided all populations report the same one.  (The
+ *              four products of an ingroup pair and the four products of (k, o) are computed once per site and shared by every
+ *              trio that contains them.)
+ *   row        pgt_dstat_row: bbaa / abba / baba = the three sums over the window's counted sites, each from +0.0; n = their
+ *              number (nskip = (hi - lo) - n); start / end / mid as pgt_fst_pops_reduce_dev fills them (PGT_WIN_COORDS
+ *              honoured); d = (abba + baba) != 0 ? (abba - baba) / (abba + baba) : 0 — Patterson's D for the topology ((i,j),k),
+ *              from the row's own three sums with one correctly rounded subtraction, addition and division.  The other two
+ *              topologies of the trio follow from the same three sums — ((i,k),j): (bbaa - baba) / (bbaa + baba);
+ *              ((j,k),i): (bbaa - abba) / (bbaa + abba) — and are not carried by the row
+ *   out        T * n_win rows, trio-major: out[t * n_win + w]
+ *   tot        DEVICE array of T pgt_dstat_total (the same sums over all counted sites, from one partial per build wave in wave
+ *              order), or NULL; n_win == 0 with tot: the global-only form
+ *   tree       pgt_dstat_pops_tree_bytes(n_pops, n) bytes (0 for n_pops outside 4 ... 7).    4 <= n_pops <= 7, n < 2^32.
+ * K = 8 (35 trios, 105 sums per node) is not offered: the running sums and the build's two register sets would not fit a wave.
+ * A one-site window carries exactly the bits of `bbaa`, `abba`, `baba` and `d` above.
+ * Arguments, alignment, refusals (each names its argument; nothing is launched), graph capture and the hints: those of
+ * pgt_fst_pops_reduce_dev (pgt_set_max_window honoured, pgt_set_window_step ignored).  Rows of a trio do not depend, bit for
+ * bit, on the populations outside the trio and the outgroup, nor on the other rows of the table.  Sums are added in a fixed
+ * order that depends on the site index and the window alone (bitwise reproducible); against an exact evaluation of the lines
+ * above they stay within 1e-9 relative + 1e-12.  Parity: none to pin; held to this definition, to an exact-rational fixture
+ * (tests/golden/dstat_exact.json) and to a NumPy model (tests/dstat_pops_model.py).  Block-jackknife Z scores, f_d / f_dM and
+ * user-chosen trio lists are not computed; the rows of a fixed-site window table are the blocks a jackknife needs.
+ * Host-buffer form: columns (host arrays of n_pops HOST pointers), table, rows and the T totals in host memory. */
+size_t pgt_dstat_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites);
+int pgt_dstat_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq,
+                              const int32_t *const *nind, uint32_t n_pops, uint64_t n, int minind,
+                              const pgt_win *win, uint64_t n_win, pgt_dstat_row *out, size_t out_bytes,
+                              pgt_dstat_total *tot, void *tree, size_t tree_bytes, void *stream);
+int pgt_dstat_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq,
+                          const int32_t *const *nind, uint32_t n_pops, uint64_t n, int minind,
+                          const pgt_win *win, uint64_t n_win, pgt_dstat_row *out, pgt_dstat_total *tot);
 
 /* ---- the sites common to K files, aligned on the device ------------------------------------------ */
 /* Replaces the two-file synchronisation of dxyWindow.cpp:315-331 (one current line per file; the file that is behind reads

@@ -332,20 +332,22 @@ struct DeviceScope {
 // their argument checks is one text for all three: pops_check_range, pops_check_dev, pops_reduce_host.
 struct PopsStat {
     const char *who;                                          // the prefix of every message
-    uint32_t min_pops;                                        // min_pops <= n_pops <= kPopsMaxPops
+    uint32_t min_pops;                                        // min_pops <= n_pops <= max_pops
     bool minind_from_1;                                       // minind < 1 is refused (dxy takes it as it comes)
     uint64_t (*tables)(uint32_t n_pops);                      // row tables, and totals, of one call
     const char *tables_word;                                  // ... and the word for them in the overflow message
     size_t row_bytes;
     size_t (*tree_bytes)(uint32_t n_pops, uint64_t n_sites);
+    uint32_t max_pops = (uint32_t)kPopsMaxPops;               // (the trios of pgt_dstat_pops_reduce stop at 7)
 };
 uint64_t pops_pairs(uint32_t n_pops) { return (uint64_t)n_pops * (n_pops - 1) / 2; }
 uint64_t pops_each(uint32_t n_pops) { return n_pops; }
+uint64_t pops_trios(uint32_t n_pops) { return (uint64_t)(n_pops - 1) * (n_pops - 2) * (n_pops - 3) / 6; }  // C(n_pops - 1, 3): the last population is the outgroup
 
 // first in both forms, and before the device form's early PGT_OK
 int pops_check_range(pgt_ctx *ctx, const PopsStat &st, uint32_t n_pops, int minind) {
-    if (n_pops < st.min_pops || n_pops > (uint32_t)kPopsMaxPops)
-        return ctx_fail(ctx, PGT_EARG, std::string(st.who) + ": n_pops must be " + std::to_string(st.min_pops) + " ... " + std::to_string(kPopsMaxPops));
+    if (n_pops < st.min_pops || n_pops > st.max_pops)
+        return ctx_fail(ctx, PGT_EARG, std::string(st.who) + ": n_pops must be " + std::to_string(st.min_pops) + " ... " + std::to_string(st.max_pops));
     if (st.minind_from_1 && minind < 1) return ctx_fail(ctx, PGT_EARG, std::string(st.who) + ": minind must be at least 1");
     return PGT_OK;
 }
@@ -427,7 +429,7 @@ pgt_ctx *pgt_open(int device) {
     } restore{caller_device, device};
     std::string init_err;
     if (init_kernels(&init_err) != PGT_OK || init_af_kernels(&init_err) != PGT_OK || init_dxy_pops_kernels(&init_err) != PGT_OK ||
-        init_fst_pops_kernels(&init_err) != PGT_OK) {
+        init_fst_pops_kernels(&init_err) != PGT_OK || init_dstat_pops_kernels(&init_err) != PGT_OK) {
         set_global_error("pgt_open: " + init_err);
         return nullptr;
     }
@@ -709,6 +711,25 @@ int pgt_pi_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *cons
     const EvSet e = events_for(ctx);
     return launch_pi_pops(pos, freq, nind, n_pops, n, minind, win, n_win, out, tot, tree, stream, e.b0, e.b1, e.q1, &ctx->error,
                           ctx->hints);
+}
+
+// ABBA-BABA patterns of all ingroup trios against the last population: one more PopsStat, with an upper bound of its own
+size_t pgt_dstat_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites) {
+    if (n_pops < 4 || n_pops > 7) return 0;
+    return dstat_pops_tree_view(tree_layout(PGT_STAT_FST, n_sites), (int)pops_trios(n_pops), nullptr, 0).bytes;
+}
+static const PopsStat kDstatPops = {"pgt_dstat_pops_reduce", 4, true, pops_trios, "n_trios", sizeof(pgt_dstat_row), pgt_dstat_pops_tree_bytes, 7};
+
+int pgt_dstat_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind,
+                              uint32_t n_pops, uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_dstat_row *out,
+                              size_t out_bytes, pgt_dstat_total *tot, void *tree, size_t tree_bytes, void *stream) {
+    PGT_USE_DEVICE(ctx);
+    bool launch;
+    if (int rc = pops_check_dev(ctx, kDstatPops, pos, freq, nind, n_pops, n, minind, win, n_win, out, out_bytes, tot, tree, tree_bytes, &launch)) return rc;
+    if (!launch) return PGT_OK;
+    const EvSet e = events_for(ctx);
+    return launch_dstat_pops(pos, freq, nind, n_pops, n, minind, win, n_win, out, tot, tree, stream, e.b0, e.b1, e.q1, &ctx->error,
+                             ctx->hints);
 }
 
 size_t pgt_align_workspace_bytes(uint32_t n_files, uint64_t n_rows_file0) {
@@ -1115,6 +1136,13 @@ int pgt_pi_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *f
                        uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_dxy_row *out, pgt_dxy_total *tot) {
     PGT_USE_DEVICE(ctx);
     return pops_reduce_host(ctx, kPiPops, pgt_pi_pops_reduce_dev, pos, freq, nind, n_pops, n, minind, win, n_win, out, tot);
+}
+
+/* ABBA-BABA patterns of all ingroup trios: the host-buffer form, as pgt_fst_pops_reduce with one table per trio */
+int pgt_dstat_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
+                          uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_dstat_row *out, pgt_dstat_total *tot) {
+    PGT_USE_DEVICE(ctx);
+    return pops_reduce_host(ctx, kDstatPops, pgt_dstat_pops_reduce_dev, pos, freq, nind, n_pops, n, minind, win, n_win, out, tot);
 }
 
 /* ---------------- window tables built on the device ---------------- */

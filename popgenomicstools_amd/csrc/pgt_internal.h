@@ -162,6 +162,20 @@ struct FstPopsTree {
     uint32_t n_partials;         // build waves that left a partial (0: no sites)
 };
 
+// ---- ABBA-BABA patterns of all ingroup trios against an outgroup (pgt_dstat_pops_kernels.hip) ------------------------------
+// The shape of FstPopsTree with three sums per TRIO: a node is 3 T doubles (Σbbaa of trio 0 .. T-1, then Σabba, then Σbaba) and
+// T u32 (neff), T = C(n_pops - 1, 3); behind the levels one such node per build wave.  n_pairs holds T (pops_tree_view's name).
+struct DstatPopsTree {
+    char *base;
+    size_t sum_off[kMaxLevels];  // byte offset of level slot k: 3 T doubles per node
+    size_t cnt_off[kMaxLevels];  // ... T u32 per node
+    size_t part_sum, part_cnt;   // [build wave][3 T] doubles / [build wave][T] u32
+    size_t bytes;
+    int n_levels;
+    int n_pairs;                 // T: the trios
+    uint32_t n_partials;         // build waves that left a partial (0: no sites)
+};
+
 // The one layout behind both (two kernel-argument types, one shape): per level and behind the levels an array of `sum_bytes`
 // of sums per pair and node (8: Σd; 16: Σa and Σ(a+b)) and an array of one u32 per pair and node, each padded to 256 bytes.
 template <class Tree>
@@ -191,6 +205,9 @@ inline DxyPopsTree dxy_pops_tree_view(const TreeLayout &t, int n_pairs, void *tr
 }
 inline FstPopsTree fst_pops_tree_view(const TreeLayout &t, int n_pairs, void *tree, int levels) {
     return pops_tree_view<FstPopsTree>(t, n_pairs, 16, tree, levels);
+}
+inline DstatPopsTree dstat_pops_tree_view(const TreeLayout &t, int n_trios, void *tree, int levels) {
+    return pops_tree_view<DstatPopsTree>(t, n_trios, 24, tree, levels);
 }
 
 // Speed-only hints of a context (pgt_set_max_window, pgt_set_window_step); 0 = unknown.
@@ -265,6 +282,13 @@ int launch_fst_pops(const uint32_t *pos, const double *const *freq, const int32_
                     void *tree, void *stream, void *ev_build0, void *ev_build1, void *ev_query1, std::string *err,
                     const Hints &hints, FstPopsEstimator estimator);
 
+// pgt_dstat_pops_kernels.hip: tot = C(n_pops - 1, 3) device totals or NULL; 4 <= n_pops <= 7 (the last population is the
+// outgroup) and minind >= 1 (checked by the caller); out = one table of n_win rows per trio, in lexicographic trio order
+int launch_dstat_pops(const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
+                      uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_dstat_row *out, pgt_dstat_total *tot,
+                      void *tree, void *stream, void *ev_build0, void *ev_build1, void *ev_query1, std::string *err,
+                      const Hints &hints);
+
 // pgt_kernels.hip: pi per population, 1 <= n_pops <= 8 and minind >= 1 (checked by the caller); out = n_pops tables of
 // n_win rows, tot = n_pops device totals or NULL; tree = n_pops trees of tree_layout(PGT_STAT_DXY, n).bytes each
 int launch_pi_pops(const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
@@ -317,6 +341,7 @@ int init_kernels(std::string *err);     // pgt_kernels.hip: one-time kernel attr
 int init_af_kernels(std::string *err);  // pgt_af_kernels.hip
 int init_dxy_pops_kernels(std::string *err);  // pgt_dxy_pops_kernels.hip
 int init_fst_pops_kernels(std::string *err);  // pgt_fst_pops_kernels.hip
+int init_dstat_pops_kernels(std::string *err);  // pgt_dstat_pops_kernels.hip
 
 // thread-local message for the ctx-less entry points
 void set_global_error(const std::string &msg);

@@ -1,0 +1,123 @@
+// dstatWindowPops (MI355X host) — sliding-window ABBA-BABA site patterns and Patterson's D (Green et al. 2010; Durand et al.
+// 2011) for ALL trios of 3 ... 6 ingroup populations against one outgroup, from their ANGSD .mafs files (plain, gzip or bgzf):
+// the introgression scan that goes with the .dxy / .fst / .pi files of dxyWindowPops / fstWindowPops / piWindowPops.
+// The reference has no such tool; the definition is that of pgt_dstat_pops_reduce_dev (include/pgtwin.h).
+//
+//   dstatWindowPops [dxyWindow's options] -out PREFIX <maf P1> ... <maf P(K-1)> <maf outgroup>        4 <= K <= 7
+//
+// Options, defaults, messages and exit codes are dxyWindowPops's (-winsize -stepsize -minind -fixedsite -sizefile
+// -skip_missing, both window modes), and so is the front end (pops_common.h): the sites (chromosome, position) that ALL
+// files list are found on the GPU and every file's columns are gathered onto them.  One pgt_dstat_pops_reduce_dev call then
+// reduces all C(K-1, 3) trios: per site the expected BBAA, ABBA and BABA pattern frequencies of ((i,j),k) against the
+// outgroup, counted where all four populations have at least -minind individuals; per window their sums and
+// D = (ABBA - BABA) / (ABBA + BABA).
+// Trio (i, j, k) -> PREFIX.pop<i+1>_pop<j+1>_pop<k+1>.dstat (`chr start end mid D BBAA ABBA BABA neff nskip`); the
+// genome-wide lines -> PREFIX.global (`i+1 j+1 k+1 D BBAA ABBA BABA neff nskip`).  stdout stays empty.
+//
+// Limits: one GPU (the first of PGT_DEVICES); no passes mode — the K parsed files and the aligned columns must fit the
+// card (and PGT_MAX_RESIDENT_SITES, where set) or the run is refused; PGT_DXY_SYNC=reference is not offered.
+#include "pops_common.h"
+
+using namespace pgthost;
+
+static void help(const DxyOptions &o) {
+    std::printf("\ndstatWindowPops [options] -out PREFIX <pop1 maf file> ... <pop(K-1) maf file> <outgroup maf file>      (4 <= K <= 7)\n\nOptions:\n"
+                "%-14s%-8sPrefix of the output files (REQUIRED)\n"
+                "%-14s%-8sWindow size in base pairs (0 for global calculation) [%u]\n"
+                "%-14s%-8sNumber of base pairs to progress window [%u]\n"
+                "%-14s%-8sMinimum number of individuals in each of the four populations with data [%d]\n"
+                "%-14s%-8s(1) Use fixed number of sites from MAF input for each window (window sizes may vary) or (0) constant window size [%d]\n"
+                "%-14s%-8sTwo-column TSV file with each row having (1) chromsome name (2) chromosome size in base pairs\n"
+                "%-14s%-8sDo not print windows with zero effective sites if INT=1 [%d]\n"
+                "\nNotes:\n"
+                "* The LAST MAF file is the outgroup; the K-1 files before it are the ingroup populations (K between 4 and 7 files)\n"
+                "* Every trio i < j < k of ingroup populations is analyzed as ((i,j),k) against the outgroup: C(K-1,3) trios\n"
+                "* Only the sites (chromosome, position) present in ALL MAF files are analyzed\n"
+                "* Per site, with p the frequencies and q = 1-p: BBAA = p_i p_j q_k q_o + q_i q_j p_k p_o, ABBA = q_i p_j p_k q_o + p_i q_j q_k p_o,\n"
+                "  BABA = p_i q_j p_k q_o + q_i p_j q_k p_o; a window's values are the SUMS over its analyzed sites, D = (ABBA - BABA)/(ABBA + BABA)\n"
+                "* The patterns are symmetric in the two alleles: it does not matter which allele the MAF files report,\n"
+                "  but ALL files must report the frequency of the SAME allele at every site\n"
+                "* The other two topologies of a trio follow from the same three sums: ((i,k),j): D = (BBAA - BABA)/(BBAA + BABA);\n"
+                "  ((j,k),i): D = (BBAA - ABBA)/(BBAA + ABBA)\n"
+                "* A site counts for a trio when its three populations and the outgroup each have at least -minind individuals with data\n"
+                "* No Z scores are computed: the window rows of a -fixedsite 1 run are the blocks a block-jackknife needs\n"
+                "* -sizefile is REQUIRED(!) with -fixedsite 0 (the default)\n"
+                "* All input MAF files need to have the same chromosomes in the same order\n"
+                "* Assumes SNPs are biallelic\n"
+                "\nLimits:\n"
+                "* One GPU is used (the first entry of PGT_DEVICES)\n"
+                "* No passes mode: input whose parsed files plus aligned columns do not fit the GPU, or PGT_MAX_RESIDENT_SITES, is refused\n"
+                "* PGT_DXY_SYNC=reference is not offered: the reference's catch-up loops are defined for two files only\n"
+                "\nOutput:\nPREFIX.pop<i>_pop<j>_pop<k>.dstat for every trio i < j < k (not with -winsize 0):\n"
+                "(1) chromosome\n(2) Window start\n(3) Window end\n(4) Window midpoint\n(5) D of ((i,j),k)\n(6) BBAA (sum)\n(7) ABBA (sum)\n(8) BABA (sum)\n"
+                "(9) number sites in MAF input that were analyzed\n"
+                "(10) number of sites in MAF input that were skipped due to too few individuals\n"
+                "PREFIX.global, one line per trio:\n(1) i\n(2) j\n(3) k\n(4) D\n(5) BBAA\n(6) ABBA\n(7) BABA\n(8) number of sites analyzed\n(9) number of sites skipped\n\n",
+                "-out", "STRING", "-winsize", "INT", o.W, "-stepsize", "INT", o.S, "-minind", "INT", o.minind, "-fixedsite", "INT", o.fixedsite,
+                "-sizefile", "FILE", "-skip_missing", "INT", o.skip_missing);
+}
+
+// chr start end mid D BBAA ABBA BABA neff nskip
+static size_t put_dstat_row(char *o, const std::string &chr, const pgt_dstat_row &r, uint32_t nskip) {
+    char *p = o;
+    std::memcpy(p, chr.data(), chr.size());
+    p += chr.size();
+    for (uint32_t u : {r.start, r.end, r.mid}) { *p++ = '\t'; p = put_u32(p, u); }
+    for (double g : {r.d, r.bbaa, r.abba, r.baba}) { *p++ = '\t'; p += fmt_g6(g, p); }
+    for (uint32_t u : {r.n, nskip}) { *p++ = '\t'; p = put_u32(p, u); }
+    *p++ = '\n';
+    return (size_t)(p - o);
+}
+
+int main(int argc, char **argv) {
+    const std::string tool = "dstatWindowPops";
+    const PopsArgs args = parse_pops_args(tool, argc, argv, help, 4, NoOwnOption{}, 7);
+    const int K = args.K;
+    const char *prefix = args.prefix;
+    const uint32_t W = args.opt.W;
+    const int minind = args.opt.minind, skip_missing = args.opt.skip_missing;
+
+    PhaseTimer timer;
+    DeviceOpener device(std::vector<int>{devices_from_env()[0]});  // one GPU; HIP start-up runs beside the opening of the files
+    const PopsSites s = load_pops(tool, args, timer, device);
+    pgt_ctx *ctx = s.ctx;
+    const std::vector<pgt_win> &win = s.win;
+    const Runs &runs = s.runs;
+    const size_t n_trios = (size_t)(K - 1) * (size_t)(K - 2) * (size_t)(K - 3) / 6, n_win = win.size();
+    pgt_dstat_row *d_rows = pops_dev_alloc<pgt_dstat_row>(ctx, n_trios * n_win);
+    pgt_dstat_total *d_tot = pops_dev_alloc<pgt_dstat_total>(ctx, n_trios);
+    const size_t tree_bytes = pgt_dstat_pops_tree_bytes((uint32_t)K, s.n_sites);
+    void *tree = nullptr;
+    check(pgt_dev_alloc(ctx, tree_bytes, &tree), ctx);
+    check(pgt_dstat_pops_reduce_dev(ctx, s.a_pos, s.a_freq.data(), s.a_nind.data(), (uint32_t)K, s.n_sites, minind, n_win ? s.d_win : nullptr, n_win,
+                                    n_win ? d_rows : nullptr, n_trios * n_win * sizeof(pgt_dstat_row), d_tot, tree, tree_bytes, nullptr), ctx);
+    RowArray<pgt_dstat_row> rows(n_trios * n_win);
+    std::vector<pgt_dstat_total> tot(n_trios);
+    check(pgt_rowbuf_read(ctx, rows.data(), d_rows, n_trios * n_win * sizeof(pgt_dstat_row), nullptr), ctx);
+    check(pgt_rowbuf_read(ctx, tot.data(), d_tot, n_trios * sizeof(pgt_dstat_total), nullptr), ctx);
+    timer.lap("gpu reduce");
+
+    const std::string global_path = std::string(prefix) + ".global";
+    FILE *global = open_out(global_path);
+    size_t t = 0;
+    for (int a = 0; a < K - 1; ++a)
+        for (int b = a + 1; b < K - 1; ++b)
+            for (int c = b + 1; c < K - 1; ++c, ++t) {
+                if (W > 0) {
+                    const std::string path = std::string(prefix) + ".pop" + std::to_string(a + 1) + "_pop" + std::to_string(b + 1) + "_pop" + std::to_string(c + 1) + ".dstat";
+                    FILE *f = open_out(path);
+                    const pgt_dstat_row *r = rows.data() + t * n_win;
+                    write_rows(n_win, longest_name(runs) + 200, [&](size_t i, char *o) -> size_t {  // -skip_missing as dxyWindow.cpp:189
+                        if (!(r[i].n > 0 || !skip_missing)) return 0;
+                        return put_dstat_row(o, runs.name[win[i].label_run], r[i], (uint32_t)(win[i].hi - win[i].lo) - r[i].n);
+                    }, f);
+                    close_out(f, path);
+                }
+                const double den = tot[t].abba + tot[t].baba;
+                const double d = den != 0.0 ? (tot[t].abba - tot[t].baba) / den : 0.0;
+                std::fprintf(global, "%d\t%d\t%d\t%g\t%g\t%g\t%g\t%llu\t%llu\n", a + 1, b + 1, c + 1, d, tot[t].bbaa, tot[t].abba, tot[t].baba,
+                             (unsigned long long)tot[t].neff, (unsigned long long)tot[t].nskip);
+            }
+    close_out(global, global_path);
+    finish(timer);
+}

@@ -1,5 +1,5 @@
-// pops_common.h — the K-file front end the all-pairs hosts (dxyWindowPops, fstWindowPops) and piWindowPops share: the command
-// line (dxyWindow's options, -out PREFIX, 2 ... 8 MAF files; piWindowPops admits one), and from the opened files to the aligned columns and the window
+// pops_common.h — the K-file front end the all-pairs hosts (dxyWindowPops, fstWindowPops), piWindowPops and dstatWindowPops share: the command
+// line (dxyWindow's options, -out PREFIX, 2 ... 8 MAF files; piWindowPops admits one, dstatWindowPops takes 4 ... 7), and from the opened files to the aligned columns and the window
 // table on the device — open, parse on the host or the device, the resident-size refusals, chromosome ids,
 // pgt_align_segments, upload, pgt_sites_align, pgt_gather_dev, the runs of the common sites, the window table.
 // The K-file form of the reference's site synchronisation (dxyWindow.cpp:315-331): the sites (chromosome, position) that
@@ -35,14 +35,14 @@ struct PopsArgs {
     char **paths = nullptr;
     std::map<std::string, uint32_t> chrsize;
 };
-// option/value pairs first; what follows the last pair are the MAF files (min_files ... 8 of them).  help(opt) prints the tool's
+// option/value pairs first; what follows the last pair are the MAF files (min_files ... max_files of them).  help(opt) prints the tool's
 // usage (no argument: exit 0).  own(option, value) -> true when the pair is an option of this tool alone, which it has taken
 // (or refused by die()); a tool without one keeps answering `Unknown command:` for every option that is not dxyWindow's
 struct NoOwnOption {
     bool operator()(const char *, const char *) const { return false; }
 };
 template <class Help, class Own = NoOwnOption>
-inline PopsArgs parse_pops_args(const std::string &tool, int argc, char **argv, Help help, int min_files = 2, Own own = Own{}) {
+inline PopsArgs parse_pops_args(const std::string &tool, int argc, char **argv, Help help, int min_files = 2, Own own = Own{}, int max_files = 8) {
     PopsArgs a;
     if (argc < 2) {
         help(a.opt);
@@ -58,8 +58,8 @@ inline PopsArgs parse_pops_args(const std::string &tool, int argc, char **argv, 
     }
     a.K = argc - i;
     a.paths = argv + i;
-    if (a.K < min_files || a.K > 8)
-        die(tool + ": between " + std::to_string(min_files) + " and 8 MAF files are needed (" + std::to_string(std::max(a.K, 0)) + " given)");
+    if (a.K < min_files || a.K > max_files)
+        die(tool + ": between " + std::to_string(min_files) + " and " + std::to_string(max_files) + " MAF files are needed (" + std::to_string(std::max(a.K, 0)) + " given)");
     if (!a.prefix || !*a.prefix) die("Must supply -out PREFIX");
     check_dxy_options(a.opt);
     if (!a.opt.fixedsite) a.chrsize = read_sizefile(a.opt.sizefile);

@@ -20,7 +20,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import (DXY_ROW_DTYPE, DXY_TOTAL_DTYPE, EXT_ROW_DTYPE, FST_ROW_DTYPE, FST_TOTAL_DTYPE, HET_ROW_DTYPE, PGT_EXT_IHS,
+from ._lib import (DSTAT_ROW_DTYPE, DSTAT_TOTAL_DTYPE, DXY_ROW_DTYPE, DXY_TOTAL_DTYPE, EXT_ROW_DTYPE, FST_ROW_DTYPE, FST_TOTAL_DTYPE, HET_ROW_DTYPE, PGT_EXT_IHS,
                    PGT_EXT_XP_MAX, PGT_EXT_XP_MIN, PGT_STAT_DXY, PGT_STAT_EXT, PGT_STAT_FST, PGT_STAT_HET,
                    SEG_DTYPE, SHARD_DTYPE, WIN_DTYPE, PgtError, check)
 
@@ -262,23 +262,28 @@ class WindowTable:
 @dataclass(frozen=True)
 class _PopsStat:
     name: str          # pgt_<name>_pops_reduce / _reduce_dev / _tree_bytes; <name>_pops_reduce* and <name>_window_pops in messages
-    min_pops: int      # min_pops ... 8 populations
+    min_pops: int      # min_pops ... max_pops populations
     per_pair: bool     # one row table per pair i < j (pair_order), else one per population
     row: np.dtype
     total: np.dtype
+    max_pops: int = 8
+    per_trio: bool = False  # one row table per ingroup trio i < j < k (trio_order); the last population is the outgroup
 
     def tables(self, n_pops: int) -> int:
+        if self.per_trio:
+            return (n_pops - 1) * (n_pops - 2) * (n_pops - 3) // 6
         return n_pops * (n_pops - 1) // 2 if self.per_pair else n_pops
 
     def check_count(self, who: str, freqs, ninds):
-        if len(ninds) != len(freqs) or not self.min_pops <= len(freqs) <= 8:
-            raise PgtError(_lib.PGT_EARG, f"{who}: {self.min_pops} ... 8 populations, one frequency and one count column each")
+        if len(ninds) != len(freqs) or not self.min_pops <= len(freqs) <= self.max_pops:
+            raise PgtError(_lib.PGT_EARG, f"{who}: {self.min_pops} ... {self.max_pops} populations, one frequency and one count column each")
 
 
 _DXY_POPS = _PopsStat("dxy", 2, True, DXY_ROW_DTYPE, DXY_TOTAL_DTYPE)
 _FST_POPS = _PopsStat("fst", 2, True, FST_ROW_DTYPE, FST_TOTAL_DTYPE)
 _PI_POPS = _PopsStat("pi", 1, False, DXY_ROW_DTYPE, DXY_TOTAL_DTYPE)
 _FST_HUDSON_POPS = _PopsStat("fst_hudson", 2, True, FST_ROW_DTYPE, FST_TOTAL_DTYPE)
+_DSTAT_POPS = _PopsStat("dstat", 4, False, DSTAT_ROW_DTYPE, DSTAT_TOTAL_DTYPE, max_pops=7, per_trio=True)
 _FST_ESTIMATORS = {"wc": _FST_POPS, "hudson": _FST_HUDSON_POPS}  # fst_window_pops(estimator=...)
 
 
@@ -415,6 +420,13 @@ class Context:
         columns, one pass: -> (rows[n_pops, n_win], totals[n_pops]) (pgt_pi_pops_reduce).  A row's sum is Σ 2p(1-p) 2n/(2n-1) over
         its counted sites (nInd >= minind); divide by neff or by the window length."""
         return self._pops_reduce(_PI_POPS, pos, freqs, ninds, minind, win)
+
+    def dstat_pops_reduce(self, pos, freqs, ninds, minind, win):
+        """ABBA-BABA rows of ALL trios i<j<k of the first len(freqs) - 1 populations (trio_order) against the LAST one, the
+        outgroup, from 4 ... 7 per-population numpy (freq, nInd) columns, one pass: -> (rows[n_trios, n_win], totals[n_trios])
+        (pgt_dstat_pops_reduce).  A row carries Σbbaa, Σabba, Σbaba over its counted sites, their number n and Patterson's
+        d = (abba - baba) / (abba + baba) for the topology ((i,j),k)."""
+        return self._pops_reduce(_DSTAT_POPS, pos, freqs, ninds, minind, win)
 
     # ---- device-resident columns (torch CUDA tensors) -------------------------------------
     @staticmethod
@@ -771,6 +783,17 @@ class Context:
         honoured (the query strategies of dxy_reduce_dev).  Returns (out, tot, tree).  Asynchronous on `stream`."""
         return self._pops_reduce_dev(_PI_POPS, pos, freqs, ninds, minind, win, out, tot, tree, stream)
 
+    @staticmethod
+    def dstat_pops_tree_bytes(n_pops: int, n_sites: int) -> int:
+        return int(_lib.load().pgt_dstat_pops_tree_bytes(int(n_pops), int(n_sites)))
+
+    def dstat_pops_reduce_dev(self, pos, freqs, ninds, minind, win, out=None, tot=None, tree=None, stream=None):
+        """ABBA-BABA rows of ALL ingroup trios (trio-major, trio_order) against the last population, the outgroup, in one pass
+        over 4 ... 7 populations' own (freq, nInd) columns (pgt_dstat_pops_reduce_dev).  freqs: float64 CUDA tensors, ninds:
+        int32 CUDA tensors.  tot: None = a fresh buffer of n_trios totals is allocated and filled; False = no genome-wide
+        lines.  Returns (out, tot, tree).  Asynchronous on `stream`."""
+        return self._pops_reduce_dev(_DSTAT_POPS, pos, freqs, ninds, minind, win, out, tot, tree, stream)
+
     def extreme_reduce_dev(self, pos, score, mode, cutoff, win, out=None, tree=None, stream=None):
         """ihsWindow / xpehhWindow rows from a device-resident score column (mode: PGT_EXT_*)."""
         import torch
@@ -1056,6 +1079,13 @@ def pair_order(n_pops: int):
     return [(i, j) for i in range(int(n_pops)) for j in range(i + 1, int(n_pops))]
 
 
+def trio_order(n_pops: int):
+    """The ingroup trios (i, j, k), i < j < k < n_pops - 1, in the order dstat_pops_reduce* lays its rows out (the last
+    population is the outgroup): (0,1,2),(0,1,3),..,(0,1,n_pops-2),(0,2,3),.."""
+    g = int(n_pops) - 1
+    return [(i, j, k) for i in range(g) for j in range(i + 1, g) for k in range(j + 1, g)]
+
+
 def _window_pops(st: _PopsStat, chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx):
     """What the *_window_pops functions share: dxy_window's refusals, the population count, host columns, the window table and
     one pass of the statistic's numpy form -> (win, rows[tables, n_win], totals[tables])."""
@@ -1073,10 +1103,11 @@ def _window_pops(st: _PopsStat, chr_ids, pos, freqs, ninds, W, S, minind, fixeds
     return win, rows, tot
 
 
-def _results_by_pair(n_pops, win, rows, tot, skip_missing, counted: str) -> dict:
-    """{(i, j): WindowResult} in pair_order; -skip_missing drops a pair's rows without counted sites (field `counted`)."""
+def _results_by_pair(n_pops, win, rows, tot, skip_missing, counted: str, keys=None) -> dict:
+    """{(i, j): WindowResult} in pair_order (or by `keys`, the tables' own order); -skip_missing drops a pair's rows without
+    counted sites (field `counted`)."""
     res = {}
-    for p, ij in enumerate(pair_order(n_pops)):
+    for p, ij in enumerate(pair_order(n_pops) if keys is None else keys):
         w, r = win, rows[p]
         if skip_missing:
             keep = r[counted] > 0
@@ -1107,6 +1138,17 @@ def fst_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: 
         raise PgtError(_lib.PGT_EARG, f'fst_window_pops: estimator must be "wc" or "hudson", not {estimator!r}')
     win, rows, tot = _window_pops(st, chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx)
     return _results_by_pair(len(freqs), win, rows, tot, skip_missing, "n")
+
+
+def dstat_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: int = 1, fixedsite: int = 0,
+                      chr_len=None, skip_missing: int = 0, ctx: Context | None = None) -> dict:
+    """Windowed ABBA-BABA (Patterson's D) for ALL trios of the first len(freqs) - 1 already synchronised populations against
+    the LAST one, the outgroup (4 ... 7 populations), in one pass: {(i, j, k): WindowResult} in trio_order, with rows of
+    (start, end, mid, n, d, bbaa, abba, baba) and the genome-wide sums as total.  All columns must report the same allele.
+    Window arguments and their errors are those of dxy_window_pops; -skip_missing drops a trio's rows without counted sites
+    from that trio's result only.  The per-site definition is pgt_dstat_pops_reduce_dev's (include/pgtwin.h)."""
+    win, rows, tot = _window_pops(_DSTAT_POPS, chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx)
+    return _results_by_pair(len(freqs), win, rows, tot, skip_missing, "n", keys=trio_order(len(freqs)))
 
 
 def pi_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: int = 1, fixedsite: int = 0,
