@@ -54,7 +54,8 @@ extern "C" {
  * Still 6: pgt_fst_total, pgt_fst_pops_tree_bytes / pgt_fst_pops_reduce_dev / pgt_fst_pops_reduce added (additive as well).
  * Still 6: pgt_pi_pops_tree_bytes / pgt_pi_pops_reduce_dev / pgt_pi_pops_reduce added (additive as well).
  * Still 6: pgt_fst_hudson_pops_tree_bytes / pgt_fst_hudson_pops_reduce_dev / pgt_fst_hudson_pops_reduce added (additive as well).
- * Still 6: pgt_dstat_row, pgt_dstat_total, pgt_dstat_pops_tree_bytes / pgt_dstat_pops_reduce_dev / pgt_dstat_pops_reduce added (additive as well). */
+ * Still 6: pgt_dstat_row, pgt_dstat_total, pgt_dstat_pops_tree_bytes / pgt_dstat_pops_reduce_dev / pgt_dstat_pops_reduce added (additive as well).
+ * Still 6: pgt_dstat_jack, pgt_dstat_jackknife_work_bytes / pgt_dstat_jackknife_dev / pgt_dstat_jackknife added (additive as well). */
 #define PGT_ABI_VERSION 6
 
 enum {
@@ -117,6 +118,12 @@ typedef struct { /* the three sums of one trio over all its counted sites */
     double bbaa, abba, baba;
     uint64_t neff, nskip;
 } pgt_dstat_total;
+
+typedef struct { /* block jackknife of one trio and topology: pgt_dstat_jackknife_dev (48 bytes) */
+    double d, d_jack, se, z; /* D of all used blocks, its jackknife estimate, standard error, d_jack / se */
+    uint64_t n_sites;        /* counted sites of the used blocks */
+    uint32_t n_blocks, pad_; /* used blocks (rows with n > 0) */
+} pgt_dstat_jack;
 
 /* ---- context ------------------------------------------------------------------------- */
 /* device: HIP ordinal, or -1 for the current device.  Fails (NULL, message via
@@ -395,8 +402,9 @@ int pgt_pi_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *f
  * bit, on the populations outside the trio and the outgroup, nor on the other rows of the table.  Sums are added in a fixed
  * order that depends on the site index and the window alone (bitwise reproducible); against an exact evaluation of the lines
  * above they stay within 1e-9 relative + 1e-12.  Parity: none to pin; held to this definition, to an exact-rational fixture
- * (tests/golden/dstat_exact.json) and to a NumPy model (tests/dstat_pops_model.py).  Block-jackknife Z scores, f_d / f_dM and
- * user-chosen trio lists are not computed; the rows of a fixed-site window table are the blocks a jackknife needs.
+ * (tests/golden/dstat_exact.json) and to a NumPy model (tests/dstat_pops_model.py).  f_d / f_dM and user-chosen trio lists are not
+ * computed; block-jackknife standard errors and Z scores come from pgt_dstat_jackknife_dev below, over the rows of a table of
+ * disjoint windows (the blocks).
  * Host-buffer form: columns (host arrays of n_pops HOST pointers), table, rows and the T totals in host memory. */
 size_t pgt_dstat_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites);
 int pgt_dstat_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq,
@@ -406,6 +414,51 @@ int pgt_dstat_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *c
 int pgt_dstat_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq,
                           const int32_t *const *nind, uint32_t n_pops, uint64_t n, int minind,
                           const pgt_win *win, uint64_t n_win, pgt_dstat_row *out, pgt_dstat_total *tot);
+
+/* ---- block-jackknife standard error and Z of Patterson's D, all trios and topologies ----------------------------------- */
+/* The weighted (delete-m_j) block jackknife of Busing, Meijer & van der Leeden (1999) — the one ADMIXTOOLS and ANGSD's
+ * ABBA-BABA use — over the window rows pgt_dstat_pops_reduce_dev wrote.  It has NO counterpart in the reference: the definition
+ * below is the contract.
+ *   rows     DEVICE pointer to the n_trios x n_win trio-major table rows[t * n_win + w], 16-byte aligned.  Every window of the
+ *            table is one block.  The caller guarantees that the windows are DISJOINT (-stepsize >= -winsize); the call cannot
+ *            check that and does not.  Only n, bbaa, abba and baba of a row are read.
+ *   items    trio t has three items u = 3 t + c, one per topology; each takes (x, y) from a row:
+ *                c = 0  ((i,j),k)  x = abba, y = baba
+ *                c = 1  ((i,k),j)  x = bbaa, y = baba
+ *                c = 2  ((j,k),i)  x = bbaa, y = abba       (the three D's of pgt_dstat_row above)
+ *   blocks   block j is USED iff its row has n > 0; m_j = n.  Over the used blocks: g = their number, n = Σ m_j (u64),
+ *            X = Σ x_j, Y = Σ y_j.  A row that is not used is selected away, never added: its sums may be NaN
+ *   per item all in f64, every operation rounded on its own, no contraction:
+ *                ratio(a, b) = (a + b) != 0 ? (a - b) / (a + b) : 0         the row's own convention
+ *                theta       = ratio(X, Y)
+ *                theta_-j    = ratio(X - x_j, Y - y_j)
+ *                h_j         = n / m_j
+ *                theta_J     = g * theta - Σ_j (1 - m_j / n) * theta_-j
+ *                tau_j       = theta + (h_j - 1) * (theta - theta_-j)        = h_j theta - (h_j - 1) theta_-j, well conditioned
+ *                sigma^2     = (1 / g) * Σ_j (tau_j - theta_J)^2 / (h_j - 1)
+ *   out      pgt_dstat_jack per item, item-major: d = theta, d_jack = theta_J, se = sqrt(sigma^2),
+ *            z = se > 0 ? theta_J / se : NaN, n_blocks = g, n_sites = n, pad_ = 0.
+ *            g < 2: d_jack = d, se = z = NaN.  g == 0 (n_win == 0 included): d = d_jack = 0, se = z = NaN.
+ *            NaN or infinite sums in a used row reach that item's outputs and no other item's.
+ *   work     DEVICE workspace of pgt_dstat_jackknife_work_bytes(n_trios, n_win) bytes (0 for n_trios outside 1 ... 20; 256 at
+ *            least otherwise), 16-byte aligned.  Every byte of it that is read is written earlier in the same call.
+ * 1 <= n_trios <= 20; the call is not tied to C(K-1, 3): any subset of a table's trios may be passed (whole trios, contiguous).
+ * Three dependent reductions (the totals; Σ (1 - m_j/n) theta_-j; the variance sum, which needs theta_J — the last two are NOT
+ * merged by expanding the square, which would subtract two large, nearly equal sums) and one closing kernel.  No atomics: a
+ * wave sums a fixed run of consecutive 64-block chunks, leaves one partial per phase (at most 1024 per item), and the partials
+ * are added in an order that is a function of n_win alone.  The outputs are bitwise reproducible, and an item's outputs are a
+ * function, bit for bit, of its own trio's rows alone: not of n_trios, not of the other trios' rows.  Against an exact
+ * evaluation of the lines above d, d_jack and se stay within 1e-9 relative + 1e-12 (tests/dstat_jack_model.py).
+ * Refusals (PGT_EARG, each names its argument; nothing is launched): NULL rows (with n_win > 0), out or work; rows or work not
+ * 16-byte aligned, out not 8-byte aligned; out_bytes below 3 * n_trios * sizeof(pgt_dstat_jack); work_bytes too small;
+ * n_trios out of range.  Asynchronous on `stream`; no allocation and no attribute call: it can be captured into a graph.
+ * pgt_set_profiling / pgt_last_kernel_ms report the call's time as the query time and 0 as the build time.
+ * Host-buffer form: rows and out in host memory; synchronous. */
+size_t pgt_dstat_jackknife_work_bytes(uint32_t n_trios, uint64_t n_win);
+int pgt_dstat_jackknife_dev(pgt_ctx *ctx, const pgt_dstat_row *rows, uint64_t n_win, uint32_t n_trios,
+                            pgt_dstat_jack *out /* 3 * n_trios, item-major u = 3t + c */, size_t out_bytes,
+                            void *work, size_t work_bytes, void *stream);
+int pgt_dstat_jackknife(pgt_ctx *ctx, const pgt_dstat_row *rows, uint64_t n_win, uint32_t n_trios, pgt_dstat_jack *out);
 
 /* ---- the sites common to K files, aligned on the device ------------------------------------------ */
 /* Replaces the two-file synchronisation of dxyWindow.cpp:315-331 (one current line per file; the file that is behind reads

@@ -33,6 +33,8 @@ FST_TOTAL_DTYPE = np.dtype([("asum", "<f8"), ("bsum", "<f8"), ("neff", "<u8"), (
 DSTAT_ROW_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("mid", "<u4"), ("n", "<u4"),
                             ("d", "<f8"), ("bbaa", "<f8"), ("abba", "<f8"), ("baba", "<f8")])
 DSTAT_TOTAL_DTYPE = np.dtype([("bbaa", "<f8"), ("abba", "<f8"), ("baba", "<f8"), ("neff", "<u8"), ("nskip", "<u8")])
+DSTAT_JACK_DTYPE = np.dtype([("d", "<f8"), ("d_jack", "<f8"), ("se", "<f8"), ("z", "<f8"), ("n_sites", "<u8"),
+                             ("n_blocks", "<u4"), ("pad_", "<u4")])  # pgt_dstat_jack: one trio and topology
 EXT_ROW_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("nsites", "<u4"), ("nbig", "<u4"),
                           ("position", "<u4"), ("pad_", "<u4"), ("value", "<f8")])
 SHARD_DTYPE = np.dtype([("win_begin", "<u8"), ("win_end", "<u8"), ("site_lo", "<u8"), ("site_hi", "<u8")])
@@ -42,7 +44,7 @@ assert WIN_DTYPE.itemsize == 32 and FST_ROW_DTYPE.itemsize == 40 and HET_ROW_DTY
 assert EXT_ROW_DTYPE.itemsize == 32
 assert DXY_ROW_DTYPE.itemsize == 24 and DXY_TOTAL_DTYPE.itemsize == 24 and SHARD_DTYPE.itemsize == 32
 assert SEG_DTYPE.itemsize == 16 and FST_TOTAL_DTYPE.itemsize == 32
-assert DSTAT_ROW_DTYPE.itemsize == 48 and DSTAT_TOTAL_DTYPE.itemsize == 40
+assert DSTAT_ROW_DTYPE.itemsize == 48 and DSTAT_TOTAL_DTYPE.itemsize == 40 and DSTAT_JACK_DTYPE.itemsize == 48
 
 # every symbol include/pgtwin.h declares (tests/test_abi.py checks the list against the header)
 SYMBOLS = [
@@ -63,6 +65,7 @@ SYMBOLS = [
     "pgt_pi_pops_tree_bytes", "pgt_pi_pops_reduce_dev", "pgt_pi_pops_reduce",
     "pgt_fst_hudson_pops_tree_bytes", "pgt_fst_hudson_pops_reduce_dev", "pgt_fst_hudson_pops_reduce",
     "pgt_dstat_pops_tree_bytes", "pgt_dstat_pops_reduce_dev", "pgt_dstat_pops_reduce",
+    "pgt_dstat_jackknife_work_bytes", "pgt_dstat_jackknife_dev", "pgt_dstat_jackknife",
 ]
 PGT_TOK_CHR, PGT_TOK_SKIP, PGT_TOK_U32, PGT_TOK_F64, PGT_TOK_I8, PGT_TOK_I32, PGT_TOK_FREQ, PGT_TOK_CHR_PREFIX = range(8)
 
@@ -138,6 +141,10 @@ def load() -> C.CDLL:
         getattr(lib, f"pgt_{stat}_pops_tree_bytes").argtypes = [u32, u64]
         getattr(lib, f"pgt_{stat}_pops_reduce_dev").argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, u64, vp, sz, vp, vp, sz, vp]
         getattr(lib, f"pgt_{stat}_pops_reduce").argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, u64, vp, vp]
+    lib.pgt_dstat_jackknife_work_bytes.restype = sz
+    lib.pgt_dstat_jackknife_work_bytes.argtypes = [u32, u64]
+    lib.pgt_dstat_jackknife_dev.argtypes = [vp, vp, u64, u32, vp, sz, vp, sz, vp]
+    lib.pgt_dstat_jackknife.argtypes = [vp, vp, u64, u32, vp]
     lib.pgt_align_segments.argtypes = [vp, vp, vp, u32, vp, sz, C.POINTER(sz)]
     lib.pgt_align_workspace_bytes.restype = sz
     lib.pgt_align_workspace_bytes.argtypes = [u32, u64]

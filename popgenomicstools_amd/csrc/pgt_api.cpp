@@ -50,6 +50,7 @@ struct pgt_ctx {
     std::string error;
     bool profiling = false;
     bool have_timing = false;
+    bool timing_query_only = false;  // the last profiled call has no build phase (pgt_dstat_jackknife_dev): ev[0] was not recorded
     pgt::Hints hints;  // pgt_set_max_window / pgt_set_window_step (0 = unknown)
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};  // build start, build end, query end
     HostIo io;
@@ -303,6 +304,7 @@ EvSet events_for(pgt_ctx *ctx) {
         e.b1 = ctx->ev[1];
         e.q1 = ctx->ev[2];
         ctx->have_timing = true;
+        ctx->timing_query_only = false;
     }
     return e;
 }
@@ -528,7 +530,9 @@ int pgt_last_kernel_ms(pgt_ctx *ctx, float *build_ms, float *query_ms) {
     if (!ctx || !build_ms || !query_ms) return ctx_fail(ctx, PGT_EARG, "pgt_last_kernel_ms: NULL argument");
     if (!ctx->have_timing) return ctx_fail(ctx, PGT_EARG, "pgt_last_kernel_ms: no profiled call yet");
     if (int rc = hip_check(ctx, hipEventSynchronize(ctx->ev[2]), "hipEventSynchronize")) return rc;
-    if (int rc = hip_check(ctx, hipEventElapsedTime(build_ms, ctx->ev[0], ctx->ev[1]), "hipEventElapsedTime")) return rc;
+    *build_ms = 0.0f;
+    if (!ctx->timing_query_only)
+        if (int rc = hip_check(ctx, hipEventElapsedTime(build_ms, ctx->ev[0], ctx->ev[1]), "hipEventElapsedTime")) return rc;
     return hip_check(ctx, hipEventElapsedTime(query_ms, ctx->ev[1], ctx->ev[2]), "hipEventElapsedTime");
 }
 
@@ -730,6 +734,44 @@ int pgt_dstat_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *c
     const EvSet e = events_for(ctx);
     return launch_dstat_pops(pos, freq, nind, n_pops, n, minind, win, n_win, out, tot, tree, stream, e.b0, e.b1, e.q1, &ctx->error,
                              ctx->hints);
+}
+
+// Block jackknife of the rows above: its own checks (no columns, no window table), the message prefix of both forms
+size_t pgt_dstat_jackknife_work_bytes(uint32_t n_trios, uint64_t n_win) {
+    if (n_trios < 1 || n_trios > kJackMaxTrios) return 0;
+    return jack_work(n_trios, n_win).bytes;
+}
+
+static int jack_check_range(pgt_ctx *ctx, uint32_t n_trios, uint64_t n_win) {
+    if (n_trios < 1 || n_trios > kJackMaxTrios)
+        return ctx_fail(ctx, PGT_EARG, "pgt_dstat_jackknife: n_trios must be 1 ... " + std::to_string(kJackMaxTrios));
+    if (n_win > (UINT64_MAX / sizeof(pgt_dstat_row)) / n_trios) return ctx_fail(ctx, PGT_EARG, "pgt_dstat_jackknife: n_trios * n_win overflows");
+    return PGT_OK;
+}
+
+int pgt_dstat_jackknife_dev(pgt_ctx *ctx, const pgt_dstat_row *rows, uint64_t n_win, uint32_t n_trios, pgt_dstat_jack *out,
+                            size_t out_bytes, void *work, size_t work_bytes, void *stream) {
+    PGT_USE_DEVICE(ctx);
+    if (int rc = jack_check_range(ctx, n_trios, n_win)) return rc;
+    const std::string who = "pgt_dstat_jackknife: ";
+    if (n_win && !rows) return ctx_fail(ctx, PGT_EARG, who + "rows is NULL");
+    if (!out) return ctx_fail(ctx, PGT_EARG, who + "out is NULL");
+    if (!work) return ctx_fail(ctx, PGT_EARG, who + "work is NULL");
+    if (!aligned16(rows)) return ctx_fail(ctx, PGT_EARG, who + "rows is not 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(out) & 7u) return ctx_fail(ctx, PGT_EARG, who + "out is not 8-byte aligned");
+    if (!aligned16(work)) return ctx_fail(ctx, PGT_EARG, who + "work is not 16-byte aligned");
+    if (int rc = room_check(ctx, (who + "out_bytes").c_str(), (uint64_t)n_trios * kJackTopologies, sizeof(pgt_dstat_jack), out_bytes)) return rc;
+    const size_t need = jack_work(n_trios, n_win).bytes;
+    if (work_bytes < need)
+        return ctx_fail(ctx, PGT_EARG, who + "work_bytes too small (" + std::to_string(work_bytes) + " bytes, " + std::to_string(need) + " needed)");
+    void *q0 = nullptr, *q1 = nullptr;
+    if (ctx->profiling) {  // the whole call is the "query"; there is no build
+        q0 = ctx->ev[1];
+        q1 = ctx->ev[2];
+        ctx->have_timing = true;
+        ctx->timing_query_only = true;
+    }
+    return launch_dstat_jackknife(rows, n_win, n_trios, out, work, stream, q0, q1, &ctx->error);
 }
 
 size_t pgt_align_workspace_bytes(uint32_t n_files, uint64_t n_rows_file0) {
@@ -1143,6 +1185,25 @@ int pgt_dstat_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const
                           uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_dstat_row *out, pgt_dstat_total *tot) {
     PGT_USE_DEVICE(ctx);
     return pops_reduce_host(ctx, kDstatPops, pgt_dstat_pops_reduce_dev, pos, freq, nind, n_pops, n, minind, win, n_win, out, tot);
+}
+
+/* block jackknife of a host table of ABBA-BABA rows: rows up, the device form on the cached workspace, 3 n_trios results down */
+int pgt_dstat_jackknife(pgt_ctx *ctx, const pgt_dstat_row *rows, uint64_t n_win, uint32_t n_trios, pgt_dstat_jack *out) {
+    PGT_USE_DEVICE(ctx);
+    if (int rc = jack_check_range(ctx, n_trios, n_win)) return rc;
+    if ((n_win && !rows) || !out) return ctx_fail(ctx, PGT_EARG, "pgt_dstat_jackknife: NULL argument");
+    const size_t row_bytes = (size_t)n_trios * n_win * sizeof(pgt_dstat_row), out_bytes = (size_t)n_trios * kJackTopologies * sizeof(pgt_dstat_jack);
+    const size_t work_bytes = jack_work(n_trios, n_win).bytes;
+    void *drows = nullptr, *dwork = nullptr, *dout = nullptr;
+    if (int rc = workspace(ctx, HostIo::kRows, row_bytes, &drows)) return rc;
+    if (int rc = workspace(ctx, HostIo::kTree, work_bytes, &dwork)) return rc;
+    if (int rc = workspace(ctx, HostIo::kTot, out_bytes, &dout)) return rc;
+    if (row_bytes)
+        if (int rc = hip_check(ctx, hipMemcpy(drows, rows, row_bytes, hipMemcpyHostToDevice), "upload rows")) return rc;
+    if (int rc = pgt_dstat_jackknife_dev(ctx, static_cast<const pgt_dstat_row *>(drows), n_win, n_trios, static_cast<pgt_dstat_jack *>(dout),
+                                         out_bytes, dwork, work_bytes, nullptr)) return rc;
+    if (int rc = hip_check(ctx, hipStreamSynchronize(nullptr), "kernels")) return rc;
+    return hip_check(ctx, hipMemcpy(out, dout, out_bytes, hipMemcpyDeviceToHost), "download jackknife");
 }
 
 /* ---------------- window tables built on the device ---------------- */

@@ -1,0 +1,282 @@
+// pgt_dstat_jack_kernels.hip — the weighted (delete-m_j) block jackknife of Busing, Meijer & van der Leeden (1999) for a RATIO OF
+// TWO BLOCK SUMS with block weights, fed here with the window rows of pgt_dstat_pops_reduce_dev: standard error and Z of
+// Patterson's D for every trio and each of its three topologies.
+//
+// Spec (include/pgtwin.h, pgt_dstat_jackknife_dev).  rows[t * n_win + w] is trio t's row of window w; every window is a block,
+// used iff its n > 0, with weight m_j = n.  Item u = 3 t + c takes (x, y) = (abba, baba) / (bbaa, baba) / (bbaa, abba) for
+// c = 0 / 1 / 2.  Over the used blocks g = their number, n = Σ m_j, X = Σ x_j, Y = Σ y_j, and with
+// ratio(a, b) = (a + b) != 0 ? (a - b) / (a + b) : 0:
+//     theta    = ratio(X, Y)                         theta_-j = ratio(X - x_j, Y - y_j)               h_j = n / m_j
+//     theta_J  = g theta - Σ_j (1 - m_j / n) theta_-j
+//     tau_j    = theta + (h_j - 1) (theta - theta_-j)
+//     sigma^2  = (1 / g) Σ_j (tau_j - theta_J)^2 / (h_j - 1)
+// Every operation is one __d*_rn intrinsic (nothing is contracted); a block that is not used is selected away, never added.
+//
+// Three dependent reductions over the rows and one closing kernel, all on the plan of jack_plan(n_win) (pgt_internal.h):
+//   phase 1  jack_totals_kernel   per wave Σbbaa, Σabba, Σbaba, Σn, g of its chunks                 -> 5 words per wave
+//   phase 2  jack_drop_kernel     re-adds phase 1's partials of its trio (theta), then per topology
+//                                 Σ (1 - m_j / n) theta_-j over its chunks                          -> 3 doubles per wave
+//   phase 3  jack_var_kernel      re-adds phases 1 and 2 (theta_J), then per topology
+//                                 Σ (tau_j - theta_J)^2 / (h_j - 1) over its chunks                 -> 3 doubles per wave
+//   close    jack_close_kernel    one wave per item: re-adds all three, writes pgt_dstat_jack
+// The grid is (ceil(n_partials / 4), n_trios) workgroups of 4 waves: blockIdx.y is the trio, wave p of it walks the chunks
+// [p * chunks_per_wave, (p + 1) * chunks_per_wave) — 64 consecutive 48-byte rows each, one row per lane, all three topologies
+// from that one read.  A lane adds its rows in chunk order, the wave closes with the fixed butterfly of wave_sum, and partials
+// are re-added by readd(): lane l adds partials l, l + 64, .. in turn, then the same butterfly.  No atomics; every order is a
+// function of n_win alone, and a wave touches its own trio's rows and partials only: an item's bits do not depend on n_trios
+// or on the other trios.  Phases 2 and 3 are not merged by expanding the square (that subtracts two large, nearly equal sums).
+// With at most 1024 partials per item the re-adding is 16 loads per lane from L2: no finishing launch between the phases.
+// Every partial a later phase reads was written by the phase before it in the same call (all n_partials waves of a trio
+// store theirs, a wave without a used block stores zeros).
+#include <hip/hip_runtime.h>
+
+#include "pgt_device.h"
+#include "pgt_internal.h"
+#include "pgt_pops_common.h"
+
+namespace pgt {
+namespace {
+
+using namespace dev;
+
+struct JackArgs {
+    const char *rows;          // n_trios x n_win pgt_dstat_row, trio-major
+    uint64_t n_win;
+    uint64_t chunks;           // jack_plan(n_win)
+    uint64_t chunks_per_wave;
+    uint32_t n_partials;
+    uint32_t n_trios;
+    uint64_t *totals;          // [trio][5][n_partials]: Σbbaa, Σabba, Σbaba as f64 bits, Σn, g
+    double *drop;              // [trio][3][n_partials]
+    double *var;               // [trio][3][n_partials]
+};
+
+__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
+#pragma unroll
+    for (int m = 1; m < kWave; m <<= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, m, kWave);
+    return v;
+}
+
+__device__ __forceinline__ double ratio(double a, double b) {
+    const double den = __dadd_rn(a, b);
+    return den != 0.0 ? __ddiv_rn(__dsub_rn(a, b), den) : 0.0;
+}
+
+// (x, y) of topology c from a row's, or the totals', three sums {bbaa, abba, baba}
+__device__ __forceinline__ double topo_x(int c, double bbaa, double abba) { return c == 0 ? abba : bbaa; }
+__device__ __forceinline__ double topo_y(int c, double abba, double baba) { return c == 2 ? abba : baba; }
+
+// Σ of n_partials doubles in index order per lane (l, l + 64, ..), then the butterfly: the same bits in every lane of every wave
+__device__ __forceinline__ double readd(const double *p, uint32_t n_partials, int lane) {
+    double a = 0.0;
+    for (uint32_t i = (uint32_t)lane; i < n_partials; i += kWave) a = __dadd_rn(a, p[i]);
+    return dev::wave_sum(a);
+}
+__device__ __forceinline__ uint64_t readd(const uint64_t *p, uint32_t n_partials, int lane) {
+    uint64_t a = 0;
+    for (uint32_t i = (uint32_t)lane; i < n_partials; i += kWave) a += p[i];
+    return wave_sum(a);
+}
+
+struct Totals {
+    double s[3];  // Σbbaa, Σabba, Σbaba over the used blocks
+    double n;     // Σ m_j as f64 (exact below 2^53 sites)
+    uint64_t n_sites;
+    uint32_t g;
+};
+__device__ __forceinline__ Totals read_totals(const JackArgs &a, uint32_t trio, int lane) {
+    const uint64_t *base = a.totals + (uint64_t)trio * kJackTotalWords * a.n_partials;
+    Totals t;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) t.s[k] = readd(reinterpret_cast<const double *>(base + (uint64_t)k * a.n_partials), a.n_partials, lane);
+    t.n_sites = readd(base + 3ull * a.n_partials, a.n_partials, lane);
+    t.g = (uint32_t)readd(base + 4ull * a.n_partials, a.n_partials, lane);
+    t.n = (double)t.n_sites;
+    return t;
+}
+
+// the wave's rows, one per lane and chunk, in chunk order: f(used, m_j, bbaa, abba, baba); a lane beyond the table sees an
+// unused block of zeros.  Rows are read by three plain 16-byte vector loads; start / end / mid / d are not looked at.
+template <class F>
+__device__ __forceinline__ void for_rows(const JackArgs &a, uint32_t trio, uint32_t p, int lane, F f) {
+    const char *rows_t = a.rows + (uint64_t)trio * a.n_win * sizeof(pgt_dstat_row);
+    const uint64_t c0 = (uint64_t)p * a.chunks_per_wave;
+    const uint64_t c1 = c0 + a.chunks_per_wave < a.chunks ? c0 + a.chunks_per_wave : a.chunks;
+#pragma unroll 2
+    for (uint64_t c = c0; c < c1; ++c) {
+        const uint64_t j = c * kJackChunk + (uint64_t)lane;
+        uint32_t m = 0;
+        double bbaa = 0.0, abba = 0.0, baba = 0.0;
+        if (j < a.n_win) {
+            const char *r = rows_t + j * sizeof(pgt_dstat_row);
+            const uint4 head = *reinterpret_cast<const uint4 *>(r);           // start, end, mid, n
+            const double2 v0 = *reinterpret_cast<const double2 *>(r + 16);    // d, bbaa
+            const double2 v1 = *reinterpret_cast<const double2 *>(r + 32);    // abba, baba
+            m = head.w;
+            bbaa = v0.y;
+            abba = v1.x;
+            baba = v1.y;
+        }
+        f(m > 0, m, bbaa, abba, baba);
+    }
+}
+static_assert(sizeof(pgt_dstat_row) == 48 && sizeof(pgt_dstat_jack) == 48, "the row layout the loads above assume");
+
+// wave p of trio blockIdx.y; -1: a wave that pads the last workgroup (it returns: no barrier is ever used)
+__device__ __forceinline__ int64_t my_partial(const JackArgs &a) {
+    const uint32_t p = blockIdx.x * (blockDim.x >> 6) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    return p < a.n_partials ? (int64_t)p : -1;
+}
+
+// ---- phase 1: the totals -----------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void jack_totals_kernel(JackArgs a) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const uint32_t trio = blockIdx.y;
+    const int64_t pp = my_partial(a);
+    if (pp < 0) return;
+    const uint32_t p = (uint32_t)pp;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    uint64_t n = 0, g = 0;
+    for_rows(a, trio, p, lane, [&](bool used, uint32_t m, double bbaa, double abba, double baba) {
+        s0 = __dadd_rn(s0, used ? bbaa : 0.0);
+        s1 = __dadd_rn(s1, used ? abba : 0.0);
+        s2 = __dadd_rn(s2, used ? baba : 0.0);
+        n += m;  // an unused block has m == 0
+        g += used ? 1u : 0u;
+    });
+    s0 = dev::wave_sum(s0);
+    s1 = dev::wave_sum(s1);
+    s2 = dev::wave_sum(s2);
+    n = wave_sum(n);
+    g = wave_sum(g);
+    if (lane == 0) {
+        uint64_t *base = a.totals + (uint64_t)trio * kJackTotalWords * a.n_partials + p;
+        reinterpret_cast<double *>(base)[0] = s0;
+        reinterpret_cast<double *>(base)[(uint64_t)a.n_partials] = s1;
+        reinterpret_cast<double *>(base)[2ull * a.n_partials] = s2;
+        base[3ull * a.n_partials] = n;
+        base[4ull * a.n_partials] = g;
+    }
+}
+
+// ---- phase 2: Σ (1 - m_j / n) theta_-j ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void jack_drop_kernel(JackArgs a) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const uint32_t trio = blockIdx.y;
+    const int64_t pp = my_partial(a);
+    if (pp < 0) return;
+    const uint32_t p = (uint32_t)pp;
+    const Totals t = read_totals(a, trio, lane);
+    double acc[kJackTopologies] = {0.0, 0.0, 0.0};
+    for_rows(a, trio, p, lane, [&](bool used, uint32_t m, double bbaa, double abba, double baba) {
+        const double w = __dsub_rn(1.0, __ddiv_rn((double)m, t.n));
+#pragma unroll
+        for (int c = 0; c < kJackTopologies; ++c) {
+            const double th = ratio(__dsub_rn(topo_x(c, t.s[0], t.s[1]), topo_x(c, bbaa, abba)),
+                                    __dsub_rn(topo_y(c, t.s[1], t.s[2]), topo_y(c, abba, baba)));
+            acc[c] = __dadd_rn(acc[c], used ? __dmul_rn(w, th) : 0.0);
+        }
+    });
+#pragma unroll
+    for (int c = 0; c < kJackTopologies; ++c) {
+        const double v = dev::wave_sum(acc[c]);
+        if (lane == 0) a.drop[((uint64_t)trio * kJackTopologies + c) * a.n_partials + p] = v;
+    }
+}
+
+// theta and theta_J of topology c from the re-added partials (the same bits wherever it is called)
+__device__ __forceinline__ void estimates(const JackArgs &a, const Totals &t, uint32_t trio, int c, int lane, double *theta, double *theta_j) {
+    *theta = ratio(topo_x(c, t.s[0], t.s[1]), topo_y(c, t.s[1], t.s[2]));
+    const double drop = readd(a.drop + ((uint64_t)trio * kJackTopologies + c) * a.n_partials, a.n_partials, lane);
+    *theta_j = __dsub_rn(__dmul_rn((double)t.g, *theta), drop);
+}
+
+// ---- phase 3: Σ (tau_j - theta_J)^2 / (h_j - 1) -----------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void jack_var_kernel(JackArgs a) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const uint32_t trio = blockIdx.y;
+    const int64_t pp = my_partial(a);
+    if (pp < 0) return;
+    const uint32_t p = (uint32_t)pp;
+    const Totals t = read_totals(a, trio, lane);
+    double theta[kJackTopologies], theta_j[kJackTopologies], acc[kJackTopologies] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int c = 0; c < kJackTopologies; ++c) estimates(a, t, trio, c, lane, &theta[c], &theta_j[c]);
+    for_rows(a, trio, p, lane, [&](bool used, uint32_t m, double bbaa, double abba, double baba) {
+        const double hm1 = __dsub_rn(__ddiv_rn(t.n, (double)m), 1.0);  // an unused block: inf, selected away below
+#pragma unroll
+        for (int c = 0; c < kJackTopologies; ++c) {
+            const double th = ratio(__dsub_rn(topo_x(c, t.s[0], t.s[1]), topo_x(c, bbaa, abba)),
+                                    __dsub_rn(topo_y(c, t.s[1], t.s[2]), topo_y(c, abba, baba)));
+            const double tau = __dadd_rn(theta[c], __dmul_rn(hm1, __dsub_rn(theta[c], th)));
+            const double dv = __dsub_rn(tau, theta_j[c]);
+            acc[c] = __dadd_rn(acc[c], used ? __ddiv_rn(__dmul_rn(dv, dv), hm1) : 0.0);
+        }
+    });
+#pragma unroll
+    for (int c = 0; c < kJackTopologies; ++c) {
+        const double v = dev::wave_sum(acc[c]);
+        if (lane == 0) a.var[((uint64_t)trio * kJackTopologies + c) * a.n_partials + p] = v;
+    }
+}
+
+// ---- close: one wave per item ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void jack_close_kernel(JackArgs a, pgt_dstat_jack *__restrict__ out) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const uint32_t u = blockIdx.x * (blockDim.x >> 6) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (u >= a.n_trios * kJackTopologies) return;
+    const uint32_t trio = u / kJackTopologies;
+    const int c = (int)(u % kJackTopologies);
+    const Totals t = read_totals(a, trio, lane);  // without a partial (n_win == 0): zeros
+    double theta, theta_j;
+    estimates(a, t, trio, c, lane, &theta, &theta_j);
+    const double vs = readd(a.var + ((uint64_t)trio * kJackTopologies + c) * a.n_partials, a.n_partials, lane);
+    pgt_dstat_jack r;
+    r.d = theta;
+    r.n_sites = t.n_sites;
+    r.n_blocks = t.g;
+    r.pad_ = 0;
+    if (t.g >= 2) {
+        r.d_jack = theta_j;
+        r.se = __dsqrt_rn(__ddiv_rn(vs, (double)t.g));
+        r.z = r.se > 0.0 ? __ddiv_rn(theta_j, r.se) : __longlong_as_double(0x7FF8000000000000ll);
+    } else {
+        r.d_jack = theta;
+        r.se = r.z = __longlong_as_double(0x7FF8000000000000ll);
+    }
+    if (lane == 0) out[u] = r;
+}
+
+}  // namespace
+
+int launch_dstat_jackknife(const pgt_dstat_row *rows, uint64_t n_win, uint32_t n_trios, pgt_dstat_jack *out, void *work,
+                           void *stream, void *ev_query0, void *ev_query1, std::string *err) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const JackPlan plan = jack_plan(n_win);
+    const JackWork w = jack_work(n_trios, n_win);
+    JackArgs a{};
+    a.rows = reinterpret_cast<const char *>(rows);
+    a.n_win = n_win;
+    a.chunks = plan.chunks;
+    a.chunks_per_wave = plan.chunks_per_wave;
+    a.n_partials = plan.n_partials;
+    a.n_trios = n_trios;
+    a.totals = reinterpret_cast<uint64_t *>(static_cast<char *>(work) + w.totals);
+    a.drop = reinterpret_cast<double *>(static_cast<char *>(work) + w.drop);
+    a.var = reinterpret_cast<double *>(static_cast<char *>(work) + w.var);
+    if (int rc = record_event(ev_query0, s, err)) return rc;
+    if (plan.n_partials > 0) {
+        const dim3 grid((plan.n_partials + 3) / 4, n_trios);
+        hipLaunchKernelGGL(jack_totals_kernel, grid, dim3(256), 0, s, a);
+        if (int rc = hip_fail(hipGetLastError(), "jack_totals_kernel", err)) return rc;
+        hipLaunchKernelGGL(jack_drop_kernel, grid, dim3(256), 0, s, a);
+        if (int rc = hip_fail(hipGetLastError(), "jack_drop_kernel", err)) return rc;
+        hipLaunchKernelGGL(jack_var_kernel, grid, dim3(256), 0, s, a);
+        if (int rc = hip_fail(hipGetLastError(), "jack_var_kernel", err)) return rc;
+    }
+    hipLaunchKernelGGL(jack_close_kernel, dim3((n_trios * kJackTopologies + 3) / 4), dim3(256), 0, s, a, out);
+    if (int rc = hip_fail(hipGetLastError(), "jack_close_kernel", err)) return rc;
+    return record_event(ev_query1, s, err);
+}
+
+}  // namespace pgt

@@ -210,6 +210,52 @@ inline DstatPopsTree dstat_pops_tree_view(const TreeLayout &t, int n_trios, void
     return pops_tree_view<DstatPopsTree>(t, n_trios, 24, tree, levels);
 }
 
+// ---- delete-m_j block jackknife of a ratio of two block sums (pgt_dstat_jack_kernels.hip) -----------------------------------
+// The rows of one trio are cut into chunks of kJackChunk consecutive blocks (one row per lane); a trio gets n_partials waves,
+// wave p takes the chunks [p * chunks_per_wave, (p + 1) * chunks_per_wave) and leaves one partial per phase.  The plan is a
+// function of n_win alone: the order of every addition is, and so are an item's bits whatever else the call holds.
+constexpr uint32_t kJackChunk = 64;          // blocks a wave reads at once: 64 rows of 48 bytes, 3 KiB contiguous
+constexpr uint32_t kJackMaxPartials = 1024;  // waves, and partials of each phase, per trio at most
+constexpr uint32_t kJackMaxTrios = 20;       // C(6, 3): what pgt_dstat_pops_reduce_dev can write
+constexpr int kJackTotalWords = 5;           // phase 1 per wave: Σbbaa, Σabba, Σbaba (f64), Σn (u64), used blocks (u64)
+constexpr int kJackTopologies = 3;           // phases 2 and 3 per wave: one f64 per topology
+struct JackPlan {
+    uint64_t chunks = 0;           // ceil(n_win / kJackChunk)
+    uint64_t chunks_per_wave = 0;  // ceil(chunks / kJackMaxPartials)
+    uint32_t n_partials = 0;       // ceil(chunks / chunks_per_wave) <= kJackMaxPartials; 0 without a block
+};
+inline JackPlan jack_plan(uint64_t n_win) {
+    JackPlan p;
+    p.chunks = n_win / kJackChunk + (n_win % kJackChunk ? 1 : 0);
+    if (p.chunks == 0) return p;
+    p.chunks_per_wave = (p.chunks + kJackMaxPartials - 1) / kJackMaxPartials;
+    p.n_partials = (uint32_t)((p.chunks + p.chunks_per_wave - 1) / p.chunks_per_wave);
+    return p;
+}
+// The workspace, in 8-byte words: [trio][word k < 5][partial] of phase 1, then [trio][topology][partial] of phase 2 and the same
+// of phase 3.  Its SIZE is that of min(chunks, kJackMaxPartials) partials — what n_partials never exceeds, and monotone in n_win
+// where n_partials itself is not (1025 chunks make 513 waves of two) — and 256 bytes at least (a call without blocks reads and
+// writes none of it).
+struct JackWork {
+    size_t totals = 0, drop = 0, var = 0;  // byte offsets of the three phases' partials
+    size_t bytes = 0;
+};
+inline JackWork jack_work(uint32_t n_trios, uint64_t n_win) {
+    JackWork w;
+    const size_t per = (size_t)n_trios * jack_plan(n_win).n_partials * 8;
+    w.totals = 0;
+    w.drop = w.totals + per * kJackTotalWords;
+    w.var = w.drop + per * kJackTopologies;
+    const JackPlan p = jack_plan(n_win);
+    const size_t cap = (size_t)(p.chunks < kJackMaxPartials ? p.chunks : kJackMaxPartials);
+    w.bytes = (((size_t)n_trios * cap * 8 * (kJackTotalWords + 2 * kJackTopologies) + 255) / 256) * 256;
+    if (w.bytes == 0) w.bytes = 256;
+    return w;
+}
+// 1 <= n_trios <= kJackMaxTrios and every pointer checked by the caller; ev_*: hipEvent_t as void* or NULL
+int launch_dstat_jackknife(const pgt_dstat_row *rows, uint64_t n_win, uint32_t n_trios, pgt_dstat_jack *out, void *work,
+                           void *stream, void *ev_query0, void *ev_query1, std::string *err);
+
 // Speed-only hints of a context (pgt_set_max_window, pgt_set_window_step); 0 = unknown.
 struct Hints {
     uint64_t max_window = 0;   // longest window in sites: tree levels with larger nodes are not built

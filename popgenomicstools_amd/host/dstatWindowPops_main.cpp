@@ -13,6 +13,9 @@
 // D = (ABBA - BABA) / (ABBA + BABA).
 // Trio (i, j, k) -> PREFIX.pop<i+1>_pop<j+1>_pop<k+1>.dstat (`chr start end mid D BBAA ABBA BABA neff nskip`); the
 // genome-wide lines -> PREFIX.global (`i+1 j+1 k+1 D BBAA ABBA BABA neff nskip`).  stdout stays empty.
+// -jackknife 1 (disjoint windows only: -stepsize equal to -winsize): one pgt_dstat_jackknife_dev call on the device rows gives
+// the delete-m_j block jackknife of every trio and topology, the run's windows being the blocks -> PREFIX.jackknife
+// (`P1 P2 P3 D D_jack SE Z nblocks nsites`, D that of ((P1,P2),P3)).  Every other file is the same with and without it.
 //
 // Limits: one GPU (the first of PGT_DEVICES); no passes mode — the K parsed files and the aligned columns must fit the
 // card (and PGT_MAX_RESIDENT_SITES, where set) or the run is refused; PGT_DXY_SYNC=reference is not offered.
@@ -29,6 +32,7 @@ static void help(const DxyOptions &o) {
                 "%-14s%-8s(1) Use fixed number of sites from MAF input for each window (window sizes may vary) or (0) constant window size [%d]\n"
                 "%-14s%-8sTwo-column TSV file with each row having (1) chromsome name (2) chromosome size in base pairs\n"
                 "%-14s%-8sDo not print windows with zero effective sites if INT=1 [%d]\n"
+                "%-14s%-8s(1) Write PREFIX.jackknife: block-jackknife standard error and Z score of D for every trio and topology [0]\n"
                 "\nNotes:\n"
                 "* The LAST MAF file is the outgroup; the K-1 files before it are the ingroup populations (K between 4 and 7 files)\n"
                 "* Every trio i < j < k of ingroup populations is analyzed as ((i,j),k) against the outgroup: C(K-1,3) trios\n"
@@ -40,7 +44,10 @@ static void help(const DxyOptions &o) {
                 "* The other two topologies of a trio follow from the same three sums: ((i,k),j): D = (BBAA - BABA)/(BBAA + BABA);\n"
                 "  ((j,k),i): D = (BBAA - ABBA)/(BBAA + ABBA)\n"
                 "* A site counts for a trio when its three populations and the outgroup each have at least -minind individuals with data\n"
-                "* No Z scores are computed: the window rows of a -fixedsite 1 run are the blocks a block-jackknife needs\n"
+                "* -jackknife 1: weighted (delete-m) block jackknife of D (Busing et al. 1999; as ADMIXTOOLS and ANGSD). The blocks are the\n"
+                "  run's windows, weighted by their number of analyzed sites; windows without an analyzed site are left out.\n"
+                "  The windows must not overlap: -winsize > 0 and -stepsize equal to -winsize. -fixedsite 1 windows hold the same number\n"
+                "  of sites and so give blocks of (nearly) equal weight; -skip_missing does not change the blocks\n"
                 "* -sizefile is REQUIRED(!) with -fixedsite 0 (the default)\n"
                 "* All input MAF files need to have the same chromosomes in the same order\n"
                 "* Assumes SNPs are biallelic\n"
@@ -52,9 +59,12 @@ static void help(const DxyOptions &o) {
                 "(1) chromosome\n(2) Window start\n(3) Window end\n(4) Window midpoint\n(5) D of ((i,j),k)\n(6) BBAA (sum)\n(7) ABBA (sum)\n(8) BABA (sum)\n"
                 "(9) number sites in MAF input that were analyzed\n"
                 "(10) number of sites in MAF input that were skipped due to too few individuals\n"
-                "PREFIX.global, one line per trio:\n(1) i\n(2) j\n(3) k\n(4) D\n(5) BBAA\n(6) ABBA\n(7) BABA\n(8) number of sites analyzed\n(9) number of sites skipped\n\n",
+                "PREFIX.global, one line per trio:\n(1) i\n(2) j\n(3) k\n(4) D\n(5) BBAA\n(6) ABBA\n(7) BABA\n(8) number of sites analyzed\n(9) number of sites skipped\n"
+                "PREFIX.jackknife (with -jackknife 1), three lines per trio i < j < k: ((i,j),k), ((i,k),j), ((j,k),i):\n"
+                "(1) P1\n(2) P2\n(3) P3: the topology ((P1,P2),P3)\n(4) D over all blocks\n(5) jackknife estimate of D\n(6) standard error\n"
+                "(7) Z = (5) / (6) (nan with fewer than two blocks or a standard error of zero)\n(8) number of blocks\n(9) number of sites in the blocks\n\n",
                 "-out", "STRING", "-winsize", "INT", o.W, "-stepsize", "INT", o.S, "-minind", "INT", o.minind, "-fixedsite", "INT", o.fixedsite,
-                "-sizefile", "FILE", "-skip_missing", "INT", o.skip_missing);
+                "-sizefile", "FILE", "-skip_missing", "INT", o.skip_missing, "-jackknife", "INT");
 }
 
 // chr start end mid D BBAA ABBA BABA neff nskip
@@ -71,7 +81,22 @@ static size_t put_dstat_row(char *o, const std::string &chr, const pgt_dstat_row
 
 int main(int argc, char **argv) {
     const std::string tool = "dstatWindowPops";
-    const PopsArgs args = parse_pops_args(tool, argc, argv, help, 4, NoOwnOption{}, 7);
+    int jackknife = 0;
+    const PopsArgs args = parse_pops_args(tool, argc, argv, help, 4, [&](const char *o, const char *v) {
+        if (std::strcmp(o, "-jackknife")) return false;
+        if (std::strcmp(v, "0") && std::strcmp(v, "1")) die(std::string("-jackknife must be 0 or 1 (given: ") + v + ")");
+        jackknife = v[0] == '1';
+        if (!jackknife) return true;
+        // refused here, while the options are read and before any file is opened: the blocks are the run's windows, which
+        // must exist and be disjoint (the option pairs are walked as parse_pops_args walks them; the last value counts)
+        DxyOptions w;
+        for (int i = 1; i + 1 < argc && argv[i][0] == '-' && argv[i][1] != '\0'; i += 2)
+            if (!std::strcmp(argv[i], "-winsize") || !std::strcmp(argv[i], "-stepsize")) dxy_option(w, argv[i], argv[i + 1]);
+        if (w.W == 0) die("-jackknife 1 needs windows as its blocks: -winsize must be > 0");
+        if (w.S < w.W)
+            die("-jackknife 1 needs windows that do not overlap: -stepsize (" + std::to_string(w.S) + ") must not be below -winsize (" + std::to_string(w.W) + ")");
+        return true;
+    }, 7);
     const int K = args.K;
     const char *prefix = args.prefix;
     const uint32_t W = args.opt.W;
@@ -95,6 +120,16 @@ int main(int argc, char **argv) {
     std::vector<pgt_dstat_total> tot(n_trios);
     check(pgt_rowbuf_read(ctx, rows.data(), d_rows, n_trios * n_win * sizeof(pgt_dstat_row), nullptr), ctx);
     check(pgt_rowbuf_read(ctx, tot.data(), d_tot, n_trios * sizeof(pgt_dstat_total), nullptr), ctx);
+    std::vector<pgt_dstat_jack> jack;
+    if (jackknife) {  // the rows are still on the device: every window of the table is a block
+        const size_t work_bytes = pgt_dstat_jackknife_work_bytes((uint32_t)n_trios, n_win);
+        void *work = nullptr;
+        check(pgt_dev_alloc(ctx, work_bytes, &work), ctx);
+        pgt_dstat_jack *d_jack = pops_dev_alloc<pgt_dstat_jack>(ctx, 3 * n_trios);
+        check(pgt_dstat_jackknife_dev(ctx, d_rows, n_win, (uint32_t)n_trios, d_jack, 3 * n_trios * sizeof(pgt_dstat_jack), work, work_bytes, nullptr), ctx);
+        jack.resize(3 * n_trios);
+        check(pgt_rowbuf_read(ctx, jack.data(), d_jack, 3 * n_trios * sizeof(pgt_dstat_jack), nullptr), ctx);
+    }
     timer.lap("gpu reduce");
 
     const std::string global_path = std::string(prefix) + ".global";
@@ -119,5 +154,22 @@ int main(int argc, char **argv) {
                              (unsigned long long)tot[t].neff, (unsigned long long)tot[t].nskip);
             }
     close_out(global, global_path);
+    if (jackknife) {  // P1 P2 P3 D D_jack SE Z nblocks nsites: trio order, then ((i,j),k), ((i,k),j), ((j,k),i)
+        const std::string path = std::string(prefix) + ".jackknife";
+        FILE *f = open_out(path);
+        t = 0;
+        for (int a = 0; a < K - 1; ++a)
+            for (int b = a + 1; b < K - 1; ++b)
+                for (int c = b + 1; c < K - 1; ++c, ++t) {
+                    const int topo[3][3] = {{a, b, c}, {a, c, b}, {b, c, a}};
+                    for (int u = 0; u < 3; ++u) {
+                        const pgt_dstat_jack &r = jack[3 * t + (size_t)u];
+                        auto g6 = [](double v) { char b_[64]; if (v != v) return std::string("nan"); std::snprintf(b_, sizeof b_, "%g", v); return std::string(b_); };
+                        std::fprintf(f, "%d\t%d\t%d\t%s\t%s\t%s\t%s\t%u\t%llu\n", topo[u][0] + 1, topo[u][1] + 1, topo[u][2] + 1, g6(r.d).c_str(),
+                                     g6(r.d_jack).c_str(), g6(r.se).c_str(), g6(r.z).c_str(), r.n_blocks, (unsigned long long)r.n_sites);
+                    }
+                }
+        close_out(f, path);
+    }
     finish(timer);
 }

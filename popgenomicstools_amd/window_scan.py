@@ -20,7 +20,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import (DSTAT_ROW_DTYPE, DSTAT_TOTAL_DTYPE, DXY_ROW_DTYPE, DXY_TOTAL_DTYPE, EXT_ROW_DTYPE, FST_ROW_DTYPE, FST_TOTAL_DTYPE, HET_ROW_DTYPE, PGT_EXT_IHS,
+from ._lib import (DSTAT_JACK_DTYPE, DSTAT_ROW_DTYPE, DSTAT_TOTAL_DTYPE, DXY_ROW_DTYPE, DXY_TOTAL_DTYPE, EXT_ROW_DTYPE, FST_ROW_DTYPE, FST_TOTAL_DTYPE, HET_ROW_DTYPE, PGT_EXT_IHS,
                    PGT_EXT_XP_MAX, PGT_EXT_XP_MIN, PGT_STAT_DXY, PGT_STAT_EXT, PGT_STAT_FST, PGT_STAT_HET,
                    SEG_DTYPE, SHARD_DTYPE, WIN_DTYPE, PgtError, check)
 
@@ -428,6 +428,18 @@ class Context:
         d = (abba - baba) / (abba + baba) for the topology ((i,j),k)."""
         return self._pops_reduce(_DSTAT_POPS, pos, freqs, ninds, minind, win)
 
+    def dstat_jackknife(self, rows) -> np.ndarray:
+        """Block-jackknife D, standard error and Z of every trio and topology from a [n_trios, n_win] numpy table of
+        DSTAT_ROW_DTYPE rows (what dstat_pops_reduce returns) over DISJOINT windows: every window is a block, used when its
+        n > 0 and weighted by it (pgt_dstat_jackknife) -> [n_trios, 3] DSTAT_JACK_DTYPE, the topologies in topology_order."""
+        rows = np.ascontiguousarray(rows, dtype=DSTAT_ROW_DTYPE)
+        if rows.ndim != 2:
+            raise PgtError(_lib.PGT_EARG, "dstat_jackknife: rows must be a [n_trios, n_win] table")
+        n_trios, n_win = rows.shape
+        out = np.zeros((n_trios, 3), dtype=DSTAT_JACK_DTYPE)
+        self._check(self._lib.pgt_dstat_jackknife(self._ctx, rows.ctypes.data if rows.size else None, n_win, n_trios, out.ctypes.data))
+        return out
+
     # ---- device-resident columns (torch CUDA tensors) -------------------------------------
     @staticmethod
     def _stream(stream):
@@ -794,6 +806,32 @@ class Context:
         lines.  Returns (out, tot, tree).  Asynchronous on `stream`."""
         return self._pops_reduce_dev(_DSTAT_POPS, pos, freqs, ninds, minind, win, out, tot, tree, stream)
 
+    @staticmethod
+    def dstat_jackknife_work_bytes(n_trios: int, n_win: int) -> int:
+        return int(_lib.load().pgt_dstat_jackknife_work_bytes(int(n_trios), int(n_win)))
+
+    def dstat_jackknife_dev(self, rows, n_win, n_trios, out=None, work=None, stream=None):
+        """Block-jackknife D, standard error and Z of n_trios trios x 3 topologies from the device rows of
+        dstat_pops_reduce_dev (uint8 CUDA tensor, trio-major, n_trios * n_win rows; the windows must be disjoint)
+        (pgt_dstat_jackknife_dev).  Returns (out, work): out holds 3 * n_trios DSTAT_JACK_DTYPE, item 3 t + c
+        (rows_from_device(out, DSTAT_JACK_DTYPE)).  Asynchronous on `stream`; no allocation when out and work are given."""
+        import torch
+        n_win, n_trios = int(n_win), int(n_trios)
+        wb = self.dstat_jackknife_work_bytes(n_trios, n_win)
+        if wb == 0:
+            raise PgtError(_lib.PGT_EARG, "dstat_jackknife_dev: n_trios must be 1 ... 20")
+        self._room("dstat_jackknife_dev: rows", rows, n_trios * n_win * DSTAT_ROW_DTYPE.itemsize)
+        if out is None:
+            out = torch.empty(3 * n_trios * DSTAT_JACK_DTYPE.itemsize, dtype=torch.uint8, device=rows.device)
+        if work is None:
+            work = torch.empty(wb, dtype=torch.uint8, device=rows.device)
+        self._room("dstat_jackknife_dev: out", out, 3 * n_trios * DSTAT_JACK_DTYPE.itemsize)
+        self._room("dstat_jackknife_dev: work", work, wb)
+        self._check(self._lib.pgt_dstat_jackknife_dev(
+            self._ctx, self._dev(rows, torch.uint8, "rows") if n_win else None, n_win, n_trios,
+            self._dev(out, torch.uint8, "out"), out.numel(), self._dev(work, torch.uint8, "work"), work.numel(), self._stream(stream)))
+        return out, work
+
     def extreme_reduce_dev(self, pos, score, mode, cutoff, win, out=None, tree=None, stream=None):
         """ihsWindow / xpehhWindow rows from a device-resident score column (mode: PGT_EXT_*)."""
         import torch
@@ -1086,6 +1124,12 @@ def trio_order(n_pops: int):
     return [(i, j, k) for i in range(g) for j in range(i + 1, g) for k in range(j + 1, g)]
 
 
+def topology_order(i, j, k):
+    """The three topologies of trio (i, j, k) in the order the block jackknife lays its items out (c = 0, 1, 2), each as
+    ((P1, P2), P3): [(i, j, k), (i, k, j), (j, k, i)] — D from (abba, baba), (bbaa, baba), (bbaa, abba) of the trio's row."""
+    return [(i, j, k), (i, k, j), (j, k, i)]
+
+
 def _window_pops(st: _PopsStat, chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx):
     """What the *_window_pops functions share: dxy_window's refusals, the population count, host columns, the window table and
     one pass of the statistic's numpy form -> (win, rows[tables, n_win], totals[tables])."""
@@ -1101,6 +1145,40 @@ def _window_pops(st: _PopsStat, chr_ids, pos, freqs, ninds, W, S, minind, fixeds
         if own:
             ctx.close()
     return win, rows, tot
+
+
+def _dstat_window_pops_jackknife(chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx):
+    """_window_pops for the ABBA-BABA rows with the rows kept ON THE DEVICE between the reduction and the block jackknife
+    (dstat_pops_reduce_dev under the hints the host-buffer form derives from the table: the same rows bit for bit, then
+    dstat_jackknife_dev on them) -> (win, rows[n_trios, n_win], totals[n_trios], jack[n_trios, 3])."""
+    st = _DSTAT_POPS
+    _refuse_dxy_window_args(W, S, minind, fixedsite, chr_len)
+    st.check_count("dstat_window_pops", freqs, ninds)
+    chr_ids, pos = _host_col(chr_ids, None), _host_col(pos, np.uint32)
+    freqs, ninds = [_host_col(f, np.float64) for f in freqs], [_host_col(c, np.int32) for c in ninds]
+    if any(c.size != pos.size for c in freqs + ninds):
+        raise PgtError(_lib.PGT_EARG, "dstat_window_pops: column lengths differ")
+    win = _dxy_window_table(chr_ids, pos, W, S, fixedsite, chr_len)
+    n_trios = st.tables(len(freqs))
+    import torch
+    ctx, own = _own_ctx(ctx)
+    try:
+        dev = torch.device("cuda", ctx.device)
+
+        def up(a):
+            return torch.from_numpy(np.ascontiguousarray(a).copy()).to(dev)
+        longest, typical, step = table_hints(win)
+        with ctx.hints(longest, 0 if step >= 2 ** 63 else step, typical):
+            out, tot, _ = ctx.dstat_pops_reduce_dev(up(pos.view(np.int32)), [up(f) for f in freqs], [up(c) for c in ninds], minind,
+                                                    windows_to_device(win, dev))
+        jack, _ = ctx.dstat_jackknife_dev(out, win.size, n_trios)
+        rows = rows_from_device(out, DSTAT_ROW_DTYPE)[: n_trios * win.size].reshape(n_trios, win.size).copy()
+        tot = rows_from_device(tot, DSTAT_TOTAL_DTYPE)[:n_trios].copy()
+        jack = rows_from_device(jack, DSTAT_JACK_DTYPE)[: 3 * n_trios].reshape(n_trios, 3).copy()
+    finally:
+        if own:
+            ctx.close()
+    return win, rows, tot, jack
 
 
 def _results_by_pair(n_pops, win, rows, tot, skip_missing, counted: str, keys=None) -> dict:
@@ -1141,14 +1219,27 @@ def fst_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: 
 
 
 def dstat_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: int = 1, fixedsite: int = 0,
-                      chr_len=None, skip_missing: int = 0, ctx: Context | None = None) -> dict:
+                      chr_len=None, skip_missing: int = 0, ctx: Context | None = None, jackknife: bool = False) -> dict:
     """Windowed ABBA-BABA (Patterson's D) for ALL trios of the first len(freqs) - 1 already synchronised populations against
     the LAST one, the outgroup (4 ... 7 populations), in one pass: {(i, j, k): WindowResult} in trio_order, with rows of
     (start, end, mid, n, d, bbaa, abba, baba) and the genome-wide sums as total.  All columns must report the same allele.
     Window arguments and their errors are those of dxy_window_pops; -skip_missing drops a trio's rows without counted sites
-    from that trio's result only.  The per-site definition is pgt_dstat_pops_reduce_dev's (include/pgtwin.h)."""
-    win, rows, tot = _window_pops(_DSTAT_POPS, chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx)
-    return _results_by_pair(len(freqs), win, rows, tot, skip_missing, "n", keys=trio_order(len(freqs)))
+    from that trio's result only.  The per-site definition is pgt_dstat_pops_reduce_dev's (include/pgtwin.h).
+    jackknife=True: the result gains the key "jackknife": {(i, j, k): 3 DSTAT_JACK_DTYPE, one per topology_order(i, j, k)} —
+    the delete-m_j block jackknife (pgt_dstat_jackknife_dev, on the device rows of the same reduction) over ALL windows of
+    the table as blocks, whatever skip_missing is
+    (a window without a counted site is no block either way).  The windows must be disjoint: 0 < S < W and W == 0 are
+    refused with PGT_EARG before any device use."""
+    if jackknife and (W == 0 or 0 < S < W):
+        raise PgtError(_lib.PGT_EARG, f"dstat_window_pops: the block jackknife needs disjoint windows as its blocks: "
+                                      f"winsize {W} must be positive and stepsize {S} at least the winsize")
+    if not jackknife:
+        win, rows, tot = _window_pops(_DSTAT_POPS, chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx)
+        return _results_by_pair(len(freqs), win, rows, tot, skip_missing, "n", keys=trio_order(len(freqs)))
+    win, rows, tot, jack = _dstat_window_pops_jackknife(chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx)
+    res = _results_by_pair(len(freqs), win, rows, tot, skip_missing, "n", keys=trio_order(len(freqs)))
+    res["jackknife"] = {ijk: jack[t] for t, ijk in enumerate(trio_order(len(freqs)))}
+    return res
 
 
 def pi_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: int = 1, fixedsite: int = 0,
