@@ -62,7 +62,7 @@ def build_lib(force: bool = False) -> str:
     that only received a prebuilt library) an existing library is used as it is."""
     import fcntl
     srcs = [os.path.join(CSRC, s) for s in LIB_SOURCES]
-    deps = srcs + [os.path.join(CSRC, "pgt_internal.h"), os.path.join(CSRC, "pgt_device.h"), os.path.join(CSRC, "pgt_pops_common.h"), os.path.join(ROOT, "include", "pgtwin.h")]
+    deps = srcs + [os.path.join(CSRC, "pgt_internal.h"), os.path.join(CSRC, "pgt_device.h"), os.path.join(CSRC, "pgt_pops_common.h"), os.path.join(CSRC, "pgt_pops_walk.h"), os.path.join(ROOT, "include", "pgtwin.h")]
     extra = os.environ.get("PGT_EXTRA_HIPCC_FLAGS", "").split()
     if "-DPGT_TUNING_BUILD" in extra:
         # the tuning library (tools/tune_*.py): tools/pgt_kernels_tuning.hip REPLACES csrc/pgt_kernels.hip — it includes the

@@ -263,7 +263,7 @@ __global__ __launch_bounds__(256, 2) void af_query_kernel(AfCols cols, const uin
     constexpr int V = Shape<NP>::kVals;
     constexpr int P = Shape<NP>::kPairs;
     const int lane = threadIdx.x & (kWave - 1);
-    const uint64_t wave0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;  // (no readfirstlane as in dxy_pops_query_kernel: the difference is unmeasured)
+    const uint64_t wave0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;  // (no readfirstlane as in pops_query_kernel of pgt_pops_walk.h: the difference is unmeasured)
     const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
 
     for (uint64_t w = wave0; w < n_win; w += n_waves) {
@@ -319,7 +319,7 @@ __global__ __launch_bounds__(256, 2) void af_query_kernel(AfCols cols, const uin
                 for (int v = 0; v < V; ++v) acc[v] += *af_node<V>(tv, level - 1, v, i);
             }
         };
-        // the range descent: the same loop as in dxy_pops_query_kernel (as ONE shared function it compiled to other code in both
+        // the range descent: the same loop as in pops_query_kernel, pgt_pops_walk.h (as ONE shared function it compiled to other code in both
         // kernels, with other register counts, so each keeps its copy: a change to one belongs in the other too)
         uint64_t clo = lo, chi = hi;
         for (int k = 0;; ++k) {

@@ -646,7 +646,7 @@ int pgt_fst_af_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const
 
 size_t pgt_dxy_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites) {
     if (n_pops < 2 || n_pops > (uint32_t)kPopsMaxPops) return 0;
-    return dxy_pops_tree_view(tree_layout(PGT_STAT_FST, n_sites), (int)(n_pops * (n_pops - 1) / 2), nullptr, 0).bytes;
+    return pops_tree_view(tree_layout(PGT_STAT_FST, n_sites), (int)pops_pairs(n_pops), 1, nullptr, 0).bytes;
 }
 static const PopsStat kDxyPops = {"pgt_dxy_pops_reduce", 2, false, pops_pairs, "n_pairs", sizeof(pgt_dxy_row), pgt_dxy_pops_tree_bytes};
 
@@ -664,7 +664,7 @@ int pgt_dxy_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *con
 
 size_t pgt_fst_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites) {
     if (n_pops < 2 || n_pops > (uint32_t)kPopsMaxPops) return 0;
-    return fst_pops_tree_view(tree_layout(PGT_STAT_FST, n_sites), (int)(n_pops * (n_pops - 1) / 2), nullptr, 0).bytes;
+    return pops_tree_view(tree_layout(PGT_STAT_FST, n_sites), (int)pops_pairs(n_pops), 2, nullptr, 0).bytes;
 }
 // minind >= 1: npool >= 2 and n1, n2 > 0 at every counted site
 static const PopsStat kFstPops = {"pgt_fst_pops_reduce", 2, true, pops_pairs, "n_pairs", sizeof(pgt_fst_row), pgt_fst_pops_tree_bytes};
@@ -720,7 +720,7 @@ int pgt_pi_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *cons
 // ABBA-BABA patterns of all ingroup trios against the last population: one more PopsStat, with an upper bound of its own
 size_t pgt_dstat_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites) {
     if (n_pops < 4 || n_pops > 7) return 0;
-    return dstat_pops_tree_view(tree_layout(PGT_STAT_FST, n_sites), (int)pops_trios(n_pops), nullptr, 0).bytes;
+    return pops_tree_view(tree_layout(PGT_STAT_FST, n_sites), (int)pops_trios(n_pops), 3, nullptr, 0).bytes;
 }
 static const PopsStat kDstatPops = {"pgt_dstat_pops_reduce", 4, true, pops_trios, "n_trios", sizeof(pgt_dstat_row), pgt_dstat_pops_tree_bytes, 7};
 

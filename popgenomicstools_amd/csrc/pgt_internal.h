@@ -130,84 +130,49 @@ inline AfTree af_tree_view(const TreeLayout &t, int n_vals, void *tree, int leve
 
 // ---- the (freq, nInd) front ends: dxy and FST of all population pairs, pi per population ------
 constexpr int kPopsMaxPops = 8;     // populations per call of pgt_{dxy,fst,pi}_pops_reduce*: sizes their pointer arrays
-constexpr int kPopsLeafPieces = 4;  // 128-site pieces per level-1 node of the two all-pairs trees below
+constexpr int kPopsLeafPieces = 4;  // 128-site pieces per level-1 node of the all-pairs trees below
 
-// ---- dxy of all population pairs (pgt_dxy_pops_kernels.hip): nodes of P = NP(NP-1)/2 {Σd, neff}, node-major ------
-// A level holds two arrays: P doubles per node (the pairs' Σd) and P u32 per node (their neff); nskip is not stored
-// (every site of a range is a data site: nskip = sites - neff).  Level 1: 512-site nodes, 16 per level-2 node; levels 2
-// and up are those of the f64 layout (8192 sites, x64 per level).  Behind the levels one {Σd, neff} per pair and build
-// wave: the genome-wide lines are their sums in wave order (as TreeLayout::partials for the two-population tree).
-struct DxyPopsTree {
+// ---- the trees of the all-pairs / all-trios front ends (pgt_pops_walk.h): nodes of S sums and a count per item, node-major ------
+// An item is a pair (dxy: P = NP(NP-1)/2 of {Σd}; FST: {Σa, Σ(a+b)}) or an ingroup trio (ABBA-BABA: T = C(NP-1, 3) of {Σbbaa,
+// Σabba, Σbaba}).  A level holds two arrays: S * items doubles per node (sum 0 of item 0 .. items-1, then sum 1, ..) and
+// items u32 per node (their neff); nskip is not stored (every site of a range is a data site: nskip = sites - neff).
+// Level 1: 512-site nodes, 16 per level-2 node; levels 2 and up are those of the f64 layout (8192 sites, x64 per level).
+// Behind the levels one such node per build wave: the genome-wide lines are their sums in wave order (as
+// TreeLayout::partials for the two-population tree).
+struct PopsTree {
     char *base;
-    size_t sum_off[kMaxLevels];  // byte offset of level slot k: P doubles per node
-    size_t cnt_off[kMaxLevels];  // ... P u32 per node
-    size_t part_sum, part_cnt;   // [build wave][P] doubles / u32
+    size_t sum_off[kMaxLevels];  // byte offset of level slot k: S * items doubles per node
+    size_t cnt_off[kMaxLevels];  // ... items u32 per node
+    size_t part_sum, part_cnt;   // [build wave][S * items] doubles / [build wave][items] u32
     size_t bytes;
     int n_levels;
-    int n_pairs;
+    int n_items;
     uint32_t n_partials;         // build waves that left a partial (0: no sites)
 };
 
-// ---- FST of all population pairs from per-population (freq, nInd) columns (pgt_fst_pops_kernels.hip) ----------------------
-// The shape of DxyPopsTree with two sums per pair: a node is 2 P doubles (Σa of pair 0 .. P-1, then Σ(a+b) of pair 0 .. P-1)
-// and P u32 (neff); a level holds the two arrays node-major.  Behind the levels one {Σa, Σ(a+b), neff} per pair and build wave.
-struct FstPopsTree {
-    char *base;
-    size_t sum_off[kMaxLevels];  // byte offset of level slot k: 2 P doubles per node
-    size_t cnt_off[kMaxLevels];  // ... P u32 per node
-    size_t part_sum, part_cnt;   // [build wave][2 P] doubles / [build wave][P] u32
-    size_t bytes;
-    int n_levels;
-    int n_pairs;
-    uint32_t n_partials;         // build waves that left a partial (0: no sites)
-};
-
-// ---- ABBA-BABA patterns of all ingroup trios against an outgroup (pgt_dstat_pops_kernels.hip) ------------------------------
-// The shape of FstPopsTree with three sums per TRIO: a node is 3 T doubles (Σbbaa of trio 0 .. T-1, then Σabba, then Σbaba) and
-// T u32 (neff), T = C(n_pops - 1, 3); behind the levels one such node per build wave.  n_pairs holds T (pops_tree_view's name).
-struct DstatPopsTree {
-    char *base;
-    size_t sum_off[kMaxLevels];  // byte offset of level slot k: 3 T doubles per node
-    size_t cnt_off[kMaxLevels];  // ... T u32 per node
-    size_t part_sum, part_cnt;   // [build wave][3 T] doubles / [build wave][T] u32
-    size_t bytes;
-    int n_levels;
-    int n_pairs;                 // T: the trios
-    uint32_t n_partials;         // build waves that left a partial (0: no sites)
-};
-
-// The one layout behind both (two kernel-argument types, one shape): per level and behind the levels an array of `sum_bytes`
-// of sums per pair and node (8: Σd; 16: Σa and Σ(a+b)) and an array of one u32 per pair and node, each padded to 256 bytes.
-template <class Tree>
-inline Tree pops_tree_view(const TreeLayout &t, int n_pairs, size_t sum_bytes, void *tree, int levels) {
-    Tree v{};
+// Its layout: per level and behind the levels an array of sums_per_item doubles per item and node (1: Σd; 2: Σa and Σ(a+b);
+// 3: the three patterns) and an array of one u32 per item and node, each padded to 256 bytes.
+inline PopsTree pops_tree_view(const TreeLayout &t, int n_items, int sums_per_item, void *tree, int levels) {
+    PopsTree v{};
     v.base = static_cast<char *>(tree);
     v.n_levels = levels;
-    v.n_pairs = n_pairs;
+    v.n_items = n_items;
+    const size_t sum_bytes = (size_t)8 * sums_per_item;
     auto pad = [](size_t b) { return ((b + 255) / 256) * 256; };
     size_t off = 0;
     for (int k = 0; k < t.n_levels; ++k) {
         const uint64_t nodes = k == 0 ? t.count[0] / kPopsLeafPieces : t.count[k];
         v.sum_off[k] = off;
-        off += pad(nodes * (size_t)n_pairs * sum_bytes);
+        off += pad(nodes * (size_t)n_items * sum_bytes);
         v.cnt_off[k] = off;
-        off += pad(nodes * (size_t)n_pairs * 4);
+        off += pad(nodes * (size_t)n_items * 4);
     }
     v.part_sum = off;
-    off += pad((size_t)kMaxBuildWaves * n_pairs * sum_bytes);
+    off += pad((size_t)kMaxBuildWaves * n_items * sum_bytes);
     v.part_cnt = off;
-    off += pad((size_t)kMaxBuildWaves * n_pairs * 4);
+    off += pad((size_t)kMaxBuildWaves * n_items * 4);
     v.bytes = off;
     return v;
-}
-inline DxyPopsTree dxy_pops_tree_view(const TreeLayout &t, int n_pairs, void *tree, int levels) {
-    return pops_tree_view<DxyPopsTree>(t, n_pairs, 8, tree, levels);
-}
-inline FstPopsTree fst_pops_tree_view(const TreeLayout &t, int n_pairs, void *tree, int levels) {
-    return pops_tree_view<FstPopsTree>(t, n_pairs, 16, tree, levels);
-}
-inline DstatPopsTree dstat_pops_tree_view(const TreeLayout &t, int n_trios, void *tree, int levels) {
-    return pops_tree_view<DstatPopsTree>(t, n_trios, 24, tree, levels);
 }
 
 // ---- delete-m_j block jackknife of a ratio of two block sums (pgt_dstat_jack_kernels.hip) -----------------------------------

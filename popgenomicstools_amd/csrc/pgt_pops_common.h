@@ -1,10 +1,10 @@
 // pgt_pops_common.h — what the "all pairs of up to 8 populations in one pass" front ends share (pgt_af_kernels.hip: FST from
-// allele frequencies; pgt_dxy_pops_kernels.hip, pgt_fst_pops_kernels.hip: dxy and FST from the populations' own (freq, nInd)
-// columns): the pair count, the wave reduce-scatter, the flush of a build wave's LDS stage, and the host
-// side of a launch (error mapping, event records, grids, the upper-level loop, the dispatch on the population count, the
-// measuring knobs).  The static balanced build grid of the two (freq, nInd) front ends is pops_build_grid below; the layout of
-// their trees is pops_tree_view in pgt_internal.h (the C ABI sizes workspaces with it).  pgt_kernels.hip keeps helpers of its
-// own: it does not include this header.
+// allele frequencies; pgt_pops_walk.h: the one walk of the (freq, nInd) front ends pgt_dxy_pops_kernels.hip,
+// pgt_fst_pops_kernels.hip and pgt_dstat_pops_kernels.hip): the pair count, the wave reduce-scatter, the flushes of a build
+// wave's LDS stage, and the host side of a launch (error mapping, event records, grids, the upper-level loop, the dispatch on
+// the population count, the measuring knobs).  The static balanced build grid of the (freq, nInd) front ends is
+// pops_build_grid below; the layout of their trees is pops_tree_view in pgt_internal.h (the C ABI sizes workspaces with it).
+// pgt_kernels.hip keeps helpers of its own: it does not include this header.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -125,6 +125,21 @@ __device__ __forceinline__ void flush_stage(double *node_block, const double *st
         __builtin_nontemporal_store(w.y, &dst[e].y);
     }
 }
+// N u32 (a multiple of 4; stage and destination 16-byte aligned): the counts beside those sums, 16 bytes per lane and store
+template <int N>
+__device__ __forceinline__ void flush_count_stage(uint32_t *node_block, const uint32_t *stage, int lane) {
+    static_assert(N % 4 == 0, "whole 16-byte elements");
+    uint4 *dst = reinterpret_cast<uint4 *>(node_block);
+    const uint4 *src = reinterpret_cast<const uint4 *>(stage);
+#pragma unroll 2
+    for (int e = lane; e < N / 4; e += kWave) {
+        const uint4 w = src[e];
+        __builtin_nontemporal_store(w.x, &dst[e].x);
+        __builtin_nontemporal_store(w.y, &dst[e].y);
+        __builtin_nontemporal_store(w.z, &dst[e].z);
+        __builtin_nontemporal_store(w.w, &dst[e].w);
+    }
+}
 
 }  // namespace dev
 
@@ -146,7 +161,7 @@ inline unsigned wave_grid(uint64_t items) {
     return (unsigned)(b > 65536 ? 65536 : b);
 }
 
-// The build grid of the (freq, nInd) front ends (launch_np of pgt_dxy_pops_kernels.hip and pgt_fst_pops_kernels.hip) over
+// The build grid of the (freq, nInd) front ends (launch_np of pgt_pops_walk.h) over
 // `n_tiles` level-2 tiles (tl.count[1] > 0): a static balanced grid of what is resident at once (one wave per SIMD: 256
 // workgroups of 4 waves; two: 512): every wave walks `rounds` tiles, all waves run in near lockstep and flush their node
 // blocks at about the same times.  (launch_af_np picks its round count by how full the last generation is; that choice is
@@ -175,20 +190,15 @@ int launch_upper_levels(void (*up)(Tree, int, uint64_t, uint64_t), const char *n
     return PGT_OK;
 }
 
-// f(std::integral_constant<int, NP>{}) for the NP = n_pops in 2 .. 8; the callers reject any other count before they get here
-template <class F>
-int dispatch_n_pops(uint32_t n_pops, const F &f) {
-    switch (n_pops) {
-        case 2: return f(std::integral_constant<int, 2>{});
-        case 3: return f(std::integral_constant<int, 3>{});
-        case 4: return f(std::integral_constant<int, 4>{});
-        case 5: return f(std::integral_constant<int, 5>{});
-        case 6: return f(std::integral_constant<int, 6>{});
-        case 7: return f(std::integral_constant<int, 7>{});
-        case 8: return f(std::integral_constant<int, 8>{});
-        default: return PGT_EARG;
-    }
+// f(std::integral_constant<int, NP>{}) for the NP = n_pops in LO .. HI, and only those are instantiated; the callers reject
+// any other count before they get here
+template <int LO, int HI, class F>
+int dispatch_pops(uint32_t n_pops, const F &f) {
+    if constexpr (LO > HI) return PGT_EARG;
+    else return n_pops == LO ? f(std::integral_constant<int, LO>{}) : dispatch_pops<LO + 1, HI>(n_pops, f);
 }
+template <class F>
+int dispatch_n_pops(uint32_t n_pops, const F &f) { return dispatch_pops<2, 8>(n_pops, f); }
 
 // a measuring knob from the environment (read once by its caller: `static const int v = env_int(..)`)
 inline int env_int(const char *name, int dflt) {

@@ -285,7 +285,7 @@ def test_exact_rows_under_every_hint_poison_and_guard(pgt, ctx, n, k):
     """Rows and totals of every pair equal the integer prefix sums BITWISE: under the hints 0 / W / 4 W, with the tree
     workspace poisoned three ways before every call, tree / out / tot between seeded guards, and the columns as views into
     padding that would show (NaN frequencies, counts of 1000).  At 1 600 001 sites the table holds windows that contain one,
-    two and all three level-3 nodes (asserted below): under the hints 0 / W / 4 W level 3 is built by dxy_pops_up_kernel and
+    two and all three level-3 nodes (asserted below): under the hints 0 / W / 4 W level 3 is built by pops_up_kernel and
     read by the query; under the fourth hint (50 000: no level above 2) the same windows are answered from level 2."""
     W = 600_000
     A, B = ExactPops(21 + k, n, k), ExactPops(22 + k, n, k)

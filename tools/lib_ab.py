@@ -118,9 +118,17 @@ def main():
     af_tree = torch.empty(int(_lib.load().pgt_af_tree_bytes(8, n)), dtype=torch.uint8, device=dev) if fr else None
     af_out = torch.empty(28 * 40 * (win.numel() // 32), dtype=torch.uint8, device=dev) if fr else None
     ni = [((n1, n2)[k % 2] + k) % 21 for k in range(8)] if fr else None  # individual counts of the 8 populations (int32, 0 ... 20)
-    dp_tree = torch.empty(ctx_b.dxy_pops_tree_bytes(8, n), dtype=torch.uint8, device=dev) if fr else None
-    dp_out = torch.empty(28 * 24 * (win.numel() // 32), dtype=torch.uint8, device=dev) if fr else None
-    dp_tot = torch.empty(28 * 24, dtype=torch.uint8, device=dev) if fr else None
+    def pops_buffers(tree_bytes, tables, row_bytes, total_bytes):
+        """(tree, rows, genome-wide lines) of ONE all-pairs / all-trios configuration, exactly as large as what it writes: a buffer
+        shared with a larger configuration would keep that one's rows behind its own, and the rows check compares whole buffers"""
+        return (torch.empty(int(tree_bytes), dtype=torch.uint8, device=dev), torch.empty(tables * row_bytes * (win.numel() // 32), dtype=torch.uint8, device=dev),
+                torch.empty(tables * total_bytes, dtype=torch.uint8, device=dev))
+
+    if fr:  # rows of 24 (dxy), 40 (FST) and 48 (ABBA-BABA) bytes; genome-wide lines of 24, 32 and 40
+        dp8, dp2 = pops_buffers(ctx_b.dxy_pops_tree_bytes(8, n), 28, 24, 24), pops_buffers(ctx_b.dxy_pops_tree_bytes(2, n), 1, 24, 24)
+        fw8, fw2 = pops_buffers(ctx_b.fst_pops_tree_bytes(8, n), 28, 40, 32), pops_buffers(ctx_b.fst_pops_tree_bytes(2, n), 1, 40, 32)
+        fh8 = pops_buffers(ctx_b.fst_hudson_pops_tree_bytes(8, n), 28, 40, 32)
+        ds7, ds4 = pops_buffers(ctx_b.dstat_pops_tree_bytes(7, n), 20, 48, 40), pops_buffers(ctx_b.dstat_pops_tree_bytes(4, n), 1, 48, 40)
     configs = [
         ("fstWindow", 16, lambda c: c.fst_reduce_dev(pos, a, b, win, out=out, tree=tree)),
         ("dxyWindow (with the genome-wide line)", 24, lambda c: c.dxy_reduce_dev(pos, p1, p2, n1, n2, 5, win, out=out, tree=tree)),
@@ -131,13 +139,18 @@ def main():
     if fr:
         configs.append(("AF front end, 8 populations", 64, lambda c: c.fst_af_reduce_dev(pos, fr, nsamp, win, out=af_out, tree=af_tree)))
         configs.append(("AF front end, 2 populations", 16, lambda c: c.fst_af_reduce_dev(pos, fr[:2], nsamp[:2], win, out=af_out, tree=af_tree)))
-        configs.append(("dxy of all pairs, 8 populations", 96, lambda c: c.dxy_pops_reduce_dev(pos, fr, ni, 5, win, out=dp_out, tot=dp_tot, tree=dp_tree)))
-        configs.append(("dxy of all pairs, 2 populations", 24, lambda c: c.dxy_pops_reduce_dev(pos, fr[:2], ni[:2], 5, win, out=dp_out, tot=dp_tot, tree=dp_tree)))
+        configs.append(("dxy of all pairs, 8 populations", 96, lambda c: c.dxy_pops_reduce_dev(pos, fr, ni, 5, win, out=dp8[1], tot=dp8[2], tree=dp8[0])))
+        configs.append(("dxy of all pairs, 2 populations", 24, lambda c: c.dxy_pops_reduce_dev(pos, fr[:2], ni[:2], 5, win, out=dp2[1], tot=dp2[2], tree=dp2[0])))
+        configs.append(("FST of all pairs, Weir-Cockerham, 8 populations", 96, lambda c: c.fst_pops_reduce_dev(pos, fr, ni, 5, win, out=fw8[1], tot=fw8[2], tree=fw8[0])))
+        configs.append(("FST of all pairs, Weir-Cockerham, 2 populations", 24, lambda c: c.fst_pops_reduce_dev(pos, fr[:2], ni[:2], 5, win, out=fw2[1], tot=fw2[2], tree=fw2[0])))
+        configs.append(("FST of all pairs, Hudson, 8 populations", 96, lambda c: c.fst_hudson_pops_reduce_dev(pos, fr, ni, 5, win, out=fh8[1], tot=fh8[2], tree=fh8[0])))
+        configs.append(("ABBA-BABA, 7 populations", 84, lambda c: c.dstat_pops_reduce_dev(pos, fr[:7], ni[:7], 5, win, out=ds7[1], tot=ds7[2], tree=ds7[0])))
+        configs.append(("ABBA-BABA, 4 populations", 48, lambda c: c.dstat_pops_reduce_dev(pos, fr[:4], ni[:4], 5, win, out=ds4[1], tot=ds4[2], tree=ds4[0])))
     print(f"A = {os.path.relpath(old, ROOT)}, B = {b_name}; {n:.0e} sites, W = {W}, S = {S}, {rounds} rounds of A B B A, {BURST} call(s) per measurement\n")
     print("| config | A build ms | B build ms | B - A paired (median) | A % of 8 TB/s | B % | A step ms | B step ms | step B - A paired | rows A = B |")
     print("|---|---|---|---|---|---|---|---|---|---|")
-    if os.environ.get("AB_ONLY"):  # e.g. AB_ONLY=AF: only the configurations whose name contains the string
-        configs = [c for c in configs if os.environ["AB_ONLY"] in c[0]]
+    if os.environ.get("AB_ONLY"):  # e.g. AB_ONLY=AF or AB_ONLY="all pairs|ABBA": only the configurations whose name contains one of the strings
+        configs = [c for c in configs if any(p in c[0] for p in os.environ["AB_ONLY"].split("|"))]
     emax = int((ewin_h["hi"] - ewin_h["lo"]).max())
     for name, bps, fn in configs:
         for c in (ctx_a, ctx_b):
