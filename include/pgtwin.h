@@ -55,7 +55,8 @@ extern "C" {
  * Still 6: pgt_pi_pops_tree_bytes / pgt_pi_pops_reduce_dev / pgt_pi_pops_reduce added (additive as well).
  * Still 6: pgt_fst_hudson_pops_tree_bytes / pgt_fst_hudson_pops_reduce_dev / pgt_fst_hudson_pops_reduce added (additive as well).
  * Still 6: pgt_dstat_row, pgt_dstat_total, pgt_dstat_pops_tree_bytes / pgt_dstat_pops_reduce_dev / pgt_dstat_pops_reduce added (additive as well).
- * Still 6: pgt_dstat_jack, pgt_dstat_jackknife_work_bytes / pgt_dstat_jackknife_dev / pgt_dstat_jackknife added (additive as well). */
+ * Still 6: pgt_dstat_jack, pgt_dstat_jackknife_work_bytes / pgt_dstat_jackknife_dev / pgt_dstat_jackknife added (additive as well).
+ * Still 6: pgt_fd_row, pgt_fd_total, pgt_fd_pops_tree_bytes / pgt_fd_pops_reduce_dev / pgt_fd_pops_reduce added (additive as well). */
 #define PGT_ABI_VERSION 6
 
 enum {
@@ -118,6 +119,18 @@ typedef struct { /* the three sums of one trio over all its counted sites */
     double bbaa, abba, baba;
     uint64_t neff, nskip;
 } pgt_dstat_total;
+
+typedef struct { /* f_d / f_dM window row of one trio ((i,j),k) against the outgroup: pgt_fd_pops_reduce_dev (56 bytes) */
+    uint32_t start, end, mid, n;
+    double fd;                   /* fd_den != 0 ? num / fd_den : 0     f_d (Martin et al. 2015), reported whatever its sign */
+    double fdm;                  /* fdm_den != 0 ? num / fdm_den : 0   f_dM (Malinsky et al. 2015) */
+    double num, fd_den, fdm_den; /* the three window sums, full precision */
+} pgt_fd_row;
+
+typedef struct { /* the three sums of one trio over all its counted sites (40 bytes) */
+    double num, fd_den, fdm_den;
+    uint64_t neff, nskip;
+} pgt_fd_total;
 
 typedef struct { /* block jackknife of one trio and topology: pgt_dstat_jackknife_dev (48 bytes) */
     double d, d_jack, se, z; /* D of all used blocks, its jackknife estimate, standard error, d_jack / se */
@@ -402,8 +415,8 @@ int pgt_pi_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *f
  * bit, on the populations outside the trio and the outgroup, nor on the other rows of the table.  Sums are added in a fixed
  * order that depends on the site index and the window alone (bitwise reproducible); against an exact evaluation of the lines
  * above they stay within 1e-9 relative + 1e-12.  Parity: none to pin; held to this definition, to an exact-rational fixture
- * (tests/golden/dstat_exact.json) and to a NumPy model (tests/dstat_pops_model.py).  f_d / f_dM and user-chosen trio lists are not
- * computed; block-jackknife standard errors and Z scores come from pgt_dstat_jackknife_dev below, over the rows of a table of
+ * (tests/golden/dstat_exact.json) and to a NumPy model (tests/dstat_pops_model.py).  f_d / f_dM of the same trios come from
+ * pgt_fd_pops_reduce_dev below; user-chosen trio lists are not computed; block-jackknife standard errors and Z scores come from pgt_dstat_jackknife_dev below, over the rows of a table of
  * disjoint windows (the blocks).
  * Host-buffer form: columns (host arrays of n_pops HOST pointers), table, rows and the T totals in host memory. */
 size_t pgt_dstat_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites);
@@ -414,6 +427,59 @@ int pgt_dstat_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *c
 int pgt_dstat_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq,
                           const int32_t *const *nind, uint32_t n_pops, uint64_t n, int minind,
                           const pgt_win *win, uint64_t n_win, pgt_dstat_row *out, pgt_dstat_total *tot);
+
+/* ---- f_d and f_dM of all ingroup trios against an outgroup ------------------------------------------------------------- */
+/* The admixture-proportion statistics to scan windows with where Patterson's D misleads (small windows: high variance, inflated
+ * where diversity is low): f_d (Martin, Davey & Jiggins 2015, MBE 32:244) and f_dM (Malinsky et al. 2015, Science 350:1493) —
+ * what Dsuite's Dinvestigate prints beside D.  It has NO counterpart in the reference: the definition below is the contract.
+ * Populations, trios, their order and the counting predicate are those of pgt_dstat_pops_reduce_dev: the LAST population o is
+ * the outgroup; trio (i, j, k), i < j < k < n_pops - 1, in lexicographic order, is read as ((P1 = i, P2 = j), P3 = k); a site
+ * counts for a trio iff all four populations have at least minind individuals; a site that is not counted is selected away,
+ * never multiplied by 0 (its columns may hold anything).  4 <= n_pops <= 7, minind >= 1, n < 2^32.
+ *   per site   p_x = freq_x[s], q_x = 1.0 - p_x; every operation rounded on its own, no contraction; abba and baba exactly the
+ *              two lines of pgt_dstat_pops_reduce_dev; in exactly this grouping:
+ *                  num  = abba - baba
+ *                  H = (p_j >= p_k) ? j : k        L = (p_j <= p_k) ? j : k        the larger / smaller of P2, P3
+ *                  G = (p_i >= p_k) ? i : k        S = (p_i <= p_k) ? i : k        the larger / smaller of P1, P3
+ *                  B1 = (q_i*p_H)*(p_H*q_o) - (p_i*q_H)*(p_H*q_o)      S(P1, PD, PD, O), PD of {P2,P3}; reported allele derived
+ *                  A1 = (p_i*q_L)*(q_L*p_o) - (q_i*p_L)*(q_L*p_o)      the same with the two alleles' roles swapped
+ *                  B2 = (p_G*q_j)*(p_G*q_o) - (q_G*p_j)*(p_G*q_o)      -S(PD, P2, PD, O), PD of {P1,P3}
+ *                  A2 = (q_S*p_j)*(q_S*p_o) - (p_S*q_j)*(q_S*p_o)      the same, roles swapped
+ *                  fd_den  = B1 + A1
+ *                  fdm_den = (p_j >= p_i ? B1 : B2) + (p_j <= p_i ? A1 : A2)
+ *              The allele-symmetric form of the D lines: each term is the pattern with the reported allele as derived, weighted
+ *              by the outgroup's ancestral frequency q_o, plus the same pattern with the alleles' roles swapped, weighted by
+ *              p_o.  With a fixed outgroup (p_o 0 or 1) it is Martin's and Malinsky's formula.  Ties need no rule: equal p give
+ *              equal q and the products commute, so either choice gives the same bits.  The selects compare the INPUT
+ *              frequencies, never the rounded q.  A NaN frequency at a counted site gives unspecified results for that trio's
+ *              rows only.
+ *   row        pgt_fd_row (56 bytes): num / fd_den / fdm_den = the three sums over the window's counted sites, each from +0.0;
+ *              n = their number; start / end / mid as pgt_dstat_row's are filled;
+ *                  fd = fd_den != 0 ? num / fd_den : 0          fdm = fdm_den != 0 ? num / fdm_den : 0
+ *              one correctly rounded division of the row's own sums each.  num is the sum of per-site differences, not the
+ *              difference of the D row's two sums: the two agree within rounding, not in bits.
+ *   out        T * n_win rows, trio-major: out[t * n_win + w]
+ *   tot        DEVICE array of T pgt_fd_total (40 bytes: the same three sums over all counted sites, neff, nskip), or NULL
+ *   tree       pgt_fd_pops_tree_bytes(n_pops, n) bytes (0 for n_pops outside 4 ... 7): the size pgt_dstat_pops_tree_bytes gives,
+ *              so one buffer serves both calls in turn.
+ * f_d is meant for windows with D >= 0 (gene flow P3 -> P2); the row reports it whatever its sign.
+ * f_dM covers both directions (P3 -> P2 positive, P3 -> P1 negative) and lies within +-1.
+ * Only the topology ((i,j),k) is computed — f_d is no function of three shared sums as D is — so the order of the columns chooses it.
+ * A one-site window carries exactly the bits of `num`, `fd_den` and `fdm_den` above.  Arguments, alignment, refusals (messages
+ * begin "pgt_fd_pops_reduce: "), graph capture, hints, bitwise reproducibility and trio isolation: those of
+ * pgt_dstat_pops_reduce_dev.  The sums' site terms have both signs: against an exact evaluation a sum stays within
+ * 1e-9 * A + 1e-12, A the window's sum of |site term|.  Held to this definition, to an exact-rational fixture
+ * (tests/golden/fd_exact.json) and to a NumPy model (tests/fd_pops_model.py).  d_f, f_G / f_hom, the other two topologies, a
+ * block jackknife of f_d and K = 8 are not computed.
+ * Host-buffer form: columns (host arrays of n_pops HOST pointers), table, rows and the T totals in host memory. */
+size_t pgt_fd_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites);
+int pgt_fd_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq,
+                           const int32_t *const *nind, uint32_t n_pops, uint64_t n, int minind,
+                           const pgt_win *win, uint64_t n_win, pgt_fd_row *out, size_t out_bytes,
+                           pgt_fd_total *tot, void *tree, size_t tree_bytes, void *stream);
+int pgt_fd_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq,
+                       const int32_t *const *nind, uint32_t n_pops, uint64_t n, int minind,
+                       const pgt_win *win, uint64_t n_win, pgt_fd_row *out, pgt_fd_total *tot);
 
 /* ---- block-jackknife standard error and Z of Patterson's D, all trios and topologies ----------------------------------- */
 /* The weighted (delete-m_j) block jackknife of Busing, Meijer & van der Leeden (1999) — the one ADMIXTOOLS and ANGSD's

@@ -33,6 +33,9 @@ FST_TOTAL_DTYPE = np.dtype([("asum", "<f8"), ("bsum", "<f8"), ("neff", "<u8"), (
 DSTAT_ROW_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("mid", "<u4"), ("n", "<u4"),
                             ("d", "<f8"), ("bbaa", "<f8"), ("abba", "<f8"), ("baba", "<f8")])
 DSTAT_TOTAL_DTYPE = np.dtype([("bbaa", "<f8"), ("abba", "<f8"), ("baba", "<f8"), ("neff", "<u8"), ("nskip", "<u8")])
+FD_ROW_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("mid", "<u4"), ("n", "<u4"),
+                         ("fd", "<f8"), ("fdm", "<f8"), ("num", "<f8"), ("fd_den", "<f8"), ("fdm_den", "<f8")])  # pgt_fd_row
+FD_TOTAL_DTYPE = np.dtype([("num", "<f8"), ("fd_den", "<f8"), ("fdm_den", "<f8"), ("neff", "<u8"), ("nskip", "<u8")])
 DSTAT_JACK_DTYPE = np.dtype([("d", "<f8"), ("d_jack", "<f8"), ("se", "<f8"), ("z", "<f8"), ("n_sites", "<u8"),
                              ("n_blocks", "<u4"), ("pad_", "<u4")])  # pgt_dstat_jack: one trio and topology
 EXT_ROW_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("nsites", "<u4"), ("nbig", "<u4"),
@@ -45,6 +48,7 @@ assert EXT_ROW_DTYPE.itemsize == 32
 assert DXY_ROW_DTYPE.itemsize == 24 and DXY_TOTAL_DTYPE.itemsize == 24 and SHARD_DTYPE.itemsize == 32
 assert SEG_DTYPE.itemsize == 16 and FST_TOTAL_DTYPE.itemsize == 32
 assert DSTAT_ROW_DTYPE.itemsize == 48 and DSTAT_TOTAL_DTYPE.itemsize == 40 and DSTAT_JACK_DTYPE.itemsize == 48
+assert FD_ROW_DTYPE.itemsize == 56 and FD_TOTAL_DTYPE.itemsize == 40
 
 # every symbol include/pgtwin.h declares (tests/test_abi.py checks the list against the header)
 SYMBOLS = [
@@ -66,6 +70,7 @@ SYMBOLS = [
     "pgt_fst_hudson_pops_tree_bytes", "pgt_fst_hudson_pops_reduce_dev", "pgt_fst_hudson_pops_reduce",
     "pgt_dstat_pops_tree_bytes", "pgt_dstat_pops_reduce_dev", "pgt_dstat_pops_reduce",
     "pgt_dstat_jackknife_work_bytes", "pgt_dstat_jackknife_dev", "pgt_dstat_jackknife",
+    "pgt_fd_pops_tree_bytes", "pgt_fd_pops_reduce_dev", "pgt_fd_pops_reduce",
 ]
 PGT_TOK_CHR, PGT_TOK_SKIP, PGT_TOK_U32, PGT_TOK_F64, PGT_TOK_I8, PGT_TOK_I32, PGT_TOK_FREQ, PGT_TOK_CHR_PREFIX = range(8)
 
@@ -136,7 +141,7 @@ def load() -> C.CDLL:
     lib.pgt_af_tree_bytes.restype = sz
     lib.pgt_af_tree_bytes.argtypes = [u32, u64]
     lib.pgt_fst_af_reduce_dev.argtypes = [vp, vp, vp, vp, u32, u64, vp, u64, vp, sz, vp, sz, vp]
-    for stat in ("dxy", "fst", "pi", "fst_hudson", "dstat"):  # the K-population statistics over (freq, nInd) columns: one argument list each form
+    for stat in ("dxy", "fst", "pi", "fst_hudson", "dstat", "fd"):  # the K-population statistics over (freq, nInd) columns: one argument list each form
         getattr(lib, f"pgt_{stat}_pops_tree_bytes").restype = sz
         getattr(lib, f"pgt_{stat}_pops_tree_bytes").argtypes = [u32, u64]
         getattr(lib, f"pgt_{stat}_pops_reduce_dev").argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, u64, vp, sz, vp, vp, sz, vp]

@@ -431,7 +431,8 @@ pgt_ctx *pgt_open(int device) {
     } restore{caller_device, device};
     std::string init_err;
     if (init_kernels(&init_err) != PGT_OK || init_af_kernels(&init_err) != PGT_OK || init_dxy_pops_kernels(&init_err) != PGT_OK ||
-        init_fst_pops_kernels(&init_err) != PGT_OK || init_dstat_pops_kernels(&init_err) != PGT_OK) {
+        init_fst_pops_kernels(&init_err) != PGT_OK || init_dstat_pops_kernels(&init_err) != PGT_OK ||
+        init_fd_pops_kernels(&init_err) != PGT_OK) {
         set_global_error("pgt_open: " + init_err);
         return nullptr;
     }
@@ -734,6 +735,22 @@ int pgt_dstat_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *c
     const EvSet e = events_for(ctx);
     return launch_dstat_pops(pos, freq, nind, n_pops, n, minind, win, n_win, out, tot, tree, stream, e.b0, e.b1, e.q1, &ctx->error,
                              ctx->hints);
+}
+
+// f_d / f_dM of the same trios: one more PopsStat; three sums per trio as D has, so the tree is the D call's size
+size_t pgt_fd_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites) { return pgt_dstat_pops_tree_bytes(n_pops, n_sites); }
+static const PopsStat kFdPops = {"pgt_fd_pops_reduce", 4, true, pops_trios, "n_trios", sizeof(pgt_fd_row), pgt_fd_pops_tree_bytes, 7};
+
+int pgt_fd_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind,
+                           uint32_t n_pops, uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_fd_row *out,
+                           size_t out_bytes, pgt_fd_total *tot, void *tree, size_t tree_bytes, void *stream) {
+    PGT_USE_DEVICE(ctx);
+    bool launch;
+    if (int rc = pops_check_dev(ctx, kFdPops, pos, freq, nind, n_pops, n, minind, win, n_win, out, out_bytes, tot, tree, tree_bytes, &launch)) return rc;
+    if (!launch) return PGT_OK;
+    const EvSet e = events_for(ctx);
+    return launch_fd_pops(pos, freq, nind, n_pops, n, minind, win, n_win, out, tot, tree, stream, e.b0, e.b1, e.q1, &ctx->error,
+                          ctx->hints);
 }
 
 // Block jackknife of the rows above: its own checks (no columns, no window table), the message prefix of both forms
@@ -1185,6 +1202,13 @@ int pgt_dstat_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const
                           uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_dstat_row *out, pgt_dstat_total *tot) {
     PGT_USE_DEVICE(ctx);
     return pops_reduce_host(ctx, kDstatPops, pgt_dstat_pops_reduce_dev, pos, freq, nind, n_pops, n, minind, win, n_win, out, tot);
+}
+
+/* f_d / f_dM of all ingroup trios: the host-buffer form, as pgt_dstat_pops_reduce */
+int pgt_fd_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
+                       uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_fd_row *out, pgt_fd_total *tot) {
+    PGT_USE_DEVICE(ctx);
+    return pops_reduce_host(ctx, kFdPops, pgt_fd_pops_reduce_dev, pos, freq, nind, n_pops, n, minind, win, n_win, out, tot);
 }
 
 /* block jackknife of a host table of ABBA-BABA rows: rows up, the device form on the cached workspace, 3 n_trios results down */

@@ -300,6 +300,12 @@ int launch_dstat_pops(const uint32_t *pos, const double *const *freq, const int3
                       void *tree, void *stream, void *ev_build0, void *ev_build1, void *ev_query1, std::string *err,
                       const Hints &hints);
 
+// pgt_fd_pops_kernels.hip: f_d / f_dM of the same trios; arguments, limits and tree size as launch_dstat_pops
+int launch_fd_pops(const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
+                   uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_fd_row *out, pgt_fd_total *tot,
+                   void *tree, void *stream, void *ev_build0, void *ev_build1, void *ev_query1, std::string *err,
+                   const Hints &hints);
+
 // pgt_kernels.hip: pi per population, 1 <= n_pops <= 8 and minind >= 1 (checked by the caller); out = n_pops tables of
 // n_win rows, tot = n_pops device totals or NULL; tree = n_pops trees of tree_layout(PGT_STAT_DXY, n).bytes each
 int launch_pi_pops(const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
@@ -353,6 +359,7 @@ int init_af_kernels(std::string *err);  // pgt_af_kernels.hip
 int init_dxy_pops_kernels(std::string *err);  // pgt_dxy_pops_kernels.hip
 int init_fst_pops_kernels(std::string *err);  // pgt_fst_pops_kernels.hip
 int init_dstat_pops_kernels(std::string *err);  // pgt_dstat_pops_kernels.hip
+int init_fd_pops_kernels(std::string *err);     // pgt_fd_pops_kernels.hip
 
 // thread-local message for the ctx-less entry points
 void set_global_error(const std::string &msg);

@@ -16,6 +16,10 @@
 // -jackknife 1 (disjoint windows only: -stepsize equal to -winsize): one pgt_dstat_jackknife_dev call on the device rows gives
 // the delete-m_j block jackknife of every trio and topology, the run's windows being the blocks -> PREFIX.jackknife
 // (`P1 P2 P3 D D_jack SE Z nblocks nsites`, D that of ((P1,P2),P3)).  Every other file is the same with and without it.
+// -fd 1: one pgt_fd_pops_reduce_dev call more on the aligned columns still on the device (in the D tree's buffer, once D's rows
+// are read: the two sizes are equal) gives f_d (Martin et al. 2015) and f_dM (Malinsky et al. 2015) of every trio ((i,j),k) ->
+// PREFIX.pop<i+1>_pop<j+1>_pop<k+1>.fd (`chr start end mid f_d f_dM num fd_den fdm_den neff nskip`) and PREFIX.fd.global
+// (`i+1 j+1 k+1 f_d f_dM num fd_den fdm_den neff nskip`).  Every other file is the same with and without it.
 //
 // Limits: one GPU (the first of PGT_DEVICES); no passes mode — the K parsed files and the aligned columns must fit the
 // card (and PGT_MAX_RESIDENT_SITES, where set) or the run is refused; PGT_DXY_SYNC=reference is not offered.
@@ -33,6 +37,7 @@ static void help(const DxyOptions &o) {
                 "%-14s%-8sTwo-column TSV file with each row having (1) chromsome name (2) chromosome size in base pairs\n"
                 "%-14s%-8sDo not print windows with zero effective sites if INT=1 [%d]\n"
                 "%-14s%-8s(1) Write PREFIX.jackknife: block-jackknife standard error and Z score of D for every trio and topology [0]\n"
+                "%-14s%-8s(1) Write PREFIX.pop<i>_pop<j>_pop<k>.fd and PREFIX.fd.global: f_d and f_dM for every trio ((i,j),k) [0]\n"
                 "\nNotes:\n"
                 "* The LAST MAF file is the outgroup; the K-1 files before it are the ingroup populations (K between 4 and 7 files)\n"
                 "* Every trio i < j < k of ingroup populations is analyzed as ((i,j),k) against the outgroup: C(K-1,3) trios\n"
@@ -48,6 +53,15 @@ static void help(const DxyOptions &o) {
                 "  run's windows, weighted by their number of analyzed sites; windows without an analyzed site are left out.\n"
                 "  The windows must not overlap: -winsize > 0 and -stepsize equal to -winsize. -fixedsite 1 windows hold the same number\n"
                 "  of sites and so give blocks of (nearly) equal weight; -skip_missing does not change the blocks\n"
+                "* -fd 1: f_d (Martin, Davey & Jiggins 2015) and f_dM (Malinsky et al. 2015) of ((i,j),k) = ((P1,P2),P3), in one more pass.\n"
+                "  Per analyzed site num = ABBA - BABA; fd_den is the same difference with P2 and P3 both replaced by whichever of the two\n"
+                "  has the higher frequency of the allele (the lower one in the term with the alleles' roles swapped); fdm_den is fd_den\n"
+                "  where p_2 >= p_1, and otherwise the difference with P1 and P3 both replaced by the higher (lower) of those two.\n"
+                "  A window's values are the SUMS over its analyzed sites, f_d = num/fd_den and f_dM = num/fdm_den (0 where the sum is 0)\n"
+                "* f_d is meant for windows with D >= 0 (gene flow P3 -> P2); the row reports it whatever its sign\n"
+                "* f_dM covers both directions: positive for P3 -> P2, negative for P3 -> P1, between -1 and 1\n"
+                "* Only the topology ((i,j),k) is computed for f_d and f_dM, so the order of the MAF files chooses it\n"
+                "* -fd 1 and -jackknife 1 may be given together; neither changes what the other writes\n"
                 "* -sizefile is REQUIRED(!) with -fixedsite 0 (the default)\n"
                 "* All input MAF files need to have the same chromosomes in the same order\n"
                 "* Assumes SNPs are biallelic\n"
@@ -62,9 +76,15 @@ static void help(const DxyOptions &o) {
                 "PREFIX.global, one line per trio:\n(1) i\n(2) j\n(3) k\n(4) D\n(5) BBAA\n(6) ABBA\n(7) BABA\n(8) number of sites analyzed\n(9) number of sites skipped\n"
                 "PREFIX.jackknife (with -jackknife 1), three lines per trio i < j < k: ((i,j),k), ((i,k),j), ((j,k),i):\n"
                 "(1) P1\n(2) P2\n(3) P3: the topology ((P1,P2),P3)\n(4) D over all blocks\n(5) jackknife estimate of D\n(6) standard error\n"
-                "(7) Z = (5) / (6) (nan with fewer than two blocks or a standard error of zero)\n(8) number of blocks\n(9) number of sites in the blocks\n\n",
+                "(7) Z = (5) / (6) (nan with fewer than two blocks or a standard error of zero)\n(8) number of blocks\n(9) number of sites in the blocks\n"
+                "PREFIX.pop<i>_pop<j>_pop<k>.fd (with -fd 1) for every trio i < j < k (not with -winsize 0):\n"
+                "(1) chromosome\n(2) Window start\n(3) Window end\n(4) Window midpoint\n(5) f_d of ((i,j),k)\n(6) f_dM of ((i,j),k)\n(7) num (sum)\n"
+                "(8) fd_den (sum)\n(9) fdm_den (sum)\n(10) number sites in MAF input that were analyzed\n"
+                "(11) number of sites in MAF input that were skipped due to too few individuals\n"
+                "PREFIX.fd.global (with -fd 1), one line per trio:\n(1) i\n(2) j\n(3) k\n(4) f_d\n(5) f_dM\n(6) num\n(7) fd_den\n(8) fdm_den\n"
+                "(9) number of sites analyzed\n(10) number of sites skipped\n\n",
                 "-out", "STRING", "-winsize", "INT", o.W, "-stepsize", "INT", o.S, "-minind", "INT", o.minind, "-fixedsite", "INT", o.fixedsite,
-                "-sizefile", "FILE", "-skip_missing", "INT", o.skip_missing, "-jackknife", "INT");
+                "-sizefile", "FILE", "-skip_missing", "INT", o.skip_missing, "-jackknife", "INT", "-fd", "INT");
 }
 
 // chr start end mid D BBAA ABBA BABA neff nskip
@@ -79,10 +99,27 @@ static size_t put_dstat_row(char *o, const std::string &chr, const pgt_dstat_row
     return (size_t)(p - o);
 }
 
+// chr start end mid f_d f_dM num fd_den fdm_den neff nskip
+static size_t put_fd_row(char *o, const std::string &chr, const pgt_fd_row &r, uint32_t nskip) {
+    char *p = o;
+    std::memcpy(p, chr.data(), chr.size());
+    p += chr.size();
+    for (uint32_t u : {r.start, r.end, r.mid}) { *p++ = '\t'; p = put_u32(p, u); }
+    for (double g : {r.fd, r.fdm, r.num, r.fd_den, r.fdm_den}) { *p++ = '\t'; p += fmt_g6(g, p); }
+    for (uint32_t u : {r.n, nskip}) { *p++ = '\t'; p = put_u32(p, u); }
+    *p++ = '\n';
+    return (size_t)(p - o);
+}
+
 int main(int argc, char **argv) {
     const std::string tool = "dstatWindowPops";
-    int jackknife = 0;
+    int jackknife = 0, fd = 0;
     const PopsArgs args = parse_pops_args(tool, argc, argv, help, 4, [&](const char *o, const char *v) {
+        if (!std::strcmp(o, "-fd")) {
+            if (std::strcmp(v, "0") && std::strcmp(v, "1")) die(std::string("-fd must be 0 or 1 (given: ") + v + ")");
+            fd = v[0] == '1';
+            return true;
+        }
         if (std::strcmp(o, "-jackknife")) return false;
         if (std::strcmp(v, "0") && std::strcmp(v, "1")) die(std::string("-jackknife must be 0 or 1 (given: ") + v + ")");
         jackknife = v[0] == '1';
@@ -130,6 +167,16 @@ int main(int argc, char **argv) {
         jack.resize(3 * n_trios);
         check(pgt_rowbuf_read(ctx, jack.data(), d_jack, 3 * n_trios * sizeof(pgt_dstat_jack), nullptr), ctx);
     }
+    RowArray<pgt_fd_row> fd_rows(fd ? n_trios * n_win : 0);
+    std::vector<pgt_fd_total> fd_tot(fd ? n_trios : 0);
+    if (fd) {  // a second reduction of the aligned columns; D's rows are read, so its tree's buffer (the same size) is free
+        pgt_fd_row *d_fd_rows = pops_dev_alloc<pgt_fd_row>(ctx, n_trios * n_win);
+        pgt_fd_total *d_fd_tot = pops_dev_alloc<pgt_fd_total>(ctx, n_trios);
+        check(pgt_fd_pops_reduce_dev(ctx, s.a_pos, s.a_freq.data(), s.a_nind.data(), (uint32_t)K, s.n_sites, minind, n_win ? s.d_win : nullptr, n_win,
+                                     n_win ? d_fd_rows : nullptr, n_trios * n_win * sizeof(pgt_fd_row), d_fd_tot, tree, tree_bytes, nullptr), ctx);
+        check(pgt_rowbuf_read(ctx, fd_rows.data(), d_fd_rows, n_trios * n_win * sizeof(pgt_fd_row), nullptr), ctx);
+        check(pgt_rowbuf_read(ctx, fd_tot.data(), d_fd_tot, n_trios * sizeof(pgt_fd_total), nullptr), ctx);
+    }
     timer.lap("gpu reduce");
 
     const std::string global_path = std::string(prefix) + ".global";
@@ -170,6 +217,29 @@ int main(int argc, char **argv) {
                     }
                 }
         close_out(f, path);
+    }
+    if (fd) {  // the .fd files and PREFIX.fd.global: the loops of the .dstat files and PREFIX.global above
+        const std::string fd_global_path = std::string(prefix) + ".fd.global";
+        FILE *fd_global = open_out(fd_global_path);
+        t = 0;
+        for (int a = 0; a < K - 1; ++a)
+            for (int b = a + 1; b < K - 1; ++b)
+                for (int c = b + 1; c < K - 1; ++c, ++t) {
+                    if (W > 0) {
+                        const std::string path = std::string(prefix) + ".pop" + std::to_string(a + 1) + "_pop" + std::to_string(b + 1) + "_pop" + std::to_string(c + 1) + ".fd";
+                        FILE *f = open_out(path);
+                        const pgt_fd_row *r = fd_rows.data() + t * n_win;
+                        write_rows(n_win, longest_name(runs) + 200, [&](size_t i, char *o) -> size_t {
+                            if (!(r[i].n > 0 || !skip_missing)) return 0;
+                            return put_fd_row(o, runs.name[win[i].label_run], r[i], (uint32_t)(win[i].hi - win[i].lo) - r[i].n);
+                        }, f);
+                        close_out(f, path);
+                    }
+                    const pgt_fd_total &g = fd_tot[t];  // the ratios from the totals by the row's rule
+                    std::fprintf(fd_global, "%d\t%d\t%d\t%g\t%g\t%g\t%g\t%g\t%llu\t%llu\n", a + 1, b + 1, c + 1, g.fd_den != 0.0 ? g.num / g.fd_den : 0.0,
+                                 g.fdm_den != 0.0 ? g.num / g.fdm_den : 0.0, g.num, g.fd_den, g.fdm_den, (unsigned long long)g.neff, (unsigned long long)g.nskip);
+                }
+        close_out(fd_global, fd_global_path);
     }
     finish(timer);
 }

@@ -20,7 +20,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import (DSTAT_JACK_DTYPE, DSTAT_ROW_DTYPE, DSTAT_TOTAL_DTYPE, DXY_ROW_DTYPE, DXY_TOTAL_DTYPE, EXT_ROW_DTYPE, FST_ROW_DTYPE, FST_TOTAL_DTYPE, HET_ROW_DTYPE, PGT_EXT_IHS,
+from ._lib import (DSTAT_JACK_DTYPE, DSTAT_ROW_DTYPE, DSTAT_TOTAL_DTYPE, DXY_ROW_DTYPE, DXY_TOTAL_DTYPE, EXT_ROW_DTYPE, FD_ROW_DTYPE, FD_TOTAL_DTYPE, FST_ROW_DTYPE, FST_TOTAL_DTYPE, HET_ROW_DTYPE, PGT_EXT_IHS,
                    PGT_EXT_XP_MAX, PGT_EXT_XP_MIN, PGT_STAT_DXY, PGT_STAT_EXT, PGT_STAT_FST, PGT_STAT_HET,
                    SEG_DTYPE, SHARD_DTYPE, WIN_DTYPE, PgtError, check)
 
@@ -284,6 +284,7 @@ _FST_POPS = _PopsStat("fst", 2, True, FST_ROW_DTYPE, FST_TOTAL_DTYPE)
 _PI_POPS = _PopsStat("pi", 1, False, DXY_ROW_DTYPE, DXY_TOTAL_DTYPE)
 _FST_HUDSON_POPS = _PopsStat("fst_hudson", 2, True, FST_ROW_DTYPE, FST_TOTAL_DTYPE)
 _DSTAT_POPS = _PopsStat("dstat", 4, False, DSTAT_ROW_DTYPE, DSTAT_TOTAL_DTYPE, max_pops=7, per_trio=True)
+_FD_POPS = _PopsStat("fd", 4, False, FD_ROW_DTYPE, FD_TOTAL_DTYPE, max_pops=7, per_trio=True)
 _FST_ESTIMATORS = {"wc": _FST_POPS, "hudson": _FST_HUDSON_POPS}  # fst_window_pops(estimator=...)
 
 
@@ -427,6 +428,13 @@ class Context:
         (pgt_dstat_pops_reduce).  A row carries Σbbaa, Σabba, Σbaba over its counted sites, their number n and Patterson's
         d = (abba - baba) / (abba + baba) for the topology ((i,j),k)."""
         return self._pops_reduce(_DSTAT_POPS, pos, freqs, ninds, minind, win)
+
+    def fd_pops_reduce(self, pos, freqs, ninds, minind, win):
+        """f_d / f_dM rows of ALL trios i<j<k of the first len(freqs) - 1 populations (trio_order), read as ((P1 = i, P2 = j),
+        P3 = k), against the LAST one, the outgroup, from 4 ... 7 per-population numpy (freq, nInd) columns, one pass:
+        -> (rows[n_trios, n_win], totals[n_trios]) (pgt_fd_pops_reduce).  A row carries Σnum, Σfd_den, Σfdm_den over its counted
+        sites, their number n, fd = num / fd_den and fdm = num / fdm_den (0 where the denominator is 0)."""
+        return self._pops_reduce(_FD_POPS, pos, freqs, ninds, minind, win)
 
     def dstat_jackknife(self, rows) -> np.ndarray:
         """Block-jackknife D, standard error and Z of every trio and topology from a [n_trios, n_win] numpy table of
@@ -805,6 +813,17 @@ class Context:
         int32 CUDA tensors.  tot: None = a fresh buffer of n_trios totals is allocated and filled; False = no genome-wide
         lines.  Returns (out, tot, tree).  Asynchronous on `stream`."""
         return self._pops_reduce_dev(_DSTAT_POPS, pos, freqs, ninds, minind, win, out, tot, tree, stream)
+
+    @staticmethod
+    def fd_pops_tree_bytes(n_pops: int, n_sites: int) -> int:
+        return int(_lib.load().pgt_fd_pops_tree_bytes(int(n_pops), int(n_sites)))
+
+    def fd_pops_reduce_dev(self, pos, freqs, ninds, minind, win, out=None, tot=None, tree=None, stream=None):
+        """f_d / f_dM rows of ALL ingroup trios (trio-major, trio_order; ((P1 = i, P2 = j), P3 = k)) against the last population,
+        the outgroup, in one pass over 4 ... 7 populations' own (freq, nInd) columns (pgt_fd_pops_reduce_dev): the arguments and
+        buffers of dstat_pops_reduce_dev (the tree is dstat_pops_tree_bytes large and may be reused between the two, one call at
+        a time), rows of FD_ROW_DTYPE, totals of FD_TOTAL_DTYPE.  Returns (out, tot, tree).  Asynchronous on `stream`."""
+        return self._pops_reduce_dev(_FD_POPS, pos, freqs, ninds, minind, win, out, tot, tree, stream)
 
     @staticmethod
     def dstat_jackknife_work_bytes(n_trios: int, n_win: int) -> int:
@@ -1240,6 +1259,19 @@ def dstat_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind
     res = _results_by_pair(len(freqs), win, rows, tot, skip_missing, "n", keys=trio_order(len(freqs)))
     res["jackknife"] = {ijk: jack[t] for t, ijk in enumerate(trio_order(len(freqs)))}
     return res
+
+
+def fd_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: int = 1, fixedsite: int = 0,
+                   chr_len=None, skip_missing: int = 0, ctx: Context | None = None) -> dict:
+    """Windowed f_d (Martin et al. 2015) and f_dM (Malinsky et al. 2015) for ALL trios of the first len(freqs) - 1 already
+    synchronised populations against the LAST one, the outgroup (4 ... 7 populations), in one pass: {(i, j, k): WindowResult}
+    in trio_order, with rows of (start, end, mid, n, fd, fdm, num, fd_den, fdm_den) and the genome-wide sums as total.
+    f_d is meant for windows with D >= 0 (P3 -> P2); the row reports it whatever its sign.  f_dM covers both directions.
+    Only the topology ((i,j),k) is computed, so the order of the columns chooses it.
+    Window arguments and their errors are those of dstat_window_pops; -skip_missing drops a trio's rows without counted sites
+    from that trio's result only.  The per-site definition is pgt_fd_pops_reduce_dev's (include/pgtwin.h)."""
+    win, rows, tot = _window_pops(_FD_POPS, chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx)
+    return _results_by_pair(len(freqs), win, rows, tot, skip_missing, "n", keys=trio_order(len(freqs)))
 
 
 def pi_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: int = 1, fixedsite: int = 0,
