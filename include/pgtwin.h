@@ -33,6 +33,19 @@
  *     has no counts: every site is counted; a NaN there stays in the rows of the pairs with that population.
  *   - genotypes: any int8 (non-missing is g >= 0, heterozygous g == 1, hetWindow.cpp:78-80); counts (n1, n2, nind[k]) and minind:
  *     any int32, compared as signed integers (dxyWindow.cpp:381).
+ *   - the K-population entry points (pgt_dxy_pops / fst_pops / fst_hudson_pops / pi_pops / dstat_pops / fd_pops _reduce_dev;
+ *     tests/test_special_values_pops.py): a NaN or an infinity in ONE population's frequency at a COUNTED site reaches exactly the
+ *     rows (and genome-wide lines) of the items — pairs, trios, the population itself — that hold that population, and of them
+ *     exactly the windows that hold the site, with the value the per-site definition gives on the IEEE operands, every operation
+ *     rounded on its own (for pgt_fd_pops_reduce_dev the definition's comparisons are all false with a NaN, so NaN in P2 leaves
+ *     fd_den finite and NaN in P1 leaves fdm_den finite); every other row keeps its bits.  Sums add by IEEE 754 in an
+ *     unspecified order: a NaN term gives NaN, +inf and -inf together NaN, infinities of one sign that infinity.  Frequencies
+ *     at the edge of [0, 1] (-0.0, denormals, 1 - 2^-53, 0, 1) are ordinary values; sums may be denormal; a ratio is 0 where its
+ *     denominator sum is 0.  Counts and minind are any int32, compared signed; where the counts are values (fst_pops,
+ *     fst_hudson_pops, pi_pops) any count from minind (>= 1) to INT32_MAX is converted exactly.  pgt_dxy_pops_reduce_dev takes
+ *     minind < 1 as well; a site beyond n, padded into the last tile, never counts, whatever minind is.
+ *   - pgt_dstat_jackknife_dev: a block's weight is any u32 (pgt_dstat_row.n); their sum is kept in u64 and is exact in the f64
+ *     arithmetic while it stays below 2^53.
  */
 #ifndef PGTWIN_H
 #define PGTWIN_H
@@ -451,8 +464,8 @@ int pgt_dstat_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const
  *              by the outgroup's ancestral frequency q_o, plus the same pattern with the alleles' roles swapped, weighted by
  *              p_o.  With a fixed outgroup (p_o 0 or 1) it is Martin's and Malinsky's formula.  Ties need no rule: equal p give
  *              equal q and the products commute, so either choice gives the same bits.  The selects compare the INPUT
- *              frequencies, never the rounded q.  A NaN frequency at a counted site gives unspecified results for that trio's
- *              rows only.
+ *              frequencies, never the rounded q.  With a NaN frequency at a counted site every comparison is false and
+ *              the lines above are evaluated as written ("Values the columns admit"), for that trio's rows only.
  *   row        pgt_fd_row (56 bytes): num / fd_den / fdm_den = the three sums over the window's counted sites, each from +0.0;
  *              n = their number; start / end / mid as pgt_dstat_row's are filled;
  *                  fd = fd_den != 0 ? num / fd_den : 0          fdm = fdm_den != 0 ? num / fdm_den : 0

@@ -1,5 +1,6 @@
-"""Inputs with NaN, infinite and full-range values for tests/test_special_values.py (GPU) and the CPU check of their
-expectations (tests/test_special_values_cpu.py).  numpy, host side; nothing here touches the product."""
+"""Inputs with NaN, infinite and full-range values for tests/test_special_values.py and tests/test_special_values_pops.py
+(GPU) and the CPU checks of their expectations (tests/test_special_values_cpu.py, tests/test_special_values_pops_cpu.py).
+numpy, host side; nothing here touches the product."""
 import numpy as np
 
 import synth
@@ -252,3 +253,367 @@ def extreme_counts(rng, n, minind):
 
 
 GARBAGE = (NAN, INF, -INF, -5.0, 7.0)
+
+
+# ---- the K-population kernels (tests/test_special_values_pops.py on the GPU, tests/test_special_values_pops_cpu.py for the expectations) ----
+# dxy_pops, fst_pops (Weir-Cockerham), fst_hudson_pops, pi_pops, dstat_pops, fd_pops: leaf 512 sites, level-2 tile 8192 sites,
+# level-3 node 64 tiles.  A special value sits at a COUNTED site here, so the expectation is the per-site definition itself
+# (the models' per-site functions) summed by window_sums below, which carries NaN and infinities where a difference of prefix
+# sums cannot.
+POPS_N = 8192 + 513          # a ragged last tile, n mod 4 == 1
+POPS_L3_N = 524288 + 8192 + 5
+POPS_L3_PLANTED = (524287, 524288)
+POPS_L3_WINDOWS = ((0, 524288), (1, 524288), (0, 524287), (524288, POPS_L3_N), (524289, POPS_L3_N), (0, POPS_L3_N))
+POPS_MININD = 5
+POPS_TABLES = ((7, 3), (512, 512), (3000, 1000))
+# both sides of a leaf edge and of a tile edge, two neighbours inside one quad, the column's first site and its last quad
+POPS_PLANTED = (0, 511, 512, 4000, 4001, 8191, 8192, POPS_N - 1)
+POPS_EDGE_VALUES = (-0.0, 5e-324, 2.0 ** -1022, 1.0 - 2.0 ** -53, 0.0, 1.0)  # inside the contract: frequencies in [0, 1]
+POPS_SUMS = {"dxy": ("sum",), "pi": ("sum",), "fst": ("asum", "bsum"), "fst_hudson": ("asum", "bsum"),
+             "dstat": ("bbaa", "abba", "baba"), "fd": ("num", "fd_den", "fdm_den")}
+POPS_SECTION1 = [("dxy", 3), ("dxy", 8), ("fst_hudson", 3), ("fst_hudson", 8), ("pi", 2), ("pi", 8), ("dstat", 4), ("dstat", 7),
+                 ("fd", 4), ("fd", 5), ("fd", 7)]  # fd: the two-wave build, the one-wave build without recompute, kRecompute
+POPS_SMALLEST_LARGEST = [("dxy", 2), ("dxy", 8), ("fst", 2), ("fst", 8), ("fst_hudson", 2), ("fst_hudson", 8), ("pi", 1), ("pi", 8),
+                         ("dstat", 4), ("dstat", 7), ("fd", 4), ("fd", 7)]
+POPS_VALUE_STATS = ("fst", "fst_hudson", "pi")  # the counts are VALUES of the per-site function, not only its predicate
+POPS_MININDS = (1, 20, I32_MAX)
+REL_A, ABS_A = 1e-9, 1e-12  # helpers.REL / ABS against the scale A = Σ|term| (tests/test_fd_pops.py derives the bound)
+
+
+def pops_dtypes(stat):
+    from popgenomicstools_amd import _lib
+    return {"dxy": (_lib.DXY_ROW_DTYPE, _lib.DXY_TOTAL_DTYPE), "pi": (_lib.DXY_ROW_DTYPE, _lib.DXY_TOTAL_DTYPE),
+            "fst": (_lib.FST_ROW_DTYPE, _lib.FST_TOTAL_DTYPE), "fst_hudson": (_lib.FST_ROW_DTYPE, _lib.FST_TOTAL_DTYPE),
+            "dstat": (_lib.DSTAT_ROW_DTYPE, _lib.DSTAT_TOTAL_DTYPE), "fd": (_lib.FD_ROW_DTYPE, _lib.FD_TOTAL_DTYPE)}[stat]
+
+
+def pops_items(stat, k):
+    """the populations every item of the call holds, in the order of the row tables: a population (pi), a pair, or a trio with
+    the outgroup (the last population) as its fourth"""
+    from popgenomicstools_amd.window_scan import pair_order, trio_order
+    if stat == "pi":
+        return [(i,) for i in range(k)]
+    if stat in ("dstat", "fd"):
+        return [tuple(t) + (k - 1,) for t in trio_order(k)]
+    return [tuple(p) for p in pair_order(k)]
+
+
+def pops_counted(item, c, minind):
+    """the predicate as the header states it: every population of the item has nind >= minind, compared as signed int32"""
+    ok = np.ones(len(c[0]), dtype=bool)
+    for x in item:
+        assert c[x].dtype == np.int32
+        ok &= c[x] >= np.int32(minind)
+    return ok
+
+
+def pops_site_terms(stat, item, f, c):
+    """-> the item's per-site terms (one array per sum of POPS_SUMS[stat]) by the models' per-site functions: float64, every
+    operation rounded on its own, whatever they are at a site that is not counted"""
+    import dstat_pops_model
+    import fd_pops_model
+    import fst_hudson_model
+    import fst_pops_model
+    import pi_pops_model
+    with np.errstate(all="ignore"):
+        if stat == "dxy":
+            i, j = item
+            return (f[i] * (1.0 - f[j]) + f[j] * (1.0 - f[i]),)
+        if stat == "pi":
+            return (pi_pops_model.site_pi(f[item[0]], c[item[0]]),)
+        if stat == "fst":
+            i, j = item
+            return fst_pops_model.site_components(f[i], f[j], c[i], c[j])
+        if stat == "fst_hudson":
+            i, j = item
+            return fst_hudson_model.site_components(f[i], f[j], c[i], c[j])
+        fn = dstat_pops_model.site_components if stat == "dstat" else fd_pops_model.site_terms
+        return fn(*(f[x] for x in item))
+
+
+def pops_ratios(stat, row):
+    """-> [(field, the stated function of the row's own sums)]"""
+    import dstat_pops_model
+    import fd_pops_model
+    if stat in ("fst", "fst_hudson"):
+        with np.errstate(all="ignore"):
+            return [("fst", np.where(row["bsum"] != 0, row["asum"] / np.where(row["bsum"] != 0, row["bsum"], 1.0), 0.0))]
+    if stat == "dstat":
+        return [("d", dstat_pops_model.d_of(row["abba"], row["baba"]))]
+    if stat == "fd":
+        return [("fd", fd_pops_model.ratio(row["num"], row["fd_den"])), ("fdm", fd_pops_model.ratio(row["num"], row["fdm_den"]))]
+    return []
+
+
+def window_sums(terms, lo, hi):
+    """The window expectation that survives non-finite terms.  terms: an item's per-site terms with the sites that are not
+    counted already 0.0 (selected away by the predicate); (lo, hi): the table.  -> (want, A, finite) per window: A is
+    Σ|finite terms|, and want follows the rule that holds in ANY order of the additions — a NaN term gives NaN, +inf and -inf
+    together give NaN, infinities of one sign give that infinity, otherwise the correctly rounded sum (math.fsum) plus +0.0.
+    Every finite term is at most 8 in magnitude, so no partial sum of at most 2^50 of them can overflow."""
+    import math
+    t = np.ascontiguousarray(terms, dtype=np.float64)
+    fin = np.isfinite(t)
+    assert np.all(np.abs(t[fin]) <= 8.0), "a finite term above 8: partial sums could overflow in some order"
+    val, mag = np.where(fin, t, 0.0), np.where(fin, np.abs(t), 0.0)
+    lo, hi = np.asarray(lo, dtype=np.int64), np.asarray(hi, dtype=np.int64)
+
+    def count(mask):
+        c = np.concatenate(([0], np.cumsum(mask)))
+        return c[hi] - c[lo]
+
+    n_nan, n_pos, n_neg, n_nonzero = count(np.isnan(t)), count(t == np.inf), count(t == -np.inf), count(mag != 0)
+    # A is a scale, not a value: a difference of extended-precision prefix sums (summed directly where that difference would
+    # lose a window of tiny terms), and exactly 0 where every term is a zero
+    pa = np.concatenate(([0], np.cumsum(mag.astype(np.longdouble))))
+    A = np.where(n_nonzero > 0, np.maximum((pa[hi] - pa[lo]).astype(np.float64), 0.0), 0.0)
+    vals, mags = val.tolist(), mag.tolist()
+    for w in np.flatnonzero((n_nonzero > 0) & (A < 1e-30)).tolist():
+        A[w] = math.fsum(mags[lo[w]:hi[w]])
+    want = np.where((n_nan > 0) | ((n_pos > 0) & (n_neg > 0)), np.nan, np.where(n_pos > 0, np.inf, np.where(n_neg > 0, -np.inf, 0.0)))
+    for w in np.flatnonzero(want == 0.0).tolist():
+        want[w] = math.fsum(vals[lo[w]:hi[w]]) + 0.0
+    return want, A, np.isfinite(want)
+
+
+def assert_sums(got, want, A, what):
+    """THE comparison rule for a column of window sums: the NaN mask and the +-inf bits exact; a finite sum within
+    1e-9 A + 1e-12, and exactly +0.0 where the window has no term but zeros (A == 0)."""
+    got, want, A = (np.atleast_1d(np.asarray(x, dtype=np.float64)) for x in (got, want, A))
+    assert got.shape == want.shape == A.shape, (what, got.shape, want.shape, A.shape)
+    gn, wn = np.isnan(got), np.isnan(want)
+    if not np.array_equal(gn, wn):
+        i = int(np.flatnonzero(gn != wn)[0])
+        raise AssertionError(f"{what}: NaN masks differ at {int((gn != wn).sum())} of {got.size} windows; first at {i}: got {got[i]!r}, want {want[i]!r}")
+    exact = (np.isinf(want) | np.isinf(got) | (A == 0)) & ~wn
+    bad = exact & (bits(got) != bits(want))
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        raise AssertionError(f"{what}: {int(bad.sum())} infinite or all-zero sums differ in their bits; first at {i}: got {got[i]!r}, want {want[i]!r}")
+    rest = ~wn & ~exact
+    over = np.abs(got[rest] - want[rest]) - (REL_A * A[rest] + ABS_A)
+    if over.size and over.max() > 0:
+        i = int(np.flatnonzero(rest)[int(np.argmax(over))])
+        raise AssertionError(f"{what}: {int((over > 0).sum())} sums beyond 1e-9 A + 1e-12; worst at {i}: got {got[i]!r}, want {want[i]!r}, A {A[i]!r}")
+
+
+def windows_of(pairs):
+    from popgenomicstools_amd._lib import WIN_DTYPE
+    win = np.zeros(len(pairs), dtype=WIN_DTYPE)
+    if len(pairs):
+        win["lo"], win["hi"] = [a for a, _ in pairs], [b for _, b in pairs]
+    return win
+
+
+def site_windows(n, W, S):
+    """windows of W sites every S sites that never cross the chromosome edge of two_chromosomes(n); the last ones are shorter"""
+    n0 = (n + 1) // 2
+    return windows_of([(a, min(a + W, end)) for start, end in ((0, n0), (n0, n)) for a in range(start, end, S)])
+
+
+def one_site_windows(sites):
+    return windows_of([(int(s), int(s) + 1) for s in sites])
+
+
+def pops_tables(n=POPS_N, planted=POPS_PLANTED, with_one_site=True):
+    """-> [(name, table)]: POPS_TABLES, the single window (0, n) and the one-site windows at the planted sites and their neighbours"""
+    out = [(f"({W},{S})", site_windows(n, W, S)) for W, S in POPS_TABLES] + [("(0,n)", windows_of([(0, n)]))]
+    if with_one_site:
+        near = sorted({s + d for s in planted for d in (-1, 0, 1) if 0 <= s + d < n})
+        out.append(("(1,1)", one_site_windows(near)))
+    return out
+
+
+def pops_clean_columns(n, k, seed, planted=POPS_PLANTED, count_hi=41):
+    """frequencies j/1024 (synth.exact_freq_columns) and counts 0 ... 40; the planted sites are counted for every population;
+    where a population is below POPS_MININD, one frequency in four is GARBAGE (NaN, +-inf, -5, 7): a site that is not counted
+    is selected away, never multiplied by 0, in the clean run and in every planted one"""
+    rng = np.random.default_rng(seed)
+    f, _ = synth.exact_freq_columns(rng, n, k)
+    c = [rng.integers(0, count_hi, n, dtype=np.int32) for _ in range(k)]
+    for x, y in zip(c, f):
+        x[list(planted)] = 9
+        wild = np.flatnonzero((x < POPS_MININD) & (rng.random(n) < 0.25))
+        y[wild] = rng.choice(np.array(GARBAGE), wild.size)
+    return f, c
+
+
+def pops_plant(f, plan, planted=POPS_PLANTED):
+    """plan: {population: a value, or one value per planted site} -> a copy of the columns with them planted"""
+    out = [x.copy() for x in f]
+    for who, v in plan.items():
+        out[who][list(planted)] = v
+    return out
+
+
+def pops_runs(stat, k):
+    """-> [(name, plan)] of section 1 for one kernel: NaN in one ingroup population (for f_d as P1, P2 and P3 of trio 0), for the
+    trio kernels NaN in the outgroup, +inf in population 1, and the in-contract edge values cycled over the planted sites of
+    populations 0 and 1 (from different starts, so that a site's two values differ)"""
+    m = len(POPS_PLANTED)
+    edge = np.array(POPS_EDGE_VALUES)
+    runs = [(f"NaN in population {who}", {who: NAN}) for who in ((0, 1, 2) if stat == "fd" else (1 if k > 1 else 0,))]
+    if stat in ("dstat", "fd"):
+        runs.append(("NaN in the outgroup", {k - 1: NAN}))
+    runs.append(("+inf in population 1", {min(1, k - 1): INF}))
+    runs.append(("edge values", {0: edge[np.arange(m) % edge.size], min(1, k - 1): edge[(np.arange(m) + 3) % edge.size]} if k > 1
+                 else {0: edge[np.arange(m) % edge.size]}))
+    return runs
+
+
+# ---- denormal and zero sums in a row -----------------------------------------------------------------------------------------
+DENORMAL_CASES = [("dstat", 4), ("fd", 4), ("fst_hudson", 3), ("dxy", 3)]
+DENORMAL_N = 7 * 43  # 43 windows of 7 sites
+
+
+def denormal_columns(k, seed=0):
+    """Frequencies that are powers of two from 2^-1074 to 2^-1, or exactly 0, in groups of 7 sites (one 7-site window each), the
+    groups cycling through five shapes: (0) exponents from the whole range; (1) every frequency at most 2^-1030: sums are
+    denormal or underflow to 0; (2) every frequency 0: numerator and denominator sums are 0 and the ratio is 0.0, not NaN;
+    (3) one site with P1 = P2 = 2^-3, P3 = 2^-1 and the outgroup 2^-2 — its f_d numerator term is exactly 0, its
+    denominator terms are not — among sites of shape (1): a denormal numerator sum over a normal denominator sum, the quotient
+    denormal; (4) exponents around -540: products of two frequencies are denormal, of three are 0.  Counts 5 ... 40, one site in
+    eight uncounted for one population.  -> (f, c)"""
+    rng = np.random.default_rng([seed, k])
+    n = DENORMAL_N
+    f = [np.zeros(n) for _ in range(k)]
+    for g in range(n // 7):
+        s = slice(7 * g, 7 * g + 7)
+        shape = g % 5
+        for p in range(k):
+            if shape == 0:
+                e = rng.choice(np.array([-1074, -1073, -1060, -1023, -1022, -1021, -600, -537, -300, -52, -20, -3, -2, -1]), 7)
+            elif shape in (1, 3):
+                e = rng.integers(-1074, -1029, 7)
+            elif shape == 4:
+                e = rng.integers(-545, -530, 7)
+            else:
+                e = None
+            if e is not None:
+                f[p][s] = np.ldexp(1.0, e)
+                if shape != 3:
+                    f[p][s][rng.random(7) < 0.2] = 0.0
+        if shape == 3:
+            at = 7 * g + int(rng.integers(0, 7))
+            for p in range(k):
+                f[p][at] = 2.0 ** -2
+            f[0][at] = f[1][at] = 2.0 ** -3
+            f[2 if k > 3 else 1][at] = 2.0 ** -1
+    c = [rng.integers(5, 41, n, dtype=np.int32) for _ in range(k)]
+    for i in np.flatnonzero(rng.random(n) < 1 / 8):
+        c[int(rng.integers(0, k))][i] = 2
+    return f, c
+
+
+def denormal_tables():
+    n = DENORMAL_N
+    return [("one site", one_site_windows(range(n))), ("7 sites", windows_of([(a, a + 7) for a in range(0, n, 7)]))]
+
+
+# ---- counts at their extremes, K populations -------------------------------------------------------------------------------
+def extreme_counts_k(rng, n, minind, k):
+    """extreme_counts for k columns: every count from {INT32_MIN, -1, 0, minind - 1, minind, INT32_MAX}"""
+    vals = np.array(sorted({I32_MIN, -1, 0, max(minind - 1, I32_MIN), minind, I32_MAX}), dtype=np.int64).astype(np.int32)
+    return [rng.choice(vals, size=n) for _ in range(k)]
+
+
+REALISTIC_MININD = 1000
+
+
+def realistic_counts_k(rng, n, k):
+    """sample sizes of a large cohort: uniform in 1 ... 100 000 (about one count in a hundred is below REALISTIC_MININD)"""
+    return [rng.integers(1, 100_001, n, dtype=np.int32) for _ in range(k)]
+
+
+def count_case_columns(stat, k, minind, realistic=False):
+    """-> (f, c) of section 3 for one kernel: frequencies j/1024, counts at their extremes (or realistic ones)"""
+    rng = np.random.default_rng([31, k, minind % 1000, len(stat), int(realistic)])
+    f, _ = synth.exact_freq_columns(rng, POPS_N, k)
+    return f, (realistic_counts_k(rng, POPS_N, k) if realistic else extreme_counts_k(rng, POPS_N, minind, k))
+
+
+def counted_site_table(stat, k, c, minind, m=300):
+    """one-site windows at up to m sites counted for the call's first item and up to m counted for its last"""
+    items = pops_items(stat, k)
+    sites = set()
+    for item in (items[0], items[-1]):
+        at = np.flatnonzero(pops_counted(item, c, minind))
+        sites |= set(at[np.linspace(0, at.size - 1, min(m, at.size)).astype(np.int64)].tolist()) if at.size else set()
+    return one_site_windows(sorted(sites))
+
+
+def exact_site(stat, fs, cs):
+    """The header's per-site definition of a VALUE statistic in exact rationals, for one counted site of one item.  fs, cs: the
+    item's frequencies (floats, taken at their exact value) and counts.  -> [(value, scale)] per sum of POPS_SUMS[stat], the
+    scale being the Σ|.| of the definition's subterms"""
+    from fractions import Fraction
+    p = [Fraction(float(x)) for x in fs]
+    n = [int(x) for x in cs]
+    if stat == "pi":
+        v = (2 * p[0]) * (1 - p[0]) * Fraction(2 * n[0], 2 * n[0] - 1)
+        return [(v, abs(v))]
+    if stat == "fst_hudson":
+        h = [p[x] * (1 - p[x]) / (2 * n[x] - 1) for x in (0, 1)]
+        d2 = (p[0] - p[1]) ** 2
+        x, y = p[0] * (1 - p[1]), p[1] * (1 - p[0])
+        return [(d2 - h[0] - h[1], d2 + abs(h[0]) + abs(h[1])), (x + y, abs(x) + abs(y))]
+    assert stat == "fst"
+    n1, n2 = n
+    f1, f2 = p
+    npool = n1 + n2
+    fpool = (n1 * f1 + n2 * f2) / npool
+    b = (n1 * 2 * f1 * (1 - f1) + n2 * 2 * f2 * (1 - f2)) / (npool - 1)
+    div = Fraction(4 * n1 * n2, npool)
+    t = [4 * n1 * (f1 - fpool) ** 2 / div, 4 * n2 * (f2 - fpool) ** 2 / div, b / div]
+    a, sa = t[0] + t[1] - t[2], abs(t[0]) + abs(t[1]) + abs(t[2])
+    return [(a, sa), (a + b, sa + abs(b))]
+
+
+def assert_within_exact(got, exact, what):
+    """got: floats; exact: [(value, scale)] of exact_site -> every |got - value| <= 1e-9 scale + 1e-12, in exact arithmetic"""
+    from fractions import Fraction
+    for i, (g, (v, s)) in enumerate(zip(got, exact)):
+        g = float(g)
+        assert g == g and abs(g) != float("inf"), (what, i, g)
+        assert abs(Fraction(g) - v) <= Fraction(REL_A) * s + Fraction(ABS_A), (what, i, g, float(v), float(s))
+
+
+# ---- jackknife weights beyond 2^32 ---------------------------------------------------------------------------------------------
+JACK_U32_N_WIN = (129, 64 * 64 + 1)  # dstat_jack_shapes.N_WIN_PARTIALS_ABOVE_64
+JACK_U32_TRIOS = 4
+_jack_u32 = {}
+
+
+def jack_u32_rows(n_win, n_trios=JACK_U32_TRIOS):
+    """dstat_jack_shapes.synth_rows with every used block's weight n = 0xFFFFFFFF (about one block in seven unused: n = 0, NaN
+    sums): Σn passes 2^32 at the second used block.  Equal weights on purpose: h_j = g for every block and amplifies no
+    rounding.  Read-only, made once."""
+    import dstat_jack_shapes
+    if (n_win, n_trios) not in _jack_u32:
+        rows = dstat_jack_shapes.synth_rows(n_win, n_trios, seed=1).copy()
+        rows["n"] = np.where(rows["n"] > 0, 0xFFFFFFFF, 0).astype(np.uint32)
+        rows.setflags(write=False)
+        _jack_u32[(n_win, n_trios)] = rows
+    return _jack_u32[(n_win, n_trios)]
+
+
+JACK_U32_GOLDEN_N_WIN = JACK_U32_N_WIN[1]  # recorded by tests/golden/make_dstat_jack_u32_exact.py
+_jack_u32_exact = {}
+
+
+def jack_u32_exact(n_win):
+    """[JACK_U32_TRIOS][3] dicts (d, d_jack, se, z, n_sites, n_blocks) of jack_u32_rows(n_win) from the exact-rational model:
+    evaluated here for 129 blocks, read from tests/golden/dstat_jack_u32_exact.json (the same evaluation, recorded) for 4 097."""
+    import dstat_jack_model
+    import helpers
+    if n_win not in _jack_u32_exact:
+        if n_win == JACK_U32_GOLDEN_N_WIN:
+            rec = helpers.load_golden("dstat_jack_u32_exact.json")
+            assert rec["n_win"] == n_win and rec["n_trios"] == JACK_U32_TRIOS and rec["seed"] == 1
+            _jack_u32_exact[n_win] = [[{k: (float.fromhex(v) if isinstance(v, str) else v) for k, v in item.items()} for item in trio]
+                                      for trio in rec["items"]]
+        else:
+            rows = jack_u32_rows(n_win)
+            _jack_u32_exact[n_win] = [[{k: v for k, v in item.items() if k != "var"} for item in dstat_jack_model.jack_rows(rows[t], dstat_jack_model.jack_exact)]
+                                      for t in range(JACK_U32_TRIOS)]
+    return _jack_u32_exact[n_win]
