@@ -33,7 +33,7 @@
  *     has no counts: every site is counted; a NaN there stays in the rows of the pairs with that population.
  *   - genotypes: any int8 (non-missing is g >= 0, heterozygous g == 1, hetWindow.cpp:78-80); counts (n1, n2, nind[k]) and minind:
  *     any int32, compared as signed integers (dxyWindow.cpp:381).
- *   - the K-population entry points (pgt_dxy_pops / fst_pops / fst_hudson_pops / pi_pops / dstat_pops / fd_pops _reduce_dev;
+ *   - the K-population entry points (pgt_dxy_pops / fst_pops / fst_hudson_pops / pi_pops / dstat_pops / fd_pops / f3_pops _reduce_dev;
  *     tests/test_special_values_pops.py): a NaN or an infinity in ONE population's frequency at a COUNTED site reaches exactly the
  *     rows (and genome-wide lines) of the items — pairs, trios, the population itself — that hold that population, and of them
  *     exactly the windows that hold the site, with the value the per-site definition gives on the IEEE operands, every operation
@@ -69,7 +69,9 @@ extern "C" {
  * Still 6: pgt_fst_hudson_pops_tree_bytes / pgt_fst_hudson_pops_reduce_dev / pgt_fst_hudson_pops_reduce added (additive as well).
  * Still 6: pgt_dstat_row, pgt_dstat_total, pgt_dstat_pops_tree_bytes / pgt_dstat_pops_reduce_dev / pgt_dstat_pops_reduce added (additive as well).
  * Still 6: pgt_dstat_jack, pgt_dstat_jackknife_work_bytes / pgt_dstat_jackknife_dev / pgt_dstat_jackknife added (additive as well).
- * Still 6: pgt_fd_row, pgt_fd_total, pgt_fd_pops_tree_bytes / pgt_fd_pops_reduce_dev / pgt_fd_pops_reduce added (additive as well). */
+ * Still 6: pgt_fd_row, pgt_fd_total, pgt_fd_pops_tree_bytes / pgt_fd_pops_reduce_dev / pgt_fd_pops_reduce added (additive as well).
+ * Still 6: pgt_f3_row, pgt_f3_total, pgt_f3_jack, pgt_f3_pops_tree_bytes / pgt_f3_pops_reduce_dev / pgt_f3_pops_reduce and
+ *          pgt_f3_jackknife_work_bytes / pgt_f3_jackknife_dev / pgt_f3_jackknife added (additive as well). */
 #define PGT_ABI_VERSION 6
 
 enum {
@@ -150,6 +152,24 @@ typedef struct { /* block jackknife of one trio and topology: pgt_dstat_jackknif
     uint64_t n_sites;        /* counted sites of the used blocks */
     uint32_t n_blocks, pad_; /* used blocks (rows with n > 0) */
 } pgt_dstat_jack;
+
+typedef struct { /* f3 window row of one trio (i, j, k), each population as the target: pgt_f3_pops_reduce_dev (48 bytes) */
+    uint32_t start, end, mid, n;
+    double reserved_;       /* +0.0 */
+    double f3_i, f3_j, f3_k; /* the three window SUMS, full precision, at the offsets of pgt_dstat_row's bbaa / abba / baba:
+                                sum / n is f3(i; j, k), f3(j; i, k), f3(k; i, j) of the window (the caller divides) */
+} pgt_f3_row;
+
+typedef struct { /* the three sums of one trio over all its counted sites (40 bytes) */
+    double f3_i, f3_j, f3_k;
+    uint64_t neff, nskip;
+} pgt_f3_total;
+
+typedef struct { /* block jackknife of one trio and target: pgt_f3_jackknife_dev (48 bytes) */
+    double f3, f3_jack, se, z; /* f3 of all used blocks, its jackknife estimate, standard error, f3_jack / se */
+    uint64_t n_sites;          /* counted sites of the used blocks */
+    uint32_t n_blocks, pad_;   /* used blocks (rows with n > 0) */
+} pgt_f3_jack;
 
 /* ---- context ------------------------------------------------------------------------- */
 /* device: HIP ordinal, or -1 for the current device.  Fails (NULL, message via
@@ -538,6 +558,91 @@ int pgt_dstat_jackknife_dev(pgt_ctx *ctx, const pgt_dstat_row *rows, uint64_t n_
                             pgt_dstat_jack *out /* 3 * n_trios, item-major u = 3t + c */, size_t out_bytes,
                             void *work, size_t work_bytes, void *stream);
 int pgt_dstat_jackknife(pgt_ctx *ctx, const pgt_dstat_row *rows, uint64_t n_win, uint32_t n_trios, pgt_dstat_jack *out);
+
+/* ---- f3 of ALL trios of the populations, every population of a trio as the target --------------------------------------- */
+/* The 3-population statistic f3(C; A, B) = E[(c - a)(c - b)] (Reich et al. 2009; Patterson et al. 2012; treemix's threepop,
+ * ADMIXTOOLS' qp3Pop / f3 without the normalisation) with the unbiased estimator of the target's p^2, from each population's own
+ * (freq, nInd) columns — the input of pgt_fst_pops_reduce_dev — over ONE position column and ONE window table, in one pass
+ * (12 B/site/population).  A significantly negative f3(C; A, B) shows that C is admixed between relatives of A and B; with an
+ * outgroup O as the target, f3(O; A, B) measures the drift A and B share.  It has NO counterpart in the reference: the
+ * definition below is the contract.
+ * n_pops = K populations, 3 <= K <= 6.  ALL populations are equal: there is no outgroup.  A trio is (i, j, k) with
+ * i < j < k < K; trios are numbered in lexicographic order (0,1,2),(0,1,3),..,(0,1,K-1),(0,2,3),..; there are T = C(K, 3) of
+ * them: 1 / 4 / 10 / 20 at K = 3 / 4 / 5 / 6.  For trio (i, j, k) and site s:
+ *   counting   nind_i[s] >= minind && nind_j[s] >= minind && nind_k[s] >= minind   (signed int32 compare; minind >= 1 required,
+ *              PGT_EARG otherwise: 2 n - 1 >= 1 wherever a term is used); a site that is not counted is selected away, never
+ *              multiplied (its frequencies may be NaN, its counts 0 or negative)
+ *   per site   p_x = freq_x[s], n_x = nind_x[s] converted exactly; every operation rounded on its own, no contraction, in
+ *              exactly this grouping:
+ *                  h_x  = (p_x * (1 - p_x)) / (2*n_x - 1)       per population (the term of pgt_fst_hudson_pops_reduce_dev)
+ *                  d_ab = p_a - p_b                              per pair a < b
+ *                  s0 = d_ij*d_ik - h_i                          target i:  f3(i; j, k)
+ *                  s1 = (-d_ij)*d_jk - h_j                       target j:  f3(j; i, k)
+ *                  s2 = d_ik*d_jk - h_k                          target k:  f3(k; i, j)
+ *              One division per population and site, one subtraction per pair and site, shared by every trio that holds them.
+ *              The three values do not depend on which allele the columns report, provided all populations report the same one
+ *              (with frequencies that are multiples of 2^-10, bit for bit).  s0 + s1 = (p_i - p_j)^2 - h_i - h_j up to rounding:
+ *              the numerator of pgt_fst_hudson_pops_reduce_dev for the pair (i, j).
+ *   row        pgt_f3_row (48 bytes): f3_i / f3_j / f3_k = the three SUMS of s0 / s1 / s2 over the window's counted sites, each
+ *              from +0.0; n = their number (nskip = (hi - lo) - n); start / end / mid as pgt_dstat_row's are filled
+ *              (PGT_WIN_COORDS honoured); reserved_ = +0.0.  The means are NOT formed: f3 of the window is sum / n, the
+ *              caller's division.  The sums sit at the offsets of pgt_dstat_row's bbaa / abba / baba.
+ *   out        T * n_win rows, trio-major: out[t * n_win + w]
+ *   tot        DEVICE array of T pgt_f3_total (40 bytes: the same three sums over all counted sites, neff, nskip), or NULL;
+ *              n_win == 0 with tot: the global-only form
+ *   tree       pgt_f3_pops_tree_bytes(n_pops, n) bytes (0 for n_pops outside 3 ... 6): a node is 3 T doubles and T u32, the node
+ *              of pgt_dstat_pops_reduce_dev at one population more.    3 <= n_pops <= 6, n < 2^32.
+ * K = 7 (35 trios, 105 sums per node) is not offered: the running sums and the build's two register sets would not fit a wave.
+ * A one-site window carries exactly the bits of s0, s1 and s2 above.  Arguments, alignment, refusals (PGT_EARG; messages begin
+ * "pgt_f3_pops_reduce: " and name their argument; a refused call launches nothing and writes nothing), graph capture and the
+ * hints: those of pgt_dstat_pops_reduce_dev (asynchronous on `stream`, no allocation, no attribute call; pgt_set_max_window
+ * honoured, pgt_set_window_step ignored).  Trio isolation: the rows of a trio are a function, bit for bit, of its own three
+ * populations' columns and the window alone — not of the other populations, of K, or of the other rows of the table.  Sums are
+ * added in a fixed order that depends on the site index and the window alone (bitwise reproducible).  The site terms have both
+ * signs: against an exact evaluation a sum stays within 1e-9 * A + 1e-12, A the window's sum of |product| + |h|.  "Values the
+ * columns admit" above holds as for the other K-population calls (tests/test_special_values_f3.py).  Held to this definition,
+ * to an exact-rational fixture (tests/golden/f3_exact.json) and to a NumPy model (tests/f3_pops_model.py).  f3 normalised by the
+ * target's heterozygosity (qp3Pop's default), f4, user-chosen trio lists and K = 7 are not computed; standard errors and Z
+ * come from pgt_f3_jackknife_dev below.
+ * Host-buffer form: columns (host arrays of n_pops HOST pointers), table, rows and the T totals in host memory. */
+size_t pgt_f3_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites);
+int pgt_f3_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq,
+                           const int32_t *const *nind, uint32_t n_pops, uint64_t n, int minind,
+                           const pgt_win *win, uint64_t n_win, pgt_f3_row *out, size_t out_bytes,
+                           pgt_f3_total *tot, void *tree, size_t tree_bytes, void *stream);
+int pgt_f3_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq,
+                       const int32_t *const *nind, uint32_t n_pops, uint64_t n, int minind,
+                       const pgt_win *win, uint64_t n_win, pgt_f3_row *out, pgt_f3_total *tot);
+
+/* ---- block-jackknife standard error and Z of f3, all trios and targets -------------------------------------------------- */
+/* The block jackknife of pgt_dstat_jackknife_dev above — the same plan, workspace, phases and order of every addition — with a
+ * MEAN as the estimator, over the window rows pgt_f3_pops_reduce_dev wrote.
+ *   rows     DEVICE pointer to the n_trios x n_win trio-major table, 16-byte aligned; every window is one block; the caller
+ *            guarantees that the windows are DISJOINT.  Only n, f3_i, f3_j and f3_k of a row are read.
+ *   items    trio t has three items u = 3 t + c, c = 0 / 1 / 2 the target i / j / k; x_j = sum c of block j's row
+ *   blocks   block j is USED iff its row has n > 0; m_j = n.  Over the used blocks: g = their number, n = Σ m_j (u64, then f64),
+ *            X = Σ x_j.  A row that is not used is selected away, never added: its sums may be NaN
+ *   per item all in f64, every operation rounded on its own, no contraction:
+ *                mean(a, b)  = b != 0 ? a / b : 0
+ *                theta       = mean(X, n)
+ *                theta_-j    = mean(X - x_j, n - m_j)
+ *            and h_j, theta_J, tau_j and sigma^2 exactly as in pgt_dstat_jackknife_dev
+ *   out      pgt_f3_jack per item, item-major: f3 = theta, f3_jack = theta_J, se = sqrt(sigma^2),
+ *            z = se > 0 ? theta_J / se : NaN, n_blocks = g, n_sites = n, pad_ = 0.
+ *            g < 2: f3_jack = f3, se = z = NaN.  g == 0 (n_win == 0 included): f3 = f3_jack = 0, se = z = NaN.
+ *   work     DEVICE workspace of pgt_f3_jackknife_work_bytes(n_trios, n_win) bytes: the value pgt_dstat_jackknife_work_bytes
+ *            gives, 16-byte aligned.  Every byte of it that is read is written earlier in the same call.
+ * 1 <= n_trios <= 20.  Bitwise reproducible; an item's outputs are a function, bit for bit, of its own trio's rows alone: not of
+ * n_trios, not of the other trios' rows.  Against an exact evaluation f3, f3_jack and se stay within 1e-9 relative + 1e-12
+ * (tests/f3_jack_model.py).  Z < -3 is the customary threshold for "the target is admixed".
+ * Refusals (PGT_EARG, messages begin "pgt_f3_jackknife: " and name their argument; nothing is launched, nothing written): those
+ * of pgt_dstat_jackknife_dev.  Asynchronous on `stream`; no allocation and no attribute call: it can be captured into a graph.
+ * Host-buffer form: rows and out in host memory; synchronous. */
+size_t pgt_f3_jackknife_work_bytes(uint32_t n_trios, uint64_t n_win);
+int pgt_f3_jackknife_dev(pgt_ctx *ctx, const pgt_f3_row *rows, uint64_t n_win, uint32_t n_trios,
+                         pgt_f3_jack *out /* 3 * n_trios, item-major u = 3t + c */, size_t out_bytes,
+                         void *work, size_t work_bytes, void *stream);
+int pgt_f3_jackknife(pgt_ctx *ctx, const pgt_f3_row *rows, uint64_t n_win, uint32_t n_trios, pgt_f3_jack *out);
 
 /* ---- the sites common to K files, aligned on the device ------------------------------------------ */
 /* Replaces the two-file synchronisation of dxyWindow.cpp:315-331 (one current line per file; the file that is behind reads

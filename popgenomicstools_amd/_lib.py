@@ -38,6 +38,11 @@ FD_ROW_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("mid", "<u4"), ("n",
 FD_TOTAL_DTYPE = np.dtype([("num", "<f8"), ("fd_den", "<f8"), ("fdm_den", "<f8"), ("neff", "<u8"), ("nskip", "<u8")])
 DSTAT_JACK_DTYPE = np.dtype([("d", "<f8"), ("d_jack", "<f8"), ("se", "<f8"), ("z", "<f8"), ("n_sites", "<u8"),
                              ("n_blocks", "<u4"), ("pad_", "<u4")])  # pgt_dstat_jack: one trio and topology
+F3_ROW_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("mid", "<u4"), ("n", "<u4"),
+                         ("reserved_", "<f8"), ("f3_i", "<f8"), ("f3_j", "<f8"), ("f3_k", "<f8")])  # pgt_f3_row: the three SUMS of one trio
+F3_TOTAL_DTYPE = np.dtype([("f3_i", "<f8"), ("f3_j", "<f8"), ("f3_k", "<f8"), ("neff", "<u8"), ("nskip", "<u8")])
+F3_JACK_DTYPE = np.dtype([("f3", "<f8"), ("f3_jack", "<f8"), ("se", "<f8"), ("z", "<f8"), ("n_sites", "<u8"),
+                          ("n_blocks", "<u4"), ("pad_", "<u4")])  # pgt_f3_jack: one trio and target
 EXT_ROW_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("nsites", "<u4"), ("nbig", "<u4"),
                           ("position", "<u4"), ("pad_", "<u4"), ("value", "<f8")])
 SHARD_DTYPE = np.dtype([("win_begin", "<u8"), ("win_end", "<u8"), ("site_lo", "<u8"), ("site_hi", "<u8")])
@@ -49,6 +54,8 @@ assert DXY_ROW_DTYPE.itemsize == 24 and DXY_TOTAL_DTYPE.itemsize == 24 and SHARD
 assert SEG_DTYPE.itemsize == 16 and FST_TOTAL_DTYPE.itemsize == 32
 assert DSTAT_ROW_DTYPE.itemsize == 48 and DSTAT_TOTAL_DTYPE.itemsize == 40 and DSTAT_JACK_DTYPE.itemsize == 48
 assert FD_ROW_DTYPE.itemsize == 56 and FD_TOTAL_DTYPE.itemsize == 40
+assert F3_ROW_DTYPE.itemsize == 48 and F3_TOTAL_DTYPE.itemsize == 40 and F3_JACK_DTYPE.itemsize == 48
+assert [F3_ROW_DTYPE.fields[k][1] for k in ("f3_i", "f3_j", "f3_k")] == [DSTAT_ROW_DTYPE.fields[k][1] for k in ("bbaa", "abba", "baba")]
 
 # every symbol include/pgtwin.h declares (tests/test_abi.py checks the list against the header)
 SYMBOLS = [
@@ -71,6 +78,8 @@ SYMBOLS = [
     "pgt_dstat_pops_tree_bytes", "pgt_dstat_pops_reduce_dev", "pgt_dstat_pops_reduce",
     "pgt_dstat_jackknife_work_bytes", "pgt_dstat_jackknife_dev", "pgt_dstat_jackknife",
     "pgt_fd_pops_tree_bytes", "pgt_fd_pops_reduce_dev", "pgt_fd_pops_reduce",
+    "pgt_f3_pops_tree_bytes", "pgt_f3_pops_reduce_dev", "pgt_f3_pops_reduce",
+    "pgt_f3_jackknife_work_bytes", "pgt_f3_jackknife_dev", "pgt_f3_jackknife",
 ]
 PGT_TOK_CHR, PGT_TOK_SKIP, PGT_TOK_U32, PGT_TOK_F64, PGT_TOK_I8, PGT_TOK_I32, PGT_TOK_FREQ, PGT_TOK_CHR_PREFIX = range(8)
 
@@ -141,15 +150,16 @@ def load() -> C.CDLL:
     lib.pgt_af_tree_bytes.restype = sz
     lib.pgt_af_tree_bytes.argtypes = [u32, u64]
     lib.pgt_fst_af_reduce_dev.argtypes = [vp, vp, vp, vp, u32, u64, vp, u64, vp, sz, vp, sz, vp]
-    for stat in ("dxy", "fst", "pi", "fst_hudson", "dstat", "fd"):  # the K-population statistics over (freq, nInd) columns: one argument list each form
+    for stat in ("dxy", "fst", "pi", "fst_hudson", "dstat", "fd", "f3"):  # the K-population statistics over (freq, nInd) columns: one argument list each form
         getattr(lib, f"pgt_{stat}_pops_tree_bytes").restype = sz
         getattr(lib, f"pgt_{stat}_pops_tree_bytes").argtypes = [u32, u64]
         getattr(lib, f"pgt_{stat}_pops_reduce_dev").argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, u64, vp, sz, vp, vp, sz, vp]
         getattr(lib, f"pgt_{stat}_pops_reduce").argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, u64, vp, vp]
-    lib.pgt_dstat_jackknife_work_bytes.restype = sz
-    lib.pgt_dstat_jackknife_work_bytes.argtypes = [u32, u64]
-    lib.pgt_dstat_jackknife_dev.argtypes = [vp, vp, u64, u32, vp, sz, vp, sz, vp]
-    lib.pgt_dstat_jackknife.argtypes = [vp, vp, u64, u32, vp]
+    for stat in ("dstat", "f3"):  # the block jackknife of the two row types: one argument list each form
+        getattr(lib, f"pgt_{stat}_jackknife_work_bytes").restype = sz
+        getattr(lib, f"pgt_{stat}_jackknife_work_bytes").argtypes = [u32, u64]
+        getattr(lib, f"pgt_{stat}_jackknife_dev").argtypes = [vp, vp, u64, u32, vp, sz, vp, sz, vp]
+        getattr(lib, f"pgt_{stat}_jackknife").argtypes = [vp, vp, u64, u32, vp]
     lib.pgt_align_segments.argtypes = [vp, vp, vp, u32, vp, sz, C.POINTER(sz)]
     lib.pgt_align_workspace_bytes.restype = sz
     lib.pgt_align_workspace_bytes.argtypes = [u32, u64]

@@ -432,7 +432,7 @@ pgt_ctx *pgt_open(int device) {
     std::string init_err;
     if (init_kernels(&init_err) != PGT_OK || init_af_kernels(&init_err) != PGT_OK || init_dxy_pops_kernels(&init_err) != PGT_OK ||
         init_fst_pops_kernels(&init_err) != PGT_OK || init_dstat_pops_kernels(&init_err) != PGT_OK ||
-        init_fd_pops_kernels(&init_err) != PGT_OK) {
+        init_fd_pops_kernels(&init_err) != PGT_OK || init_f3_pops_kernels(&init_err) != PGT_OK) {
         set_global_error("pgt_open: " + init_err);
         return nullptr;
     }
@@ -753,24 +753,52 @@ int pgt_fd_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *cons
                           ctx->hints);
 }
 
-// Block jackknife of the rows above: its own checks (no columns, no window table), the message prefix of both forms
+// f3 of ALL trios of the populations, each population of a trio as the target: one more PopsStat; three sums per trio as D has,
+// so the tree is the D call's at one population more (C(n, 3) = C((n + 1) - 1, 3))
+static uint64_t pops_all_trios(uint32_t n_pops) { return (uint64_t)n_pops * (n_pops - 1) * (n_pops - 2) / 6; }
+size_t pgt_f3_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites) {
+    if (n_pops < 3 || n_pops > 6) return 0;
+    return pops_tree_view(tree_layout(PGT_STAT_FST, n_sites), (int)pops_all_trios(n_pops), 3, nullptr, 0).bytes;
+}
+// minind >= 1: 2 nind - 1 >= 1 at every counted site
+static const PopsStat kF3Pops = {"pgt_f3_pops_reduce", 3, true, pops_all_trios, "n_trios", sizeof(pgt_f3_row), pgt_f3_pops_tree_bytes, 6};
+
+int pgt_f3_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind,
+                           uint32_t n_pops, uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_f3_row *out,
+                           size_t out_bytes, pgt_f3_total *tot, void *tree, size_t tree_bytes, void *stream) {
+    PGT_USE_DEVICE(ctx);
+    bool launch;
+    if (int rc = pops_check_dev(ctx, kF3Pops, pos, freq, nind, n_pops, n, minind, win, n_win, out, out_bytes, tot, tree, tree_bytes, &launch)) return rc;
+    if (!launch) return PGT_OK;
+    const EvSet e = events_for(ctx);
+    return launch_f3_pops(pos, freq, nind, n_pops, n, minind, win, n_win, out, tot, tree, stream, e.b0, e.b1, e.q1, &ctx->error,
+                          ctx->hints);
+}
+
+// Block jackknife of the rows above: its own checks (no columns, no window table), the message prefix of both forms.
+// One text for the two estimators (D: pgt_dstat_jackknife; the mean of f3: pgt_f3_jackknife): rows and results of both are 48
+// bytes, so plan, workspace and every check are the same, under the entry's own prefix.
 size_t pgt_dstat_jackknife_work_bytes(uint32_t n_trios, uint64_t n_win) {
     if (n_trios < 1 || n_trios > kJackMaxTrios) return 0;
     return jack_work(n_trios, n_win).bytes;
 }
+size_t pgt_f3_jackknife_work_bytes(uint32_t n_trios, uint64_t n_win) { return pgt_dstat_jackknife_work_bytes(n_trios, n_win); }
 
-static int jack_check_range(pgt_ctx *ctx, uint32_t n_trios, uint64_t n_win) {
+static int jack_check_range(pgt_ctx *ctx, const std::string &who, uint32_t n_trios, uint64_t n_win) {
     if (n_trios < 1 || n_trios > kJackMaxTrios)
-        return ctx_fail(ctx, PGT_EARG, "pgt_dstat_jackknife: n_trios must be 1 ... " + std::to_string(kJackMaxTrios));
-    if (n_win > (UINT64_MAX / sizeof(pgt_dstat_row)) / n_trios) return ctx_fail(ctx, PGT_EARG, "pgt_dstat_jackknife: n_trios * n_win overflows");
+        return ctx_fail(ctx, PGT_EARG, who + "n_trios must be 1 ... " + std::to_string(kJackMaxTrios));
+    if (n_win > (UINT64_MAX / sizeof(pgt_dstat_row)) / n_trios) return ctx_fail(ctx, PGT_EARG, who + "n_trios * n_win overflows");
     return PGT_OK;
 }
+static_assert(sizeof(pgt_f3_row) == sizeof(pgt_dstat_row) && sizeof(pgt_f3_jack) == sizeof(pgt_dstat_jack), "one set of jackknife checks");
 
-int pgt_dstat_jackknife_dev(pgt_ctx *ctx, const pgt_dstat_row *rows, uint64_t n_win, uint32_t n_trios, pgt_dstat_jack *out,
-                            size_t out_bytes, void *work, size_t work_bytes, void *stream) {
-    PGT_USE_DEVICE(ctx);
-    if (int rc = jack_check_range(ctx, n_trios, n_win)) return rc;
-    const std::string who = "pgt_dstat_jackknife: ";
+enum JackEstimator { kJackD, kJackF3Mean };
+static const char *jack_who(JackEstimator est) { return est == kJackD ? "pgt_dstat_jackknife: " : "pgt_f3_jackknife: "; }
+
+static int jackknife_dev(pgt_ctx *ctx, JackEstimator est, const void *rows, uint64_t n_win, uint32_t n_trios, void *out,
+                         size_t out_bytes, void *work, size_t work_bytes, void *stream) {
+    const std::string who = jack_who(est);
+    if (int rc = jack_check_range(ctx, who, n_trios, n_win)) return rc;
     if (n_win && !rows) return ctx_fail(ctx, PGT_EARG, who + "rows is NULL");
     if (!out) return ctx_fail(ctx, PGT_EARG, who + "out is NULL");
     if (!work) return ctx_fail(ctx, PGT_EARG, who + "work is NULL");
@@ -788,7 +816,22 @@ int pgt_dstat_jackknife_dev(pgt_ctx *ctx, const pgt_dstat_row *rows, uint64_t n_
         ctx->have_timing = true;
         ctx->timing_query_only = true;
     }
-    return launch_dstat_jackknife(rows, n_win, n_trios, out, work, stream, q0, q1, &ctx->error);
+    if (est == kJackF3Mean)
+        return launch_f3_jackknife(static_cast<const pgt_f3_row *>(rows), n_win, n_trios, static_cast<pgt_f3_jack *>(out), work, stream, q0, q1, &ctx->error);
+    return launch_dstat_jackknife(static_cast<const pgt_dstat_row *>(rows), n_win, n_trios, static_cast<pgt_dstat_jack *>(out), work, stream, q0, q1, &ctx->error);
+}
+
+int pgt_dstat_jackknife_dev(pgt_ctx *ctx, const pgt_dstat_row *rows, uint64_t n_win, uint32_t n_trios, pgt_dstat_jack *out,
+                            size_t out_bytes, void *work, size_t work_bytes, void *stream) {
+    PGT_USE_DEVICE(ctx);
+    return jackknife_dev(ctx, kJackD, rows, n_win, n_trios, out, out_bytes, work, work_bytes, stream);
+}
+
+// out: 3 n_trios items, u = 3 t + c with c the target i / j / k of trio t
+int pgt_f3_jackknife_dev(pgt_ctx *ctx, const pgt_f3_row *rows, uint64_t n_win, uint32_t n_trios, pgt_f3_jack *out,
+                         size_t out_bytes, void *work, size_t work_bytes, void *stream) {
+    PGT_USE_DEVICE(ctx);
+    return jackknife_dev(ctx, kJackF3Mean, rows, n_win, n_trios, out, out_bytes, work, work_bytes, stream);
 }
 
 size_t pgt_align_workspace_bytes(uint32_t n_files, uint64_t n_rows_file0) {
@@ -1211,11 +1254,18 @@ int pgt_fd_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *f
     return pops_reduce_host(ctx, kFdPops, pgt_fd_pops_reduce_dev, pos, freq, nind, n_pops, n, minind, win, n_win, out, tot);
 }
 
-/* block jackknife of a host table of ABBA-BABA rows: rows up, the device form on the cached workspace, 3 n_trios results down */
-int pgt_dstat_jackknife(pgt_ctx *ctx, const pgt_dstat_row *rows, uint64_t n_win, uint32_t n_trios, pgt_dstat_jack *out) {
+/* f3 of all trios: the host-buffer form, as pgt_dstat_pops_reduce */
+int pgt_f3_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
+                       uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_f3_row *out, pgt_f3_total *tot) {
     PGT_USE_DEVICE(ctx);
-    if (int rc = jack_check_range(ctx, n_trios, n_win)) return rc;
-    if ((n_win && !rows) || !out) return ctx_fail(ctx, PGT_EARG, "pgt_dstat_jackknife: NULL argument");
+    return pops_reduce_host(ctx, kF3Pops, pgt_f3_pops_reduce_dev, pos, freq, nind, n_pops, n, minind, win, n_win, out, tot);
+}
+
+/* block jackknife of a host table of rows: rows up, the device form on the cached workspace, 3 n_trios results down */
+static int jackknife_host(pgt_ctx *ctx, JackEstimator est, const void *rows, uint64_t n_win, uint32_t n_trios, void *out) {
+    const std::string who = jack_who(est);
+    if (int rc = jack_check_range(ctx, who, n_trios, n_win)) return rc;
+    if ((n_win && !rows) || !out) return ctx_fail(ctx, PGT_EARG, who + "NULL argument");
     const size_t row_bytes = (size_t)n_trios * n_win * sizeof(pgt_dstat_row), out_bytes = (size_t)n_trios * kJackTopologies * sizeof(pgt_dstat_jack);
     const size_t work_bytes = jack_work(n_trios, n_win).bytes;
     void *drows = nullptr, *dwork = nullptr, *dout = nullptr;
@@ -1224,10 +1274,19 @@ int pgt_dstat_jackknife(pgt_ctx *ctx, const pgt_dstat_row *rows, uint64_t n_win,
     if (int rc = workspace(ctx, HostIo::kTot, out_bytes, &dout)) return rc;
     if (row_bytes)
         if (int rc = hip_check(ctx, hipMemcpy(drows, rows, row_bytes, hipMemcpyHostToDevice), "upload rows")) return rc;
-    if (int rc = pgt_dstat_jackknife_dev(ctx, static_cast<const pgt_dstat_row *>(drows), n_win, n_trios, static_cast<pgt_dstat_jack *>(dout),
-                                         out_bytes, dwork, work_bytes, nullptr)) return rc;
+    if (int rc = jackknife_dev(ctx, est, drows, n_win, n_trios, dout, out_bytes, dwork, work_bytes, nullptr)) return rc;
     if (int rc = hip_check(ctx, hipStreamSynchronize(nullptr), "kernels")) return rc;
     return hip_check(ctx, hipMemcpy(out, dout, out_bytes, hipMemcpyDeviceToHost), "download jackknife");
+}
+
+int pgt_dstat_jackknife(pgt_ctx *ctx, const pgt_dstat_row *rows, uint64_t n_win, uint32_t n_trios, pgt_dstat_jack *out) {
+    PGT_USE_DEVICE(ctx);
+    return jackknife_host(ctx, kJackD, rows, n_win, n_trios, out);
+}
+
+int pgt_f3_jackknife(pgt_ctx *ctx, const pgt_f3_row *rows, uint64_t n_win, uint32_t n_trios, pgt_f3_jack *out) {
+    PGT_USE_DEVICE(ctx);
+    return jackknife_host(ctx, kJackF3Mean, rows, n_win, n_trios, out);
 }
 
 /* ---------------- window tables built on the device ---------------- */

@@ -12,6 +12,13 @@
 //     sigma^2  = (1 / g) Σ_j (tau_j - theta_J)^2 / (h_j - 1)
 // Every operation is one __d*_rn intrinsic (nothing is contracted); a block that is not used is selected away, never added.
 //
+// A second ESTIMATOR runs through the same phases (pgt_f3_jackknife_dev, over the rows of pgt_f3_pops_reduce_dev): a MEAN
+// instead of a ratio of two sums — item u = 3 t + c takes x_j = sum c of the row (the target i / j / k of the trio), and with
+// mean(a, b) = b != 0 ? a / b : 0:     theta = mean(X, n)     theta_-j = mean(X - x_j, n - m_j)     (n, m_j as f64)
+// h_j, theta_J, tau_j and sigma^2 as above.  The estimator (struct D, struct F3Mean below) is a template parameter of the phases
+// that look at an estimate; the totals, the plan, the chunking, readd(), the workspace layout and the order of every addition are
+// common, and both row types are 48 bytes with n and the three sums at the same offsets.
+//
 // Three dependent reductions over the rows and one closing kernel, all on the plan of jack_plan(n_win) (pgt_internal.h):
 //   phase 1  jack_totals_kernel   per wave Σbbaa, Σabba, Σbaba, Σn, g of its chunks                 -> 5 words per wave
 //   phase 2  jack_drop_kernel     re-adds phase 1's partials of its trio (theta), then per topology
@@ -29,6 +36,8 @@
 // Every partial a later phase reads was written by the phase before it in the same call (all n_partials waves of a trio
 // store theirs, a wave without a used block stores zeros).
 #include <hip/hip_runtime.h>
+
+#include <cstddef>
 
 #include "pgt_device.h"
 #include "pgt_internal.h"
@@ -65,6 +74,32 @@ __device__ __forceinline__ double ratio(double a, double b) {
 // (x, y) of topology c from a row's, or the totals', three sums {bbaa, abba, baba}
 __device__ __forceinline__ double topo_x(int c, double bbaa, double abba) { return c == 0 ? abba : bbaa; }
 __device__ __forceinline__ double topo_y(int c, double abba, double baba) { return c == 2 ? abba : baba; }
+
+// ---- the estimators: what theta is of three sums and a weight; everything else in this file is common to them -------------------
+// theta(c, s, n): item c's estimate from the sums s[3] and the weight n of the used blocks; theta_drop(c, s, n, x0, x1, x2, m):
+// the same with one block (its three sums, its weight m as f64) taken out.
+struct D {  // Patterson's D of topology c: ratio(x, y) of two of the three sums (the head of this file)
+    using Row = pgt_dstat_row;
+    using Out = pgt_dstat_jack;
+    static __device__ __forceinline__ double theta(int c, const double *s, double) { return ratio(topo_x(c, s[0], s[1]), topo_y(c, s[1], s[2])); }
+    static __device__ __forceinline__ double theta_drop(int c, const double *s, double, double bbaa, double abba, double baba, double) {
+        return ratio(__dsub_rn(topo_x(c, s[0], s[1]), topo_x(c, bbaa, abba)), __dsub_rn(topo_y(c, s[1], s[2]), topo_y(c, abba, baba)));
+    }
+    static __device__ __forceinline__ void set(Out &r, double th, double th_j, double se, double z) { r.d = th; r.d_jack = th_j; r.se = se; r.z = z; }
+};
+// f3 with target c of the trio (pgt_f3_jackknife_dev): a MEAN, x_j = sum c of the row, with mean(a, b) = b != 0 ? a / b : 0
+//     theta = mean(X, n)                              theta_-j = mean(X - x_j, n - m_j)        (n, m_j as f64)
+__device__ __forceinline__ double mean(double a, double b) { return b != 0.0 ? __ddiv_rn(a, b) : 0.0; }
+struct F3Mean {
+    using Row = pgt_f3_row;
+    using Out = pgt_f3_jack;
+    static __device__ __forceinline__ double pick(int c, double x0, double x1, double x2) { return c == 0 ? x0 : (c == 1 ? x1 : x2); }
+    static __device__ __forceinline__ double theta(int c, const double *s, double n) { return mean(pick(c, s[0], s[1], s[2]), n); }
+    static __device__ __forceinline__ double theta_drop(int c, const double *s, double n, double x0, double x1, double x2, double m) {
+        return mean(__dsub_rn(pick(c, s[0], s[1], s[2]), pick(c, x0, x1, x2)), __dsub_rn(n, m));
+    }
+    static __device__ __forceinline__ void set(Out &r, double th, double th_j, double se, double z) { r.f3 = th; r.f3_jack = th_j; r.se = se; r.z = z; }
+};
 
 // Σ of n_partials doubles in index order per lane (l, l + 64, ..), then the butterfly: the same bits in every lane of every wave
 __device__ __forceinline__ double readd(const double *p, uint32_t n_partials, int lane) {
@@ -121,6 +156,11 @@ __device__ __forceinline__ void for_rows(const JackArgs &a, uint32_t trio, uint3
     }
 }
 static_assert(sizeof(pgt_dstat_row) == 48 && sizeof(pgt_dstat_jack) == 48, "the row layout the loads above assume");
+// the rows of pgt_f3_pops_reduce_dev go through the same loads: n and the three sums sit where pgt_dstat_row has them
+static_assert(sizeof(pgt_f3_row) == sizeof(pgt_dstat_row) && sizeof(pgt_f3_jack) == sizeof(pgt_dstat_jack), "one row loader, one result layout");
+static_assert(offsetof(pgt_f3_row, n) == offsetof(pgt_dstat_row, n) && offsetof(pgt_f3_row, f3_i) == offsetof(pgt_dstat_row, bbaa) &&
+              offsetof(pgt_f3_row, f3_j) == offsetof(pgt_dstat_row, abba) && offsetof(pgt_f3_row, f3_k) == offsetof(pgt_dstat_row, baba),
+              "the three sums of an f3 row at the offsets of bbaa / abba / baba");
 
 // wave p of trio blockIdx.y; -1: a wave that pads the last workgroup (it returns: no barrier is ever used)
 __device__ __forceinline__ int64_t my_partial(const JackArgs &a) {
@@ -160,6 +200,7 @@ __global__ __launch_bounds__(256) void jack_totals_kernel(JackArgs a) {
 }
 
 // ---- phase 2: Σ (1 - m_j / n) theta_-j ---------------------------------------------------------------------------------------
+template <class Est>
 __global__ __launch_bounds__(256) void jack_drop_kernel(JackArgs a) {
     const int lane = threadIdx.x & (kWave - 1);
     const uint32_t trio = blockIdx.y;
@@ -172,8 +213,7 @@ __global__ __launch_bounds__(256) void jack_drop_kernel(JackArgs a) {
         const double w = __dsub_rn(1.0, __ddiv_rn((double)m, t.n));
 #pragma unroll
         for (int c = 0; c < kJackTopologies; ++c) {
-            const double th = ratio(__dsub_rn(topo_x(c, t.s[0], t.s[1]), topo_x(c, bbaa, abba)),
-                                    __dsub_rn(topo_y(c, t.s[1], t.s[2]), topo_y(c, abba, baba)));
+            const double th = Est::theta_drop(c, t.s, t.n, bbaa, abba, baba, (double)m);
             acc[c] = __dadd_rn(acc[c], used ? __dmul_rn(w, th) : 0.0);
         }
     });
@@ -185,13 +225,15 @@ __global__ __launch_bounds__(256) void jack_drop_kernel(JackArgs a) {
 }
 
 // theta and theta_J of topology c from the re-added partials (the same bits wherever it is called)
+template <class Est>
 __device__ __forceinline__ void estimates(const JackArgs &a, const Totals &t, uint32_t trio, int c, int lane, double *theta, double *theta_j) {
-    *theta = ratio(topo_x(c, t.s[0], t.s[1]), topo_y(c, t.s[1], t.s[2]));
+    *theta = Est::theta(c, t.s, t.n);
     const double drop = readd(a.drop + ((uint64_t)trio * kJackTopologies + c) * a.n_partials, a.n_partials, lane);
     *theta_j = __dsub_rn(__dmul_rn((double)t.g, *theta), drop);
 }
 
 // ---- phase 3: Σ (tau_j - theta_J)^2 / (h_j - 1) -----------------------------------------------------------------------------
+template <class Est>
 __global__ __launch_bounds__(256) void jack_var_kernel(JackArgs a) {
     const int lane = threadIdx.x & (kWave - 1);
     const uint32_t trio = blockIdx.y;
@@ -201,13 +243,12 @@ __global__ __launch_bounds__(256) void jack_var_kernel(JackArgs a) {
     const Totals t = read_totals(a, trio, lane);
     double theta[kJackTopologies], theta_j[kJackTopologies], acc[kJackTopologies] = {0.0, 0.0, 0.0};
 #pragma unroll
-    for (int c = 0; c < kJackTopologies; ++c) estimates(a, t, trio, c, lane, &theta[c], &theta_j[c]);
+    for (int c = 0; c < kJackTopologies; ++c) estimates<Est>(a, t, trio, c, lane, &theta[c], &theta_j[c]);
     for_rows(a, trio, p, lane, [&](bool used, uint32_t m, double bbaa, double abba, double baba) {
         const double hm1 = __dsub_rn(__ddiv_rn(t.n, (double)m), 1.0);  // an unused block: inf, selected away below
 #pragma unroll
         for (int c = 0; c < kJackTopologies; ++c) {
-            const double th = ratio(__dsub_rn(topo_x(c, t.s[0], t.s[1]), topo_x(c, bbaa, abba)),
-                                    __dsub_rn(topo_y(c, t.s[1], t.s[2]), topo_y(c, abba, baba)));
+            const double th = Est::theta_drop(c, t.s, t.n, bbaa, abba, baba, (double)m);
             const double tau = __dadd_rn(theta[c], __dmul_rn(hm1, __dsub_rn(theta[c], th)));
             const double dv = __dsub_rn(tau, theta_j[c]);
             acc[c] = __dadd_rn(acc[c], used ? __ddiv_rn(__dmul_rn(dv, dv), hm1) : 0.0);
@@ -221,7 +262,8 @@ __global__ __launch_bounds__(256) void jack_var_kernel(JackArgs a) {
 }
 
 // ---- close: one wave per item ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void jack_close_kernel(JackArgs a, pgt_dstat_jack *__restrict__ out) {
+template <class Est>
+__global__ __launch_bounds__(256) void jack_close_kernel(JackArgs a, typename Est::Out *__restrict__ out) {
     const int lane = threadIdx.x & (kWave - 1);
     const uint32_t u = blockIdx.x * (blockDim.x >> 6) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (u >= a.n_trios * kJackTopologies) return;
@@ -229,28 +271,25 @@ __global__ __launch_bounds__(256) void jack_close_kernel(JackArgs a, pgt_dstat_j
     const int c = (int)(u % kJackTopologies);
     const Totals t = read_totals(a, trio, lane);  // without a partial (n_win == 0): zeros
     double theta, theta_j;
-    estimates(a, t, trio, c, lane, &theta, &theta_j);
+    estimates<Est>(a, t, trio, c, lane, &theta, &theta_j);
     const double vs = readd(a.var + ((uint64_t)trio * kJackTopologies + c) * a.n_partials, a.n_partials, lane);
-    pgt_dstat_jack r;
-    r.d = theta;
+    typename Est::Out r;
     r.n_sites = t.n_sites;
     r.n_blocks = t.g;
     r.pad_ = 0;
+    const double nan = __longlong_as_double(0x7FF8000000000000ll);
     if (t.g >= 2) {
-        r.d_jack = theta_j;
-        r.se = __dsqrt_rn(__ddiv_rn(vs, (double)t.g));
-        r.z = r.se > 0.0 ? __ddiv_rn(theta_j, r.se) : __longlong_as_double(0x7FF8000000000000ll);
+        const double se = __dsqrt_rn(__ddiv_rn(vs, (double)t.g));
+        Est::set(r, theta, theta_j, se, se > 0.0 ? __ddiv_rn(theta_j, se) : nan);
     } else {
-        r.d_jack = theta;
-        r.se = r.z = __longlong_as_double(0x7FF8000000000000ll);
+        Est::set(r, theta, theta, nan, nan);
     }
     if (lane == 0) out[u] = r;
 }
 
-}  // namespace
-
-int launch_dstat_jackknife(const pgt_dstat_row *rows, uint64_t n_win, uint32_t n_trios, pgt_dstat_jack *out, void *work,
-                           void *stream, void *ev_query0, void *ev_query1, std::string *err) {
+template <class Est>
+int launch_jackknife(const typename Est::Row *rows, uint64_t n_win, uint32_t n_trios, typename Est::Out *out, void *work,
+                     void *stream, void *ev_query0, void *ev_query1, std::string *err) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     const JackPlan plan = jack_plan(n_win);
     const JackWork w = jack_work(n_trios, n_win);
@@ -269,14 +308,27 @@ int launch_dstat_jackknife(const pgt_dstat_row *rows, uint64_t n_win, uint32_t n
         const dim3 grid((plan.n_partials + 3) / 4, n_trios);
         hipLaunchKernelGGL(jack_totals_kernel, grid, dim3(256), 0, s, a);
         if (int rc = hip_fail(hipGetLastError(), "jack_totals_kernel", err)) return rc;
-        hipLaunchKernelGGL(jack_drop_kernel, grid, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(jack_drop_kernel<Est>, grid, dim3(256), 0, s, a);
         if (int rc = hip_fail(hipGetLastError(), "jack_drop_kernel", err)) return rc;
-        hipLaunchKernelGGL(jack_var_kernel, grid, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(jack_var_kernel<Est>, grid, dim3(256), 0, s, a);
         if (int rc = hip_fail(hipGetLastError(), "jack_var_kernel", err)) return rc;
     }
-    hipLaunchKernelGGL(jack_close_kernel, dim3((n_trios * kJackTopologies + 3) / 4), dim3(256), 0, s, a, out);
+    hipLaunchKernelGGL(jack_close_kernel<Est>, dim3((n_trios * kJackTopologies + 3) / 4), dim3(256), 0, s, a, out);
     if (int rc = hip_fail(hipGetLastError(), "jack_close_kernel", err)) return rc;
     return record_event(ev_query1, s, err);
+}
+
+}  // namespace
+
+int launch_dstat_jackknife(const pgt_dstat_row *rows, uint64_t n_win, uint32_t n_trios, pgt_dstat_jack *out, void *work,
+                           void *stream, void *ev_query0, void *ev_query1, std::string *err) {
+    return launch_jackknife<D>(rows, n_win, n_trios, out, work, stream, ev_query0, ev_query1, err);
+}
+
+// the rows of pgt_f3_pops_reduce_dev: item u = 3 t + c is f3 with population c (i / j / k) of trio t as the target
+int launch_f3_jackknife(const pgt_f3_row *rows, uint64_t n_win, uint32_t n_trios, pgt_f3_jack *out, void *work,
+                        void *stream, void *ev_query0, void *ev_query1, std::string *err) {
+    return launch_jackknife<F3Mean>(rows, n_win, n_trios, out, work, stream, ev_query0, ev_query1, err);
 }
 
 }  // namespace pgt

@@ -220,6 +220,9 @@ inline JackWork jack_work(uint32_t n_trios, uint64_t n_win) {
 // 1 <= n_trios <= kJackMaxTrios and every pointer checked by the caller; ev_*: hipEvent_t as void* or NULL
 int launch_dstat_jackknife(const pgt_dstat_row *rows, uint64_t n_win, uint32_t n_trios, pgt_dstat_jack *out, void *work,
                            void *stream, void *ev_query0, void *ev_query1, std::string *err);
+// the same phases with the mean estimator (F3Mean) over the rows of pgt_f3_pops_reduce_dev; plan and workspace as above
+int launch_f3_jackknife(const pgt_f3_row *rows, uint64_t n_win, uint32_t n_trios, pgt_f3_jack *out, void *work,
+                        void *stream, void *ev_query0, void *ev_query1, std::string *err);
 
 // Speed-only hints of a context (pgt_set_max_window, pgt_set_window_step); 0 = unknown.
 struct Hints {
@@ -306,6 +309,14 @@ int launch_fd_pops(const uint32_t *pos, const double *const *freq, const int32_t
                    void *tree, void *stream, void *ev_build0, void *ev_build1, void *ev_query1, std::string *err,
                    const Hints &hints);
 
+// pgt_f3_pops_kernels.hip: f3 of ALL trios of the populations (no outgroup), each population of a trio as the target;
+// tot = C(n_pops, 3) device totals or NULL; 3 <= n_pops <= 6 and minind >= 1 (checked by the caller); out = one table of n_win
+// rows per trio, in lexicographic trio order; the tree has launch_dstat_pops' layout at n_pops + 1
+int launch_f3_pops(const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
+                   uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_f3_row *out, pgt_f3_total *tot,
+                   void *tree, void *stream, void *ev_build0, void *ev_build1, void *ev_query1, std::string *err,
+                   const Hints &hints);
+
 // pgt_kernels.hip: pi per population, 1 <= n_pops <= 8 and minind >= 1 (checked by the caller); out = n_pops tables of
 // n_win rows, tot = n_pops device totals or NULL; tree = n_pops trees of tree_layout(PGT_STAT_DXY, n).bytes each
 int launch_pi_pops(const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
@@ -360,6 +371,7 @@ int init_dxy_pops_kernels(std::string *err);  // pgt_dxy_pops_kernels.hip
 int init_fst_pops_kernels(std::string *err);  // pgt_fst_pops_kernels.hip
 int init_dstat_pops_kernels(std::string *err);  // pgt_dstat_pops_kernels.hip
 int init_fd_pops_kernels(std::string *err);     // pgt_fd_pops_kernels.hip
+int init_f3_pops_kernels(std::string *err);     // pgt_f3_pops_kernels.hip
 
 // thread-local message for the ctx-less entry points
 void set_global_error(const std::string &msg);

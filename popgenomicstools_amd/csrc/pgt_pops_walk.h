@@ -35,6 +35,7 @@ constexpr int kRadix1 = kRadix / kPieces;  // level-1 nodes per level-2 node
 static_assert(kPieces == 4, "the build walks a leaf as two pairs of pieces");
 
 constexpr int trio_count(int np) { return (np - 1) * (np - 2) * (np - 3) / 6; }  // C(np - 1, 3): ingroup trios, the last population is the outgroup
+constexpr int all_trio_count(int np) { return np * (np - 1) * (np - 2) / 6; }     // C(np, 3): the trios of ALL populations (f3: no outgroup)
 
 struct PopCols {
     const double *f[kPopsMaxPops];

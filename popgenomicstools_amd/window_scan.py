@@ -20,7 +20,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import (DSTAT_JACK_DTYPE, DSTAT_ROW_DTYPE, DSTAT_TOTAL_DTYPE, DXY_ROW_DTYPE, DXY_TOTAL_DTYPE, EXT_ROW_DTYPE, FD_ROW_DTYPE, FD_TOTAL_DTYPE, FST_ROW_DTYPE, FST_TOTAL_DTYPE, HET_ROW_DTYPE, PGT_EXT_IHS,
+from ._lib import (DSTAT_JACK_DTYPE, DSTAT_ROW_DTYPE, DSTAT_TOTAL_DTYPE, DXY_ROW_DTYPE, DXY_TOTAL_DTYPE, EXT_ROW_DTYPE, F3_JACK_DTYPE, F3_ROW_DTYPE, F3_TOTAL_DTYPE, FD_ROW_DTYPE, FD_TOTAL_DTYPE, FST_ROW_DTYPE, FST_TOTAL_DTYPE, HET_ROW_DTYPE, PGT_EXT_IHS,
                    PGT_EXT_XP_MAX, PGT_EXT_XP_MIN, PGT_STAT_DXY, PGT_STAT_EXT, PGT_STAT_FST, PGT_STAT_HET,
                    SEG_DTYPE, SHARD_DTYPE, WIN_DTYPE, PgtError, check)
 
@@ -268,8 +268,11 @@ class _PopsStat:
     total: np.dtype
     max_pops: int = 8
     per_trio: bool = False  # one row table per ingroup trio i < j < k (trio_order); the last population is the outgroup
+    all_trios: bool = False  # one row table per trio i < j < k of ALL populations (all_trio_order): no outgroup
 
     def tables(self, n_pops: int) -> int:
+        if self.all_trios:
+            return n_pops * (n_pops - 1) * (n_pops - 2) // 6
         if self.per_trio:
             return (n_pops - 1) * (n_pops - 2) * (n_pops - 3) // 6
         return n_pops * (n_pops - 1) // 2 if self.per_pair else n_pops
@@ -285,6 +288,7 @@ _PI_POPS = _PopsStat("pi", 1, False, DXY_ROW_DTYPE, DXY_TOTAL_DTYPE)
 _FST_HUDSON_POPS = _PopsStat("fst_hudson", 2, True, FST_ROW_DTYPE, FST_TOTAL_DTYPE)
 _DSTAT_POPS = _PopsStat("dstat", 4, False, DSTAT_ROW_DTYPE, DSTAT_TOTAL_DTYPE, max_pops=7, per_trio=True)
 _FD_POPS = _PopsStat("fd", 4, False, FD_ROW_DTYPE, FD_TOTAL_DTYPE, max_pops=7, per_trio=True)
+_F3_POPS = _PopsStat("f3", 3, False, F3_ROW_DTYPE, F3_TOTAL_DTYPE, max_pops=6, all_trios=True)
 _FST_ESTIMATORS = {"wc": _FST_POPS, "hudson": _FST_HUDSON_POPS}  # fst_window_pops(estimator=...)
 
 
@@ -436,17 +440,34 @@ class Context:
         sites, their number n, fd = num / fd_den and fdm = num / fdm_den (0 where the denominator is 0)."""
         return self._pops_reduce(_FD_POPS, pos, freqs, ninds, minind, win)
 
+    def f3_pops_reduce(self, pos, freqs, ninds, minind, win):
+        """f3 rows of ALL trios i<j<k of len(freqs) populations (all_trio_order; no outgroup), every population of a trio as
+        the target, from 3 ... 6 per-population numpy (freq, nInd) columns, one pass: -> (rows[n_trios, n_win], totals[n_trios])
+        (pgt_f3_pops_reduce).  A row carries the three SUMS f3_i, f3_j, f3_k over its counted sites (target_order) and their
+        number n; f3 of the window is sum / n."""
+        return self._pops_reduce(_F3_POPS, pos, freqs, ninds, minind, win)
+
+    def _jackknife(self, name: str, row: np.dtype, jack: np.dtype, rows) -> np.ndarray:
+        """The numpy form of a block jackknife (pgt_<name>_jackknife) -> [n_trios, 3] of `jack`."""
+        rows = np.ascontiguousarray(rows, dtype=row)
+        if rows.ndim != 2:
+            raise PgtError(_lib.PGT_EARG, f"{name}_jackknife: rows must be a [n_trios, n_win] table")
+        n_trios, n_win = rows.shape
+        out = np.zeros((n_trios, 3), dtype=jack)
+        self._check(getattr(self._lib, f"pgt_{name}_jackknife")(self._ctx, rows.ctypes.data if rows.size else None, n_win, n_trios, out.ctypes.data))
+        return out
+
     def dstat_jackknife(self, rows) -> np.ndarray:
         """Block-jackknife D, standard error and Z of every trio and topology from a [n_trios, n_win] numpy table of
         DSTAT_ROW_DTYPE rows (what dstat_pops_reduce returns) over DISJOINT windows: every window is a block, used when its
         n > 0 and weighted by it (pgt_dstat_jackknife) -> [n_trios, 3] DSTAT_JACK_DTYPE, the topologies in topology_order."""
-        rows = np.ascontiguousarray(rows, dtype=DSTAT_ROW_DTYPE)
-        if rows.ndim != 2:
-            raise PgtError(_lib.PGT_EARG, "dstat_jackknife: rows must be a [n_trios, n_win] table")
-        n_trios, n_win = rows.shape
-        out = np.zeros((n_trios, 3), dtype=DSTAT_JACK_DTYPE)
-        self._check(self._lib.pgt_dstat_jackknife(self._ctx, rows.ctypes.data if rows.size else None, n_win, n_trios, out.ctypes.data))
-        return out
+        return self._jackknife("dstat", DSTAT_ROW_DTYPE, DSTAT_JACK_DTYPE, rows)
+
+    def f3_jackknife(self, rows) -> np.ndarray:
+        """Block-jackknife f3 (the mean over the used blocks' sites), standard error and Z of every trio and target from a
+        [n_trios, n_win] numpy table of F3_ROW_DTYPE rows (what f3_pops_reduce returns) over DISJOINT windows
+        (pgt_f3_jackknife) -> [n_trios, 3] F3_JACK_DTYPE, the targets in target_order."""
+        return self._jackknife("f3", F3_ROW_DTYPE, F3_JACK_DTYPE, rows)
 
     # ---- device-resident columns (torch CUDA tensors) -------------------------------------
     @staticmethod
@@ -829,27 +850,55 @@ class Context:
     def dstat_jackknife_work_bytes(n_trios: int, n_win: int) -> int:
         return int(_lib.load().pgt_dstat_jackknife_work_bytes(int(n_trios), int(n_win)))
 
+    def _jackknife_dev(self, name: str, row: np.dtype, jack: np.dtype, rows, n_win, n_trios, out, work, stream):
+        """The device form of a block jackknife (pgt_<name>_jackknife_dev) -> (out, work)."""
+        import torch
+        who = f"{name}_jackknife_dev"
+        n_win, n_trios = int(n_win), int(n_trios)
+        wb = int(getattr(self._lib, f"pgt_{name}_jackknife_work_bytes")(n_trios, n_win))
+        if wb == 0:
+            raise PgtError(_lib.PGT_EARG, f"{who}: n_trios must be 1 ... 20")
+        self._room(f"{who}: rows", rows, n_trios * n_win * row.itemsize)
+        if out is None:
+            out = torch.empty(3 * n_trios * jack.itemsize, dtype=torch.uint8, device=rows.device)
+        if work is None:
+            work = torch.empty(wb, dtype=torch.uint8, device=rows.device)
+        self._room(f"{who}: out", out, 3 * n_trios * jack.itemsize)
+        self._room(f"{who}: work", work, wb)
+        self._check(getattr(self._lib, f"pgt_{who}")(
+            self._ctx, self._dev(rows, torch.uint8, "rows") if n_win else None, n_win, n_trios,
+            self._dev(out, torch.uint8, "out"), out.numel(), self._dev(work, torch.uint8, "work"), work.numel(), self._stream(stream)))
+        return out, work
+
     def dstat_jackknife_dev(self, rows, n_win, n_trios, out=None, work=None, stream=None):
         """Block-jackknife D, standard error and Z of n_trios trios x 3 topologies from the device rows of
         dstat_pops_reduce_dev (uint8 CUDA tensor, trio-major, n_trios * n_win rows; the windows must be disjoint)
         (pgt_dstat_jackknife_dev).  Returns (out, work): out holds 3 * n_trios DSTAT_JACK_DTYPE, item 3 t + c
         (rows_from_device(out, DSTAT_JACK_DTYPE)).  Asynchronous on `stream`; no allocation when out and work are given."""
-        import torch
-        n_win, n_trios = int(n_win), int(n_trios)
-        wb = self.dstat_jackknife_work_bytes(n_trios, n_win)
-        if wb == 0:
-            raise PgtError(_lib.PGT_EARG, "dstat_jackknife_dev: n_trios must be 1 ... 20")
-        self._room("dstat_jackknife_dev: rows", rows, n_trios * n_win * DSTAT_ROW_DTYPE.itemsize)
-        if out is None:
-            out = torch.empty(3 * n_trios * DSTAT_JACK_DTYPE.itemsize, dtype=torch.uint8, device=rows.device)
-        if work is None:
-            work = torch.empty(wb, dtype=torch.uint8, device=rows.device)
-        self._room("dstat_jackknife_dev: out", out, 3 * n_trios * DSTAT_JACK_DTYPE.itemsize)
-        self._room("dstat_jackknife_dev: work", work, wb)
-        self._check(self._lib.pgt_dstat_jackknife_dev(
-            self._ctx, self._dev(rows, torch.uint8, "rows") if n_win else None, n_win, n_trios,
-            self._dev(out, torch.uint8, "out"), out.numel(), self._dev(work, torch.uint8, "work"), work.numel(), self._stream(stream)))
-        return out, work
+        return self._jackknife_dev("dstat", DSTAT_ROW_DTYPE, DSTAT_JACK_DTYPE, rows, n_win, n_trios, out, work, stream)
+
+    @staticmethod
+    def f3_pops_tree_bytes(n_pops: int, n_sites: int) -> int:
+        return int(_lib.load().pgt_f3_pops_tree_bytes(int(n_pops), int(n_sites)))
+
+    def f3_pops_reduce_dev(self, pos, freqs, ninds, minind, win, out=None, tot=None, tree=None, stream=None):
+        """f3 rows of ALL trios of len(freqs) populations (trio-major, all_trio_order; no outgroup), every population of a trio
+        as the target, in one pass over 3 ... 6 populations' own (freq, nInd) columns (pgt_f3_pops_reduce_dev).  freqs: float64
+        CUDA tensors, ninds: int32 CUDA tensors.  Rows of F3_ROW_DTYPE carry SUMS (f3 = sum / n), totals are F3_TOTAL_DTYPE.
+        tot: None = a fresh buffer of n_trios totals is allocated and filled; False = no genome-wide lines.
+        Returns (out, tot, tree).  Asynchronous on `stream`."""
+        return self._pops_reduce_dev(_F3_POPS, pos, freqs, ninds, minind, win, out, tot, tree, stream)
+
+    @staticmethod
+    def f3_jackknife_work_bytes(n_trios: int, n_win: int) -> int:
+        return int(_lib.load().pgt_f3_jackknife_work_bytes(int(n_trios), int(n_win)))
+
+    def f3_jackknife_dev(self, rows, n_win, n_trios, out=None, work=None, stream=None):
+        """Block-jackknife f3, standard error and Z of n_trios trios x 3 targets from the device rows of f3_pops_reduce_dev
+        (uint8 CUDA tensor, trio-major, n_trios * n_win rows; the windows must be disjoint) (pgt_f3_jackknife_dev).
+        Returns (out, work): out holds 3 * n_trios F3_JACK_DTYPE, item 3 t + c with c the target i / j / k
+        (rows_from_device(out, F3_JACK_DTYPE)).  Asynchronous on `stream`; no allocation when out and work are given."""
+        return self._jackknife_dev("f3", F3_ROW_DTYPE, F3_JACK_DTYPE, rows, n_win, n_trios, out, work, stream)
 
     def extreme_reduce_dev(self, pos, score, mode, cutoff, win, out=None, tree=None, stream=None):
         """ihsWindow / xpehhWindow rows from a device-resident score column (mode: PGT_EXT_*)."""
@@ -1143,6 +1192,19 @@ def trio_order(n_pops: int):
     return [(i, j, k) for i in range(g) for j in range(i + 1, g) for k in range(j + 1, g)]
 
 
+def all_trio_order(n_pops: int):
+    """The trios (i, j, k), i < j < k < n_pops, of ALL populations in the order f3_pops_reduce* lays its rows out (there is
+    no outgroup): (0,1,2),(0,1,3),..,(0,1,n_pops-1),(0,2,3),.."""
+    g = int(n_pops)
+    return [(i, j, k) for i in range(g) for j in range(i + 1, g) for k in range(j + 1, g)]
+
+
+def target_order(i, j, k):
+    """The three readings of trio (i, j, k) in the order its row's sums and the block jackknife's items are laid out
+    (c = 0, 1, 2), each as (target; source 1, source 2): [(i, j, k), (j, i, k), (k, i, j)]."""
+    return [(i, j, k), (j, i, k), (k, i, j)]
+
+
 def topology_order(i, j, k):
     """The three topologies of trio (i, j, k) in the order the block jackknife lays its items out (c = 0, 1, 2), each as
     ((P1, P2), P3): [(i, j, k), (i, k, j), (j, k, i)] — D from (abba, baba), (bbaa, baba), (bbaa, abba) of the trio's row."""
@@ -1166,17 +1228,16 @@ def _window_pops(st: _PopsStat, chr_ids, pos, freqs, ninds, W, S, minind, fixeds
     return win, rows, tot
 
 
-def _dstat_window_pops_jackknife(chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx):
-    """_window_pops for the ABBA-BABA rows with the rows kept ON THE DEVICE between the reduction and the block jackknife
-    (dstat_pops_reduce_dev under the hints the host-buffer form derives from the table: the same rows bit for bit, then
-    dstat_jackknife_dev on them) -> (win, rows[n_trios, n_win], totals[n_trios], jack[n_trios, 3])."""
-    st = _DSTAT_POPS
+def _trio_window_pops_jackknife(st: _PopsStat, jack_dtype, chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx):
+    """_window_pops for the rows of a trio statistic (ABBA-BABA, f3) with the rows kept ON THE DEVICE between the reduction and
+    the block jackknife (<name>_pops_reduce_dev under the hints the host-buffer form derives from the table: the same rows bit
+    for bit, then <name>_jackknife_dev on them) -> (win, rows[n_trios, n_win], totals[n_trios], jack[n_trios, 3])."""
     _refuse_dxy_window_args(W, S, minind, fixedsite, chr_len)
-    st.check_count("dstat_window_pops", freqs, ninds)
+    st.check_count(f"{st.name}_window_pops", freqs, ninds)
     chr_ids, pos = _host_col(chr_ids, None), _host_col(pos, np.uint32)
     freqs, ninds = [_host_col(f, np.float64) for f in freqs], [_host_col(c, np.int32) for c in ninds]
     if any(c.size != pos.size for c in freqs + ninds):
-        raise PgtError(_lib.PGT_EARG, "dstat_window_pops: column lengths differ")
+        raise PgtError(_lib.PGT_EARG, f"{st.name}_window_pops: column lengths differ")
     win = _dxy_window_table(chr_ids, pos, W, S, fixedsite, chr_len)
     n_trios = st.tables(len(freqs))
     import torch
@@ -1188,12 +1249,12 @@ def _dstat_window_pops_jackknife(chr_ids, pos, freqs, ninds, W, S, minind, fixed
             return torch.from_numpy(np.ascontiguousarray(a).copy()).to(dev)
         longest, typical, step = table_hints(win)
         with ctx.hints(longest, 0 if step >= 2 ** 63 else step, typical):
-            out, tot, _ = ctx.dstat_pops_reduce_dev(up(pos.view(np.int32)), [up(f) for f in freqs], [up(c) for c in ninds], minind,
-                                                    windows_to_device(win, dev))
-        jack, _ = ctx.dstat_jackknife_dev(out, win.size, n_trios)
-        rows = rows_from_device(out, DSTAT_ROW_DTYPE)[: n_trios * win.size].reshape(n_trios, win.size).copy()
-        tot = rows_from_device(tot, DSTAT_TOTAL_DTYPE)[:n_trios].copy()
-        jack = rows_from_device(jack, DSTAT_JACK_DTYPE)[: 3 * n_trios].reshape(n_trios, 3).copy()
+            out, tot, _ = ctx._pops_reduce_dev(st, up(pos.view(np.int32)), [up(f) for f in freqs], [up(c) for c in ninds], minind,
+                                               windows_to_device(win, dev), None, None, None, None)
+        jack, _ = ctx._jackknife_dev(st.name, st.row, jack_dtype, out, win.size, n_trios, None, None, None)
+        rows = rows_from_device(out, st.row)[: n_trios * win.size].reshape(n_trios, win.size).copy()
+        tot = rows_from_device(tot, st.total)[:n_trios].copy()
+        jack = rows_from_device(jack, jack_dtype)[: 3 * n_trios].reshape(n_trios, 3).copy()
     finally:
         if own:
             ctx.close()
@@ -1255,7 +1316,7 @@ def dstat_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind
     if not jackknife:
         win, rows, tot = _window_pops(_DSTAT_POPS, chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx)
         return _results_by_pair(len(freqs), win, rows, tot, skip_missing, "n", keys=trio_order(len(freqs)))
-    win, rows, tot, jack = _dstat_window_pops_jackknife(chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx)
+    win, rows, tot, jack = _trio_window_pops_jackknife(_DSTAT_POPS, DSTAT_JACK_DTYPE, chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx)
     res = _results_by_pair(len(freqs), win, rows, tot, skip_missing, "n", keys=trio_order(len(freqs)))
     res["jackknife"] = {ijk: jack[t] for t, ijk in enumerate(trio_order(len(freqs)))}
     return res
@@ -1272,6 +1333,34 @@ def fd_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: i
     from that trio's result only.  The per-site definition is pgt_fd_pops_reduce_dev's (include/pgtwin.h)."""
     win, rows, tot = _window_pops(_FD_POPS, chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx)
     return _results_by_pair(len(freqs), win, rows, tot, skip_missing, "n", keys=trio_order(len(freqs)))
+
+
+def f3_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: int = 1, fixedsite: int = 0,
+                   chr_len=None, skip_missing: int = 0, jackknife: bool = False, ctx: Context | None = None) -> dict:
+    """Windowed f3 (Reich et al. 2009; Patterson et al. 2012) for ALL trios of len(freqs) already synchronised populations
+    (3 ... 6; no outgroup), every population of a trio as the target, in one pass: {(i, j, k): WindowResult} in
+    all_trio_order, with rows of (start, end, mid, n, reserved_, f3_i, f3_j, f3_k) and the genome-wide sums as total.  The
+    three values are SUMS over the counted sites, one per target_order(i, j, k): f3 of a window is sum / n.  All columns must
+    report the same allele.  A significantly negative f3(target; a, b) shows the target to be admixed between relatives of
+    a and b; with an outgroup as the target the value measures the drift a and b share.
+    Window arguments and their errors are those of dxy_window_pops; -skip_missing drops a trio's rows without counted sites
+    from that trio's result only.  The per-site definition is pgt_f3_pops_reduce_dev's (include/pgtwin.h).
+    jackknife=True: the result gains the key "jackknife": {(i, j, k): 3 F3_JACK_DTYPE, one per target_order(i, j, k)} — the
+    delete-m_j block jackknife of the mean (pgt_f3_jackknife_dev, on the device rows of the same reduction) over ALL windows
+    of the table as blocks, whatever skip_missing is.  The windows must be disjoint: 0 < S < W and W == 0 are refused with
+    PGT_EARG before any device use.
+    Not computed: f3 normalised by the target's heterozygosity, f4, user-chosen trio lists."""
+    if jackknife and (W == 0 or 0 < S < W):
+        raise PgtError(_lib.PGT_EARG, f"f3_window_pops: the block jackknife needs disjoint windows as its blocks: "
+                                      f"winsize {W} must be positive and stepsize {S} at least the winsize")
+    keys = all_trio_order(len(freqs))
+    if not jackknife:
+        win, rows, tot = _window_pops(_F3_POPS, chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx)
+        return _results_by_pair(len(freqs), win, rows, tot, skip_missing, "n", keys=keys)
+    win, rows, tot, jack = _trio_window_pops_jackknife(_F3_POPS, F3_JACK_DTYPE, chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx)
+    res = _results_by_pair(len(freqs), win, rows, tot, skip_missing, "n", keys=keys)
+    res["jackknife"] = {ijk: jack[t] for t, ijk in enumerate(keys)}
+    return res
 
 
 def pi_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: int = 1, fixedsite: int = 0,
