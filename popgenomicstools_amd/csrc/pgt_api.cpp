@@ -438,6 +438,7 @@ pgt_ctx *pgt_open(int device) {
     }
     pgt_ctx *ctx = new pgt_ctx;
     ctx->device = device;
+    if (const char *e = std::getenv("PGT_FST_BUILD_BLOCKS")) ctx->hints.fst_build_blocks = (uint32_t)std::max(std::atoi(e), 0);  // a testing knob, see Hints
     for (auto &ev : ctx->ev)
         if ((e = hipEventCreate(&ev)) != hipSuccess) {
             set_global_error(std::string("pgt_open: hipEventCreate: ") + hipGetErrorString(e));

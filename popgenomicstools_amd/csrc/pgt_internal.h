@@ -229,6 +229,9 @@ struct Hints {
     uint64_t max_window = 0;   // longest window in sites: tree levels with larger nodes are not built
     uint64_t window_step = 0;  // typical distance between consecutive window starts: selects the query strategy
     uint64_t typical_window = 0;  // typical window length where the library saw the table itself (host tables); 0: max_window stands for it
+    uint32_t fst_build_blocks = 0;  // PGT_FST_BUILD_BLOCKS, read once by pgt_open: the fst build's workgroup cap instead of kFstBuildBlocks
+                                    // (0: unset).  A testing knob: with 1, four waves walk the whole column, so a short column reaches any
+                                    // number of tiles per wave (the deep stage of pgt_kernels.hip); rows and nodes do not depend on it
 };
 // ---- query strategies, chosen from the hints alone (the same on every rank when the hints are) ----------------
 // step == 0 (unknown) or large: one wave per window.  0 < step <= kGroupMaxStep and windows of at least two level-2

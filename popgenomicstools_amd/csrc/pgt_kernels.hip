@@ -97,6 +97,9 @@ struct TreeView {
 // is full or its work is done; all waves progress in near lockstep, hence the whole chip flushes at
 // about the same times and the memory controllers see dense write bursts: +3.4 ... +8.6 % across boxes
 // and sizes, results bit for bit the same.  The stage is private to the wave: no barrier.
+// (Round 7: a flush in mid-stream still costs — with more than kFstStage tiles per wave the fst build takes FstDeepStage
+// below, which holds 64 rows per wave and writes after the last tile; the dxy, fused, pi and extreme-score builds keep
+// NodeStage at every size: the dxy builds add their partial sums in flush order.)
 // ------------------------------------------------------------------------------------------
 // ONE COLUMN AT A TIME, FEW LOADS IN FLIGHT (round 3).  Until round 3 a wave requested `a` and `b` of 4 (or 8) leaf tiles
 // together: 8 (16) loads in flight from two streams interleaved kibibyte by kibibyte.  The extreme-score build — ONE
@@ -201,19 +204,18 @@ __device__ __forceinline__ void fst_column_sums(const double2 *__restrict__ p, i
 }
 // UNROLL: loads in flight per lane (one column at a time).  TAIL_UNROLL / TAIL_SCOPE (tuning): the queue depth of a wave's LAST
 // tile (scope 2: both columns, 1: only `b`, 0: off) — during the last round ever fewer waves are left to keep the HBM busy.
-template <int STAGE = kFstStage, int UNROLL = 4, bool NT_STORE = true, int TAIL_UNROLL = UNROLL, int TAIL_SCOPE = 0>
-__global__ __launch_bounds__(256) void fst_build_kernel(PairCols cols, uint64_t n, uint64_t n_l2, TreeView tv) {
-    extern __shared__ __attribute__((aligned(16))) char lds_stage[];
+// The walk of both fst builds; Stage = where a finished tile's node row waits (NodeStage, or FstDeepStage below).
+template <class Stage, int UNROLL, int TAIL_UNROLL, int TAIL_SCOPE>
+__device__ __forceinline__ void fst_build_body(const PairCols &cols, uint64_t n, uint64_t n_l2, const TreeView &tv, char *lds_stage,
+                                               uint64_t wave0, uint64_t n_waves) {  // this wave of the grid's n_waves (worked out in the kernel itself)
     const int lane = threadIdx.x & (kWave - 1), wib = threadIdx.x >> 6;
-    const uint64_t wave0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
     const double *__restrict__ a = cols.a[blockIdx.y];
     const double *__restrict__ b = cols.b[blockIdx.y];
     char *tree = tv.base + (size_t)blockIdx.y * tv.pair_stride;
     NodeFst *__restrict__ l1 = reinterpret_cast<NodeFst *>(tree + tv.off[0]);
     NodeFst *__restrict__ l2 = reinterpret_cast<NodeFst *>(tree + tv.off[1]);
     constexpr uint64_t kTile2 = (uint64_t)kLeafF64 * kRadix;
-    NodeStage<NodeFst, STAGE, NT_STORE> stage(lds_stage, wib, lane, l1, l2, n_waves);
+    Stage stage(lds_stage, wib, lane, l1, l2, n_waves);
 
     for (uint64_t t = wave0; t < n_l2; t += n_waves) {
         const uint64_t base = t * kTile2;
@@ -241,6 +243,115 @@ __global__ __launch_bounds__(256) void fst_build_kernel(PairCols cols, uint64_t 
         stage.put(t, NodeFst{keep_a, keep_b});
     }
     stage.flush();
+}
+template <int STAGE = kFstStage, int UNROLL = 4, bool NT_STORE = true, int TAIL_UNROLL = UNROLL, int TAIL_SCOPE = 0>
+__global__ __launch_bounds__(256) void fst_build_kernel(PairCols cols, uint64_t n, uint64_t n_l2, TreeView tv) {
+    extern __shared__ __attribute__((aligned(16))) char lds_stage[];
+    const uint64_t wave0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    fst_build_body<NodeStage<NodeFst, STAGE, NT_STORE>, UNROLL, TAIL_UNROLL, TAIL_SCOPE>(cols, n, n_l2, tv, lds_stage, wave0, n_waves);
+}
+
+// A DEEP STAGE FOR LONG COLUMNS (fst build only; round 7).  A wave that walks more than kFstStage tiles flushes NodeStage in the
+// middle of its read stream, all waves of the chip together, with no load in flight and — stores and loads sharing one in-order
+// counter — its next tile's first loads waiting behind every store of the flush: at 10^9 sites (60 tiles per wave, flushes at
+// 16, 32 and 48) the level-1 stores cost 77-82 us of 2.3-2.4 ms where at 10^8 sites (6 tiles per wave, one flush after the last
+// tile) they cost nothing (profiles/r06/round6_c_ab_af_leaf_sizes_and_fst_store_share.md, profiles/r07/fst_deep_stage_prize.md).
+// This stage holds kFstDeepStage = 64 rows per wave and writes only after the wave's last tile (or its 64th row: above
+// 64 * 2048 tiles = 1.07e9 sites it writes bursts of 64 rows instead of 16 — correct, not tuned).  Rows wait in
+// kFstDeepLdsRows = 20 LDS rows (80 KiB per workgroup: two workgroups fill a CU's 160 KiB) and in kFstDeepBlocks = 4 register
+// blocks of kFstDeepBlockRows = 11 rows (lane j keeps its 16 bytes of a row: 44 VGPRs per block): whenever the LDS rows hold 11
+// rows and a block is free they move into it as one block; the flush writes the LDS rows, then block after block moved
+// back into the LDS rows, by one row loop.  Row k holds tile first_t + k * n_waves as in NodeStage and a row's work is
+// NodeStage's on the same values (nt 16-byte row store, node_wave_sum, lane 0's level-2 store): every node and address is bit
+// for bit what it was, only written later (tests/test_fst_deep_stage.py: trees and rows byte-identical to fst_build_kernel<>'s).
+// REGISTERS.  Every register is named at compile time: the blocks are named members written by wave-uniform selects, so
+// nothing is indexed at run time.  (Arrays, or one branch per block, end in scratch: the optimiser merges the branches
+// into one copy that reaches the block through a pointer chosen at run time.  16 LDS rows + 3 blocks of 16 rows — 192 VGPRs of
+// rows — spilled 89 VGPRs under the 256 of two waves per SIMD; 176 fit.)  gfx950, -O3: 238 VGPRs, 0 AGPRs, scratch 0, no spill,
+// 2 waves per SIMD = 8 per CU as fst_build_kernel<> (59 VGPRs, whose occupancy the 64 KiB of LDS set, not the registers).
+// MEASURED (profiles/r07/fst_deep_stage_ab.md; the parent's library against this one alternating in one process, 4 calls per
+// measurement, 10 rounds, whole step at 10^9 sites): -48 us on one box and -29 us on another (2.41 -> 2.36 ms, 2.36 -> 2.33 ms),
+// below zero in every round, the same library on both sides within +-6 us; build kernel alone 2.318 -> 2.270 ms against 2.236
+// without level-1 stores at all: the stage recovers a bit over half of what the stores cost, the burst of 125 MB at the end
+// of the kernel keeps the rest.  Unrolling the row loop four times changes nothing (-0.2 us).  Whether the mid-stream stall
+// is the wave waiting for its stores' acknowledgements or the memory side turning around is NOT settled by this: OPEN.
+constexpr int kFstDeepLdsRows = 20;    // 80 KiB of LDS per workgroup: two workgroups fill the CU's 160 KiB
+constexpr int kFstDeepBlocks = 4;      // register blocks ...
+constexpr int kFstDeepBlockRows = 11;  // ... of this many rows: 44 VGPRs each
+constexpr int kFstDeepStage = kFstDeepLdsRows + kFstDeepBlocks * kFstDeepBlockRows;  // 64 rows per wave
+constexpr size_t kFstDeepStageBytes = (size_t)4 * kFstDeepLdsRows * 1024;
+static_assert(kFstDeepBlockRows <= kFstDeepLdsRows && kFstDeepStage >= 64, "a block passes through the LDS rows; 60 tiles per wave at 10^9 sites");
+struct FstDeepStage {
+    NodeFst *rows;  // LDS: [kFstDeepLdsRows][64] of this wave
+    NodeFst *l1, *l2;
+    uint64_t n_waves, first_t = 0;  // row k of the stage holds tile first_t + k * n_waves
+    int lane, parked = 0, in_lds = 0;  // rows 0 .. parked * kFstDeepBlockRows - 1 are in register blocks, the next in_lds in LDS
+    // one named member per value, not an array: a row is two register pairs picked at compile time, never an address
+#define PGT_FST_BLOCK_ROWS(M) M(0) M(1) M(2) M(3) M(4) M(5) M(6) M(7) M(8) M(9) M(10)
+    struct Block {
+#define PGT_M(k) double x##k, y##k;
+        PGT_FST_BLOCK_ROWS(PGT_M)
+#undef PGT_M
+    };
+    Block blk0{}, blk1{}, blk2{}, blk3{};
+    __device__ __forceinline__ FstDeepStage(char *lds, int wib, int lane_, NodeFst *l1_, NodeFst *l2_, uint64_t n_waves_)
+        : rows(reinterpret_cast<NodeFst *>(lds) + (size_t)wib * kFstDeepLdsRows * kWave), l1(l1_), l2(l2_), n_waves(n_waves_), lane(lane_) {}
+    // LDS rows 0 .. kFstDeepBlockRows - 1 -> block `parked`.  By wave-uniform selects into all four blocks, not by a branch per
+    // block: the optimiser merges such branches into one copy that addresses the block through a pointer chosen at run time,
+    // and with that the whole stage goes to scratch
+    __device__ __forceinline__ void park() {
+#define PGT_M(k) { const NodeFst v = rows[k * kWave + lane]; \
+        blk0.x##k = parked == 0 ? v.x : blk0.x##k; blk0.y##k = parked == 0 ? v.y : blk0.y##k; \
+        blk1.x##k = parked == 1 ? v.x : blk1.x##k; blk1.y##k = parked == 1 ? v.y : blk1.y##k; \
+        blk2.x##k = parked == 2 ? v.x : blk2.x##k; blk2.y##k = parked == 2 ? v.y : blk2.y##k; \
+        blk3.x##k = parked == 3 ? v.x : blk3.x##k; blk3.y##k = parked == 3 ? v.y : blk3.y##k; }
+        PGT_FST_BLOCK_ROWS(PGT_M)
+#undef PGT_M
+    }
+    __device__ __forceinline__ void unpark(const Block &blk) {
+#define PGT_M(k) rows[k * kWave + lane] = NodeFst{blk.x##k, blk.y##k};
+        PGT_FST_BLOCK_ROWS(PGT_M)
+#undef PGT_M
+    }
+#undef PGT_FST_BLOCK_ROWS
+    __device__ __forceinline__ void flush_rows(int row0, int count) {  // LDS rows 0 .. count - 1 hold rows row0 .. of the stage
+#pragma unroll 1
+        for (int k = 0; k < count; ++k) {
+            const uint64_t t = first_t + (uint64_t)(row0 + k) * n_waves;
+            const NodeFst v = rows[k * kWave + lane];
+            store_node_nt(&l1[t * kRadix + lane], v);
+            const NodeFst top = node_wave_sum(v);
+            if (lane == 0) l2[t] = top;
+        }
+    }
+    __device__ __forceinline__ void flush() {
+        flush_rows(parked * kFstDeepBlockRows, in_lds);
+        if (parked > 0) { unpark(blk0); flush_rows(0, kFstDeepBlockRows); }
+        if (parked > 1) { unpark(blk1); flush_rows(kFstDeepBlockRows, kFstDeepBlockRows); }
+        if (parked > 2) { unpark(blk2); flush_rows(2 * kFstDeepBlockRows, kFstDeepBlockRows); }
+        if (parked > 3) { unpark(blk3); flush_rows(3 * kFstDeepBlockRows, kFstDeepBlockRows); }
+        parked = in_lds = 0;
+    }
+    __device__ __forceinline__ void put(uint64_t t, const NodeFst &keep) {  // lane j holds the node of leaf tile j
+        if (parked == 0 && in_lds == 0) first_t = t;
+        rows[in_lds * kWave + lane] = keep;  // the wave's own LDS rows: no barrier needed
+        ++in_lds;
+        if (in_lds == kFstDeepLdsRows) return flush();  // only with every block parked
+        if (in_lds == kFstDeepBlockRows && parked < kFstDeepBlocks) {  // wave-uniform
+            park();
+            ++parked;
+            in_lds = 0;
+        }
+    }
+};
+static_assert(kFstDeepBlocks == 4, "FstDeepStage names its register blocks one by one");
+// 2 workgroups per CU as fst_build_kernel<>, i.e. 2 waves per SIMD: 256 VGPRs per wave
+__global__ __launch_bounds__(256, 2) void fst_build_kernel_deep(PairCols cols, uint64_t n, uint64_t n_l2, TreeView tv) {
+    extern __shared__ __attribute__((aligned(16))) char lds_stage[];
+    const uint64_t wave0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    fst_build_body<FstDeepStage, 4, 4, 0>(cols, n, n_l2, tv, lds_stage, wave0, n_waves);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1831,6 +1942,12 @@ inline int hip_fail(hipError_t e, const char *what, std::string *err) {
     return PGT_EDEVICE;
 }
 
+// the rounds of build_grid below: the most items a wave walks (0 items: 0)
+inline uint64_t build_rounds(uint64_t n_items, unsigned cap = 2048) {
+    const uint64_t max_waves = (uint64_t)(cap == 0 ? 1u << 28 : cap) * 4;
+    return (n_items + max_waves - 1) / max_waves;
+}
+
 inline unsigned build_grid(uint64_t n_items, unsigned cap = 2048) {
     // 4 waves per 256-thread workgroup, one work item (level-2 tile) per wave-iteration, at most `cap`
     // workgroups (what is resident at once); the rest is grid-strided.  The grid is BALANCED: with
@@ -1838,10 +1955,8 @@ inline unsigned build_grid(uint64_t n_items, unsigned cap = 2048) {
     // items (the last few r - 1) instead of some waves doing one item more than the others while the
     // rest of the chip idles — 7.45 rounds cost 8 either way, but 15259 items over 1908 waves finish
     // together (1.25e8 sites, the per-GPU shard of the 8-GPU run: +7 %).
-    if (cap == 0) cap = 1u << 28;
     if (n_items == 0) return 1;
-    const uint64_t max_waves = (uint64_t)cap * 4;
-    const uint64_t rounds = (n_items + max_waves - 1) / max_waves;
+    const uint64_t rounds = build_rounds(n_items, cap);
     const uint64_t waves = (n_items + rounds - 1) / rounds;
     uint64_t blocks = (waves + 3) / 4;
     if (blocks > (1u << 30)) blocks = 1u << 30;
@@ -1985,6 +2100,10 @@ int init_kernels(std::string *err) {  // per pgt_open, i.e. per device: function
         if (int rc = hip_fail(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFstStageBytes),
                               "hipFuncSetAttribute", err))
             return rc;
+    if (int rc = hip_fail(hipFuncSetAttribute(reinterpret_cast<const void *>(fst_build_kernel_deep),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFstDeepStageBytes),
+                          "hipFuncSetAttribute", err))
+        return rc;
     if (int rc = hip_fail(hipFuncSetAttribute(reinterpret_cast<const void *>(dxy_het_build_kernel<>),
                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kDxyHetStageBytes),
                           "hipFuncSetAttribute", err))
@@ -1994,11 +2113,21 @@ int init_kernels(std::string *err) {  // per pgt_open, i.e. per device: function
 
 // The streaming build launch of the fst tree (levels 1 and 2 of `np` pairs): one instantiation at every size (until
 // round 3 short inputs took a form with 16 loads in flight to shorten the latency-bound last tile; with one column at a
-// time the short queue wins at every size, see fst_build_kernel).
+// time the short queue wins at every size, see fst_build_kernel).  Where a wave walks more than kFstStage tiles (above
+// 16 * 2048 tiles = 268 435 456 sites) the same walk runs with the deep stage (FstDeepStage): same grid, same nodes, node rows
+// written after the wave's last tile.  cap: the context's workgroup cap (fst_build_cap).
 namespace {
-void fst_build_launch(hipStream_t s, const PairCols &cols, uint32_t np, uint64_t n, const TreeLayout &tl, const TreeView &tv) {
-    const dim3 grid(build_grid(tl.count[1], kFstBuildBlocks), np);
-    hipLaunchKernelGGL((fst_build_kernel<>), grid, dim3(256), kFstStageBytes, s, cols, n, tl.count[1], tv);
+inline unsigned fst_build_cap(const Hints &hints) {  // the fst build's workgroup cap: kFstBuildBlocks unless PGT_FST_BUILD_BLOCKS lowers it
+    return hints.fst_build_blocks >= 1 && hints.fst_build_blocks < kFstBuildBlocks ? hints.fst_build_blocks : kFstBuildBlocks;
+}
+void fst_build_launch(hipStream_t s, const PairCols &cols, uint32_t np, uint64_t n, const TreeLayout &tl, const TreeView &tv,
+                      const Hints &hints) {
+    const unsigned cap = fst_build_cap(hints);
+    const dim3 grid(build_grid(tl.count[1], cap), np);
+    if (build_rounds(tl.count[1], cap) > (uint64_t)kFstStage)
+        hipLaunchKernelGGL(fst_build_kernel_deep, grid, dim3(256), kFstDeepStageBytes, s, cols, n, tl.count[1], tv);
+    else
+        hipLaunchKernelGGL((fst_build_kernel<>), grid, dim3(256), kFstStageBytes, s, cols, n, tl.count[1], tv);
 }
 
 // launch_fst with the build launch as a parameter: the product passes fst_build_launch; tools/pgt_kernels_tuning.hip
@@ -2018,7 +2147,7 @@ int launch_fst_with(BuildFn build, const uint32_t *pos, const double *const *a, 
         const TreeView tv = make_view(tl, static_cast<char *>(tree) + (size_t)p0 * tl.bytes, tl.bytes, levels);
         if (p0 == 0) if (int rc = record(ev_build0, s, err)) return rc;
         if (n > 0) {
-            build(s, cols, np, n, tl, tv);
+            build(s, cols, np, n, tl, tv, hints);
             if (int rc = hip_fail(hipGetLastError(), "fst_build_kernel", err)) return rc;
             if (int rc = launch_upper<NodeFst>(tl, tv, np, s, err)) return rc;
         }

@@ -106,7 +106,7 @@ def main():
     pos, a, b = genome.fst_columns_t(0, n, dev)
     win = windows_to_device(pgt.build_windows_sites(genome.run_len, W, S), dev)
     tree = torch.empty(2 * ctx_b.tree_bytes(PGT_STAT_FST, n), dtype=torch.uint8, device=dev)
-    out = torch.empty(4 * 40 * (win.numel() // 32), dtype=torch.uint8, device=dev)
+    out = torch.zeros(4 * 40 * (win.numel() // 32), dtype=torch.uint8, device=dev)  # zeros: the rows check compares the whole buffer, a call writes its rows only
     p1, p2, n1, n2 = genome.dxy_columns_t(0, n, dev)
     g1, g2 = genome.genotype_t(0, 0, n, dev), genome.genotype_t(1, 0, n, dev)
     from popgenomicstools_amd._lib import PGT_EXT_IHS
@@ -178,6 +178,8 @@ def main():
                     else:
                         print(f"  {name}: returned tensor {k} ({x.numel()} bytes) differs in {int((x != y).sum())} bytes")
         ra, rb, diff, sdiff = [], [], [], []
+        for c in (ctx_a, ctx_b):  # not timed: the first measurement after the rows check read 100-170 us slow at 1e9 sites, whichever library it was
+            burst(c, fn)
         for _ in range(rounds):
             a1, b1, b2, a2 = burst(ctx_a, fn), burst(ctx_b, fn), burst(ctx_b, fn), burst(ctx_a, fn)
             ra += [a1, a2]
@@ -187,6 +189,10 @@ def main():
         ma, mb = np.median([x[0] for x in ra]), np.median([x[0] for x in rb])
         print(f"| {name} | {ma:.4f} | {mb:.4f} | {np.median(diff) * 1e3:+.1f} us | {bps * n / ma / 8e7:.1f} | {bps * n / mb / 8e7:.1f} | "
               f"{np.median([x[1] for x in ra]):.4f} | {np.median([x[1] for x in rb]):.4f} | {np.median(sdiff) * 1e3:+.1f} us | {'yes' if same else 'NO'} |")
+        # per round (A B B A: the mean of its two paired step differences), for a noise floor and a sign test
+        per_round = [(sdiff[2 * k] + sdiff[2 * k + 1]) / 2 * 1e3 for k in range(rounds)]
+        print(f"  {name}: step B - A per round, us: " + " ".join(f"{d:+.1f}" for d in per_round) +
+              f"  (median {np.median(per_round):+.1f}, spread {np.std(per_round):.1f}, {sum(d > 0 for d in per_round)} rounds above 0, {sum(d < 0 for d in per_round)} below)")
 
 
 if __name__ == "__main__":

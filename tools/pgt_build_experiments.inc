@@ -5,6 +5,8 @@
 //   launch_fst_experiment      the product kernel template with other parameters (PGT_TUNE_FST), for tools/build_ab.py and
 //                              tools/size_sweep.py
 //   fst_build_pair_kernel      round 4: two waves per level-2 tile (PGT_TUNE_FST_PAIR); +2-3 % at 1e8 sites, nothing on average
+//   fst_build_ablate_kernel   round 7, timing only: the fst build without level-1 stores / without any flush in mid-stream
+//                              (PGT_TUNE_FST_ABLATE): the prize of the deep node stage, profiles/r07/fst_deep_stage_prize.md
 // (Round 4 also tried handing tiles out by an atomic ticket counter after a static first round — a loss at every size, see
 // profiles/HISTORY.md and profiles/r04/ticket_schedule_rejected.patch.)
 // The round-1/2/3 variants that lived here (straight, software-pipelined, store-wave, LDS-DMA ring, interleaved a/b, phased
@@ -208,7 +210,47 @@ __global__ __launch_bounds__(256) void fst_build_pair_kernel(PairCols cols, uint
     flush();
 }
 
+// ------------------------------------------------------------------------------------------
+// Round 7, TIMING ONLY (the trees are wrong on purpose): what the mid-stream node flushes of a long column cost.
+//   MODE 1  NodeStage without the level-1 row stores (round 6's ablation: profiles/r06/round6_c_ab_af_leaf_sizes_and_fst_store_share.md)
+//   MODE 2  no flush in mid-stream at all: the rows that arrive while the kFstStage LDS rows are full are dropped, the rows held
+//           leave in the one flush after the wave's last tile — the most a stage that never flushes in mid-stream can gain
+//           (it writes 16 of 60 rows per wave at 10^9 sites; FstDeepStage writes them all)
+// PGT_TUNE_FST_ABLATE=<mode>; profiles/r07/fst_deep_stage_prize.md.
+// ------------------------------------------------------------------------------------------
+template <int MODE>
+struct AblateStage {
+    NodeStage<NodeFst, kFstStage, true> inner;
+    __device__ __forceinline__ AblateStage(char *lds, int wib, int lane, NodeFst *l1, NodeFst *l2, uint64_t n_waves)
+        : inner(lds, wib, lane, l1, l2, n_waves) {}
+    __device__ __forceinline__ void flush() {
+        if (MODE == 2) return inner.flush();
+        for (int k = 0; k < inner.held; ++k) {
+            const uint64_t t = inner.first_t + (uint64_t)k * inner.n_waves;
+            const NodeFst top = node_wave_sum(inner.rows[k * kWave + inner.lane]);
+            if (inner.lane == 0) inner.l2[t] = top;
+        }
+        inner.held = 0;
+    }
+    __device__ __forceinline__ void put(uint64_t t, const NodeFst &keep) {
+        if (MODE == 2 && inner.held == kFstStage) return;  // dropped
+        if (inner.held == 0) inner.first_t = t;
+        inner.rows[inner.held * kWave + inner.lane] = keep;
+        ++inner.held;
+        if (MODE == 1 && inner.held == kFstStage) flush();
+    }
+};
+template <int MODE>
+__global__ __launch_bounds__(256) void fst_build_ablate_kernel(PairCols cols, uint64_t n, uint64_t n_l2, TreeView tv) {
+    extern __shared__ __attribute__((aligned(16))) char lds_stage[];
+    const uint64_t wave0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    fst_build_body<AblateStage<MODE>, 4, 4, 0>(cols, n, n_l2, tv, lds_stage, wave0, n_waves);
+}
+
 // Returns true when an experimental launch replaced the product's fst build.
+//   PGT_TUNE_FST_ABLATE=1|2                                                   the timing-only kernels above
+//   PGT_TUNE_FST_DEEP=1                                                       the deep-stage kernel at any size
 //   PGT_TUNE_BUILD_STAMPS=<file>                                              the stamped copy
 //   PGT_TUNE_FST=<stage>:<loads in flight>:<workgroups>[:<tail loads>:<tail scope>]   the product kernel template with other
 //                parameters; tail scope 2 = a wave's whole last tile with <tail loads> in flight, 1 = its `b` column only
@@ -216,6 +258,19 @@ inline bool launch_fst_experiment(hipStream_t s, const PairCols &cols, uint32_t 
     const uint64_t n_l2 = tl.count[1];
     if (const char *path = std::getenv("PGT_TUNE_BUILD_STAMPS")) {
         launch_stamped(s, cols, np, n, n_l2, tv, path);
+        return true;
+    }
+    if (const char *e = std::getenv("PGT_TUNE_FST_ABLATE")) {
+        auto go = [&](auto kernel) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFstStageBytes);
+            hipLaunchKernelGGL(kernel, dim3(build_grid(n_l2, kFstBuildBlocks), np), dim3(256), kFstStageBytes, s, cols, n, n_l2, tv);
+        };
+        if (std::atoi(e) == 2) go(fst_build_ablate_kernel<2>);
+        else go(fst_build_ablate_kernel<1>);
+        return true;
+    }
+    if (std::getenv("PGT_TUNE_FST_DEEP")) {  // (its LDS attribute is set by init_kernels)
+        hipLaunchKernelGGL(fst_build_kernel_deep, dim3(build_grid(n_l2, kFstBuildBlocks), np), dim3(256), kFstDeepStageBytes, s, cols, n, n_l2, tv);
         return true;
     }
     if (const char *e = std::getenv("PGT_TUNE_FST_PAIR")) {

@@ -41,8 +41,8 @@ void ext_build_tuned(hipStream_t s, const ExtBuildArgs &g, uint64_t n, uint64_t 
 int launch_fst(const uint32_t *pos, const double *const *a, const double *const *b, uint32_t n_pairs,
                uint64_t n, const pgt_win *win, uint64_t n_win, pgt_fst_row *out, void *tree, void *stream,
                void *ev_build0, void *ev_build1, void *ev_query1, std::string *err, const Hints &hints) {
-    auto build = [](hipStream_t s, const PairCols &cols, uint32_t np, uint64_t n_, const TreeLayout &tl, const TreeView &tv) {
-        if (!launch_fst_experiment(s, cols, np, n_, tl, tv)) fst_build_launch(s, cols, np, n_, tl, tv);
+    auto build = [](hipStream_t s, const PairCols &cols, uint32_t np, uint64_t n_, const TreeLayout &tl, const TreeView &tv, const Hints &h) {
+        if (!launch_fst_experiment(s, cols, np, n_, tl, tv)) fst_build_launch(s, cols, np, n_, tl, tv, h);
     };
     return launch_fst_with(build, pos, a, b, n_pairs, n, win, n_win, out, tree, stream, ev_build0, ev_build1, ev_query1, err, hints);
 }
