@@ -331,7 +331,7 @@ struct DeviceScope {
     if (int rc_ = device_scope.enter(ctx)) return rc_
 
 // What is particular to one statistic of the (freq, nInd) front ends (pgt_{dxy,fst,pi}_pops_reduce and _dev); the rest of
-// their argument checks is one text for all three: pops_check_range, pops_check_dev, pops_reduce_host.
+// their argument checks is one text for all of them: pops_check_range, pops_check_dev, pops_reduce_dev, pops_reduce_host.
 struct PopsStat {
     const char *who;                                          // the prefix of every message
     uint32_t min_pops;                                        // min_pops <= n_pops <= max_pops
@@ -346,9 +346,16 @@ uint64_t pops_pairs(uint32_t n_pops) { return (uint64_t)n_pops * (n_pops - 1) / 
 uint64_t pops_each(uint32_t n_pops) { return n_pops; }
 uint64_t pops_trios(uint32_t n_pops) { return (uint64_t)(n_pops - 1) * (n_pops - 2) * (n_pops - 3) / 6; }  // C(n_pops - 1, 3): the last population is the outgroup
 
+bool pops_in_range(const PopsStat &st, uint32_t n_pops) { return n_pops >= st.min_pops && n_pops <= st.max_pops; }
+// a *_pops_tree_bytes: `sums` sums per table over the FST layout; 0 outside the statistic's populations
+size_t pops_tree_bytes(const PopsStat &st, int sums, uint32_t n_pops, uint64_t n_sites) {
+    if (!pops_in_range(st, n_pops)) return 0;
+    return pops_tree_view(tree_layout(PGT_STAT_FST, n_sites), (int)st.tables(n_pops), sums, nullptr, 0).bytes;
+}
+
 // first in both forms, and before the device form's early PGT_OK
 int pops_check_range(pgt_ctx *ctx, const PopsStat &st, uint32_t n_pops, int minind) {
-    if (n_pops < st.min_pops || n_pops > st.max_pops)
+    if (!pops_in_range(st, n_pops))
         return ctx_fail(ctx, PGT_EARG, std::string(st.who) + ": n_pops must be " + std::to_string(st.min_pops) + " ... " + std::to_string(st.max_pops));
     if (st.minind_from_1 && minind < 1) return ctx_fail(ctx, PGT_EARG, std::string(st.who) + ": minind must be at least 1");
     return PGT_OK;
@@ -385,6 +392,20 @@ int pops_check_dev(pgt_ctx *ctx, const PopsStat &st, const uint32_t *pos, const 
     if (int rc = room_check(ctx, (who + "out_bytes").c_str(), tables * n_win, st.row_bytes, out_bytes)) return rc;
     *launch = true;
     return PGT_OK;
+}
+
+// The body of every *_pops_reduce_dev entry point: the checks, then the statistic's launch (a launch_*_pops, or a callable
+// with its arguments).
+template <class Row, class Tot, class Launch>
+int pops_reduce_dev(pgt_ctx *ctx, const PopsStat &st, Launch launch_stat, const uint32_t *pos, const double *const *freq,
+                    const int32_t *const *nind, uint32_t n_pops, uint64_t n, int minind, const pgt_win *win, uint64_t n_win, Row *out,
+                    size_t out_bytes, Tot *tot, void *tree, size_t tree_bytes, void *stream) {
+    PGT_USE_DEVICE(ctx);
+    bool launch;
+    if (int rc = pops_check_dev(ctx, st, pos, freq, nind, n_pops, n, minind, win, n_win, out, out_bytes, tot, tree, tree_bytes, &launch)) return rc;
+    if (!launch) return PGT_OK;
+    const EvSet e = events_for(ctx);
+    return launch_stat(pos, freq, nind, n_pops, n, minind, win, n_win, out, tot, tree, stream, e.b0, e.b1, e.q1, &ctx->error, ctx->hints);
 }
 
 }  // namespace
@@ -646,41 +667,25 @@ int pgt_fst_af_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const
                          ctx->hints);
 }
 
-size_t pgt_dxy_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites) {
-    if (n_pops < 2 || n_pops > (uint32_t)kPopsMaxPops) return 0;
-    return pops_tree_view(tree_layout(PGT_STAT_FST, n_sites), (int)pops_pairs(n_pops), 1, nullptr, 0).bytes;
-}
+// Each statistic's populations (min_pops, max_pops) are stated once, in its PopsStat: its *_pops_tree_bytes reads them there.
 static const PopsStat kDxyPops = {"pgt_dxy_pops_reduce", 2, false, pops_pairs, "n_pairs", sizeof(pgt_dxy_row), pgt_dxy_pops_tree_bytes};
+size_t pgt_dxy_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites) { return pops_tree_bytes(kDxyPops, 1, n_pops, n_sites); }
 
 int pgt_dxy_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind,
                             uint32_t n_pops, uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_dxy_row *out,
                             size_t out_bytes, pgt_dxy_total *tot, void *tree, size_t tree_bytes, void *stream) {
-    PGT_USE_DEVICE(ctx);
-    bool launch;
-    if (int rc = pops_check_dev(ctx, kDxyPops, pos, freq, nind, n_pops, n, minind, win, n_win, out, out_bytes, tot, tree, tree_bytes, &launch)) return rc;
-    if (!launch) return PGT_OK;
-    const EvSet e = events_for(ctx);
-    return launch_dxy_pops(pos, freq, nind, n_pops, n, minind, win, n_win, out, tot, tree, stream, e.b0, e.b1, e.q1, &ctx->error,
-                           ctx->hints);
+    return pops_reduce_dev(ctx, kDxyPops, launch_dxy_pops, pos, freq, nind, n_pops, n, minind, win, n_win, out, out_bytes, tot, tree, tree_bytes, stream);
 }
 
-size_t pgt_fst_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites) {
-    if (n_pops < 2 || n_pops > (uint32_t)kPopsMaxPops) return 0;
-    return pops_tree_view(tree_layout(PGT_STAT_FST, n_sites), (int)pops_pairs(n_pops), 2, nullptr, 0).bytes;
-}
 // minind >= 1: npool >= 2 and n1, n2 > 0 at every counted site
 static const PopsStat kFstPops = {"pgt_fst_pops_reduce", 2, true, pops_pairs, "n_pairs", sizeof(pgt_fst_row), pgt_fst_pops_tree_bytes};
+size_t pgt_fst_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites) { return pops_tree_bytes(kFstPops, 2, n_pops, n_sites); }
 
 int pgt_fst_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind,
                             uint32_t n_pops, uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_fst_row *out,
                             size_t out_bytes, pgt_fst_total *tot, void *tree, size_t tree_bytes, void *stream) {
-    PGT_USE_DEVICE(ctx);
-    bool launch;
-    if (int rc = pops_check_dev(ctx, kFstPops, pos, freq, nind, n_pops, n, minind, win, n_win, out, out_bytes, tot, tree, tree_bytes, &launch)) return rc;
-    if (!launch) return PGT_OK;
-    const EvSet e = events_for(ctx);
-    return launch_fst_pops(pos, freq, nind, n_pops, n, minind, win, n_win, out, tot, tree, stream, e.b0, e.b1, e.q1, &ctx->error,
-                           ctx->hints, FstPopsEstimator::WeirCockerham);
+    return pops_reduce_dev(ctx, kFstPops, [](auto &&...a) { return launch_fst_pops(a..., FstPopsEstimator::WeirCockerham); },
+                           pos, freq, nind, n_pops, n, minind, win, n_win, out, out_bytes, tot, tree, tree_bytes, stream);
 }
 
 // Hudson's estimator on the same columns, tree layout and row types: one more PopsStat, the other per-site function
@@ -691,51 +696,31 @@ static const PopsStat kFstHudsonPops = {"pgt_fst_hudson_pops_reduce", 2, true, p
 int pgt_fst_hudson_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind,
                                    uint32_t n_pops, uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_fst_row *out,
                                    size_t out_bytes, pgt_fst_total *tot, void *tree, size_t tree_bytes, void *stream) {
-    PGT_USE_DEVICE(ctx);
-    bool launch;
-    if (int rc = pops_check_dev(ctx, kFstHudsonPops, pos, freq, nind, n_pops, n, minind, win, n_win, out, out_bytes, tot, tree, tree_bytes, &launch)) return rc;
-    if (!launch) return PGT_OK;
-    const EvSet e = events_for(ctx);
-    return launch_fst_pops(pos, freq, nind, n_pops, n, minind, win, n_win, out, tot, tree, stream, e.b0, e.b1, e.q1, &ctx->error,
-                           ctx->hints, FstPopsEstimator::Hudson);
+    return pops_reduce_dev(ctx, kFstHudsonPops, [](auto &&...a) { return launch_fst_pops(a..., FstPopsEstimator::Hudson); },
+                           pos, freq, nind, n_pops, n, minind, win, n_win, out, out_bytes, tot, tree, tree_bytes, stream);
 }
 
-size_t pgt_pi_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites) {
-    if (n_pops < 1 || n_pops > (uint32_t)kPopsMaxPops) return 0;
-    return (size_t)n_pops * tree_layout(PGT_STAT_DXY, n_sites).bytes;  // one tree of the two-population dxy layout per population
-}
 // one table per population; minind >= 1: 2 nind - 1 >= 1 at every counted site
 static const PopsStat kPiPops = {"pgt_pi_pops_reduce", 1, true, pops_each, "n_pops", sizeof(pgt_dxy_row), pgt_pi_pops_tree_bytes};
+size_t pgt_pi_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites) {
+    if (!pops_in_range(kPiPops, n_pops)) return 0;
+    return (size_t)n_pops * tree_layout(PGT_STAT_DXY, n_sites).bytes;  // one tree of the two-population dxy layout per population
+}
 
 int pgt_pi_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind,
                            uint32_t n_pops, uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_dxy_row *out,
                            size_t out_bytes, pgt_dxy_total *tot, void *tree, size_t tree_bytes, void *stream) {
-    PGT_USE_DEVICE(ctx);
-    bool launch;
-    if (int rc = pops_check_dev(ctx, kPiPops, pos, freq, nind, n_pops, n, minind, win, n_win, out, out_bytes, tot, tree, tree_bytes, &launch)) return rc;
-    if (!launch) return PGT_OK;
-    const EvSet e = events_for(ctx);
-    return launch_pi_pops(pos, freq, nind, n_pops, n, minind, win, n_win, out, tot, tree, stream, e.b0, e.b1, e.q1, &ctx->error,
-                          ctx->hints);
+    return pops_reduce_dev(ctx, kPiPops, launch_pi_pops, pos, freq, nind, n_pops, n, minind, win, n_win, out, out_bytes, tot, tree, tree_bytes, stream);
 }
 
 // ABBA-BABA patterns of all ingroup trios against the last population: one more PopsStat, with an upper bound of its own
-size_t pgt_dstat_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites) {
-    if (n_pops < 4 || n_pops > 7) return 0;
-    return pops_tree_view(tree_layout(PGT_STAT_FST, n_sites), (int)pops_trios(n_pops), 3, nullptr, 0).bytes;
-}
 static const PopsStat kDstatPops = {"pgt_dstat_pops_reduce", 4, true, pops_trios, "n_trios", sizeof(pgt_dstat_row), pgt_dstat_pops_tree_bytes, 7};
+size_t pgt_dstat_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites) { return pops_tree_bytes(kDstatPops, 3, n_pops, n_sites); }
 
 int pgt_dstat_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind,
                               uint32_t n_pops, uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_dstat_row *out,
                               size_t out_bytes, pgt_dstat_total *tot, void *tree, size_t tree_bytes, void *stream) {
-    PGT_USE_DEVICE(ctx);
-    bool launch;
-    if (int rc = pops_check_dev(ctx, kDstatPops, pos, freq, nind, n_pops, n, minind, win, n_win, out, out_bytes, tot, tree, tree_bytes, &launch)) return rc;
-    if (!launch) return PGT_OK;
-    const EvSet e = events_for(ctx);
-    return launch_dstat_pops(pos, freq, nind, n_pops, n, minind, win, n_win, out, tot, tree, stream, e.b0, e.b1, e.q1, &ctx->error,
-                             ctx->hints);
+    return pops_reduce_dev(ctx, kDstatPops, launch_dstat_pops, pos, freq, nind, n_pops, n, minind, win, n_win, out, out_bytes, tot, tree, tree_bytes, stream);
 }
 
 // f_d / f_dM of the same trios: one more PopsStat; three sums per trio as D has, so the tree is the D call's size
@@ -745,35 +730,20 @@ static const PopsStat kFdPops = {"pgt_fd_pops_reduce", 4, true, pops_trios, "n_t
 int pgt_fd_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind,
                            uint32_t n_pops, uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_fd_row *out,
                            size_t out_bytes, pgt_fd_total *tot, void *tree, size_t tree_bytes, void *stream) {
-    PGT_USE_DEVICE(ctx);
-    bool launch;
-    if (int rc = pops_check_dev(ctx, kFdPops, pos, freq, nind, n_pops, n, minind, win, n_win, out, out_bytes, tot, tree, tree_bytes, &launch)) return rc;
-    if (!launch) return PGT_OK;
-    const EvSet e = events_for(ctx);
-    return launch_fd_pops(pos, freq, nind, n_pops, n, minind, win, n_win, out, tot, tree, stream, e.b0, e.b1, e.q1, &ctx->error,
-                          ctx->hints);
+    return pops_reduce_dev(ctx, kFdPops, launch_fd_pops, pos, freq, nind, n_pops, n, minind, win, n_win, out, out_bytes, tot, tree, tree_bytes, stream);
 }
 
 // f3 of ALL trios of the populations, each population of a trio as the target: one more PopsStat; three sums per trio as D has,
 // so the tree is the D call's at one population more (C(n, 3) = C((n + 1) - 1, 3))
 static uint64_t pops_all_trios(uint32_t n_pops) { return (uint64_t)n_pops * (n_pops - 1) * (n_pops - 2) / 6; }
-size_t pgt_f3_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites) {
-    if (n_pops < 3 || n_pops > 6) return 0;
-    return pops_tree_view(tree_layout(PGT_STAT_FST, n_sites), (int)pops_all_trios(n_pops), 3, nullptr, 0).bytes;
-}
 // minind >= 1: 2 nind - 1 >= 1 at every counted site
 static const PopsStat kF3Pops = {"pgt_f3_pops_reduce", 3, true, pops_all_trios, "n_trios", sizeof(pgt_f3_row), pgt_f3_pops_tree_bytes, 6};
+size_t pgt_f3_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites) { return pops_tree_bytes(kF3Pops, 3, n_pops, n_sites); }
 
 int pgt_f3_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind,
                            uint32_t n_pops, uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_f3_row *out,
                            size_t out_bytes, pgt_f3_total *tot, void *tree, size_t tree_bytes, void *stream) {
-    PGT_USE_DEVICE(ctx);
-    bool launch;
-    if (int rc = pops_check_dev(ctx, kF3Pops, pos, freq, nind, n_pops, n, minind, win, n_win, out, out_bytes, tot, tree, tree_bytes, &launch)) return rc;
-    if (!launch) return PGT_OK;
-    const EvSet e = events_for(ctx);
-    return launch_f3_pops(pos, freq, nind, n_pops, n, minind, win, n_win, out, tot, tree, stream, e.b0, e.b1, e.q1, &ctx->error,
-                          ctx->hints);
+    return pops_reduce_dev(ctx, kF3Pops, launch_f3_pops, pos, freq, nind, n_pops, n, minind, win, n_win, out, out_bytes, tot, tree, tree_bytes, stream);
 }
 
 // Block jackknife of the rows above: its own checks (no columns, no window table), the message prefix of both forms.

@@ -87,159 +87,52 @@ static void help(const DxyOptions &o) {
                 "-sizefile", "FILE", "-skip_missing", "INT", o.skip_missing, "-jackknife", "INT", "-fd", "INT");
 }
 
-// chr start end mid D BBAA ABBA BABA neff nskip
-static size_t put_dstat_row(char *o, const std::string &chr, const pgt_dstat_row &r, uint32_t nskip) {
-    char *p = o;
-    std::memcpy(p, chr.data(), chr.size());
-    p += chr.size();
-    for (uint32_t u : {r.start, r.end, r.mid}) { *p++ = '\t'; p = put_u32(p, u); }
-    for (double g : {r.d, r.bbaa, r.abba, r.baba}) { *p++ = '\t'; p += fmt_g6(g, p); }
-    for (uint32_t u : {r.n, nskip}) { *p++ = '\t'; p = put_u32(p, u); }
-    *p++ = '\n';
-    return (size_t)(p - o);
-}
+// -fd 1: a second pass over the same columns and trios, in the D tree's buffer (the two sizes are equal; D's rows are read)
+struct FdPass {
+    using Row = pgt_fd_row;
+    using Total = pgt_fd_total;
+    static constexpr const char *ext = ".fd", *global_ext = ".fd.global";
+    static constexpr size_t row_bytes = 200;
+    static constexpr auto reduce_dev = pgt_fd_pops_reduce_dev;
+    // chr start end mid f_d f_dM num fd_den fdm_den neff nskip; the genome-wide ratios from the totals by the row's rule
+    static PopsLine line(const Row &r, uint32_t sites) { return {{r.start, r.end, r.mid}, {r.fd, r.fdm, r.num, r.fd_den, r.fdm_den}, r.n, sites - r.n}; }
+    static PopsLine total(const Total &g) {
+        return {{}, {g.fd_den != 0.0 ? g.num / g.fd_den : 0.0, g.fdm_den != 0.0 ? g.num / g.fdm_den : 0.0, g.num, g.fd_den, g.fdm_den}, g.neff, g.nskip};
+    }
+};
 
-// chr start end mid f_d f_dM num fd_den fdm_den neff nskip
-static size_t put_fd_row(char *o, const std::string &chr, const pgt_fd_row &r, uint32_t nskip) {
-    char *p = o;
-    std::memcpy(p, chr.data(), chr.size());
-    p += chr.size();
-    for (uint32_t u : {r.start, r.end, r.mid}) { *p++ = '\t'; p = put_u32(p, u); }
-    for (double g : {r.fd, r.fdm, r.num, r.fd_den, r.fdm_den}) { *p++ = '\t'; p += fmt_g6(g, p); }
-    for (uint32_t u : {r.n, nskip}) { *p++ = '\t'; p = put_u32(p, u); }
-    *p++ = '\n';
-    return (size_t)(p - o);
-}
-
-int main(int argc, char **argv) {
-    const std::string tool = "dstatWindowPops";
-    int jackknife = 0, fd = 0;
-    const PopsArgs args = parse_pops_args(tool, argc, argv, help, 4, [&](const char *o, const char *v) {
-        if (!std::strcmp(o, "-fd")) {
-            if (std::strcmp(v, "0") && std::strcmp(v, "1")) die(std::string("-fd must be 0 or 1 (given: ") + v + ")");
-            fd = v[0] == '1';
-            return true;
-        }
-        if (std::strcmp(o, "-jackknife")) return false;
-        if (std::strcmp(v, "0") && std::strcmp(v, "1")) die(std::string("-jackknife must be 0 or 1 (given: ") + v + ")");
-        jackknife = v[0] == '1';
-        if (!jackknife) return true;
-        // refused here, while the options are read and before any file is opened: the blocks are the run's windows, which
-        // must exist and be disjoint (the option pairs are walked as parse_pops_args walks them; the last value counts)
-        DxyOptions w;
-        for (int i = 1; i + 1 < argc && argv[i][0] == '-' && argv[i][1] != '\0'; i += 2)
-            if (!std::strcmp(argv[i], "-winsize") || !std::strcmp(argv[i], "-stepsize")) dxy_option(w, argv[i], argv[i + 1]);
-        if (w.W == 0) die("-jackknife 1 needs windows as its blocks: -winsize must be > 0");
-        if (w.S < w.W)
-            die("-jackknife 1 needs windows that do not overlap: -stepsize (" + std::to_string(w.S) + ") must not be below -winsize (" + std::to_string(w.W) + ")");
+struct DstatPops : PopsTool {
+    static constexpr const char *name = "dstatWindowPops";
+    static constexpr int min_files = 4, max_files = 7;
+    static constexpr auto help = ::help;
+    static constexpr int arity = 3;  // all trios of the ingroups
+    static constexpr bool outgroup = true;
+    using Row = pgt_dstat_row;
+    using Total = pgt_dstat_total;
+    static constexpr const char *ext = ".dstat";
+    static constexpr size_t row_bytes = 200;
+    static constexpr auto tree_bytes = pgt_dstat_pops_tree_bytes;
+    static constexpr auto reduce_dev = pgt_dstat_pops_reduce_dev;
+    JackknifeOption jackknife;
+    bool fd = false;
+    bool own(const char *o, const char *v, int argc, char **argv) {
+        if (std::strcmp(o, "-fd")) return jackknife.take(o, v, argc, argv);
+        if (std::strcmp(v, "0") && std::strcmp(v, "1")) die(std::string("-fd must be 0 or 1 (given: ") + v + ")");
+        fd = v[0] == '1';
         return true;
-    }, 7);
-    const int K = args.K;
-    const char *prefix = args.prefix;
-    const uint32_t W = args.opt.W;
-    const int minind = args.opt.minind, skip_missing = args.opt.skip_missing;
+    }
+    // chr start end mid D BBAA ABBA BABA neff nskip; the genome-wide D from the totals
+    static PopsLine line(const Row &r, uint32_t sites) { return {{r.start, r.end, r.mid}, {r.d, r.bbaa, r.abba, r.baba}, r.n, sites - r.n}; }
+    static PopsLine total(const Total &g) {
+        const double den = g.abba + g.baba;
+        return {{}, {den != 0.0 ? (g.abba - g.baba) / den : 0.0, g.bbaa, g.abba, g.baba}, g.neff, g.nskip};
+    }
+    // P1 P2 P3 D D_jack SE Z nblocks nsites: trio order, then ((i,j),k), ((i,k),j), ((j,k),i)
+    static constexpr int topologies[3][3] = {{0, 1, 2}, {0, 2, 1}, {1, 2, 0}};
+    void more(PopsRun &run, const Row *d_rows) {
+        if (jackknife.on) pops_jackknife(run, d_rows, pgt_dstat_jackknife_dev, pgt_dstat_jackknife_work_bytes, topologies);
+        if (fd) pops_pass(FdPass{}, run);
+    }
+};
 
-    PhaseTimer timer;
-    DeviceOpener device(std::vector<int>{devices_from_env()[0]});  // one GPU; HIP start-up runs beside the opening of the files
-    const PopsSites s = load_pops(tool, args, timer, device);
-    pgt_ctx *ctx = s.ctx;
-    const std::vector<pgt_win> &win = s.win;
-    const Runs &runs = s.runs;
-    const size_t n_trios = (size_t)(K - 1) * (size_t)(K - 2) * (size_t)(K - 3) / 6, n_win = win.size();
-    pgt_dstat_row *d_rows = pops_dev_alloc<pgt_dstat_row>(ctx, n_trios * n_win);
-    pgt_dstat_total *d_tot = pops_dev_alloc<pgt_dstat_total>(ctx, n_trios);
-    const size_t tree_bytes = pgt_dstat_pops_tree_bytes((uint32_t)K, s.n_sites);
-    void *tree = nullptr;
-    check(pgt_dev_alloc(ctx, tree_bytes, &tree), ctx);
-    check(pgt_dstat_pops_reduce_dev(ctx, s.a_pos, s.a_freq.data(), s.a_nind.data(), (uint32_t)K, s.n_sites, minind, n_win ? s.d_win : nullptr, n_win,
-                                    n_win ? d_rows : nullptr, n_trios * n_win * sizeof(pgt_dstat_row), d_tot, tree, tree_bytes, nullptr), ctx);
-    RowArray<pgt_dstat_row> rows(n_trios * n_win);
-    std::vector<pgt_dstat_total> tot(n_trios);
-    check(pgt_rowbuf_read(ctx, rows.data(), d_rows, n_trios * n_win * sizeof(pgt_dstat_row), nullptr), ctx);
-    check(pgt_rowbuf_read(ctx, tot.data(), d_tot, n_trios * sizeof(pgt_dstat_total), nullptr), ctx);
-    std::vector<pgt_dstat_jack> jack;
-    if (jackknife) {  // the rows are still on the device: every window of the table is a block
-        const size_t work_bytes = pgt_dstat_jackknife_work_bytes((uint32_t)n_trios, n_win);
-        void *work = nullptr;
-        check(pgt_dev_alloc(ctx, work_bytes, &work), ctx);
-        pgt_dstat_jack *d_jack = pops_dev_alloc<pgt_dstat_jack>(ctx, 3 * n_trios);
-        check(pgt_dstat_jackknife_dev(ctx, d_rows, n_win, (uint32_t)n_trios, d_jack, 3 * n_trios * sizeof(pgt_dstat_jack), work, work_bytes, nullptr), ctx);
-        jack.resize(3 * n_trios);
-        check(pgt_rowbuf_read(ctx, jack.data(), d_jack, 3 * n_trios * sizeof(pgt_dstat_jack), nullptr), ctx);
-    }
-    RowArray<pgt_fd_row> fd_rows(fd ? n_trios * n_win : 0);
-    std::vector<pgt_fd_total> fd_tot(fd ? n_trios : 0);
-    if (fd) {  // a second reduction of the aligned columns; D's rows are read, so its tree's buffer (the same size) is free
-        pgt_fd_row *d_fd_rows = pops_dev_alloc<pgt_fd_row>(ctx, n_trios * n_win);
-        pgt_fd_total *d_fd_tot = pops_dev_alloc<pgt_fd_total>(ctx, n_trios);
-        check(pgt_fd_pops_reduce_dev(ctx, s.a_pos, s.a_freq.data(), s.a_nind.data(), (uint32_t)K, s.n_sites, minind, n_win ? s.d_win : nullptr, n_win,
-                                     n_win ? d_fd_rows : nullptr, n_trios * n_win * sizeof(pgt_fd_row), d_fd_tot, tree, tree_bytes, nullptr), ctx);
-        check(pgt_rowbuf_read(ctx, fd_rows.data(), d_fd_rows, n_trios * n_win * sizeof(pgt_fd_row), nullptr), ctx);
-        check(pgt_rowbuf_read(ctx, fd_tot.data(), d_fd_tot, n_trios * sizeof(pgt_fd_total), nullptr), ctx);
-    }
-    timer.lap("gpu reduce");
-
-    const std::string global_path = std::string(prefix) + ".global";
-    FILE *global = open_out(global_path);
-    size_t t = 0;
-    for (int a = 0; a < K - 1; ++a)
-        for (int b = a + 1; b < K - 1; ++b)
-            for (int c = b + 1; c < K - 1; ++c, ++t) {
-                if (W > 0) {
-                    const std::string path = std::string(prefix) + ".pop" + std::to_string(a + 1) + "_pop" + std::to_string(b + 1) + "_pop" + std::to_string(c + 1) + ".dstat";
-                    FILE *f = open_out(path);
-                    const pgt_dstat_row *r = rows.data() + t * n_win;
-                    write_rows(n_win, longest_name(runs) + 200, [&](size_t i, char *o) -> size_t {  // -skip_missing as dxyWindow.cpp:189
-                        if (!(r[i].n > 0 || !skip_missing)) return 0;
-                        return put_dstat_row(o, runs.name[win[i].label_run], r[i], (uint32_t)(win[i].hi - win[i].lo) - r[i].n);
-                    }, f);
-                    close_out(f, path);
-                }
-                const double den = tot[t].abba + tot[t].baba;
-                const double d = den != 0.0 ? (tot[t].abba - tot[t].baba) / den : 0.0;
-                std::fprintf(global, "%d\t%d\t%d\t%g\t%g\t%g\t%g\t%llu\t%llu\n", a + 1, b + 1, c + 1, d, tot[t].bbaa, tot[t].abba, tot[t].baba,
-                             (unsigned long long)tot[t].neff, (unsigned long long)tot[t].nskip);
-            }
-    close_out(global, global_path);
-    if (jackknife) {  // P1 P2 P3 D D_jack SE Z nblocks nsites: trio order, then ((i,j),k), ((i,k),j), ((j,k),i)
-        const std::string path = std::string(prefix) + ".jackknife";
-        FILE *f = open_out(path);
-        t = 0;
-        for (int a = 0; a < K - 1; ++a)
-            for (int b = a + 1; b < K - 1; ++b)
-                for (int c = b + 1; c < K - 1; ++c, ++t) {
-                    const int topo[3][3] = {{a, b, c}, {a, c, b}, {b, c, a}};
-                    for (int u = 0; u < 3; ++u) {
-                        const pgt_dstat_jack &r = jack[3 * t + (size_t)u];
-                        auto g6 = [](double v) { char b_[64]; if (v != v) return std::string("nan"); std::snprintf(b_, sizeof b_, "%g", v); return std::string(b_); };
-                        std::fprintf(f, "%d\t%d\t%d\t%s\t%s\t%s\t%s\t%u\t%llu\n", topo[u][0] + 1, topo[u][1] + 1, topo[u][2] + 1, g6(r.d).c_str(),
-                                     g6(r.d_jack).c_str(), g6(r.se).c_str(), g6(r.z).c_str(), r.n_blocks, (unsigned long long)r.n_sites);
-                    }
-                }
-        close_out(f, path);
-    }
-    if (fd) {  // the .fd files and PREFIX.fd.global: the loops of the .dstat files and PREFIX.global above
-        const std::string fd_global_path = std::string(prefix) + ".fd.global";
-        FILE *fd_global = open_out(fd_global_path);
-        t = 0;
-        for (int a = 0; a < K - 1; ++a)
-            for (int b = a + 1; b < K - 1; ++b)
-                for (int c = b + 1; c < K - 1; ++c, ++t) {
-                    if (W > 0) {
-                        const std::string path = std::string(prefix) + ".pop" + std::to_string(a + 1) + "_pop" + std::to_string(b + 1) + "_pop" + std::to_string(c + 1) + ".fd";
-                        FILE *f = open_out(path);
-                        const pgt_fd_row *r = fd_rows.data() + t * n_win;
-                        write_rows(n_win, longest_name(runs) + 200, [&](size_t i, char *o) -> size_t {
-                            if (!(r[i].n > 0 || !skip_missing)) return 0;
-                            return put_fd_row(o, runs.name[win[i].label_run], r[i], (uint32_t)(win[i].hi - win[i].lo) - r[i].n);
-                        }, f);
-                        close_out(f, path);
-                    }
-                    const pgt_fd_total &g = fd_tot[t];  // the ratios from the totals by the row's rule
-                    std::fprintf(fd_global, "%d\t%d\t%d\t%g\t%g\t%g\t%g\t%g\t%llu\t%llu\n", a + 1, b + 1, c + 1, g.fd_den != 0.0 ? g.num / g.fd_den : 0.0,
-                                 g.fdm_den != 0.0 ? g.num / g.fdm_den : 0.0, g.num, g.fd_den, g.fdm_den, (unsigned long long)g.neff, (unsigned long long)g.nskip);
-                }
-        close_out(fd_global, fd_global_path);
-    }
-    finish(timer);
-}
+int main(int argc, char **argv) { return run_pops_tool<DstatPops>(argc, argv); }

@@ -18,7 +18,7 @@
 
 using namespace pgthost;
 
-static void help(unsigned W, unsigned S, int minind, int fixedsite, int skip_missing) {
+static void help(const DxyOptions &o) {
     std::printf("\ndxyWindowPops [options] -out PREFIX <pop1 maf file> <pop2 maf file> ... <popK maf file>      (2 <= K <= 8)\n\nOptions:\n"
                 "%-14s%-8sPrefix of the output files (REQUIRED)\n"
                 "%-14s%-8sWindow size in base pairs (0 for global calculation) [%u]\n"
@@ -43,51 +43,25 @@ static void help(unsigned W, unsigned S, int minind, int fixedsite, int skip_mis
                 "(5) number sites in MAF input that were analyzed\n"
                 "(6) number of sites in MAF input that were skipped due to too few individuals\n"
                 "PREFIX.global, one line per pair:\n(1) i\n(2) j\n(3) dxy\n(4) number of sites analyzed\n(5) number of sites skipped\n\n",
-                "-out", "STRING", "-winsize", "INT", W, "-stepsize", "INT", S, "-minind", "INT", minind, "-fixedsite", "INT", fixedsite,
-                "-sizefile", "FILE", "-skip_missing", "INT", skip_missing);
+                "-out", "STRING", "-winsize", "INT", o.W, "-stepsize", "INT", o.S, "-minind", "INT", o.minind, "-fixedsite", "INT", o.fixedsite,
+                "-sizefile", "FILE", "-skip_missing", "INT", o.skip_missing);
 }
 
-int main(int argc, char **argv) {
-    const std::string tool = "dxyWindowPops";
-    const PopsArgs args = parse_pops_args(tool, argc, argv, [](const DxyOptions &o) { help(o.W, o.S, o.minind, o.fixedsite, o.skip_missing); });
-    const int K = args.K;
-    const char *prefix = args.prefix;
-    const uint32_t W = args.opt.W;
-    const int minind = args.opt.minind, skip_missing = args.opt.skip_missing;
 
-    PhaseTimer timer;
-    DeviceOpener device(std::vector<int>{devices_from_env()[0]});  // one GPU; HIP start-up runs beside the opening of the files
-    const PopsSites s = load_pops(tool, args, timer, device);
-    pgt_ctx *ctx = s.ctx;
-    const std::vector<pgt_win> &win = s.win;
-    const Runs &runs = s.runs;
-    const size_t n_pairs = (size_t)K * (size_t)(K - 1) / 2, n_win = win.size();
-    pgt_dxy_row *d_rows = pops_dev_alloc<pgt_dxy_row>(ctx, n_pairs * n_win);
-    pgt_dxy_total *d_tot = pops_dev_alloc<pgt_dxy_total>(ctx, n_pairs);
-    const size_t tree_bytes = pgt_dxy_pops_tree_bytes((uint32_t)K, s.n_sites);
-    void *tree = nullptr;
-    check(pgt_dev_alloc(ctx, tree_bytes, &tree), ctx);
-    check(pgt_dxy_pops_reduce_dev(ctx, s.a_pos, s.a_freq.data(), s.a_nind.data(), (uint32_t)K, s.n_sites, minind, n_win ? s.d_win : nullptr, n_win,
-                                  n_win ? d_rows : nullptr, n_pairs * n_win * sizeof(pgt_dxy_row), d_tot, tree, tree_bytes, nullptr), ctx);
-    RowArray<pgt_dxy_row> rows(n_pairs * n_win);
-    std::vector<pgt_dxy_total> tot(n_pairs);
-    check(pgt_rowbuf_read(ctx, rows.data(), d_rows, n_pairs * n_win * sizeof(pgt_dxy_row), nullptr), ctx);
-    check(pgt_rowbuf_read(ctx, tot.data(), d_tot, n_pairs * sizeof(pgt_dxy_total), nullptr), ctx);
-    timer.lap("gpu reduce");
+struct DxyPops : PopsTool {
+    static constexpr const char *name = "dxyWindowPops";
+    static constexpr int min_files = 2;
+    static constexpr auto help = ::help;
+    static constexpr int arity = 2;  // all pairs
+    using Row = pgt_dxy_row;
+    using Total = pgt_dxy_total;
+    static constexpr const char *ext = ".dxy";
+    static constexpr size_t row_bytes = 80;
+    static constexpr auto tree_bytes = pgt_dxy_pops_tree_bytes;
+    static constexpr auto reduce_dev = pgt_dxy_pops_reduce_dev;
+    // chr start end dxy neff nskip: dxyWindow's row (dxyWindow.cpp:190), the skipped count the library's
+    static PopsLine line(const Row &r, uint32_t) { return {{r.start, r.end}, {r.sum}, r.neff, r.nskip}; }
+    static PopsLine total(const Total &g) { return {{}, {g.sum}, g.neff, g.nskip}; }
+};
 
-    const std::string global_path = std::string(prefix) + ".global";
-    FILE *global = open_out(global_path);
-    size_t p = 0;
-    for (int a = 0; a < K; ++a)
-        for (int b = a + 1; b < K; ++b, ++p) {
-            if (W > 0) {
-                const std::string path = pair_path(prefix, a, b, ".dxy");
-                FILE *f = open_out(path);
-                write_dxy_rows(rows.data() + p * n_win, n_win, runs, [&](size_t w) { return win[w].label_run; }, skip_missing, f);
-                close_out(f, path);
-            }
-            std::fprintf(global, "%d\t%d\t%g\t%llu\t%llu\n", a + 1, b + 1, tot[p].sum, (unsigned long long)tot[p].neff, (unsigned long long)tot[p].nskip);
-        }
-    close_out(global, global_path);
-    finish(timer);
-}
+int main(int argc, char **argv) { return run_pops_tool<DxyPops>(argc, argv); }

@@ -75,108 +75,29 @@ static void help(const DxyOptions &o) {
 
 static double mean_of(double sum, uint64_t neff) { return neff ? sum / (double)neff : 0.0; }
 
-// chr start end mid f3_i f3_j f3_k neff nskip
-static size_t put_f3_row(char *o, const std::string &chr, const pgt_f3_row &r, uint32_t nskip) {
-    char *p = o;
-    std::memcpy(p, chr.data(), chr.size());
-    p += chr.size();
-    for (uint32_t u : {r.start, r.end, r.mid}) { *p++ = '\t'; p = put_u32(p, u); }
-    for (double g : {mean_of(r.f3_i, r.n), mean_of(r.f3_j, r.n), mean_of(r.f3_k, r.n)}) { *p++ = '\t'; p += fmt_g6(g, p); }
-    for (uint32_t u : {r.n, nskip}) { *p++ = '\t'; p = put_u32(p, u); }
-    *p++ = '\n';
-    return (size_t)(p - o);
-}
-
-int main(int argc, char **argv) {
-    const std::string tool = "f3WindowPops";
-    int jackknife = 0;
-    const PopsArgs args = parse_pops_args(tool, argc, argv, help, 3, [&](const char *o, const char *v) {
-        if (std::strcmp(o, "-jackknife")) return false;
-        if (std::strcmp(v, "0") && std::strcmp(v, "1")) die(std::string("-jackknife must be 0 or 1 (given: ") + v + ")");
-        jackknife = v[0] == '1';
-        if (!jackknife) return true;
-        // refused here, while the options are read and before any file is opened, as dstatWindowPops does: the blocks are the
-        // run's windows, which must exist and be disjoint (the last value of an option counts)
-        DxyOptions w;
-        for (int i = 1; i + 1 < argc && argv[i][0] == '-' && argv[i][1] != '\0'; i += 2)
-            if (!std::strcmp(argv[i], "-winsize") || !std::strcmp(argv[i], "-stepsize")) dxy_option(w, argv[i], argv[i + 1]);
-        if (w.W == 0) die("-jackknife 1 needs windows as its blocks: -winsize must be > 0");
-        if (w.S < w.W)
-            die("-jackknife 1 needs windows that do not overlap: -stepsize (" + std::to_string(w.S) + ") must not be below -winsize (" + std::to_string(w.W) + ")");
-        return true;
-    }, 6);
-    const int K = args.K;
-    const char *prefix = args.prefix;
-    const uint32_t W = args.opt.W;
-    const int minind = args.opt.minind, skip_missing = args.opt.skip_missing;
-
-    PhaseTimer timer;
-    DeviceOpener device(std::vector<int>{devices_from_env()[0]});  // one GPU; HIP start-up runs beside the opening of the files
-    const PopsSites s = load_pops(tool, args, timer, device);
-    pgt_ctx *ctx = s.ctx;
-    const std::vector<pgt_win> &win = s.win;
-    const Runs &runs = s.runs;
-    const size_t n_trios = (size_t)K * (size_t)(K - 1) * (size_t)(K - 2) / 6, n_win = win.size();
-    pgt_f3_row *d_rows = pops_dev_alloc<pgt_f3_row>(ctx, n_trios * n_win);
-    pgt_f3_total *d_tot = pops_dev_alloc<pgt_f3_total>(ctx, n_trios);
-    const size_t tree_bytes = pgt_f3_pops_tree_bytes((uint32_t)K, s.n_sites);
-    void *tree = nullptr;
-    check(pgt_dev_alloc(ctx, tree_bytes, &tree), ctx);
-    check(pgt_f3_pops_reduce_dev(ctx, s.a_pos, s.a_freq.data(), s.a_nind.data(), (uint32_t)K, s.n_sites, minind, n_win ? s.d_win : nullptr, n_win,
-                                 n_win ? d_rows : nullptr, n_trios * n_win * sizeof(pgt_f3_row), d_tot, tree, tree_bytes, nullptr), ctx);
-    RowArray<pgt_f3_row> rows(n_trios * n_win);
-    std::vector<pgt_f3_total> tot(n_trios);
-    check(pgt_rowbuf_read(ctx, rows.data(), d_rows, n_trios * n_win * sizeof(pgt_f3_row), nullptr), ctx);
-    check(pgt_rowbuf_read(ctx, tot.data(), d_tot, n_trios * sizeof(pgt_f3_total), nullptr), ctx);
-    std::vector<pgt_f3_jack> jack;
-    if (jackknife) {  // the rows are still on the device: every window of the table is a block
-        const size_t work_bytes = pgt_f3_jackknife_work_bytes((uint32_t)n_trios, n_win);
-        void *work = nullptr;
-        check(pgt_dev_alloc(ctx, work_bytes, &work), ctx);
-        pgt_f3_jack *d_jack = pops_dev_alloc<pgt_f3_jack>(ctx, 3 * n_trios);
-        check(pgt_f3_jackknife_dev(ctx, d_rows, n_win, (uint32_t)n_trios, d_jack, 3 * n_trios * sizeof(pgt_f3_jack), work, work_bytes, nullptr), ctx);
-        jack.resize(3 * n_trios);
-        check(pgt_rowbuf_read(ctx, jack.data(), d_jack, 3 * n_trios * sizeof(pgt_f3_jack), nullptr), ctx);
+struct F3Pops : PopsTool {
+    static constexpr const char *name = "f3WindowPops";
+    static constexpr int min_files = 3, max_files = 6;
+    static constexpr auto help = ::help;
+    static constexpr int arity = 3;  // all trios
+    using Row = pgt_f3_row;
+    using Total = pgt_f3_total;
+    static constexpr const char *ext = ".f3";
+    static constexpr size_t row_bytes = 200;
+    static constexpr auto tree_bytes = pgt_f3_pops_tree_bytes;
+    static constexpr auto reduce_dev = pgt_f3_pops_reduce_dev;
+    JackknifeOption jackknife;
+    bool own(const char *o, const char *v, int argc, char **argv) { return jackknife.take(o, v, argc, argv); }
+    // chr start end mid f3_i f3_j f3_k neff nskip; the genome-wide means from the totals by the row's rule
+    static PopsLine line(const Row &r, uint32_t sites) {
+        return {{r.start, r.end, r.mid}, {mean_of(r.f3_i, r.n), mean_of(r.f3_j, r.n), mean_of(r.f3_k, r.n)}, r.n, sites - r.n};
     }
-    timer.lap("gpu reduce");
-
-    const std::string global_path = std::string(prefix) + ".global";
-    FILE *global = open_out(global_path);
-    size_t t = 0;
-    for (int a = 0; a < K; ++a)
-        for (int b = a + 1; b < K; ++b)
-            for (int c = b + 1; c < K; ++c, ++t) {
-                if (W > 0) {
-                    const std::string path = std::string(prefix) + ".pop" + std::to_string(a + 1) + "_pop" + std::to_string(b + 1) + "_pop" + std::to_string(c + 1) + ".f3";
-                    FILE *f = open_out(path);
-                    const pgt_f3_row *r = rows.data() + t * n_win;
-                    write_rows(n_win, longest_name(runs) + 200, [&](size_t i, char *o) -> size_t {  // -skip_missing as dxyWindow.cpp:189
-                        if (!(r[i].n > 0 || !skip_missing)) return 0;
-                        return put_f3_row(o, runs.name[win[i].label_run], r[i], (uint32_t)(win[i].hi - win[i].lo) - r[i].n);
-                    }, f);
-                    close_out(f, path);
-                }
-                const pgt_f3_total &g = tot[t];  // the means from the totals by the row's rule
-                std::fprintf(global, "%d\t%d\t%d\t%g\t%g\t%g\t%llu\t%llu\n", a + 1, b + 1, c + 1, mean_of(g.f3_i, g.neff), mean_of(g.f3_j, g.neff),
-                             mean_of(g.f3_k, g.neff), (unsigned long long)g.neff, (unsigned long long)g.nskip);
-            }
-    close_out(global, global_path);
-    if (jackknife) {  // target src1 src2 f3 f3_jack SE Z nblocks nsites: trio order, then (i; j,k), (j; i,k), (k; i,j)
-        const std::string path = std::string(prefix) + ".jackknife";
-        FILE *f = open_out(path);
-        t = 0;
-        for (int a = 0; a < K; ++a)
-            for (int b = a + 1; b < K; ++b)
-                for (int c = b + 1; c < K; ++c, ++t) {
-                    const int target[3][3] = {{a, b, c}, {b, a, c}, {c, a, b}};
-                    for (int u = 0; u < 3; ++u) {
-                        const pgt_f3_jack &r = jack[3 * t + (size_t)u];
-                        auto g6 = [](double v) { char b_[64]; if (v != v) return std::string("nan"); std::snprintf(b_, sizeof b_, "%g", v); return std::string(b_); };
-                        std::fprintf(f, "%d\t%d\t%d\t%s\t%s\t%s\t%s\t%u\t%llu\n", target[u][0] + 1, target[u][1] + 1, target[u][2] + 1, g6(r.f3).c_str(),
-                                     g6(r.f3_jack).c_str(), g6(r.se).c_str(), g6(r.z).c_str(), r.n_blocks, (unsigned long long)r.n_sites);
-                    }
-                }
-        close_out(f, path);
+    static PopsLine total(const Total &g) { return {{}, {mean_of(g.f3_i, g.neff), mean_of(g.f3_j, g.neff), mean_of(g.f3_k, g.neff)}, g.neff, g.nskip}; }
+    // target src1 src2 f3 f3_jack SE Z nblocks nsites: trio order, then (i; j,k), (j; i,k), (k; i,j)
+    static constexpr int targets[3][3] = {{0, 1, 2}, {1, 0, 2}, {2, 0, 1}};
+    void more(PopsRun &run, const Row *d_rows) {
+        if (jackknife.on) pops_jackknife(run, d_rows, pgt_f3_jackknife_dev, pgt_f3_jackknife_work_bytes, targets);
     }
-    finish(timer);
-}
+};
+
+int main(int argc, char **argv) { return run_pops_tool<F3Pops>(argc, argv); }

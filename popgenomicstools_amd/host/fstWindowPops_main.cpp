@@ -52,61 +52,27 @@ static void help(const DxyOptions &o) {
                 "-sizefile", "FILE", "-skip_missing", "INT", o.skip_missing, "-estimator", "STRING");
 }
 
-int main(int argc, char **argv) {
-    const std::string tool = "fstWindowPops";
-    bool hudson = false;
-    const PopsArgs args = parse_pops_args(tool, argc, argv, help, 2, [&](const char *o, const char *v) {
+struct FstPops : PopsTool {
+    static constexpr const char *name = "fstWindowPops";
+    static constexpr int min_files = 2;
+    static constexpr auto help = ::help;
+    static constexpr int arity = 2;  // all pairs
+    using Row = pgt_fst_row;
+    using Total = pgt_fst_total;
+    static constexpr const char *ext = ".fst";
+    static constexpr size_t row_bytes = 100;
+    static constexpr auto tree_bytes = pgt_fst_pops_tree_bytes;  // one size for both estimators
+    decltype(&pgt_fst_pops_reduce_dev) reduce_dev = pgt_fst_pops_reduce_dev;
+    bool own(const char *o, const char *v, int, char **) {
         if (std::strcmp(o, "-estimator")) return false;
-        if (!std::strcmp(v, "hudson")) hudson = true;
-        else if (!std::strcmp(v, "wc")) hudson = false;
+        if (!std::strcmp(v, "hudson")) reduce_dev = pgt_fst_hudson_pops_reduce_dev;
+        else if (!std::strcmp(v, "wc")) reduce_dev = pgt_fst_pops_reduce_dev;
         else die(std::string("-estimator must be wc or hudson (given: ") + v + ")");
         return true;
-    });
-    const int K = args.K;
-    const char *prefix = args.prefix;
-    const uint32_t W = args.opt.W;
-    const int minind = args.opt.minind, skip_missing = args.opt.skip_missing;
+    }
+    // chr start end mid fst neff nskip: fstWindow's row (fstWindow.cpp:88) and the skipped count
+    static PopsLine line(const Row &r, uint32_t sites) { return {{r.start, r.end, r.mid}, {r.fst}, r.n, sites - r.n}; }
+    static PopsLine total(const Total &g) { return {{}, {g.bsum != 0.0 ? g.asum / g.bsum : 0.0}, g.neff, g.nskip}; }
+};
 
-    PhaseTimer timer;
-    DeviceOpener device(std::vector<int>{devices_from_env()[0]});  // one GPU; HIP start-up runs beside the opening of the files
-    const PopsSites s = load_pops(tool, args, timer, device);
-    pgt_ctx *ctx = s.ctx;
-    const std::vector<pgt_win> &win = s.win;
-    const Runs &runs = s.runs;
-    const size_t n_pairs = (size_t)K * (size_t)(K - 1) / 2, n_win = win.size();
-    pgt_fst_row *d_rows = pops_dev_alloc<pgt_fst_row>(ctx, n_pairs * n_win);
-    pgt_fst_total *d_tot = pops_dev_alloc<pgt_fst_total>(ctx, n_pairs);
-    const size_t tree_bytes = pgt_fst_pops_tree_bytes((uint32_t)K, s.n_sites);
-    void *tree = nullptr;
-    check(pgt_dev_alloc(ctx, tree_bytes, &tree), ctx);
-    check((hudson ? pgt_fst_hudson_pops_reduce_dev : pgt_fst_pops_reduce_dev)(ctx, s.a_pos, s.a_freq.data(), s.a_nind.data(), (uint32_t)K, s.n_sites, minind, n_win ? s.d_win : nullptr, n_win,
-            n_win ? d_rows : nullptr, n_pairs * n_win * sizeof(pgt_fst_row), d_tot, tree, tree_bytes, nullptr), ctx);
-    RowArray<pgt_fst_row> rows(n_pairs * n_win);
-    std::vector<pgt_fst_total> tot(n_pairs);
-    check(pgt_rowbuf_read(ctx, rows.data(), d_rows, n_pairs * n_win * sizeof(pgt_fst_row), nullptr), ctx);
-    check(pgt_rowbuf_read(ctx, tot.data(), d_tot, n_pairs * sizeof(pgt_fst_total), nullptr), ctx);
-    timer.lap("gpu reduce");
-
-    const std::string global_path = std::string(prefix) + ".global";
-    FILE *global = open_out(global_path);
-    size_t p = 0;
-    for (int a = 0; a < K; ++a)
-        for (int b = a + 1; b < K; ++b, ++p) {
-            if (W > 0) {
-                const std::string path = pair_path(prefix, a, b, ".fst");
-                FILE *f = open_out(path);
-                const pgt_fst_row *r = rows.data() + p * n_win;
-                // chr start end mid fst neff nskip: fstWindow's row (fstWindow.cpp:88) and the skipped count; -skip_missing as dxyWindow.cpp:189
-                write_rows(n_win, longest_name(runs) + 100, [&](size_t i, char *o) -> size_t {
-                    if (!(r[i].n > 0 || !skip_missing)) return 0;
-                    const uint32_t nskip = (uint32_t)(win[i].hi - win[i].lo) - r[i].n;
-                    return put_row(o, runs.name[win[i].label_run], {r[i].start, r[i].end, r[i].mid}, r[i].fst, {r[i].n, nskip});
-                }, f);
-                close_out(f, path);
-            }
-            const double fst = tot[p].bsum != 0.0 ? tot[p].asum / tot[p].bsum : 0.0;
-            std::fprintf(global, "%d\t%d\t%g\t%llu\t%llu\n", a + 1, b + 1, fst, (unsigned long long)tot[p].neff, (unsigned long long)tot[p].nskip);
-        }
-    close_out(global, global_path);
-    finish(timer);
-}
+int main(int argc, char **argv) { return run_pops_tool<FstPops>(argc, argv); }

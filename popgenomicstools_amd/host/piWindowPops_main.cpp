@@ -49,52 +49,21 @@ static void help(const DxyOptions &o) {
                 "-sizefile", "FILE", "-skip_missing", "INT", o.skip_missing);
 }
 
-int main(int argc, char **argv) {
-    const std::string tool = "piWindowPops";
-    const PopsArgs args = parse_pops_args(tool, argc, argv, help, 1);
-    const int K = args.K;
-    const char *prefix = args.prefix;
-    const uint32_t W = args.opt.W;
-    const int minind = args.opt.minind, skip_missing = args.opt.skip_missing;
+struct PiPops : PopsTool {
+    static constexpr const char *name = "piWindowPops";
+    static constexpr int min_files = 1;
+    static constexpr auto help = ::help;
+    static constexpr int arity = 1;  // each population
+    using Row = pgt_dxy_row;
+    using Total = pgt_dxy_total;
+    static constexpr const char *ext = ".pi";
+    static constexpr size_t row_bytes = 80;
+    static constexpr auto tree_bytes = pgt_pi_pops_tree_bytes;
+    static constexpr auto reduce_dev = pgt_pi_pops_reduce_dev;
+    static constexpr bool window_hints = true;  // the only one of the five tools that sets them
+    // chr start end pi_sum neff nskip: dxyWindow's row (dxyWindow.cpp:190), the skipped count the library's
+    static PopsLine line(const Row &r, uint32_t) { return {{r.start, r.end}, {r.sum}, r.neff, r.nskip}; }
+    static PopsLine total(const Total &g) { return {{}, {g.sum}, g.neff, g.nskip}; }
+};
 
-    PhaseTimer timer;
-    DeviceOpener device(std::vector<int>{devices_from_env()[0]});  // one GPU; HIP start-up runs beside the opening of the files
-    const PopsSites s = load_pops(tool, args, timer, device);
-    pgt_ctx *ctx = s.ctx;
-    const std::vector<pgt_win> &win = s.win;
-    const Runs &runs = s.runs;
-    const size_t n_pops = (size_t)K, n_win = win.size();
-    pgt_dxy_row *d_rows = pops_dev_alloc<pgt_dxy_row>(ctx, n_pops * n_win);
-    pgt_dxy_total *d_tot = pops_dev_alloc<pgt_dxy_total>(ctx, n_pops);
-    const size_t tree_bytes = pgt_pi_pops_tree_bytes((uint32_t)K, s.n_sites);
-    void *tree = nullptr;
-    check(pgt_dev_alloc(ctx, tree_bytes, &tree), ctx);
-    if (n_win) {  // the table is known here: the hints choose the query strategy (rows do not depend on them beyond the last bits)
-        uint64_t max_window = 0, typical = 0, step = 0;
-        check(pgt_table_hints(win.data(), n_win, &max_window, &typical, &step), ctx);
-        check(pgt_set_max_window(ctx, max_window), ctx);
-        check(pgt_set_typical_window(ctx, typical), ctx);
-        check(pgt_set_window_step(ctx, step), ctx);
-    }
-    check(pgt_pi_pops_reduce_dev(ctx, s.a_pos, s.a_freq.data(), s.a_nind.data(), (uint32_t)K, s.n_sites, minind, n_win ? s.d_win : nullptr, n_win,
-                                 n_win ? d_rows : nullptr, n_pops * n_win * sizeof(pgt_dxy_row), d_tot, tree, tree_bytes, nullptr), ctx);
-    RowArray<pgt_dxy_row> rows(n_pops * n_win);
-    std::vector<pgt_dxy_total> tot(n_pops);
-    check(pgt_rowbuf_read(ctx, rows.data(), d_rows, n_pops * n_win * sizeof(pgt_dxy_row), nullptr), ctx);
-    check(pgt_rowbuf_read(ctx, tot.data(), d_tot, n_pops * sizeof(pgt_dxy_total), nullptr), ctx);
-    timer.lap("gpu reduce");
-
-    const std::string global_path = std::string(prefix) + ".global";
-    FILE *global = open_out(global_path);
-    for (int a = 0; a < K; ++a) {
-        if (W > 0) {
-            const std::string path = std::string(prefix) + ".pop" + std::to_string(a + 1) + ".pi";
-            FILE *f = open_out(path);
-            write_dxy_rows(rows.data() + (size_t)a * n_win, n_win, runs, [&](size_t w) { return win[w].label_run; }, skip_missing, f);
-            close_out(f, path);
-        }
-        std::fprintf(global, "%d\t%g\t%llu\t%llu\n", a + 1, tot[(size_t)a].sum, (unsigned long long)tot[(size_t)a].neff, (unsigned long long)tot[(size_t)a].nskip);
-    }
-    close_out(global, global_path);
-    finish(timer);
-}
+int main(int argc, char **argv) { return run_pops_tool<PiPops>(argc, argv); }

@@ -1,11 +1,24 @@
-// pops_common.h — the K-file front end the all-pairs hosts (dxyWindowPops, fstWindowPops), piWindowPops and dstatWindowPops share: the command
-// line (dxyWindow's options, -out PREFIX, 2 ... 8 MAF files; piWindowPops admits one, dstatWindowPops takes 4 ... 7), and from the opened files to the aligned columns and the window
-// table on the device — open, parse on the host or the device, the resident-size refusals, chromosome ids,
-// pgt_align_segments, upload, pgt_sites_align, pgt_gather_dev, the runs of the common sites, the window table.
-// The K-file form of the reference's site synchronisation (dxyWindow.cpp:315-331): the sites (chromosome, position) that
-// ALL files list are found on the GPU (a single file is its own site list: nothing to align).  Messages carry the tool's name.
+// pops_common.h — the five K-population hosts (dxyWindowPops, fstWindowPops, piWindowPops, dstatWindowPops, f3WindowPops) are one
+// program, run_pops_tool<Tool>: the command line (dxyWindow's options, the tool's own, -out PREFIX, the tool's number of MAF
+// files), from the opened files to the aligned columns and the window table on the device (load_pops — open, parse on the host or
+// the device, the resident-size refusals, chromosome ids, pgt_align_segments, upload, pgt_sites_align, pgt_gather_dev, the runs of
+// the common sites, the window table), one reduction of all the tool's tables (pops_pass), and PREFIX.pop<i>[_pop<j>[_pop<k>]]<ext>
+// per table with PREFIX.global.  The K-file form of the reference's site synchronisation (dxyWindow.cpp:315-331): the sites
+// (chromosome, position) that ALL files list are found on the GPU (a single file is its own site list: nothing to align).
+// Messages carry the tool's name.  A tool is a struct (derived from PopsTool, which holds what most tools leave alone) with
+//     name, min_files, max_files, help(options)      the help text is the tool's own, verbatim
+//     own(option, value, argc, argv)                  an option of this tool alone: taken (or refused by die()) -> true
+//     arity, outgroup                                 its tables: all pairs (2), each population (1), all trios (3) of the K files —
+//                                                     of the K-1 before the last with an outgroup
+//     Row, Total, ext, global_ext, row_bytes, tree_bytes, reduce_dev    the reduction and its files
+//     line(row, sites of the window), total(total)    the numbers of a row behind `chr`, of a PREFIX.global line behind the indices
+//     window_hints                                    the window table's hints are set before the reduction (piWindowPops alone)
+//     more(run, rows on the device)                   further device work on the same columns: pops_jackknife, a second pops_pass
+// and its main is `return run_pops_tool<Tool>(argc, argv);`.
 #pragma once
 
+#include <cstddef>
+#include <functional>
 #include <memory>
 
 #include "dxy_common.h"
@@ -35,17 +48,15 @@ struct PopsArgs {
     char **paths = nullptr;
     std::map<std::string, uint32_t> chrsize;
 };
-// option/value pairs first; what follows the last pair are the MAF files (min_files ... max_files of them).  help(opt) prints the tool's
-// usage (no argument: exit 0).  own(option, value) -> true when the pair is an option of this tool alone, which it has taken
-// (or refused by die()); a tool without one keeps answering `Unknown command:` for every option that is not dxyWindow's
-struct NoOwnOption {
-    bool operator()(const char *, const char *) const { return false; }
-};
-template <class Help, class Own = NoOwnOption>
-inline PopsArgs parse_pops_args(const std::string &tool, int argc, char **argv, Help help, int min_files = 2, Own own = Own{}, int max_files = 8) {
+// option/value pairs first; what follows the last pair are the MAF files (Tool::min_files ... Tool::max_files of them).
+// Tool::help(opt) prints the tool's usage (no argument: exit 0).  tool.own(option, value, argc, argv) -> true when the pair is an
+// option of this tool alone, which it has taken (or refused by die()); a tool without one keeps answering `Unknown command:` for
+// every option that is not dxyWindow's.  The refusals come in this order, all before a file is opened or the device is touched.
+template <class Tool>
+inline PopsArgs parse_pops_args(Tool &tool, int argc, char **argv) {
     PopsArgs a;
     if (argc < 2) {
-        help(a.opt);
+        Tool::help(a.opt);
         std::exit(0);
     }
     int i = 1;
@@ -53,18 +64,38 @@ inline PopsArgs parse_pops_args(const std::string &tool, int argc, char **argv, 
         const char *o = argv[i];
         if (i + 1 >= argc) die(std::string("Missing value for ") + o);
         if (!std::strcmp(o, "-out")) a.prefix = argv[i + 1];
-        else if (own(o, argv[i + 1])) continue;
+        else if (tool.own(o, argv[i + 1], argc, argv)) continue;
         else if (!dxy_option(a.opt, o, argv[i + 1])) unknown_dxy_option(o);
     }
     a.K = argc - i;
     a.paths = argv + i;
-    if (a.K < min_files || a.K > max_files)
-        die(tool + ": between " + std::to_string(min_files) + " and " + std::to_string(max_files) + " MAF files are needed (" + std::to_string(std::max(a.K, 0)) + " given)");
+    if (a.K < Tool::min_files || a.K > Tool::max_files)
+        die(std::string(Tool::name) + ": between " + std::to_string(Tool::min_files) + " and " + std::to_string(Tool::max_files) + " MAF files are needed (" + std::to_string(std::max(a.K, 0)) + " given)");
     if (!a.prefix || !*a.prefix) die("Must supply -out PREFIX");
     check_dxy_options(a.opt);
     if (!a.opt.fixedsite) a.chrsize = read_sizefile(a.opt.sizefile);
     return a;
 }
+
+// -jackknife 0|1 of the trio tools.  With 1 the run is refused here, while the options are read and before any file is opened,
+// unless its windows exist and are disjoint: they are the blocks (the option pairs are walked as parse_pops_args walks them, so
+// the last value of -winsize / -stepsize counts wherever -jackknife stands).
+struct JackknifeOption {
+    bool on = false;
+    bool take(const char *o, const char *v, int argc, char **argv) {
+        if (std::strcmp(o, "-jackknife")) return false;
+        if (std::strcmp(v, "0") && std::strcmp(v, "1")) die(std::string("-jackknife must be 0 or 1 (given: ") + v + ")");
+        on = v[0] == '1';
+        if (!on) return true;
+        DxyOptions w;
+        for (int i = 1; i + 1 < argc && argv[i][0] == '-' && argv[i][1] != '\0'; i += 2)
+            if (!std::strcmp(argv[i], "-winsize") || !std::strcmp(argv[i], "-stepsize")) dxy_option(w, argv[i], argv[i + 1]);
+        if (w.W == 0) die("-jackknife 1 needs windows as its blocks: -winsize must be > 0");
+        if (w.S < w.W)
+            die("-jackknife 1 needs windows that do not overlap: -stepsize (" + std::to_string(w.S) + ") must not be below -winsize (" + std::to_string(w.W) + ")");
+        return true;
+    }
+};
 
 // ---- from the files to the aligned columns ------------------------------------------------------------------------------
 // everything the reduction needs, on the device: the shared position column, every file's frequency and count column
@@ -312,8 +343,184 @@ inline FILE *open_out(const std::string &path) {
 inline void close_out(FILE *f, const std::string &path) {
     if (std::fflush(f) != 0 || std::ferror(f) || std::fclose(f) != 0) die("Error writing the output: " + path);
 }
-inline std::string pair_path(const char *prefix, int a, int b, const char *ext) {
-    return std::string(prefix) + ".pop" + std::to_string(a + 1) + "_pop" + std::to_string(b + 1) + ext;
+
+// ---- the tables of a call -----------------------------------------------------------------------------------------------
+// one table: the (0-based) populations of a pair, a population or a trio
+struct PopsIndex {
+    int n;
+    int pop[3];
+};
+// all i < j < .. of `pops` populations, `arity` of them each, in the library's table order: (0,1),(0,2),..,(1,2),..
+// (a loop beyond the arity runs once; what it leaves in `pop` is not looked at)
+inline std::vector<PopsIndex> pops_tuples(int arity, int pops) {
+    std::vector<PopsIndex> t;
+    for (int a = 0; a < pops; ++a)
+        for (int b = arity > 1 ? a + 1 : pops - 1; b < pops; ++b)
+            for (int c = arity > 2 ? b + 1 : pops - 1; c < pops; ++c) t.push_back({arity, {a, b, c}});
+    return t;
+}
+// `pop1_pop2_pop3` of a file name ("pop", "_"), `1 2 3` at the head of a PREFIX.global line ("", "\t")
+inline std::string tuple_text(const PopsIndex &ix, const char *before, const char *between) {
+    std::string s;
+    for (int k = 0; k < ix.n; ++k) s += std::string(k ? between : "") + before + std::to_string(ix.pop[k] + 1);
+    return s;
+}
+
+// ---- one line of a table's file, or of PREFIX.global --------------------------------------------------------------------
+// a row: `chr start end [mid]`, its doubles, `n nskip`; a genome-wide line: the table's indices, its doubles, `neff nskip`
+struct PopsLine {
+    uint32_t lead[3];
+    double g[5];
+    int n_lead = 0, n_g = 0;
+    uint64_t n, nskip;
+    PopsLine(std::initializer_list<uint32_t> lead_, std::initializer_list<double> g_, uint64_t n_, uint64_t nskip_) : n(n_), nskip(nskip_) {
+        for (uint32_t u : lead_) lead[n_lead++] = u;
+        for (double v : g_) g[n_g++] = v;
+    }
+};
+// the row as put_row writes it, with any number of %g columns
+inline size_t put_pops_line(char *o, const std::string &chr, const PopsLine &l) {
+    char *p = o;
+    std::memcpy(p, chr.data(), chr.size());
+    p += chr.size();
+    for (int k = 0; k < l.n_lead; ++k) { *p++ = '\t'; p = put_u32(p, l.lead[k]); }
+    for (int k = 0; k < l.n_g; ++k) { *p++ = '\t'; p += fmt_g6(l.g[k], p); }
+    for (uint32_t u : {(uint32_t)l.n, (uint32_t)l.nskip}) { *p++ = '\t'; p = put_u32(p, u); }
+    *p++ = '\n';
+    return (size_t)(p - o);
+}
+
+// ---- the run ------------------------------------------------------------------------------------------------------------
+// What the passes of a run share.  A pass reduces and reads its results back at once, and queues what writes its files: every
+// reduction of a run is done, under the "gpu reduce" lap, before the first output file is opened.
+struct PopsRun {
+    const PopsArgs &args;
+    const PopsSites &s;
+    std::vector<PopsIndex> tables;
+    void *tree = nullptr;  // one buffer for the passes, one after the other: a later pass has the size of the first
+    size_t tree_bytes = 0;
+    std::vector<std::function<void()>> writers;
+};
+
+// One reduction of the aligned columns over all tables of the run, and its files: PREFIX.<table><ext> per table (not with
+// -winsize 0) and PREFIX<global_ext>.  -> the rows on the device, table after table
+template <class Pass>
+typename Pass::Row *pops_pass(const Pass &pass, PopsRun &run) {
+    using Row = typename Pass::Row;
+    using Total = typename Pass::Total;
+    const PopsSites &s = run.s;
+    pgt_ctx *ctx = s.ctx;
+    const size_t n_tab = run.tables.size(), n_win = s.win.size();
+    Row *d_rows = pops_dev_alloc<Row>(ctx, n_tab * n_win);
+    Total *d_tot = pops_dev_alloc<Total>(ctx, n_tab);
+    check(pass.reduce_dev(ctx, s.a_pos, s.a_freq.data(), s.a_nind.data(), (uint32_t)run.args.K, s.n_sites, run.args.opt.minind, n_win ? s.d_win : nullptr, n_win,
+                          n_win ? d_rows : nullptr, n_tab * n_win * sizeof(Row), d_tot, run.tree, run.tree_bytes, nullptr), ctx);
+    auto rows = std::make_shared<RowArray<Row>>(n_tab * n_win);
+    auto tot = std::make_shared<std::vector<Total>>(n_tab);
+    check(pgt_rowbuf_read(ctx, rows->data(), d_rows, n_tab * n_win * sizeof(Row), nullptr), ctx);
+    check(pgt_rowbuf_read(ctx, tot->data(), d_tot, n_tab * sizeof(Total), nullptr), ctx);
+    run.writers.push_back([&run, rows, tot, n_win] {
+        const char *prefix = run.args.prefix;
+        const int skip_missing = run.args.opt.skip_missing;
+        const std::vector<pgt_win> &win = run.s.win;
+        const Runs &runs = run.s.runs;
+        const std::string global_path = std::string(prefix) + Pass::global_ext;
+        FILE *global = open_out(global_path);
+        for (size_t t = 0; t < run.tables.size(); ++t) {
+            const PopsIndex &ix = run.tables[t];
+            if (run.args.opt.W > 0) {
+                const std::string path = std::string(prefix) + "." + tuple_text(ix, "pop", "_") + Pass::ext;
+                FILE *f = open_out(path);
+                const Row *r = rows->data() + t * n_win;
+                write_rows(n_win, longest_name(runs) + Pass::row_bytes, [&](size_t i, char *o) -> size_t {  // -skip_missing as dxyWindow.cpp:189
+                    const PopsLine l = Pass::line(r[i], (uint32_t)(win[i].hi - win[i].lo));
+                    if (!(l.n > 0 || !skip_missing)) return 0;
+                    return put_pops_line(o, runs.name[win[i].label_run], l);
+                }, f);
+                close_out(f, path);
+            }
+            const PopsLine g = Pass::total((*tot)[t]);
+            std::fputs(tuple_text(ix, "", "\t").c_str(), global);
+            for (int k = 0; k < g.n_g; ++k) std::fprintf(global, "\t%g", g.g[k]);
+            std::fprintf(global, "\t%llu\t%llu\n", (unsigned long long)g.n, (unsigned long long)g.nskip);
+        }
+        close_out(global, global_path);
+    });
+    return d_rows;
+}
+
+// -jackknife 1: the delete-m_j block jackknife of every trio of the run on its rows still on the device, every window of the table
+// a block -> PREFIX.jackknife, three lines per trio (`P1 P2 P3 estimate jackknife_estimate SE Z nblocks nsites`).  order[u]:
+// which of the trio's populations line u names first, second and third.  The two entry points' results are one layout.
+struct PopsJack {
+    double est, est_jack, se, z;
+    uint64_t n_sites;
+    uint32_t n_blocks, pad_;
+};
+template <class Row, class Jack>
+void pops_jackknife(PopsRun &run, const Row *d_rows, int (*jackknife_dev)(pgt_ctx *, const Row *, uint64_t, uint32_t, Jack *, size_t, void *, size_t, void *),
+                    size_t (*work_bytes)(uint32_t, uint64_t), const int (&order)[3][3]) {
+    static_assert(sizeof(Jack) == sizeof(PopsJack) && offsetof(Jack, se) == offsetof(PopsJack, se) && offsetof(Jack, z) == offsetof(PopsJack, z) &&
+                  offsetof(Jack, n_sites) == offsetof(PopsJack, n_sites) && offsetof(Jack, n_blocks) == offsetof(PopsJack, n_blocks),
+                  "the estimate and its jackknife estimate, then se, z, n_sites, n_blocks");
+    pgt_ctx *ctx = run.s.ctx;
+    const size_t n_trios = run.tables.size(), n_win = run.s.win.size();
+    const size_t bytes = work_bytes((uint32_t)n_trios, n_win);
+    void *work = nullptr;
+    check(pgt_dev_alloc(ctx, bytes, &work), ctx);
+    Jack *d_jack = pops_dev_alloc<Jack>(ctx, 3 * n_trios);
+    check(jackknife_dev(ctx, d_rows, n_win, (uint32_t)n_trios, d_jack, 3 * n_trios * sizeof(Jack), work, bytes, nullptr), ctx);
+    auto jack = std::make_shared<std::vector<PopsJack>>(3 * n_trios);
+    check(pgt_rowbuf_read(ctx, jack->data(), d_jack, 3 * n_trios * sizeof(Jack), nullptr), ctx);
+    run.writers.push_back([&run, jack, &order] {  // (order: a constant of the tool)
+        const std::string path = std::string(run.args.prefix) + ".jackknife";
+        FILE *f = open_out(path);
+        auto g6 = [](double v) { char b_[64]; if (v != v) return std::string("nan"); std::snprintf(b_, sizeof b_, "%g", v); return std::string(b_); };
+        for (size_t t = 0; t < run.tables.size(); ++t)
+            for (int u = 0; u < 3; ++u) {
+                const int *pop = run.tables[t].pop;
+                const PopsJack &r = (*jack)[3 * t + (size_t)u];
+                std::fprintf(f, "%d\t%d\t%d\t%s\t%s\t%s\t%s\t%u\t%llu\n", pop[order[u][0]] + 1, pop[order[u][1]] + 1, pop[order[u][2]] + 1, g6(r.est).c_str(),
+                             g6(r.est_jack).c_str(), g6(r.se).c_str(), g6(r.z).c_str(), r.n_blocks, (unsigned long long)r.n_sites);
+            }
+        close_out(f, path);
+    });
+}
+
+// ---- the tool -----------------------------------------------------------------------------------------------------------
+// what most tools leave as it is
+struct PopsTool {
+    static constexpr int max_files = 8;
+    static constexpr bool outgroup = false;      // the LAST file is the outgroup: it is in no table
+    static constexpr bool window_hints = false;  // the hints choose the query strategy, and rows may differ in their last bits between strategies
+    static constexpr const char *global_ext = ".global";
+    bool own(const char *, const char *, int, char **) { return false; }
+    template <class Row>
+    void more(PopsRun &, const Row *) {}
+};
+
+template <class Tool>
+int run_pops_tool(int argc, char **argv) {
+    Tool tool;
+    const PopsArgs args = parse_pops_args(tool, argc, argv);
+    PhaseTimer timer;
+    DeviceOpener device(std::vector<int>{devices_from_env()[0]});  // one GPU; HIP start-up runs beside the opening of the files
+    const PopsSites s = load_pops(Tool::name, args, timer, device);
+    pgt_ctx *ctx = s.ctx;
+    PopsRun run{args, s, pops_tuples(Tool::arity, args.K - (Tool::outgroup ? 1 : 0))};
+    run.tree_bytes = Tool::tree_bytes((uint32_t)args.K, s.n_sites);
+    check(pgt_dev_alloc(ctx, run.tree_bytes, &run.tree), ctx);
+    if (Tool::window_hints && !s.win.empty()) {  // the table is known here
+        uint64_t max_window = 0, typical = 0, step = 0;
+        check(pgt_table_hints(s.win.data(), s.win.size(), &max_window, &typical, &step), ctx);
+        check(pgt_set_max_window(ctx, max_window), ctx);
+        check(pgt_set_typical_window(ctx, typical), ctx);
+        check(pgt_set_window_step(ctx, step), ctx);
+    }
+    tool.more(run, pops_pass(tool, run));
+    timer.lap("gpu reduce");
+    for (const auto &write : run.writers) write();
+    finish(timer);
 }
 
 }  // namespace pgthost
