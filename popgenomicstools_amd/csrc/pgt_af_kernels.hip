@@ -386,9 +386,9 @@ __global__ __launch_bounds__(256, 2) void af_query_kernel(AfCols cols, const uin
 
 template <int NP>
 int launch_af_np(const AfCols &cols, const uint32_t *pos, uint64_t n, const pgt_win *win, uint64_t n_win,
-                 pgt_fst_row *out, const AfTree &tv, const TreeLayout &tl, hipStream_t s, void *ev_b0, void *ev_b1,
-                 void *ev_q1, std::string *err) {
-    if (int rc = record_event(ev_b0, s, err)) return rc;
+                 pgt_fst_row *out, const AfTree &tv, const TreeLayout &tl, hipStream_t s, const LaunchEnv &e) {
+    std::string *err = e.err;
+    if (int rc = record_event(e.ev_build0, s, err)) return rc;
     if (n > 0) {
         // Balanced grid-stride over the level-2 tiles: r = ceil(tiles / (4 cap)) rounds, ceil(tiles / r) waves,
         // so every wave does r tiles.  Measured at 10^8 sites, 8 populations (profiles/r02/af_caps.txt): the
@@ -421,12 +421,12 @@ int launch_af_np(const AfCols &cols, const uint32_t *pos, uint64_t n, const pgt_
         if (int rc = hip_fail(hipGetLastError(), "af_build_kernel", err)) return rc;
         if (int rc = launch_upper_levels(af_up_kernel, "af_up_kernel", Shape<NP>::kVals, tv, tl, s, err)) return rc;
     }
-    if (int rc = record_event(ev_b1, s, err)) return rc;
+    if (int rc = record_event(e.ev_build1, s, err)) return rc;
     if (n_win > 0) {
         hipLaunchKernelGGL((af_query_kernel<NP>), dim3(wave_grid(n_win)), dim3(256), 0, s, cols, pos, tv, win, n_win, out, n);
         if (int rc = hip_fail(hipGetLastError(), "af_query_kernel", err)) return rc;
     }
-    return record_event(ev_q1, s, err);
+    return record_event(e.ev_query1, s, err);
 }
 
 }  // namespace
@@ -446,20 +446,19 @@ int init_af_kernels(std::string *err) {
 }
 
 int launch_fst_af(const uint32_t *pos, const double *const *freq, const double *nsamp, uint32_t n_pops, uint64_t n,
-                  const pgt_win *win, uint64_t n_win, pgt_fst_row *out, void *tree, void *stream, void *ev_build0,
-                  void *ev_build1, void *ev_query1, std::string *err, const Hints &hints) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
+                  const pgt_win *win, uint64_t n_win, pgt_fst_row *out, void *tree, const LaunchEnv &e) {
+    hipStream_t s = static_cast<hipStream_t>(e.stream);
     if (n_pops < 2 || n_pops > (uint32_t)kAfMaxPops) {
-        if (err) *err = "pgt_fst_af_reduce: 2 <= n_pops <= 8";
+        if (e.err) *e.err = "pgt_fst_af_reduce: 2 <= n_pops <= 8";
         return PGT_EARG;
     }
     const TreeLayout tl = tree_layout(PGT_STAT_FST, n);
     const int n_vals = (int)(n_pops + n_pops * (n_pops - 1) / 2);
-    const AfTree tv = af_tree_view(tl, n_vals, tree, useful_levels(tl, PGT_STAT_FST, hints.max_window));
+    const AfTree tv = af_tree_view(tl, n_vals, tree, useful_levels(tl, PGT_STAT_FST, e.hints.max_window));
     AfCols cols{};
     for (uint32_t k = 0; k < n_pops; ++k) { cols.f[k] = freq[k]; cols.nsamp[k] = nsamp[k]; }
     return dispatch_n_pops(n_pops, [&](auto np) {
-        return launch_af_np<decltype(np)::value>(cols, pos, n, win, n_win, out, tv, tl, s, ev_build0, ev_build1, ev_query1, err);
+        return launch_af_np<decltype(np)::value>(cols, pos, n, win, n_win, out, tv, tl, s, e);
     });
 }
 

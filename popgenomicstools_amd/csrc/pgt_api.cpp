@@ -294,19 +294,12 @@ int check_windows_host(pgt_ctx *ctx, const pgt_win *win, uint64_t n_win, uint64_
     return PGT_OK;
 }
 
-struct EvSet {
-    void *b0 = nullptr, *b1 = nullptr, *q1 = nullptr;
-};
-EvSet events_for(pgt_ctx *ctx) {
-    EvSet e;
-    if (ctx->profiling) {
-        e.b0 = ctx->ev[0];
-        e.b1 = ctx->ev[1];
-        e.q1 = ctx->ev[2];
-        ctx->have_timing = true;
-        ctx->timing_query_only = false;
-    }
-    return e;
+// what a launcher ends in (LaunchEnv): the caller's stream, the context's events when it profiles, its message and hints
+LaunchEnv events_for(pgt_ctx *ctx, void *stream) {
+    if (!ctx->profiling) return LaunchEnv{stream, nullptr, nullptr, nullptr, &ctx->error, ctx->hints};
+    ctx->have_timing = true;
+    ctx->timing_query_only = false;
+    return LaunchEnv{stream, ctx->ev[0], ctx->ev[1], ctx->ev[2], &ctx->error, ctx->hints};
 }
 
 // Every entry point runs on ctx's device and leaves the CALLER's current device as it found it (a
@@ -404,8 +397,7 @@ int pops_reduce_dev(pgt_ctx *ctx, const PopsStat &st, Launch launch_stat, const 
     bool launch;
     if (int rc = pops_check_dev(ctx, st, pos, freq, nind, n_pops, n, minind, win, n_win, out, out_bytes, tot, tree, tree_bytes, &launch)) return rc;
     if (!launch) return PGT_OK;
-    const EvSet e = events_for(ctx);
-    return launch_stat(pos, freq, nind, n_pops, n, minind, win, n_win, out, tot, tree, stream, e.b0, e.b1, e.q1, &ctx->error, ctx->hints);
+    return launch_stat(pos, freq, nind, n_pops, n, minind, win, n_win, out, tot, tree, events_for(ctx, stream));
 }
 
 }  // namespace
@@ -575,8 +567,7 @@ int pgt_fst_reduce_pairs_dev(pgt_ctx *ctx, const uint32_t *pos, const double *co
         return ctx_fail(ctx, PGT_EARG, "pgt_fst_reduce: tree workspace too small or misaligned");
     if (n_win > UINT64_MAX / n_pairs) return ctx_fail(ctx, PGT_EARG, "pgt_fst_reduce: n_pairs * n_win overflows");
     if (int rc = room_check(ctx, "pgt_fst_reduce", (uint64_t)n_pairs * n_win, sizeof(pgt_fst_row), out_bytes)) return rc;
-    const EvSet e = events_for(ctx);
-    return launch_fst(pos, a, b, n_pairs, n, win, n_win, out, tree, stream, e.b0, e.b1, e.q1, &ctx->error, ctx->hints);
+    return launch_fst(pos, a, b, n_pairs, n, win, n_win, out, tree, events_for(ctx, stream));
 }
 
 int pgt_fst_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *a, const double *b, uint64_t n,
@@ -596,8 +587,7 @@ int pgt_het_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const int8_t *g, uint6
     if (!aligned16(tree) || tree_bytes < pgt_tree_bytes(PGT_STAT_HET, n))
         return ctx_fail(ctx, PGT_EARG, "pgt_het_reduce: tree workspace too small or misaligned");
     if (int rc = room_check(ctx, "pgt_het_reduce", n_win, sizeof(pgt_het_row), out_bytes)) return rc;
-    const EvSet e = events_for(ctx);
-    return launch_het(pos, g, n, win, n_win, out, tree, stream, e.b0, e.b1, e.q1, &ctx->error, ctx->hints);
+    return launch_het(pos, g, n, win, n_win, out, tree, events_for(ctx, stream));
 }
 
 int pgt_dxy_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *p1, const double *p2, const int32_t *n1,
@@ -613,9 +603,7 @@ int pgt_dxy_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *p1, cons
     if (!aligned16(tree) || tree_bytes < pgt_tree_bytes(PGT_STAT_DXY, n))
         return ctx_fail(ctx, PGT_EARG, "pgt_dxy_reduce: tree workspace too small or misaligned");
     if (int rc = room_check(ctx, "pgt_dxy_reduce", n_win, sizeof(pgt_dxy_row), out_bytes)) return rc;
-    const EvSet e = events_for(ctx);
-    return launch_dxy(pos, p1, p2, n1, n2, n, minind, win, n_win, out, tot, tree, stream, e.b0, e.b1, e.q1,
-                      &ctx->error, ctx->hints);
+    return launch_dxy(pos, p1, p2, n1, n2, n, minind, win, n_win, out, tot, tree, events_for(ctx, stream));
 }
 
 int pgt_dxy_het_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *p1, const double *p2, const int32_t *n1,
@@ -635,9 +623,8 @@ int pgt_dxy_het_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *p1, 
         return ctx_fail(ctx, PGT_EARG, "pgt_dxy_het_reduce: tree workspace too small or misaligned");
     if (int rc = room_check(ctx, "pgt_dxy_het_reduce (dxy rows)", n_win, sizeof(pgt_dxy_row), dxy_out_bytes)) return rc;
     if (int rc = room_check(ctx, "pgt_dxy_het_reduce (het rows)", n_win, sizeof(pgt_het_row), het_out_bytes)) return rc;
-    const EvSet e = events_for(ctx);
     return launch_dxy_het(pos, p1, p2, n1, n2, g1, g2, n, minind, win, n_win, dxy_out, tot, het_out1, het_out2, tree,
-                          stream, e.b0, e.b1, e.q1, &ctx->error, ctx->hints);
+                          events_for(ctx, stream));
 }
 
 size_t pgt_af_tree_bytes(uint32_t n_pops, uint64_t n_sites) {
@@ -662,9 +649,7 @@ int pgt_fst_af_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const
         return ctx_fail(ctx, PGT_EARG, "pgt_fst_af_reduce: tree workspace too small or misaligned");
     if (n_win > UINT64_MAX / 28) return ctx_fail(ctx, PGT_EARG, "pgt_fst_af_reduce: n_pairs * n_win overflows");
     if (int rc = room_check(ctx, "pgt_fst_af_reduce", (uint64_t)(n_pops * (n_pops - 1) / 2) * n_win, sizeof(pgt_fst_row), out_bytes)) return rc;
-    const EvSet e = events_for(ctx);
-    return launch_fst_af(pos, freq, nsamp, n_pops, n, win, n_win, out, tree, stream, e.b0, e.b1, e.q1, &ctx->error,
-                         ctx->hints);
+    return launch_fst_af(pos, freq, nsamp, n_pops, n, win, n_win, out, tree, events_for(ctx, stream));
 }
 
 // Each statistic's populations (min_pops, max_pops) are stated once, in its PopsStat: its *_pops_tree_bytes reads them there.
@@ -874,9 +859,7 @@ int pgt_extreme_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *scor
     if (!aligned16(tree) || tree_bytes < pgt_tree_bytes(PGT_STAT_EXT, n))
         return ctx_fail(ctx, PGT_EARG, "pgt_extreme_reduce: tree workspace too small or misaligned");
     if (int rc = room_check(ctx, "pgt_extreme_reduce", n_win, sizeof(pgt_ext_row), out_bytes)) return rc;
-    const EvSet e = events_for(ctx);
-    return launch_ext(pos, score, n, mode, cutoff, win, n_win, out, tree, stream, e.b0, e.b1, e.q1, &ctx->error,
-                      ctx->hints);
+    return launch_ext(pos, score, n, mode, cutoff, win, n_win, out, tree, events_for(ctx, stream));
 }
 
 /* ---------------- device-side text ingest ---------------- */

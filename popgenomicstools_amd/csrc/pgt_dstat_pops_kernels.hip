@@ -115,8 +115,8 @@ int init_dstat_pops_kernels(std::string *err) {
 // 4 <= n_pops <= 7 and minind >= 1: checked by the caller
 int launch_dstat_pops(const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops, uint64_t n,
                       int minind, const pgt_win *win, uint64_t n_win, pgt_dstat_row *out, pgt_dstat_total *tot, void *tree,
-                      void *stream, void *ev_build0, void *ev_build1, void *ev_query1, std::string *err, const Hints &hints) {
-    return launch_pops<DstatPops>(pos, freq, nind, n_pops, n, minind, win, n_win, out, tot, tree, stream, ev_build0, ev_build1, ev_query1, err, hints);
+                      const LaunchEnv &e) {
+    return launch_pops<DstatPops>(pos, freq, nind, n_pops, n, minind, win, n_win, out, tot, tree, e);
 }
 
 }  // namespace pgt

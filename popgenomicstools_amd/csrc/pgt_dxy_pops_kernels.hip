@@ -79,8 +79,8 @@ int init_dxy_pops_kernels(std::string *err) {
 
 int launch_dxy_pops(const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops, uint64_t n,
                     int minind, const pgt_win *win, uint64_t n_win, pgt_dxy_row *out, pgt_dxy_total *tot, void *tree,
-                    void *stream, void *ev_build0, void *ev_build1, void *ev_query1, std::string *err, const Hints &hints) {
-    return launch_pops<DxyPops>(pos, freq, nind, n_pops, n, minind, win, n_win, out, tot, tree, stream, ev_build0, ev_build1, ev_query1, err, hints);
+                    const LaunchEnv &e) {
+    return launch_pops<DxyPops>(pos, freq, nind, n_pops, n, minind, win, n_win, out, tot, tree, e);
 }
 
 }  // namespace pgt

@@ -155,11 +155,10 @@ int init_fst_pops_kernels(std::string *err) {
 // 2 <= n_pops <= 8 and minind >= 1: checked by the caller; both estimators share the tree's layout
 int launch_fst_pops(const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops, uint64_t n,
                     int minind, const pgt_win *win, uint64_t n_win, pgt_fst_row *out, pgt_fst_total *tot, void *tree,
-                    void *stream, void *ev_build0, void *ev_build1, void *ev_query1, std::string *err, const Hints &hints,
-                    FstPopsEstimator estimator) {
+                    const LaunchEnv &e, FstPopsEstimator estimator) {
     if (estimator == FstPopsEstimator::Hudson)
-        return launch_pops<FstPops<Hudson>>(pos, freq, nind, n_pops, n, minind, win, n_win, out, tot, tree, stream, ev_build0, ev_build1, ev_query1, err, hints);
-    return launch_pops<FstPops<WeirCockerham>>(pos, freq, nind, n_pops, n, minind, win, n_win, out, tot, tree, stream, ev_build0, ev_build1, ev_query1, err, hints);
+        return launch_pops<FstPops<Hudson>>(pos, freq, nind, n_pops, n, minind, win, n_win, out, tot, tree, e);
+    return launch_pops<FstPops<WeirCockerham>>(pos, freq, nind, n_pops, n, minind, win, n_win, out, tot, tree, e);
 }
 
 }  // namespace pgt

@@ -259,36 +259,37 @@ inline uint32_t group_size(uint64_t n_win) {
     return n_win >= 64ull * 8192 ? 64u : (n_win >= 32ull * 8192 ? 32u : 16u);
 }
 
-// ---- launchers implemented in pgt_kernels.hip (stream = hipStream_t as void*) ----------
+// What every launcher below ends in: where it runs, what it records, where its message goes, what it may assume
+struct LaunchEnv {
+    void *stream;                             // hipStream_t as void*
+    void *ev_build0, *ev_build1, *ev_query1;  // hipEvent_t as void* or NULL: recorded before the build, behind it, behind the query
+    std::string *err;
+    const Hints &hints;
+};
+
+// ---- launchers implemented in pgt_kernels.hip ----------
 int launch_fst(const uint32_t *pos, const double *const *a, const double *const *b, uint32_t n_pairs,
-               uint64_t n, const pgt_win *win, uint64_t n_win, pgt_fst_row *out, void *tree,
-               void *stream, void *ev_build0, void *ev_build1, void *ev_query1, std::string *err, const Hints &hints);
+               uint64_t n, const pgt_win *win, uint64_t n_win, pgt_fst_row *out, void *tree, const LaunchEnv &e);
 int launch_het(const uint32_t *pos, const int8_t *g, uint64_t n, const pgt_win *win, uint64_t n_win,
-               pgt_het_row *out, void *tree, void *stream, void *ev_build0, void *ev_build1,
-               void *ev_query1, std::string *err, const Hints &hints);
+               pgt_het_row *out, void *tree, const LaunchEnv &e);
 int launch_dxy(const uint32_t *pos, const double *p1, const double *p2, const int32_t *n1,
                const int32_t *n2, uint64_t n, int minind, const pgt_win *win, uint64_t n_win,
-               pgt_dxy_row *out, pgt_dxy_total *tot, void *tree, void *stream, void *ev_build0,
-               void *ev_build1, void *ev_query1, std::string *err, const Hints &hints);
+               pgt_dxy_row *out, pgt_dxy_total *tot, void *tree, const LaunchEnv &e);
 
 int launch_dxy_het(const uint32_t *pos, const double *p1, const double *p2, const int32_t *n1,
                    const int32_t *n2, const int8_t *g1, const int8_t *g2, uint64_t n, int minind,
                    const pgt_win *win, uint64_t n_win, pgt_dxy_row *dxy_out, pgt_dxy_total *tot,
-                   pgt_het_row *het_out1, pgt_het_row *het_out2, void *tree, void *stream,
-                   void *ev_build0, void *ev_build1, void *ev_query1, std::string *err, const Hints &hints);
+                   pgt_het_row *het_out1, pgt_het_row *het_out2, void *tree, const LaunchEnv &e);
 
 int launch_ext(const uint32_t *pos, const double *score, uint64_t n, int mode, double cutoff, const pgt_win *win,
-               uint64_t n_win, pgt_ext_row *out, void *tree, void *stream, void *ev_build0, void *ev_build1,
-               void *ev_query1, std::string *err, const Hints &hints);
+               uint64_t n_win, pgt_ext_row *out, void *tree, const LaunchEnv &e);
 int launch_fst_af(const uint32_t *pos, const double *const *freq, const double *nsamp, uint32_t n_pops,
-                  uint64_t n, const pgt_win *win, uint64_t n_win, pgt_fst_row *out, void *tree, void *stream,
-                  void *ev_build0, void *ev_build1, void *ev_query1, std::string *err, const Hints &hints);
+                  uint64_t n, const pgt_win *win, uint64_t n_win, pgt_fst_row *out, void *tree, const LaunchEnv &e);
 
 // pgt_dxy_pops_kernels.hip: tot = n_pairs device totals or NULL; 2 <= n_pops <= 8 (checked by the caller)
 int launch_dxy_pops(const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
                     uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_dxy_row *out, pgt_dxy_total *tot,
-                    void *tree, void *stream, void *ev_build0, void *ev_build1, void *ev_query1, std::string *err,
-                    const Hints &hints);
+                    void *tree, const LaunchEnv &e);
 
 // pgt_fst_pops_kernels.hip: tot = n_pairs device totals or NULL; 2 <= n_pops <= 8 and minind >= 1 (checked by the caller).
 // The estimator selects the per-site function the kernels are instantiated with (pgt_fst_pops_reduce_dev: WeirCockerham,
@@ -296,36 +297,31 @@ int launch_dxy_pops(const uint32_t *pos, const double *const *freq, const int32_
 enum class FstPopsEstimator { WeirCockerham, Hudson };
 int launch_fst_pops(const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
                     uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_fst_row *out, pgt_fst_total *tot,
-                    void *tree, void *stream, void *ev_build0, void *ev_build1, void *ev_query1, std::string *err,
-                    const Hints &hints, FstPopsEstimator estimator);
+                    void *tree, const LaunchEnv &e, FstPopsEstimator estimator);
 
 // pgt_dstat_pops_kernels.hip: tot = C(n_pops - 1, 3) device totals or NULL; 4 <= n_pops <= 7 (the last population is the
 // outgroup) and minind >= 1 (checked by the caller); out = one table of n_win rows per trio, in lexicographic trio order
 int launch_dstat_pops(const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
                       uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_dstat_row *out, pgt_dstat_total *tot,
-                      void *tree, void *stream, void *ev_build0, void *ev_build1, void *ev_query1, std::string *err,
-                      const Hints &hints);
+                      void *tree, const LaunchEnv &e);
 
 // pgt_fd_pops_kernels.hip: f_d / f_dM of the same trios; arguments, limits and tree size as launch_dstat_pops
 int launch_fd_pops(const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
                    uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_fd_row *out, pgt_fd_total *tot,
-                   void *tree, void *stream, void *ev_build0, void *ev_build1, void *ev_query1, std::string *err,
-                   const Hints &hints);
+                   void *tree, const LaunchEnv &e);
 
 // pgt_f3_pops_kernels.hip: f3 of ALL trios of the populations (no outgroup), each population of a trio as the target;
 // tot = C(n_pops, 3) device totals or NULL; 3 <= n_pops <= 6 and minind >= 1 (checked by the caller); out = one table of n_win
 // rows per trio, in lexicographic trio order; the tree has launch_dstat_pops' layout at n_pops + 1
 int launch_f3_pops(const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
                    uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_f3_row *out, pgt_f3_total *tot,
-                   void *tree, void *stream, void *ev_build0, void *ev_build1, void *ev_query1, std::string *err,
-                   const Hints &hints);
+                   void *tree, const LaunchEnv &e);
 
 // pgt_kernels.hip: pi per population, 1 <= n_pops <= 8 and minind >= 1 (checked by the caller); out = n_pops tables of
 // n_win rows, tot = n_pops device totals or NULL; tree = n_pops trees of tree_layout(PGT_STAT_DXY, n).bytes each
 int launch_pi_pops(const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
                    uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_dxy_row *out, pgt_dxy_total *tot,
-                   void *tree, void *stream, void *ev_build0, void *ev_build1, void *ev_query1, std::string *err,
-                   const Hints &hints);
+                   void *tree, const LaunchEnv &e);
 
 // pgt_align_kernels.hip: the sites common to K position columns (pgt_sites_align) and the gather behind it.
 // The workspace, every part 256-byte aligned: the plan (segments as u32 pairs, first tile per chromosome), the first output

@@ -185,6 +185,78 @@ template <int U>
 __device__ __forceinline__ int tile_rotation(uint64_t wave) {
     return (int)(((wave * 0x9E3779B1ull) >> 13) & (uint64_t)(kRadix - U));  // a multiple of U below 64 (U a power of two)
 }
+// The rotation as a full-tile function receives it: still a multiple of the batch U.  (The compiler optimises a build's full-tile
+// lambda before it inlines it into the walk; without this it no longer knows that the loads of a batch share one base.)
+template <int U>
+__device__ __forceinline__ int batch_aligned(int rot) {
+    __builtin_assume(rot % U == 0);
+    return rot;
+}
+
+// THE WALK OF EVERY STAGED BUILD (fst, dxy, pi, fused, extreme score).  A build wave's place in the launch: grid.x strides over
+// the level-2 tiles; grid.y, where a build has one, picks the columns and the tree.
+struct BuildWave {
+    int lane, wib;            // lane of the wave, wave of the workgroup
+    uint64_t wave0, n_waves;  // this wave of the grid's n_waves: it walks tiles wave0, wave0 + n_waves, ..
+};
+// A macro, for the __global__ function itself: only there does the compiler fold blockDim.x to the one load of a launch with
+// uniform workgroups (in a __device__ function, inlined or not, it stays a select between two loads)
+#define PGT_BUILD_WAVE()                                                                                                        \
+    BuildWave {                                                                                                                 \
+        (int)(threadIdx.x & (kWave - 1)), (int)(threadIdx.x >> 6), ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6,     \
+            ((uint64_t)gridDim.x * blockDim.x) >> 6                                                                             \
+    }
+// the tree of y-slice `slice` (0 where the grid has none) and the two levels a build writes itself
+template <class Node>
+struct TreeRows { char *tree; Node *l1, *l2; };
+template <class Node>
+__device__ __forceinline__ TreeRows<Node> tree_rows(const TreeView &tv, unsigned slice) {
+    char *tree = tv.base + (size_t)slice * tv.pair_stride;
+    return {tree, reinterpret_cast<Node *>(tree + tv.off[0]), reinterpret_cast<Node *>(tree + tv.off[1])};
+}
+template <class Node> constexpr bool kTreeHasPartials = false;  // TreeLayout::partials: the dxy layout alone (dxy, fused, pi)
+template <> constexpr bool kTreeHasPartials<NodeDxy> = true;
+// The wave's tiles of TILE sites (64 leaves), one after the other, into `stage`.  A build supplies
+//   full_tile(base, rot) -> node a tile that lies wholly inside the column, from its first site `base`, walked from leaf `rot`
+//                                (tile_rotation<U>): lane j returns leaf j's node
+//   ragged_leaf(tile0) -> node   one leaf of the column's last, partial tile from its first site tile0 < n, site by site (sites
+//                                beyond n count as nothing): the leaf's node in every lane
+template <uint64_t TILE, int U, class Node, class Stage, class FullTile, class RaggedLeaf>
+__device__ __forceinline__ void build_walk_into(Stage &stage, const BuildWave &w, const TreeRows<Node> &tr, const TreeView &tv, uint64_t n,
+                                                uint64_t n_l2, FullTile full_tile, RaggedLeaf ragged_leaf) {
+    for (uint64_t t = w.wave0; t < n_l2; t += w.n_waves) {
+        const uint64_t base = t * TILE;
+        Node keep = node_identity<Node>();
+        if (base + TILE <= n) {
+            keep = full_tile(base, tile_rotation<U>(w.wave0));
+        } else {
+            for (int j = 0; j < kRadix; ++j) {
+                const uint64_t tile0 = base + (uint64_t)j * (TILE / kRadix);
+                if (tile0 >= n) break;  // wave-uniform
+                const Node a = ragged_leaf(tile0);
+                if (w.lane == j) keep = a;
+            }
+        }
+        stage.put(t, keep);
+    }
+    stage.flush();
+    // THE GENOME-WIDE LINE WITHOUT UPPER LEVELS (round 5).  dxyWindow's last line (dxyWindow.cpp:382-385,429-433) is the sum over
+    // ALL sites; it used to be the query [0, n), for which every tree level above 2 had to be built: two or three
+    // tree_up launches of ~5 us each behind every dxy / fused build whose windows (W = 50000 sites) need none of them.
+    // Every wave now leaves the sum of the level-2 nodes it wrote (tile order), and the total is the sum of these <= 2048
+    // partials in wave order — fixed by the static grid, hence a function of the input alone.
+    if constexpr (kTreeHasPartials<Node>)
+        if (w.lane == 0) reinterpret_cast<Node *>(tr.tree + tv.partials)[w.wave0] = stage.sum;
+}
+// the same with a stage of the wave's own in `lds_stage` (NodeStage, FstDeepStage)
+template <class Node, class Stage, uint64_t TILE, int U, class FullTile, class RaggedLeaf>
+__device__ __forceinline__ void build_walk(const BuildWave &w, const TreeView &tv, unsigned slice, char *lds_stage, uint64_t n, uint64_t n_l2,
+                                           FullTile full_tile, RaggedLeaf ragged_leaf) {
+    const TreeRows<Node> tr = tree_rows<Node>(tv, slice);
+    Stage stage(lds_stage, w.wib, w.lane, tr.l1, tr.l2, w.n_waves);
+    build_walk_into<TILE, U>(stage, w, tr, tv, n, n_l2, full_tile, ragged_leaf);
+}
+
 // 64 KiB of one column of a level-2 tile -> the 64 leaf sums, lane j keeps leaf j's; U loads in flight per lane; the walk
 // starts at leaf `rot` (a multiple of U) and wraps
 template <int U>
@@ -206,50 +278,35 @@ __device__ __forceinline__ void fst_column_sums(const double2 *__restrict__ p, i
 // tile (scope 2: both columns, 1: only `b`, 0: off) — during the last round ever fewer waves are left to keep the HBM busy.
 // The walk of both fst builds; Stage = where a finished tile's node row waits (NodeStage, or FstDeepStage below).
 template <class Stage, int UNROLL, int TAIL_UNROLL, int TAIL_SCOPE>
-__device__ __forceinline__ void fst_build_body(const PairCols &cols, uint64_t n, uint64_t n_l2, const TreeView &tv, char *lds_stage,
-                                               uint64_t wave0, uint64_t n_waves) {  // this wave of the grid's n_waves (worked out in the kernel itself)
-    const int lane = threadIdx.x & (kWave - 1), wib = threadIdx.x >> 6;
+__device__ __forceinline__ void fst_build_body(const BuildWave &w, const PairCols &cols, uint64_t n, uint64_t n_l2, const TreeView &tv,
+                                               char *lds_stage) {
     const double *__restrict__ a = cols.a[blockIdx.y];
     const double *__restrict__ b = cols.b[blockIdx.y];
-    char *tree = tv.base + (size_t)blockIdx.y * tv.pair_stride;
-    NodeFst *__restrict__ l1 = reinterpret_cast<NodeFst *>(tree + tv.off[0]);
-    NodeFst *__restrict__ l2 = reinterpret_cast<NodeFst *>(tree + tv.off[1]);
     constexpr uint64_t kTile2 = (uint64_t)kLeafF64 * kRadix;
-    Stage stage(lds_stage, wib, lane, l1, l2, n_waves);
-
-    for (uint64_t t = wave0; t < n_l2; t += n_waves) {
-        const uint64_t base = t * kTile2;
-        double keep_a = 0.0, keep_b = 0.0;
-        if (base + kTile2 <= n) {
+    build_walk<NodeFst, Stage, kTile2, UNROLL>(
+        w, tv, blockIdx.y, lds_stage, n, n_l2,
+        [&](uint64_t base, int rot) {
             const double2 *__restrict__ pa = reinterpret_cast<const double2 *>(a + base);
             const double2 *__restrict__ pb = reinterpret_cast<const double2 *>(b + base);
-            const bool last = TAIL_SCOPE != 0 && t + n_waves >= n_l2;  // wave-uniform: this wave's last tile
-            const int rot = tile_rotation<UNROLL>(wave0);
-            if (TAIL_SCOPE == 2 && last) fst_column_sums<TAIL_UNROLL>(pa, lane, keep_a);
-            else fst_column_sums<UNROLL>(pa, lane, keep_a, rot);  // the tile's 64 KiB of `a` ...
-            if (TAIL_SCOPE != 0 && last) fst_column_sums<TAIL_UNROLL>(pb, lane, keep_b);
-            else fst_column_sums<UNROLL>(pb, lane, keep_b, rot);  // ... then its 64 KiB of `b`
-        } else {
-            for (int j = 0; j < kRadix; ++j) {
-                const uint64_t i0 = base + (uint64_t)j * kLeafF64 + 2 * lane;
-                if (base + (uint64_t)j * kLeafF64 >= n) break;  // wave-uniform
-                const double a0 = i0 < n ? a[i0] : 0.0, a1 = i0 + 1 < n ? a[i0 + 1] : 0.0;
-                const double b0 = i0 < n ? b[i0] : 0.0, b1 = i0 + 1 < n ? b[i0 + 1] : 0.0;
-                const double sa = wave_sum(a0 + a1);
-                const double sb = wave_sum(b0 + b1);
-                if (lane == j) { keep_a = sa; keep_b = sb; }
-            }
-        }
-        stage.put(t, NodeFst{keep_a, keep_b});
-    }
-    stage.flush();
+            const bool last = TAIL_SCOPE != 0 && base / kTile2 + w.n_waves >= n_l2;  // wave-uniform: this wave's last tile
+            double keep_a = 0.0, keep_b = 0.0;
+            if (TAIL_SCOPE == 2 && last) fst_column_sums<TAIL_UNROLL>(pa, w.lane, keep_a);
+            else fst_column_sums<UNROLL>(pa, w.lane, keep_a, rot);  // the tile's 64 KiB of `a` ...
+            if (TAIL_SCOPE != 0 && last) fst_column_sums<TAIL_UNROLL>(pb, w.lane, keep_b);
+            else fst_column_sums<UNROLL>(pb, w.lane, keep_b, rot);  // ... then its 64 KiB of `b`
+            return NodeFst{keep_a, keep_b};
+        },
+        [&](uint64_t tile0) {
+            const uint64_t i0 = tile0 + 2 * w.lane;
+            const double a0 = i0 < n ? a[i0] : 0.0, a1 = i0 + 1 < n ? a[i0 + 1] : 0.0;
+            const double b0 = i0 < n ? b[i0] : 0.0, b1 = i0 + 1 < n ? b[i0 + 1] : 0.0;
+            return NodeFst{wave_sum(a0 + a1), wave_sum(b0 + b1)};
+        });
 }
 template <int STAGE = kFstStage, int UNROLL = 4, bool NT_STORE = true, int TAIL_UNROLL = UNROLL, int TAIL_SCOPE = 0>
 __global__ __launch_bounds__(256) void fst_build_kernel(PairCols cols, uint64_t n, uint64_t n_l2, TreeView tv) {
     extern __shared__ __attribute__((aligned(16))) char lds_stage[];
-    const uint64_t wave0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
-    fst_build_body<NodeStage<NodeFst, STAGE, NT_STORE>, UNROLL, TAIL_UNROLL, TAIL_SCOPE>(cols, n, n_l2, tv, lds_stage, wave0, n_waves);
+    fst_build_body<NodeStage<NodeFst, STAGE, NT_STORE>, UNROLL, TAIL_UNROLL, TAIL_SCOPE>(PGT_BUILD_WAVE(), cols, n, n_l2, tv, lds_stage);
 }
 
 // A DEEP STAGE FOR LONG COLUMNS (fst build only; round 7).  A wave that walks more than kFstStage tiles flushes NodeStage in the
@@ -349,9 +406,7 @@ static_assert(kFstDeepBlocks == 4, "FstDeepStage names its register blocks one b
 // 2 workgroups per CU as fst_build_kernel<>, i.e. 2 waves per SIMD: 256 VGPRs per wave
 __global__ __launch_bounds__(256, 2) void fst_build_kernel_deep(PairCols cols, uint64_t n, uint64_t n_l2, TreeView tv) {
     extern __shared__ __attribute__((aligned(16))) char lds_stage[];
-    const uint64_t wave0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
-    fst_build_body<FstDeepStage, 4, 4, 0>(cols, n, n_l2, tv, lds_stage, wave0, n_waves);
+    fst_build_body<FstDeepStage, 4, 4, 0>(PGT_BUILD_WAVE(), cols, n, n_l2, tv, lds_stage);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -496,80 +551,64 @@ __device__ __forceinline__ NodeDxy dxy_leaf_node(const double2 &x1, const double
 // before this batch is computed (+0.5 / -1.6); super-batches of 8 or 16 leaf tiles in which EVERY stream is visited for two or
 // four consecutive 4-load bursts — counts, then p1 held in registers, then p2 consumed burst by burst as the fst build consumes
 // its column (-2.2 / -0.6 and -3.4 / +0.3).
-template <int U = 4>  // leaf tiles per batch (even: the count columns are read per PAIR of leaf tiles)
-__device__ __forceinline__ void dxy_build_body(const double *__restrict__ p1, const double *__restrict__ p2,
-                                               const int32_t *__restrict__ n1, const int32_t *__restrict__ n2,
-                                               uint64_t n, int minind, uint64_t n_l2, const TreeView &tv, char *lds_stage) {
-    const int lane = threadIdx.x & (kWave - 1);
-    const uint64_t wave0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
-    NodeDxy *__restrict__ l1 = reinterpret_cast<NodeDxy *>(tv.base + tv.off[0]);
-    NodeDxy *__restrict__ l2 = reinterpret_cast<NodeDxy *>(tv.base + tv.off[1]);
-    constexpr uint64_t kTile2 = (uint64_t)kLeafF64 * kRadix;
-    NodeStage<NodeDxy, kFstStage, true> stage(lds_stage, threadIdx.x >> 6, lane, l1, l2, n_waves);  // deferred node stores
-
-    for (uint64_t t = wave0; t < n_l2; t += n_waves) {
-        const uint64_t base = t * kTile2;
-        NodeDxy keep{0.0, 0u, 0u};
-        if (base + kTile2 <= n) {
-            const double2 *__restrict__ q1 = reinterpret_cast<const double2 *>(p1 + base);
-            const double2 *__restrict__ q2 = reinterpret_cast<const double2 *>(p2 + base);
-            const int4 *__restrict__ m1 = reinterpret_cast<const int4 *>(n1 + base);  // base is a multiple of 8192: 16-byte aligned
-            const int4 *__restrict__ m2 = reinterpret_cast<const int4 *>(n2 + base);
-            const int rot = tile_rotation<U>(wave0);  // see fst_column_sums: the walk over the tile starts at a leaf of the wave's own
-#pragma unroll 1
-            for (int j0 = 0; j0 < kRadix; j0 += U) {
-                const int j = (j0 + rot) & (kRadix - 1);
-                double2 x1[U], x2[U];
-                int4 k1[U / 2], k2[U / 2];  // one 16-byte load per lane and PAIR of leaf tiles
+// One batch: leaf tiles j .. j + U - 1 of a full tile (U even: the count columns are read per PAIR of leaf tiles); lane j + u
+// keeps leaf j + u's node.  The dxy build's and the fused build's.
+template <int U>
+__device__ __forceinline__ void dxy_batch(const double2 *__restrict__ q1, const double2 *__restrict__ q2, const int4 *__restrict__ m1,
+                                          const int4 *__restrict__ m2, int j, int minind, int lane, NodeDxy &keep) {
+    double2 x1[U], x2[U];
+    int4 k1[U / 2], k2[U / 2];  // one 16-byte load per lane and PAIR of leaf tiles
 #pragma unroll
-                for (int u = 0; u < U; ++u) x1[u] = load16<true>(q1 + (j + u) * kWave + lane);
-                load_fence(x1[U - 1].y);
+    for (int u = 0; u < U; ++u) x1[u] = load16<true>(q1 + (j + u) * kWave + lane);
+    load_fence(x1[U - 1].y);
 #pragma unroll
-                for (int u = 0; u < U; ++u) x2[u] = load16<true>(q2 + (j + u) * kWave + lane);
-                load_fence(x2[U - 1].y);
+    for (int u = 0; u < U; ++u) x2[u] = load16<true>(q2 + (j + u) * kWave + lane);
+    load_fence(x2[U - 1].y);
 #pragma unroll
-                for (int u = 0; u < U / 2; ++u) k1[u] = load16_nt(m1 + (j / 2 + u) * kWave + lane);
+    for (int u = 0; u < U / 2; ++u) k1[u] = load16_nt(m1 + (j / 2 + u) * kWave + lane);
 #pragma unroll
-                for (int u = 0; u < U / 2; ++u) k2[u] = load16_nt(m2 + (j / 2 + u) * kWave + lane);
+    for (int u = 0; u < U / 2; ++u) k2[u] = load16_nt(m2 + (j / 2 + u) * kWave + lane);
 #pragma unroll
-                for (int u = 0; u < U; u += 2) {
-                    const PairPred pp = count_pair_pred(k1[u / 2], k2[u / 2], minind);
-                    const NodeDxy a0 = dxy_leaf_node<0>(x1[u], x2[u], pp, lane);
-                    const NodeDxy a1 = dxy_leaf_node<1>(x1[u + 1], x2[u + 1], pp, lane);
-                    if (lane == j + u) keep = a0;
-                    if (lane == j + u + 1) keep = a1;
-                }
-            }
-        } else {
-            for (int j = 0; j < kRadix; ++j) {
-                const uint64_t tile0 = base + (uint64_t)j * kLeafF64;
-                if (tile0 >= n) break;  // wave-uniform
-                NodeDxy acc{0.0, 0u, 0u};
-                for (int q = 0; q < 2; ++q) {
-                    const uint64_t i = tile0 + 2 * lane + q;
-                    if (i < n) dxy_acc(acc, dxy_site(p1[i], p2[i], n1[i], n2[i], minind));
-                }
-                acc = node_wave_sum(acc);
-                if (lane == j) keep = acc;
-            }
-        }
-        stage.put(t, keep);
+    for (int u = 0; u < U; u += 2) {
+        const PairPred pp = count_pair_pred(k1[u / 2], k2[u / 2], minind);
+        const NodeDxy a0 = dxy_leaf_node<0>(x1[u], x2[u], pp, lane);
+        const NodeDxy a1 = dxy_leaf_node<1>(x1[u + 1], x2[u + 1], pp, lane);
+        if (lane == j + u) keep = a0;
+        if (lane == j + u + 1) keep = a1;
     }
-    stage.flush();
-    // THE GENOME-WIDE LINE WITHOUT UPPER LEVELS (round 5).  dxyWindow's last line (dxyWindow.cpp:382-385,429-433) is the sum over
-    // ALL sites; it used to be the query [0, n), for which every tree level above 2 had to be built: two or three
-    // tree_up launches of ~5 us each behind every dxy / fused build whose windows (W = 50000 sites) need none of them.
-    // Every wave now leaves the sum of the level-2 nodes it wrote (tile order), and the total is the sum of these <= 2048
-    // partials in wave order — fixed by the static grid, hence a function of the input alone.
-    if (lane == 0) reinterpret_cast<NodeDxy *>(tv.base + tv.partials)[wave0] = stage.sum;
+}
+// one leaf of the last, partial tile, site by site (the dxy build's and the fused build's)
+__device__ __forceinline__ NodeDxy dxy_ragged_leaf(const double *__restrict__ p1, const double *__restrict__ p2, const int32_t *__restrict__ n1,
+                                                   const int32_t *__restrict__ n2, uint64_t tile0, uint64_t n, int minind, int lane) {
+    NodeDxy acc{0.0, 0u, 0u};
+    for (int q = 0; q < 2; ++q) {
+        const uint64_t i = tile0 + 2 * lane + q;
+        if (i < n) dxy_acc(acc, dxy_site(p1[i], p2[i], n1[i], n2[i], minind));
+    }
+    return node_wave_sum(acc);
 }
 
 __global__ __launch_bounds__(256) void dxy_build_kernel(const double *p1, const double *p2, const int32_t *n1,
                                                         const int32_t *n2, uint64_t n, int minind, uint64_t n_l2,
                                                         TreeView tv) {
     extern __shared__ __attribute__((aligned(16))) char lds_stage[];
-    dxy_build_body<>(p1, p2, n1, n2, n, minind, n_l2, tv, lds_stage);
+    const BuildWave w = PGT_BUILD_WAVE();
+    constexpr int U = 4;  // leaf tiles per batch
+    constexpr uint64_t kTile2 = (uint64_t)kLeafF64 * kRadix;
+    build_walk<NodeDxy, NodeStage<NodeDxy, kFstStage, true>, kTile2, U>(  // deferred node stores
+        w, tv, 0, lds_stage, n, n_l2,
+        [&](uint64_t base, int rot) {  // rot: see fst_column_sums, the walk over the tile starts at a leaf of the wave's own
+            rot = batch_aligned<U>(rot);
+            NodeDxy keep = node_identity<NodeDxy>();
+            const double2 *__restrict__ q1 = reinterpret_cast<const double2 *>(p1 + base);
+            const double2 *__restrict__ q2 = reinterpret_cast<const double2 *>(p2 + base);
+            const int4 *__restrict__ m1 = reinterpret_cast<const int4 *>(n1 + base);  // base is a multiple of 8192: 16-byte aligned
+            const int4 *__restrict__ m2 = reinterpret_cast<const int4 *>(n2 + base);
+#pragma unroll 1
+            for (int j0 = 0; j0 < kRadix; j0 += U) dxy_batch<U>(q1, q2, m1, m2, (j0 + rot) & (kRadix - 1), minind, w.lane, keep);
+            return keep;
+        },
+        [&](uint64_t tile0) { return dxy_ragged_leaf(p1, p2, n1, n2, tile0, n, minind, w.lane); });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -622,24 +661,18 @@ template <int U = 4>  // leaf tiles per batch (even)
 __global__ __launch_bounds__(256) void pi_build_kernel(PopCols cols, uint64_t n, int minind, uint64_t n_l2, TreeView tv) {
     static_assert(U % 2 == 0, "the columns are read per PAIR of leaf tiles");
     extern __shared__ __attribute__((aligned(16))) char lds_stage[];
-    const int lane = threadIdx.x & (kWave - 1);
-    const uint64_t wave0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    const BuildWave w = PGT_BUILD_WAVE();
+    const int lane = w.lane;
     const double *__restrict__ f = cols.f[blockIdx.y];
     const int32_t *__restrict__ ni = cols.n[blockIdx.y];
-    char *tree = tv.base + (size_t)blockIdx.y * tv.pair_stride;
-    NodeDxy *__restrict__ l1 = reinterpret_cast<NodeDxy *>(tree + tv.off[0]);
-    NodeDxy *__restrict__ l2 = reinterpret_cast<NodeDxy *>(tree + tv.off[1]);
     constexpr uint64_t kTile2 = (uint64_t)kLeafF64 * kRadix;
-    NodeStage<NodeDxy, kFstStage, true> stage(lds_stage, threadIdx.x >> 6, lane, l1, l2, n_waves);  // deferred node stores
-
-    for (uint64_t t = wave0; t < n_l2; t += n_waves) {
-        const uint64_t base = t * kTile2;
-        NodeDxy keep{0.0, 0u, 0u};
-        if (base + kTile2 <= n) {
+    build_walk<NodeDxy, NodeStage<NodeDxy, kFstStage, true>, kTile2, U>(  // deferred node stores
+        w, tv, blockIdx.y, lds_stage, n, n_l2,
+        [&](uint64_t base, int rot) {  // rot: see fst_column_sums
+            rot = batch_aligned<U>(rot);
+            NodeDxy keep = node_identity<NodeDxy>();
             const double2 *__restrict__ q = reinterpret_cast<const double2 *>(f + base);
             const int4 *__restrict__ m = reinterpret_cast<const int4 *>(ni + base);  // base is a multiple of 8192: 16-byte aligned
-            const int rot = tile_rotation<U>(wave0);  // see fst_column_sums
 #pragma unroll 1
             for (int j0 = 0; j0 < kRadix; j0 += U) {
                 const int j = (j0 + rot) & (kRadix - 1);
@@ -669,23 +702,16 @@ __global__ __launch_bounds__(256) void pi_build_kernel(PopCols cols, uint64_t n,
                     if (lane == j + 2 * u + 1) keep = NodeDxy{s1, neff1, (uint32_t)kLeafF64 - neff1};
                 }
             }
-        } else {  // the last, partial tile: site by site, sites beyond n count as nothing
-            for (int j = 0; j < kRadix; ++j) {
-                const uint64_t tile0 = base + (uint64_t)j * kLeafF64;
-                if (tile0 >= n) break;  // wave-uniform
-                NodeDxy acc{0.0, 0u, 0u};
-                for (int q = 0; q < 2; ++q) {
-                    const uint64_t i = tile0 + 2 * lane + q;
-                    if (i < n) pi_acc(acc, f[i], ni[i], minind);
-                }
-                acc = node_wave_sum(acc);
-                if (lane == j) keep = acc;
+            return keep;
+        },
+        [&](uint64_t tile0) {
+            NodeDxy acc{0.0, 0u, 0u};
+            for (int q = 0; q < 2; ++q) {
+                const uint64_t i = tile0 + 2 * lane + q;
+                if (i < n) pi_acc(acc, f[i], ni[i], minind);
             }
-        }
-        stage.put(t, keep);
-    }
-    stage.flush();
-    if (lane == 0) reinterpret_cast<NodeDxy *>(tree + tv.partials)[wave0] = stage.sum;  // the genome-wide line: see dxy_build_body
+            return node_wave_sum(acc);
+        });
 }
 
 // BASELINE config 3: dxyWindow + hetWindow (two genotype columns) over one position column and one
@@ -694,7 +720,7 @@ __global__ __launch_bounds__(256) void pi_build_kernel(PopCols cols, uint64_t n,
 // exactly one het work item (8 leaf tiles of 1024 sites, 8 KiB per column).  A genotype column's 8 KiB are
 // requested in ONE burst of eight 16-byte loads per lane — column 0 before the first batch of dxy loads of the
 // tile, column 1 before the batch in the middle — and awaited like every other column burst (one column at a
-// time, see dxy_build_body); the byte counts go through the same packed-word popcounts as het_build_body and
+// time, see dxy_batch); the byte counts go through the same packed-word popcounts as het_build_body and
 // ONE wave reduction per leaf (nonmissing and nhet packed into one register: both are at most 1024).
 // Measured in one process, interleaved (% of the HBM peak on 26 B/site at 10^8 / 10^9 sites).  First
 // (profiles/r03/fused_ab.txt, all columns of a batch requested together): 8 dxy loads per batch + genotype bursts
@@ -729,52 +755,76 @@ __device__ __forceinline__ uint32_t het_count_packed(const uint4 &w) {  // nonmi
     return nm | (nh << 16);
 }
 
+// The genotype side of the fused build's stage, NodeStage's companion: the 2 x 8 level-1 het nodes of every staged tile,
+// [tile of the stage][column][leaf], behind the four waves' dxy rows
+struct HetStage {
+    NodeHet *rows;       // LDS: [kFstStage][2][kHetChunk] of this wave
+    const TreeView &tv;  // the two genotype trees, pair_stride apart
+    uint64_t n_waves, first_t = 0;  // row k holds tile first_t + k * n_waves
+    int lane, held = 0;
+    __device__ __forceinline__ HetStage(char *lds, int wib, int lane_, const TreeView &tv_, uint64_t n_waves_)
+        : rows(reinterpret_cast<NodeHet *>(lds) + (size_t)wib * kFstStage * 2 * kHetChunk), tv(tv_), n_waves(n_waves_), lane(lane_) {}
+    __device__ __forceinline__ void flush() {
+        // 16 lanes: column = lane / 8, leaf = lane % 8 -> one 64-byte run per column and tile
+        for (int k = 0; k < held; ++k) {
+            const uint64_t t = first_t + (uint64_t)k * n_waves;
+            if (lane < 2 * kHetChunk) {
+                NodeHet *dst = reinterpret_cast<NodeHet *>(tv.base + (size_t)(lane >> 3) * tv.pair_stride + tv.off[0]);
+                dst[t * kHetChunk + (lane & 7)] = rows[k * 2 * kHetChunk + lane];
+            }
+        }
+        held = 0;
+    }
+    __device__ __forceinline__ void put(uint64_t t, uint32_t packed) {  // lane c * 8 + u: nonmissing | nhet << 16 of leaf u of column c
+        if (held == 0) first_t = t;
+        if (lane < 2 * kHetChunk) rows[held * 2 * kHetChunk + lane] = NodeHet{packed & 0xFFFFu, packed >> 16};
+        ++held;
+    }
+};
+// The fused build's stage: a tile's dxy row and its genotype nodes are put together and leave together
+struct DxyHetStage : NodeStage<NodeDxy, kFstStage, true> {
+    using DxyStage = NodeStage<NodeDxy, kFstStage, true>;
+    HetStage het;
+    uint32_t hkeep = 0;  // of the tile in work, lane c * 8 + u: packed counts of leaf u of genotype column c
+    __device__ __forceinline__ DxyHetStage(char *lds, const BuildWave &w, const TreeRows<NodeDxy> &tr, const TreeView &tv_het)
+        : DxyStage(lds, w.wib, w.lane, tr.l1, tr.l2, w.n_waves), het(lds + kFstStageBytes, w.wib, w.lane, tv_het, w.n_waves) {}
+    __device__ __forceinline__ void flush() {
+        DxyStage::flush();
+        het.flush();
+    }
+    __device__ __forceinline__ void put(uint64_t t, const NodeDxy &keep) {
+        het.put(t, hkeep);
+        hkeep = 0;
+        const bool full = held + 1 == kFstStage;
+        DxyStage::put(t, keep);  // flushes the dxy rows when the stage is full
+        if (full) het.flush();
+    }
+};
+
 template <int U = 4>  // dxy leaf tiles per batch
 __global__ __launch_bounds__(256) void dxy_het_build_kernel(DxyHetBuildArgs f) {
     static_assert(kRadix % (2 * U) == 0 && U % 2 == 0, "a batch starts in the middle of the tile; counts are read per pair of leaf tiles");
     static_assert((uint64_t)kLeafF64 * kRadix == (uint64_t)kLeafI8 * kHetChunk, "a dxy level-2 tile is one het work item");
     extern __shared__ __attribute__((aligned(16))) char lds_stage[];
-    const int lane = threadIdx.x & (kWave - 1), wib = threadIdx.x >> 6;
-    const uint64_t wave0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    const BuildWave w = PGT_BUILD_WAVE();
+    const int lane = w.lane;
     const uint64_t n = f.n;
-    NodeDxy *__restrict__ l1 = reinterpret_cast<NodeDxy *>(f.tv_dxy.base + f.tv_dxy.off[0]);
-    NodeDxy *__restrict__ l2 = reinterpret_cast<NodeDxy *>(f.tv_dxy.base + f.tv_dxy.off[1]);
     constexpr uint64_t kTile2 = (uint64_t)kLeafF64 * kRadix;  // 8192 sites
-    NodeStage<NodeDxy, kFstStage, true> stage(lds_stage, wib, lane, l1, l2, n_waves);
-    // het side of the stage: [tile of the stage][column][leaf] behind the four waves' dxy rows
-    NodeHet *hstage = reinterpret_cast<NodeHet *>(lds_stage + kFstStageBytes) + (size_t)wib * kFstStage * 2 * kHetChunk;
-    int hheld = 0;
-    uint64_t hfirst = 0;
-    auto hflush = [&]() {
-        // 16 lanes: column = lane / 8, leaf = lane % 8 -> one 64-byte run per column and tile
-        for (int k = 0; k < hheld; ++k) {
-            const uint64_t t = hfirst + (uint64_t)k * n_waves;
-            if (lane < 2 * kHetChunk) {
-                NodeHet *dst = reinterpret_cast<NodeHet *>(f.tv_het.base + (size_t)(lane >> 3) * f.tv_het.pair_stride + f.tv_het.off[0]);
-                dst[t * kHetChunk + (lane & 7)] = hstage[k * 2 * kHetChunk + lane];
-            }
-        }
-        hheld = 0;
-    };
-
-    for (uint64_t t = wave0; t < f.n_l2_dxy; t += n_waves) {
-        const uint64_t base = t * kTile2;
-        NodeDxy keep{0.0, 0u, 0u};
-        uint32_t hkeep = 0;  // lane c * 8 + u: packed counts of leaf u of genotype column c
-        if (base + kTile2 <= n) {
+    const TreeRows<NodeDxy> tr = tree_rows<NodeDxy>(f.tv_dxy, 0);
+    DxyHetStage stage(lds_stage, w, tr, f.tv_het);
+    build_walk_into<kTile2, U>(
+        stage, w, tr, f.tv_dxy, n, f.n_l2_dxy,
+        [&](uint64_t base, int rot) {  // rot: see fst_column_sums (the genotype bursts keep their places in the walk)
+            rot = batch_aligned<U>(rot);
+            NodeDxy keep = node_identity<NodeDxy>();
             const double2 *__restrict__ q1 = reinterpret_cast<const double2 *>(f.p1 + base);
             const double2 *__restrict__ q2 = reinterpret_cast<const double2 *>(f.p2 + base);
             const int4 *__restrict__ m1 = reinterpret_cast<const int4 *>(f.n1 + base);  // 16-byte loads: see count_pair_pred
             const int4 *__restrict__ m2 = reinterpret_cast<const int4 *>(f.n2 + base);
             const uint4 *__restrict__ h0 = reinterpret_cast<const uint4 *>(f.g[0] + base);
             const uint4 *__restrict__ h1 = reinterpret_cast<const uint4 *>(f.g[1] + base);
-            const int rot = tile_rotation<U>(wave0);  // see fst_column_sums (the genotype bursts keep their places in the walk)
 #pragma unroll 1
             for (int j0 = 0; j0 < kRadix; j0 += U) {
-                const int j = (j0 + rot) & (kRadix - 1);
-                double2 x1[U], x2[U];
-                int4 k1[U / 2], k2[U / 2];
                 uint4 gb[kHetChunk];
                 const bool burst = j0 == 0 || j0 == kRadix / 2;  // wave-uniform: genotype column 0 / 1
                 if (burst) {  // the genotype column's 8 KiB: a burst of its own, awaited
@@ -782,71 +832,35 @@ __global__ __launch_bounds__(256) void dxy_het_build_kernel(DxyHetBuildArgs f) {
                     for (int u = 0; u < kHetChunk; ++u) gb[u] = load16_nt((j0 == 0 ? h0 : h1) + u * kWave + lane);
                     load_fence((int)gb[kHetChunk - 1].w);
                 }
-                // the dxy columns one at a time, as in dxy_build_body
-#pragma unroll
-                for (int u = 0; u < U; ++u) x1[u] = load16<true>(q1 + (j + u) * kWave + lane);
-                load_fence(x1[U - 1].y);
-#pragma unroll
-                for (int u = 0; u < U; ++u) x2[u] = load16<true>(q2 + (j + u) * kWave + lane);
-                load_fence(x2[U - 1].y);
-#pragma unroll
-                for (int u = 0; u < U / 2; ++u) k1[u] = load16_nt(m1 + (j / 2 + u) * kWave + lane);
-#pragma unroll
-                for (int u = 0; u < U / 2; ++u) k2[u] = load16_nt(m2 + (j / 2 + u) * kWave + lane);
-#pragma unroll
-                for (int u = 0; u < U; u += 2) {
-                    const PairPred pp = count_pair_pred(k1[u / 2], k2[u / 2], f.minind);
-                    const NodeDxy a0 = dxy_leaf_node<0>(x1[u], x2[u], pp, lane);
-                    const NodeDxy a1 = dxy_leaf_node<1>(x1[u + 1], x2[u + 1], pp, lane);
-                    if (lane == j + u) keep = a0;
-                    if (lane == j + u + 1) keep = a1;
-                }
+                dxy_batch<U>(q1, q2, m1, m2, (j0 + rot) & (kRadix - 1), f.minind, lane, keep);  // the dxy columns one at a time
                 if (burst) {
 #pragma unroll
                     for (int u = 0; u < kHetChunk; ++u) {
                         const uint32_t c = wave_sum(het_count_packed(gb[u]));  // both fields <= 1024: no carry between them
-                        if (lane == (j0 == 0 ? 0 : kHetChunk) + u) hkeep = c;
+                        if (lane == (j0 == 0 ? 0 : kHetChunk) + u) stage.hkeep = c;
                     }
                 }
             }
-        } else {  // the last, partial tile: site by site, sites beyond n count as nothing
-            for (int j = 0; j < kRadix; ++j) {
-                const uint64_t tile0 = base + (uint64_t)j * kLeafF64;
-                if (tile0 >= n) break;  // wave-uniform
-                NodeDxy acc{0.0, 0u, 0u};
-                for (int q = 0; q < 2; ++q) {
-                    const uint64_t i = tile0 + 2 * lane + q;
-                    if (i < n) dxy_acc(acc, dxy_site(f.p1[i], f.p2[i], f.n1[i], f.n2[i], f.minind));
-                }
-                acc = node_wave_sum(acc);
-                if (lane == j) keep = acc;
-            }
-            for (int hb = 0; hb < 2 * kHetChunk; ++hb) {
-                const int8_t *__restrict__ g = f.g[hb >> 3];
-                const uint64_t tile0 = base + (uint64_t)(hb & 7) * kLeafI8;
-                uint32_t nm = 0, nh = 0;
-                for (int q = 0; q < 16; ++q) {
-                    const uint64_t i = tile0 + (uint64_t)lane * 16 + q;
-                    if (i < n) {
-                        const int v = g[i];
-                        nm += v >= 0;
-                        nh += v == 1;
+            return keep;
+        },
+        [&](uint64_t tile0) {  // the last, partial tile: site by site, sites beyond n count as nothing
+            if ((tile0 & (uint64_t)(kLeafI8 - 1)) == 0)  // wave-uniform: a genotype leaf of both columns starts at every eighth dxy leaf
+                for (int c = 0; c < 2; ++c) {  // byte by byte, as het_build_body's last item
+                    const int8_t *__restrict__ g = f.g[c];
+                    uint32_t nm = 0, nh = 0;
+                    for (int q = 0; q < 16; ++q) {
+                        const uint64_t i = tile0 + (uint64_t)lane * 16 + q;
+                        if (i < n) {
+                            const int v = g[i];
+                            nm += v >= 0;
+                            nh += v == 1;
+                        }
                     }
+                    const uint32_t packed = wave_sum(nm | (nh << 16));
+                    if (lane == c * kHetChunk + (int)(tile0 / kLeafI8 & (uint64_t)(kHetChunk - 1))) stage.hkeep = packed;
                 }
-                const uint32_t c = wave_sum(nm | (nh << 16));
-                if (lane == hb) hkeep = c;
-            }
-        }
-        if (hheld == 0) hfirst = t;
-        if (lane < 2 * kHetChunk) hstage[hheld * 2 * kHetChunk + lane] = NodeHet{hkeep & 0xFFFFu, hkeep >> 16};
-        ++hheld;
-        const bool full = stage.held + 1 == kFstStage;
-        stage.put(t, keep);  // flushes the dxy rows when the stage is full
-        if (full) hflush();
-    }
-    stage.flush();
-    hflush();
-    if (lane == 0) reinterpret_cast<NodeDxy *>(f.tv_dxy.base + f.tv_dxy.partials)[wave0] = stage.sum;  // see dxy_build_body
+            return dxy_ragged_leaf(f.p1, f.p2, f.n1, f.n2, tile0, n, f.minind, lane);
+        });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1168,22 +1182,18 @@ __device__ __forceinline__ NodeExt ext_leaf_tile(const double (&k)[4], bool (&va
 constexpr int kExtStage = 16;  // tiles staged per wave (16 KiB of LDS): 64 KiB per workgroup -> 2 per CU, as the fst build
 constexpr int kExtStageSmall = 8;  // short inputs: 8 KiB per wave, 32 KiB per workgroup -> 4 per CU = 16 waves (ext_build_launch)
 constexpr uint64_t kExtSmallTiles = 20000;  // level-2 tiles of 16384 sites (3.3e8 sites) up to which an input counts as short
-template <int STAGE = kExtStage, int UNROLL = 4, bool DEFER = true>
+template <int STAGE = kExtStage, int UNROLL = 4>
 __global__ __launch_bounds__(256) void ext_build_kernel(ExtBuildArgs g, uint64_t n, uint64_t n_l2, TreeView tv) {
     extern __shared__ __attribute__((aligned(16))) char lds_stage[];
-    const int lane = threadIdx.x & (kWave - 1);
-    const uint64_t wave0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
-    NodeExt *__restrict__ l1 = reinterpret_cast<NodeExt *>(tv.base + tv.off[0]);
-    NodeExt *__restrict__ l2 = reinterpret_cast<NodeExt *>(tv.base + tv.off[1]);
+    const BuildWave w = PGT_BUILD_WAVE();
+    const int lane = w.lane;
     constexpr uint64_t kTile2 = (uint64_t)kLeafExt * kRadix;  // 16384 sites
-    NodeStage<NodeExt, STAGE, true> stage(lds_stage, threadIdx.x >> 6, lane, l1, l2, n_waves);
-    for (uint64_t t = wave0; t < n_l2; t += n_waves) {
-        const uint64_t base = t * kTile2;
-        NodeExt keep = node_identity<NodeExt>();
-        if (base + kTile2 <= n) {
+    build_walk<NodeExt, NodeStage<NodeExt, STAGE, true>, kTile2, UNROLL>(
+        w, tv, 0, lds_stage, n, n_l2,
+        [&](uint64_t base, int rot) {  // rot: see fst_column_sums
+            rot = batch_aligned<UNROLL>(rot);
+            NodeExt keep = node_identity<NodeExt>();
             const double2 *__restrict__ ps = reinterpret_cast<const double2 *>(g.s + base);
-            const int rot = tile_rotation<UNROLL>(wave0);  // see fst_column_sums
 #pragma unroll 1
             for (int j0 = 0; j0 < kRadix; j0 += UNROLL) {
                 const int j = (j0 + rot) & (kRadix - 1);
@@ -1201,31 +1211,19 @@ __global__ __launch_bounds__(256) void ext_build_kernel(ExtBuildArgs g, uint64_t
                     if (lane == j + u) keep = a;
                 }
             }
-        } else {  // last, partial level-2 tile
-            for (int j = 0; j < kRadix; ++j) {
-                const uint64_t tile0 = base + (uint64_t)j * kLeafExt;
-                if (tile0 >= n) break;  // wave-uniform
-                double k[4];
-                bool valid[4];
+            return keep;
+        },
+        [&](uint64_t tile0) {  // last, partial level-2 tile
+            double k[4];
+            bool valid[4];
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const uint64_t i = tile0 + (uint64_t)(q >> 1) * 2 * kWave + 2 * lane + (q & 1);
-                    valid[q] = i < n;
-                    k[q] = valid[q] ? ExtTraits::key_of(g.s[i], g.mode) : 0.0;
-                }
-                const NodeExt a = ext_leaf_tile(k, valid, g.thr, tile0, lane);
-                if (lane == j) keep = a;
+            for (int q = 0; q < 4; ++q) {
+                const uint64_t i = tile0 + (uint64_t)(q >> 1) * 2 * kWave + 2 * lane + (q & 1);
+                valid[q] = i < n;
+                k[q] = valid[q] ? ExtTraits::key_of(g.s[i], g.mode) : 0.0;
             }
-        }
-        if constexpr (DEFER) {
-            stage.put(t, keep);
-        } else {
-            l1[t * kRadix + lane] = keep;
-            const NodeExt tot = node_wave_sum(keep);
-            if (lane == 0) l2[t] = tot;
-        }
-    }
-    if constexpr (DEFER) stage.flush();
+            return ext_leaf_tile(k, valid, g.thr, tile0, lane);
+        });
 }
 
 template <class Tr>
@@ -2026,6 +2024,26 @@ int launch_query(hipStream_t s, const Hints &hints, uint64_t leaf, unsigned tabl
     return hip_fail(hipGetLastError(), what, err);
 }
 
+// What a launcher does around its two launches: ev_build0, with sites the build (`build(s)` launches the streaming kernel, named
+// `build_name` in the error; the levels above those it wrote follow: launch_upper with n_trees, first, n_level1 — 2 and 0 where
+// the build wrote levels 1 and 2), ev_build1, with
+// `with_query` the query (`query(s)` launches it and returns its error code), ev_query1.
+template <class Node, class Build, class Query>
+int launch_build_query(const LaunchEnv &e, const TreeLayout &tl, const TreeView &tv, unsigned n_trees, int first, uint64_t n_level1, uint64_t n,
+                       const char *build_name, Build build, bool with_query, Query query) {
+    hipStream_t s = static_cast<hipStream_t>(e.stream);
+    if (int rc = record(e.ev_build0, s, e.err)) return rc;
+    if (n > 0) {
+        build(s);
+        if (int rc = hip_fail(hipGetLastError(), build_name, e.err)) return rc;
+        if (int rc = launch_upper<Node>(tl, tv, n_trees, s, e.err, first, n_level1)) return rc;
+    }
+    if (int rc = record(e.ev_build1, s, e.err)) return rc;
+    if (with_query)
+        if (int rc = query(s)) return rc;
+    return record(e.ev_query1, s, e.err);
+}
+
 // ------------------------------------------------------------------------------------------
 // The site-window table written on the device from the per-run plan (pgt_windows.cpp: plan_entry_windows /
 // for_each_window are the host form of exactly this): thread i finds its run by bisection over the runs'
@@ -2095,7 +2113,7 @@ int launch_windows_from_plan(const RunPlan *d_plan, uint64_t n_runs, uint64_t n_
 int init_kernels(std::string *err) {  // per pgt_open, i.e. per device: function attributes are per device
     const void *staged[] = {reinterpret_cast<const void *>(fst_build_kernel<>),
                             reinterpret_cast<const void *>(dxy_build_kernel), reinterpret_cast<const void *>(pi_build_kernel<>),
-                            reinterpret_cast<const void *>(ext_build_kernel<>), reinterpret_cast<const void *>(ext_build_kernel<kExtStageSmall, 2, true>)};
+                            reinterpret_cast<const void *>(ext_build_kernel<>), reinterpret_cast<const void *>(ext_build_kernel<kExtStageSmall, 2>)};
     for (const void *k : staged)
         if (int rc = hip_fail(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFstStageBytes),
                               "hipFuncSetAttribute", err))
@@ -2135,129 +2153,114 @@ void fst_build_launch(hipStream_t s, const PairCols &cols, uint32_t np, uint64_t
 // its experiments.  No preprocessor switch lives in this file.
 template <class BuildFn>
 int launch_fst_with(BuildFn build, const uint32_t *pos, const double *const *a, const double *const *b, uint32_t n_pairs,
-                    uint64_t n, const pgt_win *win, uint64_t n_win, pgt_fst_row *out, void *tree, void *stream,
-                    void *ev_build0, void *ev_build1, void *ev_query1, std::string *err, const Hints &hints) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
+                    uint64_t n, const pgt_win *win, uint64_t n_win, pgt_fst_row *out, void *tree, const LaunchEnv &e) {
+    hipStream_t s = static_cast<hipStream_t>(e.stream);
     const TreeLayout tl = tree_layout(PGT_STAT_FST, n);
-    const int levels = useful_levels(tl, PGT_STAT_FST, hints.max_window);
+    const int levels = useful_levels(tl, PGT_STAT_FST, e.hints.max_window);
     for (uint32_t p0 = 0; p0 < n_pairs; p0 += kMaxPairs) {
         const uint32_t np = n_pairs - p0 < (uint32_t)kMaxPairs ? n_pairs - p0 : (uint32_t)kMaxPairs;
         PairCols cols{};
         for (uint32_t p = 0; p < np; ++p) { cols.a[p] = a[p0 + p]; cols.b[p] = b[p0 + p]; }
         const TreeView tv = make_view(tl, static_cast<char *>(tree) + (size_t)p0 * tl.bytes, tl.bytes, levels);
-        if (p0 == 0) if (int rc = record(ev_build0, s, err)) return rc;
+        if (p0 == 0) if (int rc = record(e.ev_build0, s, e.err)) return rc;
         if (n > 0) {
-            build(s, cols, np, n, tl, tv, hints);
-            if (int rc = hip_fail(hipGetLastError(), "fst_build_kernel", err)) return rc;
-            if (int rc = launch_upper<NodeFst>(tl, tv, np, s, err)) return rc;
+            build(s, cols, np, n, tl, tv, e.hints);
+            if (int rc = hip_fail(hipGetLastError(), "fst_build_kernel", e.err)) return rc;
+            if (int rc = launch_upper<NodeFst>(tl, tv, np, s, e.err)) return rc;
         }
-        if (p0 + np >= n_pairs) if (int rc = record(ev_build1, s, err)) return rc;
+        if (p0 + np >= n_pairs) if (int rc = record(e.ev_build1, s, e.err)) return rc;
         if (n_win > 0)
-            if (int rc = launch_query<FstTraits>(s, hints, kLeafF64, np, false, true, FstTraits::Args{cols}, pos, tv, win, n_win,
-                                                 out + (uint64_t)p0 * n_win, n, nullptr, "query_kernel<fst>", err))
+            if (int rc = launch_query<FstTraits>(s, e.hints, kLeafF64, np, false, true, FstTraits::Args{cols}, pos, tv, win, n_win,
+                                                 out + (uint64_t)p0 * n_win, n, nullptr, "query_kernel<fst>", e.err))
                 return rc;
     }
-    return record(ev_query1, s, err);
+    return record(e.ev_query1, s, e.err);
 }
 }  // namespace
 
 int launch_fst(const uint32_t *pos, const double *const *a, const double *const *b, uint32_t n_pairs,
-               uint64_t n, const pgt_win *win, uint64_t n_win, pgt_fst_row *out, void *tree, void *stream,
-               void *ev_build0, void *ev_build1, void *ev_query1, std::string *err, const Hints &hints) {
-    return launch_fst_with(fst_build_launch, pos, a, b, n_pairs, n, win, n_win, out, tree, stream, ev_build0, ev_build1, ev_query1,
-                           err, hints);
+               uint64_t n, const pgt_win *win, uint64_t n_win, pgt_fst_row *out, void *tree, const LaunchEnv &e) {
+    return launch_fst_with(fst_build_launch, pos, a, b, n_pairs, n, win, n_win, out, tree, e);
 }
 
 int launch_het(const uint32_t *pos, const int8_t *g, uint64_t n, const pgt_win *win, uint64_t n_win,
-               pgt_het_row *out, void *tree, void *stream, void *ev_build0, void *ev_build1, void *ev_query1,
-               std::string *err, const Hints &hints) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
+               pgt_het_row *out, void *tree, const LaunchEnv &e) {
     const TreeLayout tl = tree_layout(PGT_STAT_HET, n);
-    const TreeView tv = make_view(tl, tree, tl.bytes, useful_levels(tl, PGT_STAT_HET, hints.max_window));
-    if (int rc = record(ev_build0, s, err)) return rc;
-    if (n > 0) {
-        const uint64_t n_items = het_items(n);
-        // short inputs live on many short work items and want the waves (128-VGPR build, 16 waves per CU): 12.7 against 13.7 us
-        // at 3e7 sites, 32.9 against 34.8 at 1.25e8; long ones stream better with the 254-VGPR build: 149 against 172 us at 10^9
-        // (interleaved A/B in one process, profiles/r06/het_kernel_crossover_ab.md)
-        // The grid is what is RESIDENT at once (round 6): 1024 workgroups of the 128-VGPR build (16 waves per CU), 512 of the
-        // 254-VGPR one (8) — until then both took up to 2048, i.e. 1.5 ... 4 generations of workgroups, and a last generation that
-        // is half empty idles half the chip: 10^8 sites 25.0 -> 22.7 us, 3e8 57.6 -> 50.8 (65 -> 74 % of the HBM peak), 10^9
-        // 158.2 -> 152.5 (79 -> 82 %), interleaved A/B (profiles/r06/het_grid_resident_ab.md).
-        if (n_items <= kHetSmallItems)
-            hipLaunchKernelGGL(het_build_kernel_w4, dim3(build_grid(n_items, 1024)), dim3(256), 0, s, g, n, n_items, tv);
-        else
-            hipLaunchKernelGGL(het_build_kernel, dim3(build_grid(n_items, 512)), dim3(256), 0, s, g, n, n_items, tv);
-        if (int rc = hip_fail(hipGetLastError(), "het_build_kernel", err)) return rc;
-        if (int rc = launch_upper<NodeHet>(tl, tv, 1, s, err, 1, n_items * kHetChunk)) return rc;
-    }
-    if (int rc = record(ev_build1, s, err)) return rc;
-    if (n_win > 0)
-        if (int rc = launch_query<HetTraits>(s, hints, kLeafI8, 1, false, false, HetTraits::Args{g}, pos, tv, win, n_win, out, n, nullptr,
-                                             "query_kernel<het>", err))
-            return rc;
-    return record(ev_query1, s, err);
+    const TreeView tv = make_view(tl, tree, tl.bytes, useful_levels(tl, PGT_STAT_HET, e.hints.max_window));
+    const uint64_t n_items = het_items(n);
+    return launch_build_query<NodeHet>(
+        e, tl, tv, 1, 1, n_items * kHetChunk, n, "het_build_kernel",
+        [&](hipStream_t s) {
+            // short inputs live on many short work items and want the waves (128-VGPR build, 16 waves per CU): 12.7 against 13.7 us
+            // at 3e7 sites, 32.9 against 34.8 at 1.25e8; long ones stream better with the 254-VGPR build: 149 against 172 us at 10^9
+            // (interleaved A/B in one process, profiles/r06/het_kernel_crossover_ab.md)
+            // The grid is what is RESIDENT at once (round 6): 1024 workgroups of the 128-VGPR build (16 waves per CU), 512 of the
+            // 254-VGPR one (8) — until then both took up to 2048, i.e. 1.5 ... 4 generations of workgroups, and a last generation that
+            // is half empty idles half the chip: 10^8 sites 25.0 -> 22.7 us, 3e8 57.6 -> 50.8 (65 -> 74 % of the HBM peak), 10^9
+            // 158.2 -> 152.5 (79 -> 82 %), interleaved A/B (profiles/r06/het_grid_resident_ab.md).
+            if (n_items <= kHetSmallItems)
+                hipLaunchKernelGGL(het_build_kernel_w4, dim3(build_grid(n_items, 1024)), dim3(256), 0, s, g, n, n_items, tv);
+            else
+                hipLaunchKernelGGL(het_build_kernel, dim3(build_grid(n_items, 512)), dim3(256), 0, s, g, n, n_items, tv);
+        },
+        n_win > 0,
+        [&](hipStream_t s) {
+            return launch_query<HetTraits>(s, e.hints, kLeafI8, 1, false, false, HetTraits::Args{g}, pos, tv, win, n_win, out, n, nullptr,
+                                           "query_kernel<het>", e.err);
+        });
 }
 
 int launch_dxy(const uint32_t *pos, const double *p1, const double *p2, const int32_t *n1, const int32_t *n2,
                uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_dxy_row *out, pgt_dxy_total *tot,
-               void *tree, void *stream, void *ev_build0, void *ev_build1, void *ev_query1, std::string *err,
-               const Hints &hints) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
+               void *tree, const LaunchEnv &e) {
     const TreeLayout tl = tree_layout(PGT_STAT_DXY, n);
-    // the genome-wide total is the sum of the build waves' partial sums (dxy_build_body): it needs no level of its own
-    TreeView tv = make_view(tl, tree, tl.bytes, useful_levels(tl, PGT_STAT_DXY, hints.max_window));
-    if (int rc = record(ev_build0, s, err)) return rc;
-    if (n > 0) {
-        const dim3 grid(build_grid(tl.count[1], kFstBuildBlocks));
-        tv.n_partials = grid.x * 4;  // every wave of the grid writes one (waves without a tile: the identity)
-        hipLaunchKernelGGL(dxy_build_kernel, grid, dim3(256), kFstStageBytes, s, p1, p2, n1, n2, n, minind, tl.count[1], tv);
-        if (int rc = hip_fail(hipGetLastError(), "dxy_build_kernel", err)) return rc;
-        if (int rc = launch_upper<NodeDxy>(tl, tv, 1, s, err)) return rc;
-    }
-    if (int rc = record(ev_build1, s, err)) return rc;
-    if (n_win > 0 || tot)
-        if (int rc = launch_query<DxyTraits>(s, hints, kLeafF64, 1, true, true, DxyTraits::Args{p1, p2, n1, n2, minind}, pos, tv, win,
-                                             n_win, out, n, tot, "query_kernel<dxy>", err))
-            return rc;
-    return record(ev_query1, s, err);
+    // the genome-wide total is the sum of the build waves' partial sums (build_walk_into): it needs no level of its own
+    TreeView tv = make_view(tl, tree, tl.bytes, useful_levels(tl, PGT_STAT_DXY, e.hints.max_window));
+    const dim3 grid(build_grid(tl.count[1], kFstBuildBlocks));
+    if (n > 0) tv.n_partials = grid.x * 4;  // every wave of the grid writes one (waves without a tile: the identity)
+    return launch_build_query<NodeDxy>(
+        e, tl, tv, 1, 2, 0, n, "dxy_build_kernel",
+        [&](hipStream_t s) {
+            hipLaunchKernelGGL(dxy_build_kernel, grid, dim3(256), kFstStageBytes, s, p1, p2, n1, n2, n, minind, tl.count[1], tv);
+        },
+        n_win > 0 || tot,
+        [&](hipStream_t s) {
+            return launch_query<DxyTraits>(s, e.hints, kLeafF64, 1, true, true, DxyTraits::Args{p1, p2, n1, n2, minind}, pos, tv, win,
+                                           n_win, out, n, tot, "query_kernel<dxy>", e.err);
+        });
 }
 
 // pi of n_pops populations (1 ... 8, checked by the caller): one build launch with grid.y = population, one tree of the
 // two-population dxy layout per population (tl.bytes apart), then the query strategy launch_dxy would choose, batched over
 // the populations; out: n_pops tables of n_win rows, tot: n_pops lines or NULL
 int launch_pi_pops(const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops, uint64_t n,
-                   int minind, const pgt_win *win, uint64_t n_win, pgt_dxy_row *out, pgt_dxy_total *tot, void *tree, void *stream,
-                   void *ev_build0, void *ev_build1, void *ev_query1, std::string *err, const Hints &hints) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
+                   int minind, const pgt_win *win, uint64_t n_win, pgt_dxy_row *out, pgt_dxy_total *tot, void *tree,
+                   const LaunchEnv &e) {
     const TreeLayout tl = tree_layout(PGT_STAT_DXY, n);
-    TreeView tv = make_view(tl, tree, tl.bytes, useful_levels(tl, PGT_STAT_DXY, hints.max_window));
+    TreeView tv = make_view(tl, tree, tl.bytes, useful_levels(tl, PGT_STAT_DXY, e.hints.max_window));
     PiTraits::Args args{};
     for (uint32_t k = 0; k < n_pops; ++k) { args.cols.f[k] = freq[k]; args.cols.n[k] = nind[k]; }
     args.minind = minind;
-    if (int rc = record(ev_build0, s, err)) return rc;
-    if (n > 0) {
-        const dim3 grid(build_grid(tl.count[1], kFstBuildBlocks), n_pops);
-        tv.n_partials = grid.x * 4;  // see launch_dxy
-        hipLaunchKernelGGL(pi_build_kernel<>, grid, dim3(256), kFstStageBytes, s, args.cols, n, minind, tl.count[1], tv);
-        if (int rc = hip_fail(hipGetLastError(), "pi_build_kernel", err)) return rc;
-        if (int rc = launch_upper<NodeDxy>(tl, tv, n_pops, s, err)) return rc;
-    }
-    if (int rc = record(ev_build1, s, err)) return rc;
-    if (n_win > 0 || tot)
-        if (int rc = launch_query<PiTraits>(s, hints, kLeafF64, n_pops, true, true, args, pos, tv, win, n_win, out, n, tot,
-                                            "query_kernel<pi>", err))
-            return rc;
-    return record(ev_query1, s, err);
+    const dim3 grid(build_grid(tl.count[1], kFstBuildBlocks), n_pops);
+    if (n > 0) tv.n_partials = grid.x * 4;  // see launch_dxy
+    return launch_build_query<NodeDxy>(
+        e, tl, tv, n_pops, 2, 0, n, "pi_build_kernel",
+        [&](hipStream_t s) {
+            hipLaunchKernelGGL(pi_build_kernel<>, grid, dim3(256), kFstStageBytes, s, args.cols, n, minind, tl.count[1], tv);
+        },
+        n_win > 0 || tot,
+        [&](hipStream_t s) {
+            return launch_query<PiTraits>(s, e.hints, kLeafF64, n_pops, true, true, args, pos, tv, win, n_win, out, n, tot,
+                                          "query_kernel<pi>", e.err);
+        });
 }
 
 // grid = exactly the workgroups that are resident together (LDS-limited), so that all waves run in near
 // lockstep and their staged node rows are flushed at about the same times (see NodeStage)
 namespace {
-template <int STAGE, int UNROLL, bool DEFER>
+template <int STAGE, int UNROLL>
 void launch_ext_variant(hipStream_t s, const ExtBuildArgs &g, uint64_t n, uint64_t n_l2, const TreeView &tv, unsigned cap) {
-    const size_t lds = DEFER ? (size_t)4 * STAGE * 1024 : 0;
-    hipLaunchKernelGGL((ext_build_kernel<STAGE, UNROLL, DEFER>), dim3(build_grid(n_l2, cap)), dim3(256), lds, s, g, n, n_l2, tv);
+    hipLaunchKernelGGL((ext_build_kernel<STAGE, UNROLL>), dim3(build_grid(n_l2, cap)), dim3(256), (size_t)4 * STAGE * 1024, s, g, n, n_l2, tv);
 }
 void ext_build_launch(hipStream_t s, const ExtBuildArgs &g, uint64_t n, uint64_t n_l2, const TreeView &tv) {
     // Short inputs (up to 20000 tiles of 16384 sites = 3.3e8 sites): 16 waves per CU with 4 loads in flight each (two leaf tiles
@@ -2268,49 +2271,40 @@ void ext_build_launch(hipStream_t s, const ExtBuildArgs &g, uint64_t n, uint64_t
     // (10^9: 84.7 % against 81.8).  profiles/r05/build_ab_ext_geometry_with_rotation.md; round 4 had measured -12 % at 1.25e8
     // sites for the same geometry without the rotation.
     if (n_l2 <= kExtSmallTiles)
-        launch_ext_variant<kExtStageSmall, 2, true>(s, g, n, n_l2, tv, 2 * kFstBuildBlocks);
+        launch_ext_variant<kExtStageSmall, 2>(s, g, n, n_l2, tv, 2 * kFstBuildBlocks);
     else
-        launch_ext_variant<kExtStage, 4, true>(s, g, n, n_l2, tv, kFstBuildBlocks);
+        launch_ext_variant<kExtStage, 4>(s, g, n, n_l2, tv, kFstBuildBlocks);
 }
 
 template <class BuildFn>  // the build launch is a parameter for the same reason as in launch_fst_with
 int launch_ext_with(BuildFn build, const uint32_t *pos, const double *score, uint64_t n, int mode, double cutoff, const pgt_win *win,
-                    uint64_t n_win, pgt_ext_row *out, void *tree, void *stream, void *ev_build0, void *ev_build1,
-                    void *ev_query1, std::string *err, const Hints &hints) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
+                    uint64_t n_win, pgt_ext_row *out, void *tree, const LaunchEnv &e) {
     const TreeLayout tl = tree_layout(PGT_STAT_EXT, n);
-    const TreeView tv = make_view(tl, tree, tl.bytes, useful_levels(tl, PGT_STAT_EXT, hints.max_window));
+    const TreeView tv = make_view(tl, tree, tl.bytes, useful_levels(tl, PGT_STAT_EXT, e.hints.max_window));
     const double thr = mode == PGT_EXT_XP_MIN ? -cutoff : cutoff;  // s < cutoff  <=>  -s > -cutoff
-    if (int rc = record(ev_build0, s, err)) return rc;
-    if (n > 0) {
-        build(s, ExtBuildArgs{score, mode, thr}, n, tl.count[1], tv);
-        if (int rc = hip_fail(hipGetLastError(), "ext_build_kernel", err)) return rc;
-        if (int rc = launch_upper<NodeExt>(tl, tv, 1, s, err)) return rc;
-    }
-    if (int rc = record(ev_build1, s, err)) return rc;
-    if (n_win > 0) {
-        ExtTraits::Args args{score, mode, thr};
-        hipLaunchKernelGGL(query_kernel<ExtTraits>, dim3(query_grid(n_win)), dim3(256), 0, s, args, pos, tv, win, n_win,
-                           out, n, (pgt_dxy_total *)nullptr);
-        if (int rc = hip_fail(hipGetLastError(), "query_kernel<ext>", err)) return rc;
-    }
-    return record(ev_query1, s, err);
+    return launch_build_query<NodeExt>(
+        e, tl, tv, 1, 2, 0, n, "ext_build_kernel", [&](hipStream_t s) { build(s, ExtBuildArgs{score, mode, thr}, n, tl.count[1], tv); }, n_win > 0,
+        [&](hipStream_t s) {
+            ExtTraits::Args args{score, mode, thr};
+            hipLaunchKernelGGL(query_kernel<ExtTraits>, dim3(query_grid(n_win)), dim3(256), 0, s, args, pos, tv, win, n_win,
+                               out, n, (pgt_dxy_total *)nullptr);
+            return hip_fail(hipGetLastError(), "query_kernel<ext>", e.err);
+        });
 }
 }  // namespace
 
 int launch_ext(const uint32_t *pos, const double *score, uint64_t n, int mode, double cutoff, const pgt_win *win,
-               uint64_t n_win, pgt_ext_row *out, void *tree, void *stream, void *ev_build0, void *ev_build1,
-               void *ev_query1, std::string *err, const Hints &hints) {
-    return launch_ext_with(ext_build_launch, pos, score, n, mode, cutoff, win, n_win, out, tree, stream, ev_build0, ev_build1,
-                           ev_query1, err, hints);
+               uint64_t n_win, pgt_ext_row *out, void *tree, const LaunchEnv &e) {
+    return launch_ext_with(ext_build_launch, pos, score, n, mode, cutoff, win, n_win, out, tree, e);
 }
 
 int launch_dxy_het(const uint32_t *pos, const double *p1, const double *p2, const int32_t *n1, const int32_t *n2,
                    const int8_t *g1, const int8_t *g2, uint64_t n, int minind, const pgt_win *win, uint64_t n_win,
                    pgt_dxy_row *dxy_out, pgt_dxy_total *tot, pgt_het_row *het_out1, pgt_het_row *het_out2, void *tree,
-                   void *stream, void *ev_build0, void *ev_build1, void *ev_query1, std::string *err,
-                   const Hints &hints) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
+                   const LaunchEnv &e) {
+    hipStream_t s = static_cast<hipStream_t>(e.stream);
+    std::string *err = e.err;
+    const Hints &hints = e.hints;
     const TreeLayout td = tree_layout(PGT_STAT_DXY, n), th = tree_layout(PGT_STAT_HET, n);
     char *base = static_cast<char *>(tree);
     const int lh = useful_levels(th, PGT_STAT_HET, hints.max_window);
@@ -2318,7 +2312,7 @@ int launch_dxy_het(const uint32_t *pos, const double *p1, const double *p2, cons
     const TreeView tvh = make_view(th, base + td.bytes, th.bytes, lh);  // the two genotype trees, th.bytes apart
     TreeView tvh1 = tvh;
     tvh1.base += th.bytes;
-    if (int rc = record(ev_build0, s, err)) return rc;
+    if (int rc = record(e.ev_build0, s, err)) return rc;
     if (n > 0) {
         const uint64_t n_items = het_items(n);  // == td.count[1]: a dxy level-2 tile is one het work item
         const dim3 grid(build_grid(td.count[1], kFstBuildBlocks));
@@ -2329,7 +2323,7 @@ int launch_dxy_het(const uint32_t *pos, const double *p1, const double *p2, cons
         if (int rc = launch_upper<NodeDxy>(td, tvd, 1, s, err)) return rc;
         if (int rc = launch_upper<NodeHet>(th, tvh, 2, s, err, 1, n_items * kHetChunk)) return rc;  // both genotype trees per launch
     }
-    if (int rc = record(ev_build1, s, err)) return rc;
+    if (int rc = record(e.ev_build1, s, err)) return rc;
     if (n_win > 0 || tot) {
         DxyHetQueryArgs q{DxyTraits::Args{p1, p2, n1, n2, minind}, {g1, g2}, tvd, {tvh, tvh1}, dxy_out, tot,
                           {het_out1, het_out2}};
@@ -2347,7 +2341,7 @@ int launch_dxy_het(const uint32_t *pos, const double *p1, const double *p2, cons
             hipLaunchKernelGGL(dxy_het_query_kernel, dim3(query_grid(n_win + 1), 3), dim3(256), 0, s, q, pos, win, n_win, n);
         if (int rc = hip_fail(hipGetLastError(), "dxy_het_query_kernel", err)) return rc;
     }
-    return record(ev_query1, s, err);
+    return record(e.ev_query1, s, err);
 }
 
 }  // namespace pgt

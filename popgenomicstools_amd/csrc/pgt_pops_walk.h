@@ -525,9 +525,9 @@ constexpr size_t stage_bytes() { return (size_t)4 * dev::kRadix1 * Stat::items(N
 
 template <class Stat, int NP>
 int launch_np(const dev::PopCols &cols, const uint32_t *pos, uint64_t n, int minind, const pgt_win *win, uint64_t n_win,
-              typename Stat::Row *out, typename Stat::Total *tot, PopsTree tv, const TreeLayout &tl, hipStream_t s, void *ev_b0,
-              void *ev_b1, void *ev_q1, std::string *err) {
-    if (int rc = record_event(ev_b0, s, err)) return rc;
+              typename Stat::Row *out, typename Stat::Total *tot, PopsTree tv, const TreeLayout &tl, hipStream_t s, const LaunchEnv &e) {
+    std::string *err = e.err;
+    if (int rc = record_event(e.ev_build0, s, err)) return rc;
     tv.n_partials = 0;
     if (n > 0) {
         const bool w1 = NP >= one_wave_from<Stat>();
@@ -543,12 +543,12 @@ int launch_np(const dev::PopCols &cols, const uint32_t *pos, uint64_t n, int min
         if (int rc = hip_fail(hipGetLastError(), Stat::kKernelNames[0], err)) return rc;
         if (int rc = launch_upper_levels(dev::pops_up_kernel<Stat::kSumsPerItem>, Stat::kKernelNames[1], Stat::kSumsPerItem * Stat::items(NP), tv, tl, s, err)) return rc;
     }
-    if (int rc = record_event(ev_b1, s, err)) return rc;
+    if (int rc = record_event(e.ev_build1, s, err)) return rc;
     if (n_win > 0 || tot) {
         hipLaunchKernelGGL((dev::pops_query_kernel<Stat, NP>), dim3(wave_grid(n_win + (tot ? 1 : 0))), dim3(256), 0, s, cols, minind, pos, tv, win, n_win, out, tot, n);
         if (int rc = hip_fail(hipGetLastError(), Stat::kKernelNames[2], err)) return rc;
     }
-    return record_event(ev_q1, s, err);
+    return record_event(e.ev_query1, s, err);
 }
 
 // every build kernel of the statistic may use its stage (called once from pgt_open through the statistic's init function, so
@@ -568,14 +568,14 @@ void allow_lds() {
 template <class Stat>
 int launch_pops(const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops, uint64_t n,
                 int minind, const pgt_win *win, uint64_t n_win, typename Stat::Row *out, typename Stat::Total *tot, void *tree,
-                void *stream, void *ev_build0, void *ev_build1, void *ev_query1, std::string *err, const Hints &hints) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
+                const LaunchEnv &e) {
+    hipStream_t s = static_cast<hipStream_t>(e.stream);
     const TreeLayout tl = tree_layout(PGT_STAT_FST, n);  // node counts of the f64 layout (levels 2 and up; level 1: a quarter)
-    const PopsTree tv = pops_tree_view(tl, Stat::items((int)n_pops), Stat::kSumsPerItem, tree, useful_levels(tl, PGT_STAT_FST, hints.max_window));
+    const PopsTree tv = pops_tree_view(tl, Stat::items((int)n_pops), Stat::kSumsPerItem, tree, useful_levels(tl, PGT_STAT_FST, e.hints.max_window));
     dev::PopCols cols{};
     for (uint32_t k = 0; k < n_pops; ++k) { cols.f[k] = freq[k]; cols.c[k] = nind[k]; }
     return dispatch_pops<Stat::kMinPops, Stat::kMaxPops>(n_pops, [&](auto np) {
-        return launch_np<Stat, decltype(np)::value>(cols, pos, n, minind, win, n_win, out, tot, tv, tl, s, ev_build0, ev_build1, ev_query1, err);
+        return launch_np<Stat, decltype(np)::value>(cols, pos, n, minind, win, n_win, out, tot, tv, tl, s, e);
     });
 }
 

@@ -166,6 +166,7 @@ def main():
                 if t is not None:
                     t.zero_()
             return kept
+        rows(ctx_a)  # discarded: it leaves the shared buffers cleared, so that A's copy below holds no rows of the configuration before
         ra_, rb_ = rows(ctx_a), rows(ctx_b)
         same = all(torch.equal(x, y) for x, y in zip(ra_, rb_))
         if not same:  # say WHICH tensor differs and by how much (a 24-byte tensor is the genome-wide dxy line: f64 sum, two u64 counts)

@@ -243,9 +243,7 @@ struct AblateStage {
 template <int MODE>
 __global__ __launch_bounds__(256) void fst_build_ablate_kernel(PairCols cols, uint64_t n, uint64_t n_l2, TreeView tv) {
     extern __shared__ __attribute__((aligned(16))) char lds_stage[];
-    const uint64_t wave0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
-    fst_build_body<AblateStage<MODE>, 4, 4, 0>(cols, n, n_l2, tv, lds_stage, wave0, n_waves);
+    fst_build_body<AblateStage<MODE>, 4, 4, 0>(PGT_BUILD_WAVE(), cols, n, n_l2, tv, lds_stage);
 }
 
 // Returns true when an experimental launch replaced the product's fst build.
