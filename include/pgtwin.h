@@ -33,7 +33,7 @@
  *     has no counts: every site is counted; a NaN there stays in the rows of the pairs with that population.
  *   - genotypes: any int8 (non-missing is g >= 0, heterozygous g == 1, hetWindow.cpp:78-80); counts (n1, n2, nind[k]) and minind:
  *     any int32, compared as signed integers (dxyWindow.cpp:381).
- *   - the K-population entry points (pgt_dxy_pops / fst_pops / fst_hudson_pops / pi_pops / dstat_pops / fd_pops / f3_pops _reduce_dev;
+ *   - the K-population entry points (pgt_dxy_pops / fst_pops / fst_hudson_pops / pi_pops / dstat_pops / fd_pops / f3_pops / pbs_pops / pbs_hudson_pops _reduce_dev;
  *     tests/test_special_values_pops.py): a NaN or an infinity in ONE population's frequency at a COUNTED site reaches exactly the
  *     rows (and genome-wide lines) of the items — pairs, trios, the population itself — that hold that population, and of them
  *     exactly the windows that hold the site, with the value the per-site definition gives on the IEEE operands, every operation
@@ -71,7 +71,9 @@ extern "C" {
  * Still 6: pgt_dstat_jack, pgt_dstat_jackknife_work_bytes / pgt_dstat_jackknife_dev / pgt_dstat_jackknife added (additive as well).
  * Still 6: pgt_fd_row, pgt_fd_total, pgt_fd_pops_tree_bytes / pgt_fd_pops_reduce_dev / pgt_fd_pops_reduce added (additive as well).
  * Still 6: pgt_f3_row, pgt_f3_total, pgt_f3_jack, pgt_f3_pops_tree_bytes / pgt_f3_pops_reduce_dev / pgt_f3_pops_reduce and
- *          pgt_f3_jackknife_work_bytes / pgt_f3_jackknife_dev / pgt_f3_jackknife added (additive as well). */
+ *          pgt_f3_jackknife_work_bytes / pgt_f3_jackknife_dev / pgt_f3_jackknife added (additive as well).
+ * Still 6: pgt_pbs_row, pgt_pbs_total, pgt_pbs_pops_work_bytes / pgt_pbs_pops_reduce_dev / pgt_pbs_hudson_pops_reduce_dev /
+ *          pgt_pbs_pops_reduce / pgt_pbs_hudson_pops_reduce added (additive as well). */
 #define PGT_ABI_VERSION 6
 
 enum {
@@ -170,6 +172,20 @@ typedef struct { /* block jackknife of one trio and target: pgt_f3_jackknife_dev
     uint64_t n_sites;          /* counted sites of the used blocks */
     uint32_t n_blocks, pad_;   /* used blocks (rows with n > 0) */
 } pgt_f3_jack;
+
+typedef struct { /* population-branch-statistic window row of one trio (i, j, k): pgt_pbs_pops_reduce_dev (88 bytes) */
+    uint32_t start, end, mid, n;    /* offsets 0, 4, 8, 12 */
+    double pbs_i, pbs_j, pbs_k;     /* offsets 16, 24, 32: PBS with i, j, k as the focal population, from the six sums below */
+    double num_ij, num_ik, num_jk;  /* offsets 40, 48, 56: the FST numerators of the trio's pairs over the TRIO's counted sites */
+    double den_ij, den_ik, den_jk;  /* offsets 64, 72, 80: the FST denominators over the same sites; fst_xy = num_xy / den_xy */
+} pgt_pbs_row;
+
+typedef struct { /* the same nine doubles of one trio over all its counted sites (88 bytes) */
+    double pbs_i, pbs_j, pbs_k;     /* offsets 0, 8, 16 */
+    double num_ij, num_ik, num_jk;  /* offsets 24, 32, 40 */
+    double den_ij, den_ik, den_jk;  /* offsets 48, 56, 64 */
+    uint64_t neff, nskip;           /* offsets 72, 80 */
+} pgt_pbs_total;
 
 /* ---- context ------------------------------------------------------------------------- */
 /* device: HIP ordinal, or -1 for the current device.  Fails (NULL, message via
@@ -643,6 +659,72 @@ int pgt_f3_jackknife_dev(pgt_ctx *ctx, const pgt_f3_row *rows, uint64_t n_win, u
                          pgt_f3_jack *out /* 3 * n_trios, item-major u = 3t + c */, size_t out_bytes,
                          void *work, size_t work_bytes, void *stream);
 int pgt_f3_jackknife(pgt_ctx *ctx, const pgt_f3_row *rows, uint64_t n_win, uint32_t n_trios, pgt_f3_jack *out);
+
+/* ---- the population branch statistic (PBS) of ALL trios, every population of a trio as the focal one -------------------- */
+/* PBS (Yi et al. 2010), the windowed selection scan for a focal population against two others, from each population's own
+ * (freq, nInd) columns — the input of pgt_fst_pops_reduce_dev — over ONE position column and ONE window table.  It has NO
+ * counterpart in the reference: the definition below is the contract.
+ * n_pops = K populations, 3 <= K <= 6.  ALL populations are equal.  A trio is (i, j, k) with i < j < k < K; trios are numbered
+ * as pgt_f3_pops_reduce_dev numbers them, T = C(K, 3) = 1 / 4 / 10 / 20.  For trio (i, j, k) and site s:
+ *   counting   nind_i[s] >= minind && nind_j[s] >= minind && nind_k[s] >= minind   (signed int32 compare; minind >= 1 required,
+ *              PGT_EARG otherwise); a site that is not counted is selected away, never multiplied: its columns may hold
+ *              anything.  This is the TRIO's site set.  It is NOT the site set of the pair tables of pgt_fst_pops_reduce_dev,
+ *              which count a pair's site whatever the third population holds: wherever the third population lacks data, three
+ *              pair tables cover three different site sets and their FSTs are not branches of one tree.  Here the three pairs
+ *              of a trio are summed over the same sites (as ANGSD's realSFS fst does with three populations).
+ *   per site   for each of the trio's pairs (x, y) = (i, j), (i, k), (j, k) exactly the two values the all-pairs FST call adds
+ *              for that pair at a counted site, with the site's own sample sizes:
+ *                  pgt_pbs_pops_reduce_dev          num = a, den = a + b of pgt_fst_pops_reduce_dev (Weir-Cockerham)
+ *                  pgt_pbs_hudson_pops_reduce_dev   num, den of pgt_fst_hudson_pops_reduce_dev, every operation rounded on its own
+ *   row        pgt_pbs_row (88 bytes; offsets at the struct): start / end / mid as pgt_f3_row's are filled (PGT_WIN_COORDS
+ *              honoured); n = the trio's counted sites (nskip = (hi - lo) - n); num_ij, num_ik, num_jk, den_ij, den_ik, den_jk =
+ *              the six SUMS over those sites, each from +0.0; and from the row's own sums, every operation ONE rounding:
+ *                  fst_xy = den_xy != 0 ? num_xy / den_xy : 0           (fstWindow.cpp:85)
+ *                  T_xy   = -log(1 - fst_xy)                            (double log of the device library, at most 1 ulp)
+ *                  pbs_i  = ((T_ij + T_ik) - T_jk) * 0.5 + 0.0
+ *                  pbs_j  = ((T_ij + T_jk) - T_ik) * 0.5 + 0.0
+ *                  pbs_k  = ((T_ik + T_jk) - T_ij) * 0.5 + 0.0
+ *              NOTHING IS CLAMPED; the IEEE results stand: a negative FST gives a negative T (and may give a negative PBS);
+ *              fst == 1 (a window of fixed differences only) gives T = +inf and PBS = +/-inf; inf - inf gives NaN (two pairs of
+ *              the trio fixed); a NaN sum gives NaN.  A window without a counted site has all six sums and all three pbs +0.0.
+ *              The FSTs are not stored: they are the caller's division, and a caller who wants another rule (FST truncated at
+ *              0, PBSn1) applies it to the sums.
+ *   out        T * n_win rows, trio-major: out[t * n_win + w]
+ *   tot        DEVICE array of T pgt_pbs_total (88 bytes: the same nine doubles over all counted sites, neff, nskip), or NULL;
+ *              n_win == 0 with tot: the global-only form
+ *   work       DEVICE workspace of pgt_pbs_pops_work_bytes(n_pops, n, n_win) bytes (0 for n_pops outside 3 ... 6), 16-byte
+ *              aligned: the tree of pgt_f3_pops_reduce_dev (3 T doubles and T u32 per node) and, behind it, 2 T n_win scratch rows
+ *              and 2 T scratch totals of 40 bytes.  The columns are walked twice (the numerators, then the denominators: six
+ *              sums per trio do not fit a node), the tree is reused, and a third kernel merges the passes.  Every byte that
+ *              is read is written earlier in the same call.    3 <= n_pops <= 6, n < 2^32.
+ * Arguments, alignment, refusals (PGT_EARG; the messages of BOTH estimators begin "pgt_pbs_pops_reduce: " and name their
+ * argument: "n_pops must be 3 ... 6", "minind must be at least 1", "work is not 16-byte aligned", "work_bytes too small",
+ * "out_bytes"; a refused call launches nothing and writes nothing), graph capture and the hints: those of
+ * pgt_f3_pops_reduce_dev (asynchronous, ONE chain of kernels on `stream`, no allocation, no attribute call;
+ * pgt_set_max_window honoured, pgt_set_window_step ignored; a profiled call reports the first pass and the second build as
+ * the build, the rest as the query).  Trio isolation: the rows of a trio are a function, bit for bit, of its own three
+ * populations' columns and the window alone.  Sums are added in a fixed order that depends on the site index and the window
+ * alone (bitwise reproducible).  A one-site window carries, with the Hudson estimator, exactly the bits of num and den.
+ * Against an exact evaluation a sum stays within 1e-9 * A + 1e-12, A the window's sum of the absolute values of the terms a
+ * site's value is built from.  Held to this definition, to an exact-rational fixture (tests/golden/pbs_exact.json) and to a
+ * NumPy model (tests/pbs_pops_model.py).  Not computed: PBSn1, truncation of negative FST, a block jackknife, user-chosen
+ * trio lists, K = 7.
+ * Host-buffer form: columns (host arrays of n_pops HOST pointers), table, rows and the T totals in host memory. */
+size_t pgt_pbs_pops_work_bytes(uint32_t n_pops, uint64_t n_sites, uint64_t n_win);
+int pgt_pbs_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq,
+                            const int32_t *const *nind, uint32_t n_pops, uint64_t n, int minind,
+                            const pgt_win *win, uint64_t n_win, pgt_pbs_row *out, size_t out_bytes,
+                            pgt_pbs_total *tot, void *work, size_t work_bytes, void *stream);
+int pgt_pbs_hudson_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq,
+                                   const int32_t *const *nind, uint32_t n_pops, uint64_t n, int minind,
+                                   const pgt_win *win, uint64_t n_win, pgt_pbs_row *out, size_t out_bytes,
+                                   pgt_pbs_total *tot, void *work, size_t work_bytes, void *stream);
+int pgt_pbs_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq,
+                        const int32_t *const *nind, uint32_t n_pops, uint64_t n, int minind,
+                        const pgt_win *win, uint64_t n_win, pgt_pbs_row *out, pgt_pbs_total *tot);
+int pgt_pbs_hudson_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq,
+                               const int32_t *const *nind, uint32_t n_pops, uint64_t n, int minind,
+                               const pgt_win *win, uint64_t n_win, pgt_pbs_row *out, pgt_pbs_total *tot);
 
 /* ---- the sites common to K files, aligned on the device ------------------------------------------ */
 /* Replaces the two-file synchronisation of dxyWindow.cpp:315-331 (one current line per file; the file that is behind reads

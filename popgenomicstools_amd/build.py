@@ -19,8 +19,8 @@ BIN = os.path.join(PKG, "bin")
 LIB = os.path.join(PKG, "libpgtwin.so")
 FLAGS = os.path.join(PKG, "libpgtwin.flags")
 
-LIB_SOURCES = ["pgt_kernels.hip", "pgt_af_kernels.hip", "pgt_dxy_pops_kernels.hip", "pgt_fst_pops_kernels.hip", "pgt_dstat_pops_kernels.hip", "pgt_fd_pops_kernels.hip", "pgt_f3_pops_kernels.hip", "pgt_dstat_jack_kernels.hip", "pgt_align_kernels.hip", "pgt_ingest.hip", "pgt_api.cpp", "pgt_windows.cpp"]
-HOST_TOOLS = ["fstWindow", "hetWindow", "dxyWindow", "dxyWindowPops", "fstWindowPops", "piWindowPops", "dstatWindowPops", "f3WindowPops", "ihsWindow", "xpehhWindow"]
+LIB_SOURCES = ["pgt_kernels.hip", "pgt_af_kernels.hip", "pgt_dxy_pops_kernels.hip", "pgt_fst_pops_kernels.hip", "pgt_dstat_pops_kernels.hip", "pgt_fd_pops_kernels.hip", "pgt_f3_pops_kernels.hip", "pgt_pbs_pops_kernels.hip", "pgt_dstat_jack_kernels.hip", "pgt_align_kernels.hip", "pgt_ingest.hip", "pgt_api.cpp", "pgt_windows.cpp"]
+HOST_TOOLS = ["fstWindow", "hetWindow", "dxyWindow", "dxyWindowPops", "fstWindowPops", "piWindowPops", "dstatWindowPops", "f3WindowPops", "pbsWindowPops", "ihsWindow", "xpehhWindow"]
 
 
 def _hipcc() -> str:
@@ -62,7 +62,7 @@ def build_lib(force: bool = False) -> str:
     that only received a prebuilt library) an existing library is used as it is."""
     import fcntl
     srcs = [os.path.join(CSRC, s) for s in LIB_SOURCES]
-    deps = srcs + [os.path.join(CSRC, "pgt_internal.h"), os.path.join(CSRC, "pgt_device.h"), os.path.join(CSRC, "pgt_pops_common.h"), os.path.join(CSRC, "pgt_pops_walk.h"), os.path.join(ROOT, "include", "pgtwin.h")]
+    deps = srcs + [os.path.join(CSRC, "pgt_internal.h"), os.path.join(CSRC, "pgt_device.h"), os.path.join(CSRC, "pgt_pops_common.h"), os.path.join(CSRC, "pgt_pops_walk.h"), os.path.join(CSRC, "pgt_fst_site.h"), os.path.join(ROOT, "include", "pgtwin.h")]
     extra = os.environ.get("PGT_EXTRA_HIPCC_FLAGS", "").split()
     if "-DPGT_TUNING_BUILD" in extra:
         # the tuning library (tools/tune_*.py): tools/pgt_kernels_tuning.hip REPLACES csrc/pgt_kernels.hip — it includes the

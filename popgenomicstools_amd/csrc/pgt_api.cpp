@@ -334,6 +334,10 @@ struct PopsStat {
     size_t row_bytes;
     size_t (*tree_bytes)(uint32_t n_pops, uint64_t n_sites);
     uint32_t max_pops = (uint32_t)kPopsMaxPops;               // (the trios of pgt_dstat_pops_reduce stop at 7)
+    // a workspace that holds more than the tree and depends on the window count (pgt_pbs_pops_reduce): its size instead of
+    // tree_bytes, and its name in the messages
+    size_t (*work_bytes)(uint32_t n_pops, uint64_t n_sites, uint64_t n_win) = nullptr;
+    const char *work_word = "tree";
 };
 uint64_t pops_pairs(uint32_t n_pops) { return (uint64_t)n_pops * (n_pops - 1) / 2; }
 uint64_t pops_each(uint32_t n_pops) { return n_pops; }
@@ -344,6 +348,11 @@ bool pops_in_range(const PopsStat &st, uint32_t n_pops) { return n_pops >= st.mi
 size_t pops_tree_bytes(const PopsStat &st, int sums, uint32_t n_pops, uint64_t n_sites) {
     if (!pops_in_range(st, n_pops)) return 0;
     return pops_tree_view(tree_layout(PGT_STAT_FST, n_sites), (int)st.tables(n_pops), sums, nullptr, 0).bytes;
+}
+
+// the bytes behind the `tree` (or `work`) argument of a call
+size_t pops_work_bytes(const PopsStat &st, uint32_t n_pops, uint64_t n_sites, uint64_t n_win) {
+    return st.work_bytes ? st.work_bytes(n_pops, n_sites, n_win) : st.tree_bytes(n_pops, n_sites);
 }
 
 // first in both forms, and before the device form's early PGT_OK
@@ -364,7 +373,7 @@ int pops_check_dev(pgt_ctx *ctx, const PopsStat &st, const uint32_t *pos, const 
     const std::string who = std::string(st.who) + ": ";
     if (!freq) return ctx_fail(ctx, PGT_EARG, who + "freq is NULL");
     if (!nind) return ctx_fail(ctx, PGT_EARG, who + "nind is NULL");
-    if (!tree) return ctx_fail(ctx, PGT_EARG, who + "tree is NULL");
+    if (!tree) return ctx_fail(ctx, PGT_EARG, who + st.work_word + " is NULL");
     if (n_win && !win) return ctx_fail(ctx, PGT_EARG, who + "win is NULL");
     if (n_win && !out) return ctx_fail(ctx, PGT_EARG, who + "out is NULL");
     if (n_win && n && !pos) return ctx_fail(ctx, PGT_EARG, who + "pos is NULL");  // windows without PGT_WIN_COORDS read pos[lo], pos[hi-1]
@@ -376,10 +385,10 @@ int pops_check_dev(pgt_ctx *ctx, const PopsStat &st, const uint32_t *pos, const 
         if (!aligned16(nind[k])) return ctx_fail(ctx, PGT_EARG, who + "nind" + at + " is not 16-byte aligned");
     }
     if (n >= (1ull << 32)) return ctx_fail(ctx, PGT_EARG, who + "n: at most 2^32-1 sites per call");
-    if (!aligned16(tree)) return ctx_fail(ctx, PGT_EARG, who + "tree is not 16-byte aligned");
-    if (tree_bytes < st.tree_bytes(n_pops, n))
-        return ctx_fail(ctx, PGT_EARG, who + "tree_bytes too small (" + std::to_string(tree_bytes) + " bytes, " +
-                                           std::to_string(st.tree_bytes(n_pops, n)) + " needed)");
+    if (!aligned16(tree)) return ctx_fail(ctx, PGT_EARG, who + st.work_word + " is not 16-byte aligned");
+    if (tree_bytes < pops_work_bytes(st, n_pops, n, n_win))
+        return ctx_fail(ctx, PGT_EARG, who + st.work_word + "_bytes too small (" + std::to_string(tree_bytes) + " bytes, " +
+                                           std::to_string(pops_work_bytes(st, n_pops, n, n_win)) + " needed)");
     const uint64_t tables = st.tables(n_pops);
     if (n_win > UINT64_MAX / tables) return ctx_fail(ctx, PGT_EARG, who + st.tables_word + " * n_win overflows");
     if (int rc = room_check(ctx, (who + "out_bytes").c_str(), tables * n_win, st.row_bytes, out_bytes)) return rc;
@@ -445,7 +454,7 @@ pgt_ctx *pgt_open(int device) {
     std::string init_err;
     if (init_kernels(&init_err) != PGT_OK || init_af_kernels(&init_err) != PGT_OK || init_dxy_pops_kernels(&init_err) != PGT_OK ||
         init_fst_pops_kernels(&init_err) != PGT_OK || init_dstat_pops_kernels(&init_err) != PGT_OK ||
-        init_fd_pops_kernels(&init_err) != PGT_OK || init_f3_pops_kernels(&init_err) != PGT_OK) {
+        init_fd_pops_kernels(&init_err) != PGT_OK || init_f3_pops_kernels(&init_err) != PGT_OK || init_pbs_pops_kernels(&init_err) != PGT_OK) {
         set_global_error("pgt_open: " + init_err);
         return nullptr;
     }
@@ -729,6 +738,31 @@ int pgt_f3_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *cons
                            uint32_t n_pops, uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_f3_row *out,
                            size_t out_bytes, pgt_f3_total *tot, void *tree, size_t tree_bytes, void *stream) {
     return pops_reduce_dev(ctx, kF3Pops, launch_f3_pops, pos, freq, nind, n_pops, n, minind, win, n_win, out, out_bytes, tot, tree, tree_bytes, stream);
+}
+
+// The population branch statistic of the same trios, every population of a trio as the focal one: two passes of the walk and a
+// finishing kernel behind one entry point per FST estimator; the workspace holds a pass's tree (f3's) and the passes' scratch
+// rows and totals, so its size knows the window count.  minind >= 1: the estimators' divisors at every counted site
+size_t pgt_pbs_pops_work_bytes(uint32_t n_pops, uint64_t n_sites, uint64_t n_win) {
+    if (n_pops < 3 || n_pops > 6) return 0;
+    return pbs_work(n_pops, n_sites, n_win).bytes;
+}
+static_assert(sizeof(pgt_pbs_row) == 88 && offsetof(pgt_pbs_row, num_ij) == 40 && sizeof(pgt_pbs_total) == 88 && offsetof(pgt_pbs_total, neff) == 72 &&
+              sizeof(PbsPassRow) == 40 && sizeof(PbsPassTotal) == 40, "the documented layouts");
+static const PopsStat kPbsPops = {"pgt_pbs_pops_reduce", 3, true, pops_all_trios, "n_trios", sizeof(pgt_pbs_row), nullptr, 6, pgt_pbs_pops_work_bytes, "work"};
+
+int pgt_pbs_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind,
+                            uint32_t n_pops, uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_pbs_row *out,
+                            size_t out_bytes, pgt_pbs_total *tot, void *work, size_t work_bytes, void *stream) {
+    return pops_reduce_dev(ctx, kPbsPops, [](auto &&...a) { return launch_pbs_pops(a..., FstPopsEstimator::WeirCockerham); },
+                           pos, freq, nind, n_pops, n, minind, win, n_win, out, out_bytes, tot, work, work_bytes, stream);
+}
+
+int pgt_pbs_hudson_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind,
+                                   uint32_t n_pops, uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_pbs_row *out,
+                                   size_t out_bytes, pgt_pbs_total *tot, void *work, size_t work_bytes, void *stream) {
+    return pops_reduce_dev(ctx, kPbsPops, [](auto &&...a) { return launch_pbs_pops(a..., FstPopsEstimator::Hudson); },
+                           pos, freq, nind, n_pops, n, minind, win, n_win, out, out_bytes, tot, work, work_bytes, stream);
 }
 
 // Block jackknife of the rows above: its own checks (no columns, no window table), the message prefix of both forms.
@@ -1052,7 +1086,7 @@ int pops_reduce_host(pgt_ctx *ctx, const PopsStat &st,
     const int32_t *pn[kPopsMaxPops];
     for (uint32_t k = 0; k < n_pops; ++k) { pf[k] = static_cast<double *>(df[k].p); pn[k] = static_cast<int32_t *>(dn[k].p); }
     const size_t row_bytes = (size_t)(tables * n_win) * sizeof(Row);
-    return reduce_tables_with_workspace<Row>(ctx, st.who, st.tree_bytes(n_pops, n), tables, n, win, n_win, out, row_bytes, tot,
+    return reduce_tables_with_workspace<Row>(ctx, st.who, pops_work_bytes(st, n_pops, n, n_win), tables, n, win, n_win, out, row_bytes, tot,
         [&](const pgt_win *dw, Row *dr, void *tree, size_t tb, Tot *dtot) {
             return dev(ctx, static_cast<uint32_t *>(dpos.p), pf, pn, n_pops, n, minind, dw, n_win, dr, row_bytes, dtot, tree, tb, nullptr);
         });
@@ -1213,6 +1247,19 @@ int pgt_f3_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *f
                        uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_f3_row *out, pgt_f3_total *tot) {
     PGT_USE_DEVICE(ctx);
     return pops_reduce_host(ctx, kF3Pops, pgt_f3_pops_reduce_dev, pos, freq, nind, n_pops, n, minind, win, n_win, out, tot);
+}
+
+/* PBS of all trios: the host-buffer form, as pgt_f3_pops_reduce, one per FST estimator */
+int pgt_pbs_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
+                        uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_pbs_row *out, pgt_pbs_total *tot) {
+    PGT_USE_DEVICE(ctx);
+    return pops_reduce_host(ctx, kPbsPops, pgt_pbs_pops_reduce_dev, pos, freq, nind, n_pops, n, minind, win, n_win, out, tot);
+}
+
+int pgt_pbs_hudson_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
+                               uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_pbs_row *out, pgt_pbs_total *tot) {
+    PGT_USE_DEVICE(ctx);
+    return pops_reduce_host(ctx, kPbsPops, pgt_pbs_hudson_pops_reduce_dev, pos, freq, nind, n_pops, n, minind, win, n_win, out, tot);
 }
 
 /* block jackknife of a host table of rows: rows up, the device form on the cached workspace, 3 n_trios results down */

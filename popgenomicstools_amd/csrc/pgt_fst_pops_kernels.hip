@@ -23,6 +23,7 @@
 // Tree, build walk and query: pgt_pops_walk.h, with two sums per pair.  The counts are needed as VALUES here, not only for
 // the predicate (CountValues).  Rows of a pair are functions of the pair's own four columns and the window alone: every
 // pair's arithmetic reads only its two populations' registers.
+#include "pgt_fst_site.h"
 #include "pgt_pops_walk.h"
 
 namespace pgt {
@@ -30,88 +31,10 @@ namespace {
 
 using namespace dev;
 
-// 1/d for d >= 1 (finite): the hardware estimate and two Newton steps
-__device__ __forceinline__ double recip(double d) {
-    double x = __builtin_amdgcn_rcp(d);
-    x = fma(x, fma(-d, x, 1.0), x);
-    x = fma(x, fma(-d, x, 1.0), x);
-    return x;
-}
-
 // ---- per-site contribution ---------------------------------------------------------------------------------------------
-// f[k], c.n(k): population k's frequency and individual count at the site (a site outside the range carries a count of 0:
-// never counted, minind >= 1).  The estimator is a compile-time tag with a static per-site function: the walk knows only
-// that a pair keeps two sums (acc[v], acc[P + v]) and a count (cnt[v]).
-struct WeirCockerham {  // the spec at the top of this file: acc[v] += a, acc[P + v] += a + b
-    template <int NP, class C>
-    static __device__ __forceinline__ void site(double *acc, uint32_t *cnt, const double *f, const C &c) {
-        constexpr int P = pair_count(NP);
-        double nd[NP], n4[NP], na[NP];
-        bool ok[NP];
-#pragma unroll
-        for (int k = 0; k < NP; ++k) {
-            nd[k] = (double)c.n(k);
-            ok[k] = c.ok(k);
-            n4[k] = 4.0 * nd[k];
-            na[k] = nd[k] * ((2.0 * f[k]) * (1.0 - f[k]));  // n_k alpha_k, betaAFOutlier.R:408-410
-        }
-        int v = 0;
-#pragma unroll
-        for (int i = 0; i < NP; ++i)
-#pragma unroll
-            for (int j = i + 1; j < NP; ++j) {
-                const bool counted = ok[i] && ok[j];
-                const double npool = nd[i] + nd[j];
-                const double p4 = n4[i] * nd[j];                // 4 n1 n2
-                const double q = recip((npool - 1.0) * p4);
-                const double t = (na[i] + na[j]) * q;
-                const double b = t * p4;
-                const double d = f[i] - f[j];
-                const double a = d * d - t * npool;
-                const double ab = a + b;
-                acc[v] = acc[v] + (counted ? a : 0.0);
-                acc[P + v] = acc[P + v] + (counted ? ab : 0.0);
-                cnt[v] += (uint32_t)__popcll(__ballot(counted));
-                ++v;
-            }
-    }
-};
-
-// Hudson's estimator as a ratio of averages (Hudson, Slatkin & Maddison 1992; Bhatia et al. 2013, eq. 10), the definition of
-// pgt_fst_hudson_pops_reduce_dev in include/pgtwin.h: acc[v] += (p1 - p2)^2 - h_1 - h_2 with h_k = p_k (1 - p_k) / (2 n_k - 1),
-// acc[P + v] += p1 (1 - p2) + p2 (1 - p1) — dxy_site_pred's roundings (pgt_kernels.hip), so a pair's denominator IS its dxy.
-// Every operation is rounded on its own.  The only division is per population and site (pi_site's divisor 2 n - 1: odd, never
-// 0), not per pair; an uncounted site (n_k <= 0: a negative divisor; any frequency) is selected away, never multiplied.
-struct Hudson {
-    template <int NP, class C>
-    static __device__ __forceinline__ void site(double *acc, uint32_t *cnt, const double *f, const C &c) {
-        constexpr int P = pair_count(NP);
-        double om[NP], h[NP];
-        bool ok[NP];
-#pragma unroll
-        for (int k = 0; k < NP; ++k) {
-            ok[k] = c.ok(k);
-            om[k] = __dsub_rn(1.0, f[k]);
-            const double m = __dsub_rn(__dmul_rn(2.0, (double)c.n(k)), 1.0);  // haploid sample size minus one
-            h[k] = __ddiv_rn(__dmul_rn(f[k], om[k]), m);
-        }
-        int v = 0;
-#pragma unroll
-        for (int i = 0; i < NP; ++i)
-#pragma unroll
-            for (int j = i + 1; j < NP; ++j) {
-                const bool counted = ok[i] && ok[j];
-                const double d = __dsub_rn(f[i], f[j]);
-                const double num = __dsub_rn(__dsub_rn(__dmul_rn(d, d), h[i]), h[j]);
-                const double den = __dadd_rn(__dmul_rn(f[i], om[j]), __dmul_rn(f[j], om[i]));
-                acc[v] = acc[v] + (counted ? num : 0.0);
-                acc[P + v] = acc[P + v] + (counted ? den : 0.0);
-                cnt[v] += (uint32_t)__popcll(__ballot(counted));
-                ++v;
-            }
-    }
-};
-
+// The estimator is a compile-time tag with a static per-site function (WeirCockerham, Hudson: pgt_fst_site.h, where the trio
+// statistic of pgt_pbs_pops_kernels.hip finds the same arithmetic): the walk knows only that a pair keeps two sums (acc[v],
+// acc[P + v]) and a count (cnt[v]).
 // Two statistics that share everything but `site` (the estimator's)
 template <class Est>
 struct FstPops : Est {

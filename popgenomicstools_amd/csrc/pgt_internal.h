@@ -317,6 +317,47 @@ int launch_f3_pops(const uint32_t *pos, const double *const *freq, const int32_t
                    uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_f3_row *out, pgt_f3_total *tot,
                    void *tree, const LaunchEnv &e);
 
+// pgt_pbs_pops_kernels.hip: the population branch statistic of ALL trios, every population of a trio as the focal one, in two
+// passes of the walk (three numerators, then three denominators per trio) and a finishing kernel.  A pass writes scratch rows
+// and scratch totals; the workspace holds the tree of one pass (pgt_f3_pops_reduce_dev's: 3 T doubles and T u32 per node,
+// reused by the second pass), then the scratch rows of the two passes (T * n_win each), then their scratch totals (T each),
+// every part padded to 256 bytes.
+struct PbsPassRow {  // 40 bytes
+    uint32_t start, end, mid, n;
+    double s[3];  // the pass's sums of the pairs (i,j), (i,k), (j,k)
+};
+struct PbsPassTotal {  // 40 bytes
+    double s[3];
+    uint64_t neff, nskip;
+};
+struct PbsWork {
+    uint32_t n_trios = 0;
+    size_t tree_bytes = 0;       // the tree at offset 0
+    size_t rows[2] = {0, 0};     // byte offsets of the passes' scratch rows ...
+    size_t tot[2] = {0, 0};      // ... and scratch totals
+    size_t bytes = 0;
+};
+// 3 <= n_pops <= 6 (checked by the caller)
+inline PbsWork pbs_work(uint32_t n_pops, uint64_t n_sites, uint64_t n_win) {
+    PbsWork w;
+    auto pad = [](size_t b) { return ((b + 255) / 256) * 256; };
+    w.n_trios = n_pops * (n_pops - 1) * (n_pops - 2) / 6;
+    w.tree_bytes = pops_tree_view(tree_layout(PGT_STAT_FST, n_sites), (int)w.n_trios, 3, nullptr, 0).bytes;
+    const size_t row_bytes = pad((size_t)w.n_trios * n_win * sizeof(PbsPassRow)), tot_bytes = pad((size_t)w.n_trios * sizeof(PbsPassTotal));
+    w.rows[0] = pad(w.tree_bytes);
+    w.rows[1] = w.rows[0] + row_bytes;
+    w.tot[0] = w.rows[1] + row_bytes;
+    w.tot[1] = w.tot[0] + tot_bytes;
+    w.bytes = w.tot[1] + tot_bytes;
+    return w;
+}
+// tot = C(n_pops, 3) device totals or NULL; 3 <= n_pops <= 6, minind >= 1, and n_win > 0 or tot (checked by the caller);
+// out = one table of n_win rows per trio, in lexicographic trio order; work = pbs_work(..).bytes; the estimator names the
+// per-site values of a pair (pgt_fst_site.h), as in launch_fst_pops
+int launch_pbs_pops(const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
+                    uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_pbs_row *out, pgt_pbs_total *tot,
+                    void *work, const LaunchEnv &e, FstPopsEstimator estimator);
+
 // pgt_kernels.hip: pi per population, 1 <= n_pops <= 8 and minind >= 1 (checked by the caller); out = n_pops tables of
 // n_win rows, tot = n_pops device totals or NULL; tree = n_pops trees of tree_layout(PGT_STAT_DXY, n).bytes each
 int launch_pi_pops(const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
@@ -371,6 +412,7 @@ int init_fst_pops_kernels(std::string *err);  // pgt_fst_pops_kernels.hip
 int init_dstat_pops_kernels(std::string *err);  // pgt_dstat_pops_kernels.hip
 int init_fd_pops_kernels(std::string *err);     // pgt_fd_pops_kernels.hip
 int init_f3_pops_kernels(std::string *err);     // pgt_f3_pops_kernels.hip
+int init_pbs_pops_kernels(std::string *err);    // pgt_pbs_pops_kernels.hip
 
 // thread-local message for the ctx-less entry points
 void set_global_error(const std::string &msg);

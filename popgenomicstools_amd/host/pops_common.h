@@ -1,4 +1,4 @@
-// pops_common.h — the five K-population hosts (dxyWindowPops, fstWindowPops, piWindowPops, dstatWindowPops, f3WindowPops) are one
+// pops_common.h — the K-population hosts (dxyWindowPops, fstWindowPops, piWindowPops, dstatWindowPops, f3WindowPops, pbsWindowPops) are one
 // program, run_pops_tool<Tool>: the command line (dxyWindow's options, the tool's own, -out PREFIX, the tool's number of MAF
 // files), from the opened files to the aligned columns and the window table on the device (load_pops — open, parse on the host or
 // the device, the resident-size refusals, chromosome ids, pgt_align_segments, upload, pgt_sites_align, pgt_gather_dev, the runs of
@@ -10,7 +10,8 @@
 //     own(option, value, argc, argv)                  an option of this tool alone: taken (or refused by die()) -> true
 //     arity, outgroup                                 its tables: all pairs (2), each population (1), all trios (3) of the K files —
 //                                                     of the K-1 before the last with an outgroup
-//     Row, Total, ext, global_ext, row_bytes, tree_bytes, reduce_dev    the reduction and its files
+//     Row, Total, ext, global_ext, row_bytes, tree_bytes, reduce_dev    the reduction and its files; tree_bytes(K, sites), or
+//                                                     (K, sites, windows) where the workspace holds more than the tree
 //     line(row, sites of the window), total(total)    the numbers of a row behind `chr`, of a PREFIX.global line behind the indices
 //     window_hints                                    the window table's hints are set before the reduction (piWindowPops alone)
 //     more(run, rows on the device)                   further device work on the same columns: pops_jackknife, a second pops_pass
@@ -20,6 +21,7 @@
 #include <cstddef>
 #include <functional>
 #include <memory>
+#include <type_traits>
 
 #include "dxy_common.h"
 
@@ -370,7 +372,7 @@ inline std::string tuple_text(const PopsIndex &ix, const char *before, const cha
 // a row: `chr start end [mid]`, its doubles, `n nskip`; a genome-wide line: the table's indices, its doubles, `neff nskip`
 struct PopsLine {
     uint32_t lead[3];
-    double g[5];
+    double g[6];
     int n_lead = 0, n_g = 0;
     uint64_t n, nskip;
     PopsLine(std::initializer_list<uint32_t> lead_, std::initializer_list<double> g_, uint64_t n_, uint64_t nskip_) : n(n_), nskip(nskip_) {
@@ -508,7 +510,10 @@ int run_pops_tool(int argc, char **argv) {
     const PopsSites s = load_pops(Tool::name, args, timer, device);
     pgt_ctx *ctx = s.ctx;
     PopsRun run{args, s, pops_tuples(Tool::arity, args.K - (Tool::outgroup ? 1 : 0))};
-    run.tree_bytes = Tool::tree_bytes((uint32_t)args.K, s.n_sites);
+    if constexpr (std::is_invocable_v<decltype(Tool::tree_bytes), uint32_t, uint64_t, uint64_t>)
+        run.tree_bytes = Tool::tree_bytes((uint32_t)args.K, s.n_sites, s.win.size());  // the table is known here
+    else
+        run.tree_bytes = Tool::tree_bytes((uint32_t)args.K, s.n_sites);
     check(pgt_dev_alloc(ctx, run.tree_bytes, &run.tree), ctx);
     if (Tool::window_hints && !s.win.empty()) {  // the table is known here
         uint64_t max_window = 0, typical = 0, step = 0;

@@ -20,7 +20,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import (DSTAT_JACK_DTYPE, DSTAT_ROW_DTYPE, DSTAT_TOTAL_DTYPE, DXY_ROW_DTYPE, DXY_TOTAL_DTYPE, EXT_ROW_DTYPE, F3_JACK_DTYPE, F3_ROW_DTYPE, F3_TOTAL_DTYPE, FD_ROW_DTYPE, FD_TOTAL_DTYPE, FST_ROW_DTYPE, FST_TOTAL_DTYPE, HET_ROW_DTYPE, PGT_EXT_IHS,
+from ._lib import (DSTAT_JACK_DTYPE, DSTAT_ROW_DTYPE, DSTAT_TOTAL_DTYPE, DXY_ROW_DTYPE, DXY_TOTAL_DTYPE, EXT_ROW_DTYPE, F3_JACK_DTYPE, F3_ROW_DTYPE, F3_TOTAL_DTYPE, FD_ROW_DTYPE, FD_TOTAL_DTYPE, FST_ROW_DTYPE, FST_TOTAL_DTYPE, HET_ROW_DTYPE, PBS_ROW_DTYPE, PBS_TOTAL_DTYPE, PGT_EXT_IHS,
                    PGT_EXT_XP_MAX, PGT_EXT_XP_MIN, PGT_STAT_DXY, PGT_STAT_EXT, PGT_STAT_FST, PGT_STAT_HET,
                    SEG_DTYPE, SHARD_DTYPE, WIN_DTYPE, PgtError, check)
 
@@ -289,6 +289,9 @@ _FST_HUDSON_POPS = _PopsStat("fst_hudson", 2, True, FST_ROW_DTYPE, FST_TOTAL_DTY
 _DSTAT_POPS = _PopsStat("dstat", 4, False, DSTAT_ROW_DTYPE, DSTAT_TOTAL_DTYPE, max_pops=7, per_trio=True)
 _FD_POPS = _PopsStat("fd", 4, False, FD_ROW_DTYPE, FD_TOTAL_DTYPE, max_pops=7, per_trio=True)
 _F3_POPS = _PopsStat("f3", 3, False, F3_ROW_DTYPE, F3_TOTAL_DTYPE, max_pops=6, all_trios=True)
+_PBS_POPS = _PopsStat("pbs", 3, False, PBS_ROW_DTYPE, PBS_TOTAL_DTYPE, max_pops=6, all_trios=True)
+_PBS_HUDSON_POPS = _PopsStat("pbs_hudson", 3, False, PBS_ROW_DTYPE, PBS_TOTAL_DTYPE, max_pops=6, all_trios=True)
+_PBS_ESTIMATORS = {"wc": _PBS_POPS, "hudson": _PBS_HUDSON_POPS}  # pbs_window_pops(estimator=...), Context.pbs_pops_reduce*(estimator=...)
 _FST_ESTIMATORS = {"wc": _FST_POPS, "hudson": _FST_HUDSON_POPS}  # fst_window_pops(estimator=...)
 
 
@@ -446,6 +449,14 @@ class Context:
         (pgt_f3_pops_reduce).  A row carries the three SUMS f3_i, f3_j, f3_k over its counted sites (target_order) and their
         number n; f3 of the window is sum / n."""
         return self._pops_reduce(_F3_POPS, pos, freqs, ninds, minind, win)
+
+    def pbs_pops_reduce(self, pos, freqs, ninds, minind, win, estimator="wc"):
+        """Population-branch-statistic rows of ALL trios i<j<k of len(freqs) populations (all_trio_order), every population of a
+        trio as the focal one, from 3 ... 6 per-population numpy (freq, nInd) columns: -> (rows[n_trios, n_win], totals[n_trios])
+        (pgt_pbs_pops_reduce; estimator="hudson": pgt_pbs_hudson_pops_reduce).  A row carries pbs_i, pbs_j, pbs_k, the six SUMS
+        num_xy / den_xy of the trio's pairs over the sites counted for the whole trio, and their number n; fst_xy = num_xy / den_xy.
+        Nothing is clamped: inf and nan are the IEEE results of FST = 1."""
+        return self._pops_reduce(_pbs_estimator("pbs_pops_reduce", estimator), pos, freqs, ninds, minind, win)
 
     def _jackknife(self, name: str, row: np.dtype, jack: np.dtype, rows) -> np.ndarray:
         """The numpy form of a block jackknife (pgt_<name>_jackknife) -> [n_trios, 3] of `jack`."""
@@ -748,8 +759,9 @@ class Context:
             self._stream(stream)))
         return out, tree
 
-    def _pops_reduce_dev(self, st: _PopsStat, pos, freqs, ninds, minind, win, out, tot, tree, stream):
-        """The device form of a K-population statistic (pgt_<name>_pops_reduce_dev) -> (out, tot, tree)."""
+    def _pops_reduce_dev(self, st: _PopsStat, pos, freqs, ninds, minind, win, out, tot, tree, stream, work_bytes=None, work_word="tree"):
+        """The device form of a K-population statistic (pgt_<name>_pops_reduce_dev) -> (out, tot, tree).  work_bytes(n_pops, n,
+        n_win): the size of a workspace that holds more than the tree, named work_word in the messages."""
         import torch
         who = f"{st.name}_pops_reduce_dev"
         n_pops = len(freqs)
@@ -757,7 +769,7 @@ class Context:
         n = freqs[0].numel()
         tables = st.tables(n_pops)
         n_win = win.numel() // WIN_DTYPE.itemsize
-        tb = int(getattr(self._lib, f"pgt_{st.name}_pops_tree_bytes")(n_pops, n))
+        tb = int(work_bytes(n_pops, n, n_win)) if work_bytes else int(getattr(self._lib, f"pgt_{st.name}_pops_tree_bytes")(n_pops, n))
         dev = pos.device
         if tree is None:
             tree = torch.empty(tb, dtype=torch.uint8, device=dev)
@@ -769,7 +781,7 @@ class Context:
             tot = None
         self._same_len(who, n, pos, *freqs, *ninds)
         self._room(f"{who}: out", out, tables * n_win * st.row.itemsize)
-        self._room(f"{who}: tree", tree, tb)
+        self._room(f"{who}: {work_word}", tree, tb)
         if tot is not None:
             self._room(f"{who}: tot", tot, tables * st.total.itemsize)
         pf = (C.c_void_p * n_pops)(*[self._col(t, torch.float64, f"freqs[{k}]") for k, t in enumerate(freqs)])
@@ -779,7 +791,7 @@ class Context:
             self._dev(win, torch.uint8, "win") if n_win else None, n_win,
             self._dev(out, torch.uint8, "out") if n_win else None, out.numel(),
             self._dev(tot, torch.uint8, "tot") if tot is not None else None,
-            self._dev(tree, torch.uint8, "tree"), tree.numel(), self._stream(stream)))
+            self._dev(tree, torch.uint8, work_word), tree.numel(), self._stream(stream)))
         return out, tot, tree
 
     @staticmethod
@@ -888,6 +900,20 @@ class Context:
         tot: None = a fresh buffer of n_trios totals is allocated and filled; False = no genome-wide lines.
         Returns (out, tot, tree).  Asynchronous on `stream`."""
         return self._pops_reduce_dev(_F3_POPS, pos, freqs, ninds, minind, win, out, tot, tree, stream)
+
+    @staticmethod
+    def pbs_pops_work_bytes(n_pops: int, n_sites: int, n_win: int) -> int:
+        return int(_lib.load().pgt_pbs_pops_work_bytes(int(n_pops), int(n_sites), int(n_win)))
+
+    def pbs_pops_reduce_dev(self, pos, freqs, ninds, minind, win, estimator="wc", out=None, tot=None, work=None, stream=None):
+        """Population-branch-statistic rows of ALL trios of len(freqs) populations (trio-major, all_trio_order), every population
+        of a trio as the focal one, from 3 ... 6 populations' own (freq, nInd) columns (pgt_pbs_pops_reduce_dev; estimator="hudson":
+        pgt_pbs_hudson_pops_reduce_dev).  freqs: float64 CUDA tensors, ninds: int32 CUDA tensors.  Rows of PBS_ROW_DTYPE, totals of
+        PBS_TOTAL_DTYPE.  work: pbs_pops_work_bytes(n_pops, n, n_win) bytes (the tree of one pass and the scratch rows of both).
+        tot: None = a fresh buffer of n_trios totals is allocated and filled; False = no genome-wide lines.
+        Returns (out, tot, work).  Asynchronous on `stream`: one chain of kernels."""
+        st = _pbs_estimator("pbs_pops_reduce_dev", estimator)
+        return self._pops_reduce_dev(st, pos, freqs, ninds, minind, win, out, tot, work, stream, self._lib.pgt_pbs_pops_work_bytes, "work")
 
     @staticmethod
     def f3_jackknife_work_bytes(n_trios: int, n_win: int) -> int:
@@ -1361,6 +1387,29 @@ def f3_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: i
     res = _results_by_pair(len(freqs), win, rows, tot, skip_missing, "n", keys=keys)
     res["jackknife"] = {ijk: jack[t] for t, ijk in enumerate(keys)}
     return res
+
+
+def _pbs_estimator(who: str, estimator) -> _PopsStat:
+    st = _PBS_ESTIMATORS.get(estimator) if isinstance(estimator, str) else None
+    if st is None:
+        raise PgtError(_lib.PGT_EARG, f'{who}: estimator must be "wc" or "hudson", not {estimator!r}')
+    return st
+
+
+def pbs_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: int = 1, fixedsite: int = 0,
+                    chr_len=None, skip_missing: int = 0, estimator: str = "wc", ctx: Context | None = None) -> dict:
+    """Windowed population branch statistic (Yi et al. 2010) for ALL trios of len(freqs) already synchronised populations
+    (3 ... 6), every population of a trio as the focal one: {(i, j, k): WindowResult} in all_trio_order, with rows of (start,
+    end, mid, n, pbs_i, pbs_j, pbs_k, num_ij, num_ik, num_jk, den_ij, den_ik, den_jk) and the genome-wide line as total.  The
+    sums are those of the FST estimator ("wc" or "hudson", as fst_window_pops) over the sites where ALL THREE populations have
+    minind individuals — not the pairs' own site sets, which is what fst_window_pops reports; fst_xy = num_xy / den_xy.
+    Nothing is clamped: a negative FST gives a negative branch, FST = 1 gives inf, inf - inf gives nan.
+    Window arguments and their errors are those of dxy_window_pops; -skip_missing drops a trio's rows without counted sites
+    from that trio's result only.  The definition is pgt_pbs_pops_reduce_dev's (include/pgtwin.h).
+    Not computed: PBSn1, truncation of negative FST, a block jackknife, user-chosen trio lists."""
+    st = _pbs_estimator("pbs_window_pops", estimator)
+    win, rows, tot = _window_pops(st, chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx)
+    return _results_by_pair(len(freqs), win, rows, tot, skip_missing, "n", keys=all_trio_order(len(freqs)))
 
 
 def pi_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: int = 1, fixedsite: int = 0,
