@@ -33,7 +33,7 @@
  *     has no counts: every site is counted; a NaN there stays in the rows of the pairs with that population.
  *   - genotypes: any int8 (non-missing is g >= 0, heterozygous g == 1, hetWindow.cpp:78-80); counts (n1, n2, nind[k]) and minind:
  *     any int32, compared as signed integers (dxyWindow.cpp:381).
- *   - the K-population entry points (pgt_dxy_pops / fst_pops / fst_hudson_pops / pi_pops / dstat_pops / fd_pops / f3_pops / pbs_pops / pbs_hudson_pops _reduce_dev;
+ *   - the K-population entry points (pgt_dxy_pops / fst_pops / fst_hudson_pops / pi_pops / dstat_pops / fd_pops / f3_pops / pbs_pops / pbs_hudson_pops / f4_pops _reduce_dev;
  *     tests/test_special_values_pops.py): a NaN or an infinity in ONE population's frequency at a COUNTED site reaches exactly the
  *     rows (and genome-wide lines) of the items — pairs, trios, the population itself — that hold that population, and of them
  *     exactly the windows that hold the site, with the value the per-site definition gives on the IEEE operands, every operation
@@ -73,7 +73,9 @@ extern "C" {
  * Still 6: pgt_f3_row, pgt_f3_total, pgt_f3_jack, pgt_f3_pops_tree_bytes / pgt_f3_pops_reduce_dev / pgt_f3_pops_reduce and
  *          pgt_f3_jackknife_work_bytes / pgt_f3_jackknife_dev / pgt_f3_jackknife added (additive as well).
  * Still 6: pgt_pbs_row, pgt_pbs_total, pgt_pbs_pops_work_bytes / pgt_pbs_pops_reduce_dev / pgt_pbs_hudson_pops_reduce_dev /
- *          pgt_pbs_pops_reduce / pgt_pbs_hudson_pops_reduce added (additive as well). */
+ *          pgt_pbs_pops_reduce / pgt_pbs_hudson_pops_reduce added (additive as well).
+ * Still 6: pgt_f4_row, pgt_f4_total, pgt_f4_jack, pgt_f4_pops_tree_bytes / pgt_f4_pops_reduce_dev / pgt_f4_pops_reduce and
+ *          pgt_f4_jackknife_work_bytes / pgt_f4_jackknife_dev / pgt_f4_jackknife added (additive as well). */
 #define PGT_ABI_VERSION 6
 
 enum {
@@ -172,6 +174,24 @@ typedef struct { /* block jackknife of one trio and target: pgt_f3_jackknife_dev
     uint64_t n_sites;          /* counted sites of the used blocks */
     uint32_t n_blocks, pad_;   /* used blocks (rows with n > 0) */
 } pgt_f3_jack;
+
+typedef struct { /* f4 window row of one quartet (i, j, k, l) in its three pairings: pgt_f4_pops_reduce_dev (48 bytes) */
+    uint32_t start, end, mid, n;
+    double reserved_;                    /* +0.0 */
+    double f4_ij_kl, f4_ik_jl, f4_il_jk; /* the three window SUMS, full precision, at the offsets of pgt_f3_row's f3_i / f3_j /
+                                            f3_k: sum / n is f4(i,j; k,l), f4(i,k; j,l), f4(i,l; j,k) of the window (the caller divides) */
+} pgt_f4_row;
+
+typedef struct { /* the three sums of one quartet over all its counted sites (40 bytes) */
+    double f4_ij_kl, f4_ik_jl, f4_il_jk;
+    uint64_t neff, nskip;
+} pgt_f4_total;
+
+typedef struct { /* block jackknife of one quartet and pairing: pgt_f4_jackknife_dev (48 bytes, the layout of pgt_f3_jack) */
+    double f4, f4_jack, se, z; /* f4 of all used blocks, its jackknife estimate, standard error, f4_jack / se */
+    uint64_t n_sites;          /* counted sites of the used blocks */
+    uint32_t n_blocks, pad_;   /* used blocks (rows with n > 0) */
+} pgt_f4_jack;
 
 typedef struct { /* population-branch-statistic window row of one trio (i, j, k): pgt_pbs_pops_reduce_dev (88 bytes) */
     uint32_t start, end, mid, n;    /* offsets 0, 4, 8, 12 */
@@ -659,6 +679,86 @@ int pgt_f3_jackknife_dev(pgt_ctx *ctx, const pgt_f3_row *rows, uint64_t n_win, u
                          pgt_f3_jack *out /* 3 * n_trios, item-major u = 3t + c */, size_t out_bytes,
                          void *work, size_t work_bytes, void *stream);
 int pgt_f3_jackknife(pgt_ctx *ctx, const pgt_f3_row *rows, uint64_t n_win, uint32_t n_trios, pgt_f3_jack *out);
+
+/* ---- f4 of ALL quartets of the populations, every quartet in its three pairings ------------------------------------------ */
+/* The 4-population statistic f4(A, B; C, D) = E[(a - b)(c - d)] (Reich et al. 2009; Patterson et al. 2012; treemix's fourpop,
+ * ADMIXTOOLS' qpDstat in f4mode), the treeness test: its expectation is 0 when ((A,B),(C,D)) is the tree.  It needs no
+ * designated outgroup (pgt_dstat_pops_reduce_dev does) and has no finite-sample bias term (f3 has).  From each population's own
+ * (freq, nInd) columns — the input of pgt_f3_pops_reduce_dev — over ONE position column and ONE window table, in one pass
+ * (12 B/site/population).  It has NO counterpart in the reference: the definition below is the contract.
+ * n_pops = K populations, 4 <= K <= 6.  ALL populations are equal.  A quartet is (i, j, k, l) with i < j < k < l < K; quartets
+ * are numbered in lexicographic order (0,1,2,3),(0,1,2,4),..,(0,1,3,4),..; there are Q = C(K, 4) of them: 1 / 5 / 15 at
+ * K = 4 / 5 / 6.  For quartet (i, j, k, l) and site s:
+ *   counting   nind_x[s] >= minind for x = i, j, k and l (signed int32 compare; minind >= 1 required, PGT_EARG otherwise, as
+ *              pgt_dstat_pops_reduce_dev refuses it); a site that is not counted is selected away, never multiplied (its
+ *              frequencies may be NaN, its counts 0 or negative).  The counts enter through this predicate ONLY.
+ *   per site   p_x = freq_x[s]; every operation rounded on its own, no contraction, in exactly this grouping:
+ *                  d_ab = p_a - p_b                              per pair a < b, shared by every quartet that holds the pair
+ *                  s0 = d_ij * d_kl                              f4(i, j; k, l)
+ *                  s1 = d_ik * d_jl                              f4(i, k; j, l)
+ *                  s2 = d_il * d_jk                              f4(i, l; j, k)
+ *              No division, no bias term.  In real arithmetic s0 - s1 + s2 = 0; the three are stored all the same, so that the
+ *              row has the layout and the three items per row of pgt_f3_row.  The three values do not depend on which allele
+ *              the columns report, provided all populations report the same one (with frequencies that are multiples of
+ *              2^-10, bit for bit).  With an outgroup O as the last population, f4(i, j; k, O) is the numerator of Patterson's D:
+ *              baba - abba of pgt_dstat_pops_reduce_dev's trio (i, j, k) = (p_i - p_j)(p_k - p_O).
+ *   row        pgt_f4_row (48 bytes): f4_ij_kl / f4_ik_jl / f4_il_jk = the three SUMS of s0 / s1 / s2 over the window's counted
+ *              sites, each from +0.0; n = their number (nskip = (hi - lo) - n); start / end / mid as pgt_dstat_row's are filled
+ *              (PGT_WIN_COORDS honoured); reserved_ = +0.0.  The means are NOT formed: f4 of the window is sum / n, the
+ *              caller's division.  The sums sit at the offsets of pgt_f3_row's f3_i / f3_j / f3_k.
+ *   out        Q * n_win rows, quartet-major: out[q * n_win + w]
+ *   tot        DEVICE array of Q pgt_f4_total (40 bytes: the same three sums over all counted sites, neff, nskip), or NULL;
+ *              n_win == 0 with tot: the global-only form
+ *   tree       pgt_f4_pops_tree_bytes(n_pops, n) bytes (0 for n_pops outside 4 ... 6): a node is 3 Q doubles (s0 of quartet
+ *              0 .. Q-1, then s1, then s2) and Q u32.    4 <= n_pops <= 6, n < 2^32.
+ * K = 7 (35 quartets, 105 sums per node) is not offered, for the reason pgt_f3_pops_reduce_dev stops at 6.
+ * A one-site window carries exactly the bits of s0, s1 and s2 above.  Arguments, alignment, refusals (PGT_EARG; messages begin
+ * "pgt_f4_pops_reduce: " and name their argument; a refused call launches nothing and writes nothing), graph capture and the
+ * hints: those of pgt_f3_pops_reduce_dev (asynchronous on `stream`, no allocation, no attribute call; pgt_set_max_window
+ * honoured, pgt_set_window_step ignored).  Quartet isolation: the rows of a quartet are a function, bit for bit, of its own four
+ * populations' columns and the window alone — not of the other populations, of K, or of the other rows of the table.  Sums are
+ * added in a fixed order that depends on the site index and the window alone (bitwise reproducible).  The site terms have both
+ * signs: against an exact evaluation a sum stays within 1e-9 * A + 1e-12, A the window's sum of |product| (of the same pairing);
+ * no bound relative to the value is given.  "Values the columns admit" above holds as for the other K-population calls
+ * (tests/test_special_values_f4.py).  Held to this definition, to an exact-rational fixture (tests/golden/f4_exact.json) and to
+ * a NumPy model (tests/f4_pops_model.py).  f4-ratio admixture proportions, user-chosen quartet lists and K = 7 are not
+ * computed; standard errors and Z come from pgt_f4_jackknife_dev below.
+ * Host-buffer form: columns (host arrays of n_pops HOST pointers), table, rows and the Q totals in host memory. */
+size_t pgt_f4_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites);
+int pgt_f4_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq,
+                           const int32_t *const *nind, uint32_t n_pops, uint64_t n, int minind,
+                           const pgt_win *win, uint64_t n_win, pgt_f4_row *out, size_t out_bytes,
+                           pgt_f4_total *tot, void *tree, size_t tree_bytes, void *stream);
+int pgt_f4_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq,
+                       const int32_t *const *nind, uint32_t n_pops, uint64_t n, int minind,
+                       const pgt_win *win, uint64_t n_win, pgt_f4_row *out, pgt_f4_total *tot);
+
+/* ---- block-jackknife standard error and Z of f4, all quartets and pairings ---------------------------------------------- */
+/* The block jackknife of the MEAN of pgt_f3_jackknife_dev above — the same estimator, arithmetic, plan, workspace, phases and
+ * order of every addition — over the window rows pgt_f4_pops_reduce_dev wrote: the same bytes viewed as pgt_f3_row and given
+ * to pgt_f3_jackknife_dev yield the same bits.
+ *   rows     DEVICE pointer to the n_quartets x n_win quartet-major table, 16-byte aligned; every window is one block; the
+ *            caller guarantees that the windows are DISJOINT.  Only n and the three sums of a row are read.
+ *   items    quartet q has three items u = 3 q + c, c = 0 / 1 / 2 the pairing (ij;kl) / (ik;jl) / (il;jk); x_j = sum c of
+ *            block j's row
+ *   blocks, per item: as pgt_f3_jackknife_dev (a row that is not used is selected away, never added: its sums may be NaN)
+ *   out      pgt_f4_jack per item, item-major: f4 = theta, f4_jack = theta_J, se = sqrt(sigma^2),
+ *            z = se > 0 ? theta_J / se : NaN, n_blocks = g, n_sites = n, pad_ = 0.
+ *            g < 2: f4_jack = f4, se = z = NaN.  g == 0 (n_win == 0 included): f4 = f4_jack = 0, se = z = NaN.
+ *   work     DEVICE workspace of pgt_f4_jackknife_work_bytes(n_quartets, n_win) bytes (0 for n_quartets outside 1 ... 15): the
+ *            value pgt_dstat_jackknife_work_bytes gives, 16-byte aligned.  Every byte of it that is read is written earlier in
+ *            the same call.
+ * 1 <= n_quartets <= 15.  Bitwise reproducible; an item's outputs are a function, bit for bit, of its own quartet's rows alone:
+ * not of n_quartets, not of the other quartets' rows.  Against an exact evaluation f4, f4_jack and se stay within 1e-9
+ * relative + 1e-12 (tests/f3_jack_model.py).  |Z| above about 3 rejects the tree ((a,b),(c,d)) of the pairing.
+ * Refusals (PGT_EARG, messages begin "pgt_f4_jackknife: " and name their argument; nothing is launched, nothing written): those
+ * of pgt_dstat_jackknife_dev.  Asynchronous on `stream`; no allocation and no attribute call: it can be captured into a graph.
+ * Host-buffer form: rows and out in host memory; synchronous. */
+size_t pgt_f4_jackknife_work_bytes(uint32_t n_quartets, uint64_t n_win);
+int pgt_f4_jackknife_dev(pgt_ctx *ctx, const pgt_f4_row *rows, uint64_t n_win, uint32_t n_quartets,
+                         pgt_f4_jack *out /* 3 * n_quartets, item-major u = 3q + c */, size_t out_bytes,
+                         void *work, size_t work_bytes, void *stream);
+int pgt_f4_jackknife(pgt_ctx *ctx, const pgt_f4_row *rows, uint64_t n_win, uint32_t n_quartets, pgt_f4_jack *out);
 
 /* ---- the population branch statistic (PBS) of ALL trios, every population of a trio as the focal one -------------------- */
 /* PBS (Yi et al. 2010), the windowed selection scan for a focal population against two others, from each population's own

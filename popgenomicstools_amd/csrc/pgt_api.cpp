@@ -454,7 +454,8 @@ pgt_ctx *pgt_open(int device) {
     std::string init_err;
     if (init_kernels(&init_err) != PGT_OK || init_af_kernels(&init_err) != PGT_OK || init_dxy_pops_kernels(&init_err) != PGT_OK ||
         init_fst_pops_kernels(&init_err) != PGT_OK || init_dstat_pops_kernels(&init_err) != PGT_OK ||
-        init_fd_pops_kernels(&init_err) != PGT_OK || init_f3_pops_kernels(&init_err) != PGT_OK || init_pbs_pops_kernels(&init_err) != PGT_OK) {
+        init_fd_pops_kernels(&init_err) != PGT_OK || init_f3_pops_kernels(&init_err) != PGT_OK || init_pbs_pops_kernels(&init_err) != PGT_OK ||
+        init_f4_pops_kernels(&init_err) != PGT_OK) {
         set_global_error("pgt_open: " + init_err);
         return nullptr;
     }
@@ -765,30 +766,56 @@ int pgt_pbs_hudson_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const doub
                            pos, freq, nind, n_pops, n, minind, win, n_win, out, out_bytes, tot, work, work_bytes, stream);
 }
 
+// f4 of ALL quartets of the populations, each quartet in its three pairings: one more PopsStat; three sums per quartet
+static uint64_t pops_all_quartets(uint32_t n_pops) { return (uint64_t)n_pops * (n_pops - 1) * (n_pops - 2) * (n_pops - 3) / 24; }
+// minind >= 1: what pgt_dstat_pops_reduce_dev accepts (the counts decide the predicate alone)
+static const PopsStat kF4Pops = {"pgt_f4_pops_reduce", 4, true, pops_all_quartets, "n_quartets", sizeof(pgt_f4_row), pgt_f4_pops_tree_bytes, 6};
+size_t pgt_f4_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites) { return pops_tree_bytes(kF4Pops, 3, n_pops, n_sites); }
+static_assert(sizeof(pgt_f4_row) == 48 && offsetof(pgt_f4_row, reserved_) == 16 && offsetof(pgt_f4_row, f4_ij_kl) == offsetof(pgt_f3_row, f3_i) &&
+              offsetof(pgt_f4_row, f4_ik_jl) == offsetof(pgt_f3_row, f3_j) && offsetof(pgt_f4_row, f4_il_jk) == offsetof(pgt_f3_row, f3_k) &&
+              sizeof(pgt_f4_total) == 40 && offsetof(pgt_f4_total, neff) == 24 && sizeof(pgt_f4_jack) == 48, "the documented layouts");
+
+int pgt_f4_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind,
+                           uint32_t n_pops, uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_f4_row *out,
+                           size_t out_bytes, pgt_f4_total *tot, void *tree, size_t tree_bytes, void *stream) {
+    return pops_reduce_dev(ctx, kF4Pops, launch_f4_pops, pos, freq, nind, n_pops, n, minind, win, n_win, out, out_bytes, tot, tree, tree_bytes, stream);
+}
+
 // Block jackknife of the rows above: its own checks (no columns, no window table), the message prefix of both forms.
-// One text for the two estimators (D: pgt_dstat_jackknife; the mean of f3: pgt_f3_jackknife): rows and results of both are 48
-// bytes, so plan, workspace and every check are the same, under the entry's own prefix.
+// One text for the estimators (D: pgt_dstat_jackknife; the mean of f3: pgt_f3_jackknife; the mean of f4: pgt_f4_jackknife): rows
+// and results of all are 48 bytes, so plan, workspace and every check are the same, under the entry's own prefix, name of the
+// tables and largest number of them.
 size_t pgt_dstat_jackknife_work_bytes(uint32_t n_trios, uint64_t n_win) {
     if (n_trios < 1 || n_trios > kJackMaxTrios) return 0;
     return jack_work(n_trios, n_win).bytes;
 }
 size_t pgt_f3_jackknife_work_bytes(uint32_t n_trios, uint64_t n_win) { return pgt_dstat_jackknife_work_bytes(n_trios, n_win); }
+size_t pgt_f4_jackknife_work_bytes(uint32_t n_quartets, uint64_t n_win) {
+    return n_quartets <= kJackMaxQuartets ? pgt_dstat_jackknife_work_bytes(n_quartets, n_win) : 0;
+}
 
-static int jack_check_range(pgt_ctx *ctx, const std::string &who, uint32_t n_trios, uint64_t n_win) {
-    if (n_trios < 1 || n_trios > kJackMaxTrios)
-        return ctx_fail(ctx, PGT_EARG, who + "n_trios must be 1 ... " + std::to_string(kJackMaxTrios));
-    if (n_win > (UINT64_MAX / sizeof(pgt_dstat_row)) / n_trios) return ctx_fail(ctx, PGT_EARG, who + "n_trios * n_win overflows");
+enum JackEstimator { kJackD, kJackF3Mean, kJackF4Mean };
+static const char *jack_who(JackEstimator est) {
+    return est == kJackD ? "pgt_dstat_jackknife: " : (est == kJackF3Mean ? "pgt_f3_jackknife: " : "pgt_f4_jackknife: ");
+}
+static const char *jack_tables_word(JackEstimator est) { return est == kJackF4Mean ? "n_quartets" : "n_trios"; }
+static uint32_t jack_max_tables(JackEstimator est) { return est == kJackF4Mean ? kJackMaxQuartets : kJackMaxTrios; }
+static_assert(kJackMaxQuartets <= kJackMaxTrios, "jack_work is sized for up to kJackMaxTrios tables");
+
+static int jack_check_range(pgt_ctx *ctx, JackEstimator est, uint32_t n_trios, uint64_t n_win) {
+    const std::string who = jack_who(est), word = jack_tables_word(est);
+    if (n_trios < 1 || n_trios > jack_max_tables(est))
+        return ctx_fail(ctx, PGT_EARG, who + word + " must be 1 ... " + std::to_string(jack_max_tables(est)));
+    if (n_win > (UINT64_MAX / sizeof(pgt_dstat_row)) / n_trios) return ctx_fail(ctx, PGT_EARG, who + word + " * n_win overflows");
     return PGT_OK;
 }
 static_assert(sizeof(pgt_f3_row) == sizeof(pgt_dstat_row) && sizeof(pgt_f3_jack) == sizeof(pgt_dstat_jack), "one set of jackknife checks");
-
-enum JackEstimator { kJackD, kJackF3Mean };
-static const char *jack_who(JackEstimator est) { return est == kJackD ? "pgt_dstat_jackknife: " : "pgt_f3_jackknife: "; }
+static_assert(sizeof(pgt_f4_row) == sizeof(pgt_dstat_row) && sizeof(pgt_f4_jack) == sizeof(pgt_dstat_jack), "one set of jackknife checks");
 
 static int jackknife_dev(pgt_ctx *ctx, JackEstimator est, const void *rows, uint64_t n_win, uint32_t n_trios, void *out,
                          size_t out_bytes, void *work, size_t work_bytes, void *stream) {
     const std::string who = jack_who(est);
-    if (int rc = jack_check_range(ctx, who, n_trios, n_win)) return rc;
+    if (int rc = jack_check_range(ctx, est, n_trios, n_win)) return rc;
     if (n_win && !rows) return ctx_fail(ctx, PGT_EARG, who + "rows is NULL");
     if (!out) return ctx_fail(ctx, PGT_EARG, who + "out is NULL");
     if (!work) return ctx_fail(ctx, PGT_EARG, who + "work is NULL");
@@ -806,6 +833,8 @@ static int jackknife_dev(pgt_ctx *ctx, JackEstimator est, const void *rows, uint
         ctx->have_timing = true;
         ctx->timing_query_only = true;
     }
+    if (est == kJackF4Mean)
+        return launch_f4_jackknife(static_cast<const pgt_f4_row *>(rows), n_win, n_trios, static_cast<pgt_f4_jack *>(out), work, stream, q0, q1, &ctx->error);
     if (est == kJackF3Mean)
         return launch_f3_jackknife(static_cast<const pgt_f3_row *>(rows), n_win, n_trios, static_cast<pgt_f3_jack *>(out), work, stream, q0, q1, &ctx->error);
     return launch_dstat_jackknife(static_cast<const pgt_dstat_row *>(rows), n_win, n_trios, static_cast<pgt_dstat_jack *>(out), work, stream, q0, q1, &ctx->error);
@@ -822,6 +851,13 @@ int pgt_f3_jackknife_dev(pgt_ctx *ctx, const pgt_f3_row *rows, uint64_t n_win, u
                          size_t out_bytes, void *work, size_t work_bytes, void *stream) {
     PGT_USE_DEVICE(ctx);
     return jackknife_dev(ctx, kJackF3Mean, rows, n_win, n_trios, out, out_bytes, work, work_bytes, stream);
+}
+
+// out: 3 n_quartets items, u = 3 q + c with c the pairing (ij;kl) / (ik;jl) / (il;jk) of quartet q
+int pgt_f4_jackknife_dev(pgt_ctx *ctx, const pgt_f4_row *rows, uint64_t n_win, uint32_t n_quartets, pgt_f4_jack *out,
+                         size_t out_bytes, void *work, size_t work_bytes, void *stream) {
+    PGT_USE_DEVICE(ctx);
+    return jackknife_dev(ctx, kJackF4Mean, rows, n_win, n_quartets, out, out_bytes, work, work_bytes, stream);
 }
 
 size_t pgt_align_workspace_bytes(uint32_t n_files, uint64_t n_rows_file0) {
@@ -1249,6 +1285,13 @@ int pgt_f3_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *f
     return pops_reduce_host(ctx, kF3Pops, pgt_f3_pops_reduce_dev, pos, freq, nind, n_pops, n, minind, win, n_win, out, tot);
 }
 
+/* f4 of all quartets: the host-buffer form, as pgt_f3_pops_reduce */
+int pgt_f4_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
+                       uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_f4_row *out, pgt_f4_total *tot) {
+    PGT_USE_DEVICE(ctx);
+    return pops_reduce_host(ctx, kF4Pops, pgt_f4_pops_reduce_dev, pos, freq, nind, n_pops, n, minind, win, n_win, out, tot);
+}
+
 /* PBS of all trios: the host-buffer form, as pgt_f3_pops_reduce, one per FST estimator */
 int pgt_pbs_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
                         uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_pbs_row *out, pgt_pbs_total *tot) {
@@ -1265,7 +1308,7 @@ int pgt_pbs_hudson_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *
 /* block jackknife of a host table of rows: rows up, the device form on the cached workspace, 3 n_trios results down */
 static int jackknife_host(pgt_ctx *ctx, JackEstimator est, const void *rows, uint64_t n_win, uint32_t n_trios, void *out) {
     const std::string who = jack_who(est);
-    if (int rc = jack_check_range(ctx, who, n_trios, n_win)) return rc;
+    if (int rc = jack_check_range(ctx, est, n_trios, n_win)) return rc;
     if ((n_win && !rows) || !out) return ctx_fail(ctx, PGT_EARG, who + "NULL argument");
     const size_t row_bytes = (size_t)n_trios * n_win * sizeof(pgt_dstat_row), out_bytes = (size_t)n_trios * kJackTopologies * sizeof(pgt_dstat_jack);
     const size_t work_bytes = jack_work(n_trios, n_win).bytes;
@@ -1288,6 +1331,11 @@ int pgt_dstat_jackknife(pgt_ctx *ctx, const pgt_dstat_row *rows, uint64_t n_win,
 int pgt_f3_jackknife(pgt_ctx *ctx, const pgt_f3_row *rows, uint64_t n_win, uint32_t n_trios, pgt_f3_jack *out) {
     PGT_USE_DEVICE(ctx);
     return jackknife_host(ctx, kJackF3Mean, rows, n_win, n_trios, out);
+}
+
+int pgt_f4_jackknife(pgt_ctx *ctx, const pgt_f4_row *rows, uint64_t n_win, uint32_t n_quartets, pgt_f4_jack *out) {
+    PGT_USE_DEVICE(ctx);
+    return jackknife_host(ctx, kJackF4Mean, rows, n_win, n_quartets, out);
 }
 
 /* ---------------- window tables built on the device ---------------- */

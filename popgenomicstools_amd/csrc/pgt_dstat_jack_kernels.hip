@@ -15,9 +15,10 @@
 // A second ESTIMATOR runs through the same phases (pgt_f3_jackknife_dev, over the rows of pgt_f3_pops_reduce_dev): a MEAN
 // instead of a ratio of two sums — item u = 3 t + c takes x_j = sum c of the row (the target i / j / k of the trio), and with
 // mean(a, b) = b != 0 ? a / b : 0:     theta = mean(X, n)     theta_-j = mean(X - x_j, n - m_j)     (n, m_j as f64)
-// h_j, theta_J, tau_j and sigma^2 as above.  The estimator (struct D, struct F3Mean below) is a template parameter of the phases
-// that look at an estimate; the totals, the plan, the chunking, readd(), the workspace layout and the order of every addition are
-// common, and both row types are 48 bytes with n and the three sums at the same offsets.
+// h_j, theta_J, tau_j and sigma^2 as above.  The estimator (struct D, struct Mean below: F3Mean, and F4Mean over the rows of
+// pgt_f4_pops_reduce_dev) is a template parameter of the phases that look at an estimate; the totals, the plan, the chunking,
+// readd(), the workspace layout and the order of every addition are common, and all row types are 48 bytes with n and the three
+// sums at the same offsets.
 //
 // Three dependent reductions over the rows and one closing kernel, all on the plan of jack_plan(n_win) (pgt_internal.h):
 //   phase 1  jack_totals_kernel   per wave Σbbaa, Σabba, Σbaba, Σn, g of its chunks                 -> 5 words per wave
@@ -90,16 +91,23 @@ struct D {  // Patterson's D of topology c: ratio(x, y) of two of the three sums
 // f3 with target c of the trio (pgt_f3_jackknife_dev): a MEAN, x_j = sum c of the row, with mean(a, b) = b != 0 ? a / b : 0
 //     theta = mean(X, n)                              theta_-j = mean(X - x_j, n - m_j)        (n, m_j as f64)
 __device__ __forceinline__ double mean(double a, double b) { return b != 0.0 ? __ddiv_rn(a, b) : 0.0; }
-struct F3Mean {
-    using Row = pgt_f3_row;
-    using Out = pgt_f3_jack;
+// One body for the two row and result types that carry a mean (the rows of pgt_f3_pops_reduce_dev and of pgt_f4_pops_reduce_dev:
+// n and the three sums at the same offsets; the results differ in the names of their first two fields alone).
+__device__ __forceinline__ void set_estimates(pgt_f3_jack &r, double th, double th_j) { r.f3 = th; r.f3_jack = th_j; }
+__device__ __forceinline__ void set_estimates(pgt_f4_jack &r, double th, double th_j) { r.f4 = th; r.f4_jack = th_j; }
+template <class RowT, class OutT>
+struct Mean {
+    using Row = RowT;
+    using Out = OutT;
     static __device__ __forceinline__ double pick(int c, double x0, double x1, double x2) { return c == 0 ? x0 : (c == 1 ? x1 : x2); }
     static __device__ __forceinline__ double theta(int c, const double *s, double n) { return mean(pick(c, s[0], s[1], s[2]), n); }
     static __device__ __forceinline__ double theta_drop(int c, const double *s, double n, double x0, double x1, double x2, double m) {
         return mean(__dsub_rn(pick(c, s[0], s[1], s[2]), pick(c, x0, x1, x2)), __dsub_rn(n, m));
     }
-    static __device__ __forceinline__ void set(Out &r, double th, double th_j, double se, double z) { r.f3 = th; r.f3_jack = th_j; r.se = se; r.z = z; }
+    static __device__ __forceinline__ void set(Out &r, double th, double th_j, double se, double z) { set_estimates(r, th, th_j); r.se = se; r.z = z; }
 };
+using F3Mean = Mean<pgt_f3_row, pgt_f3_jack>;  // item c: f3 with target c of the trio
+using F4Mean = Mean<pgt_f4_row, pgt_f4_jack>;  // item c: f4 of pairing c of the quartet, (ij;kl) / (ik;jl) / (il;jk)
 
 // Σ of n_partials doubles in index order per lane (l, l + 64, ..), then the butterfly: the same bits in every lane of every wave
 __device__ __forceinline__ double readd(const double *p, uint32_t n_partials, int lane) {
@@ -161,6 +169,14 @@ static_assert(sizeof(pgt_f3_row) == sizeof(pgt_dstat_row) && sizeof(pgt_f3_jack)
 static_assert(offsetof(pgt_f3_row, n) == offsetof(pgt_dstat_row, n) && offsetof(pgt_f3_row, f3_i) == offsetof(pgt_dstat_row, bbaa) &&
               offsetof(pgt_f3_row, f3_j) == offsetof(pgt_dstat_row, abba) && offsetof(pgt_f3_row, f3_k) == offsetof(pgt_dstat_row, baba),
               "the three sums of an f3 row at the offsets of bbaa / abba / baba");
+// ... and so do the rows of pgt_f4_pops_reduce_dev
+static_assert(sizeof(pgt_f4_row) == sizeof(pgt_f3_row) && sizeof(pgt_f4_jack) == sizeof(pgt_f3_jack), "one row loader, one result layout");
+static_assert(offsetof(pgt_f4_row, n) == offsetof(pgt_f3_row, n) && offsetof(pgt_f4_row, f4_ij_kl) == offsetof(pgt_f3_row, f3_i) &&
+              offsetof(pgt_f4_row, f4_ik_jl) == offsetof(pgt_f3_row, f3_j) && offsetof(pgt_f4_row, f4_il_jk) == offsetof(pgt_f3_row, f3_k),
+              "the three sums of an f4 row at the offsets of f3_i / f3_j / f3_k");
+static_assert(offsetof(pgt_f4_jack, f4) == offsetof(pgt_f3_jack, f3) && offsetof(pgt_f4_jack, f4_jack) == offsetof(pgt_f3_jack, f3_jack) &&
+              offsetof(pgt_f4_jack, se) == offsetof(pgt_f3_jack, se) && offsetof(pgt_f4_jack, n_blocks) == offsetof(pgt_f3_jack, n_blocks),
+              "pgt_f4_jack in pgt_f3_jack's layout");
 
 // wave p of trio blockIdx.y; -1: a wave that pads the last workgroup (it returns: no barrier is ever used)
 __device__ __forceinline__ int64_t my_partial(const JackArgs &a) {
@@ -329,6 +345,12 @@ int launch_dstat_jackknife(const pgt_dstat_row *rows, uint64_t n_win, uint32_t n
 int launch_f3_jackknife(const pgt_f3_row *rows, uint64_t n_win, uint32_t n_trios, pgt_f3_jack *out, void *work,
                         void *stream, void *ev_query0, void *ev_query1, std::string *err) {
     return launch_jackknife<F3Mean>(rows, n_win, n_trios, out, work, stream, ev_query0, ev_query1, err);
+}
+
+// the rows of pgt_f4_pops_reduce_dev: item u = 3 q + c is f4 of pairing c, (ij;kl) / (ik;jl) / (il;jk), of quartet q
+int launch_f4_jackknife(const pgt_f4_row *rows, uint64_t n_win, uint32_t n_quartets, pgt_f4_jack *out, void *work,
+                        void *stream, void *ev_query0, void *ev_query1, std::string *err) {
+    return launch_jackknife<F4Mean>(rows, n_win, n_quartets, out, work, stream, ev_query0, ev_query1, err);
 }
 
 }  // namespace pgt

@@ -223,6 +223,10 @@ int launch_dstat_jackknife(const pgt_dstat_row *rows, uint64_t n_win, uint32_t n
 // the same phases with the mean estimator (F3Mean) over the rows of pgt_f3_pops_reduce_dev; plan and workspace as above
 int launch_f3_jackknife(const pgt_f3_row *rows, uint64_t n_win, uint32_t n_trios, pgt_f3_jack *out, void *work,
                         void *stream, void *ev_query0, void *ev_query1, std::string *err);
+// the mean estimator again, over the rows of pgt_f4_pops_reduce_dev: 1 <= n_quartets <= kJackMaxQuartets
+constexpr uint32_t kJackMaxQuartets = 15;    // C(6, 4): what pgt_f4_pops_reduce_dev can write
+int launch_f4_jackknife(const pgt_f4_row *rows, uint64_t n_win, uint32_t n_quartets, pgt_f4_jack *out, void *work,
+                        void *stream, void *ev_query0, void *ev_query1, std::string *err);
 
 // Speed-only hints of a context (pgt_set_max_window, pgt_set_window_step); 0 = unknown.
 struct Hints {
@@ -315,6 +319,13 @@ int launch_fd_pops(const uint32_t *pos, const double *const *freq, const int32_t
 // rows per trio, in lexicographic trio order; the tree has launch_dstat_pops' layout at n_pops + 1
 int launch_f3_pops(const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
                    uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_f3_row *out, pgt_f3_total *tot,
+                   void *tree, const LaunchEnv &e);
+
+// pgt_f4_pops_kernels.hip: f4 of ALL quartets of the populations (no outgroup), each quartet in its three pairings;
+// tot = C(n_pops, 4) device totals or NULL; 4 <= n_pops <= 6 and minind >= 1 (checked by the caller); out = one table of n_win
+// rows per quartet, in lexicographic quartet order; a node is 3 C(n_pops, 4) doubles and C(n_pops, 4) u32
+int launch_f4_pops(const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
+                   uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_f4_row *out, pgt_f4_total *tot,
                    void *tree, const LaunchEnv &e);
 
 // pgt_pbs_pops_kernels.hip: the population branch statistic of ALL trios, every population of a trio as the focal one, in two
@@ -413,6 +424,7 @@ int init_dstat_pops_kernels(std::string *err);  // pgt_dstat_pops_kernels.hip
 int init_fd_pops_kernels(std::string *err);     // pgt_fd_pops_kernels.hip
 int init_f3_pops_kernels(std::string *err);     // pgt_f3_pops_kernels.hip
 int init_pbs_pops_kernels(std::string *err);    // pgt_pbs_pops_kernels.hip
+int init_f4_pops_kernels(std::string *err);     // pgt_f4_pops_kernels.hip
 
 // thread-local message for the ctx-less entry points
 void set_global_error(const std::string &msg);

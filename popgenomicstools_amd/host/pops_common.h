@@ -1,14 +1,14 @@
-// pops_common.h — the K-population hosts (dxyWindowPops, fstWindowPops, piWindowPops, dstatWindowPops, f3WindowPops, pbsWindowPops) are one
+// pops_common.h — the K-population hosts (dxyWindowPops, fstWindowPops, piWindowPops, dstatWindowPops, f3WindowPops, f4WindowPops, pbsWindowPops) are one
 // program, run_pops_tool<Tool>: the command line (dxyWindow's options, the tool's own, -out PREFIX, the tool's number of MAF
 // files), from the opened files to the aligned columns and the window table on the device (load_pops — open, parse on the host or
 // the device, the resident-size refusals, chromosome ids, pgt_align_segments, upload, pgt_sites_align, pgt_gather_dev, the runs of
-// the common sites, the window table), one reduction of all the tool's tables (pops_pass), and PREFIX.pop<i>[_pop<j>[_pop<k>]]<ext>
+// the common sites, the window table), one reduction of all the tool's tables (pops_pass), and PREFIX.pop<i>[_pop<j>[_pop<k>[_pop<l>]]]<ext>
 // per table with PREFIX.global.  The K-file form of the reference's site synchronisation (dxyWindow.cpp:315-331): the sites
 // (chromosome, position) that ALL files list are found on the GPU (a single file is its own site list: nothing to align).
 // Messages carry the tool's name.  A tool is a struct (derived from PopsTool, which holds what most tools leave alone) with
 //     name, min_files, max_files, help(options)      the help text is the tool's own, verbatim
 //     own(option, value, argc, argv)                  an option of this tool alone: taken (or refused by die()) -> true
-//     arity, outgroup                                 its tables: all pairs (2), each population (1), all trios (3) of the K files —
+//     arity, outgroup                                 its tables: all pairs (2), each population (1), all trios (3), all quartets (4) of the K files —
 //                                                     of the K-1 before the last with an outgroup
 //     Row, Total, ext, global_ext, row_bytes, tree_bytes, reduce_dev    the reduction and its files; tree_bytes(K, sites), or
 //                                                     (K, sites, windows) where the workspace holds more than the tree
@@ -347,10 +347,10 @@ inline void close_out(FILE *f, const std::string &path) {
 }
 
 // ---- the tables of a call -----------------------------------------------------------------------------------------------
-// one table: the (0-based) populations of a pair, a population or a trio
+// one table: the (0-based) populations of a pair, a population, a trio or a quartet
 struct PopsIndex {
     int n;
-    int pop[3];
+    int pop[4];
 };
 // all i < j < .. of `pops` populations, `arity` of them each, in the library's table order: (0,1),(0,2),..,(1,2),..
 // (a loop beyond the arity runs once; what it leaves in `pop` is not looked at)
@@ -358,7 +358,8 @@ inline std::vector<PopsIndex> pops_tuples(int arity, int pops) {
     std::vector<PopsIndex> t;
     for (int a = 0; a < pops; ++a)
         for (int b = arity > 1 ? a + 1 : pops - 1; b < pops; ++b)
-            for (int c = arity > 2 ? b + 1 : pops - 1; c < pops; ++c) t.push_back({arity, {a, b, c}});
+            for (int c = arity > 2 ? b + 1 : pops - 1; c < pops; ++c)
+                for (int d = arity > 3 ? c + 1 : pops - 1; d < pops; ++d) t.push_back({arity, {a, b, c, d}});
     return t;
 }
 // `pop1_pop2_pop3` of a file name ("pop", "_"), `1 2 3` at the head of a PREFIX.global line ("", "\t")
@@ -452,16 +453,17 @@ typename Pass::Row *pops_pass(const Pass &pass, PopsRun &run) {
 }
 
 // -jackknife 1: the delete-m_j block jackknife of every trio of the run on its rows still on the device, every window of the table
-// a block -> PREFIX.jackknife, three lines per trio (`P1 P2 P3 estimate jackknife_estimate SE Z nblocks nsites`).  order[u]:
-// which of the trio's populations line u names first, second and third.  The two entry points' results are one layout.
+// a block -> PREFIX.jackknife, three lines per trio (`P1 P2 P3 estimate jackknife_estimate SE Z nblocks nsites`) or quartet
+// (`P1 P2 P3 P4 ..`).  order[u]: which of the table's populations line u names first, second, third (and fourth).  The entry
+// points' results are one layout.
 struct PopsJack {
     double est, est_jack, se, z;
     uint64_t n_sites;
     uint32_t n_blocks, pad_;
 };
-template <class Row, class Jack>
+template <class Row, class Jack, size_t N>
 void pops_jackknife(PopsRun &run, const Row *d_rows, int (*jackknife_dev)(pgt_ctx *, const Row *, uint64_t, uint32_t, Jack *, size_t, void *, size_t, void *),
-                    size_t (*work_bytes)(uint32_t, uint64_t), const int (&order)[3][3]) {
+                    size_t (*work_bytes)(uint32_t, uint64_t), const int (&order)[3][N]) {
     static_assert(sizeof(Jack) == sizeof(PopsJack) && offsetof(Jack, se) == offsetof(PopsJack, se) && offsetof(Jack, z) == offsetof(PopsJack, z) &&
                   offsetof(Jack, n_sites) == offsetof(PopsJack, n_sites) && offsetof(Jack, n_blocks) == offsetof(PopsJack, n_blocks),
                   "the estimate and its jackknife estimate, then se, z, n_sites, n_blocks");
@@ -482,8 +484,9 @@ void pops_jackknife(PopsRun &run, const Row *d_rows, int (*jackknife_dev)(pgt_ct
             for (int u = 0; u < 3; ++u) {
                 const int *pop = run.tables[t].pop;
                 const PopsJack &r = (*jack)[3 * t + (size_t)u];
-                std::fprintf(f, "%d\t%d\t%d\t%s\t%s\t%s\t%s\t%u\t%llu\n", pop[order[u][0]] + 1, pop[order[u][1]] + 1, pop[order[u][2]] + 1, g6(r.est).c_str(),
-                             g6(r.est_jack).c_str(), g6(r.se).c_str(), g6(r.z).c_str(), r.n_blocks, (unsigned long long)r.n_sites);
+                for (size_t k = 0; k < N; ++k) std::fprintf(f, "%d\t", pop[order[u][k]] + 1);
+                std::fprintf(f, "%s\t%s\t%s\t%s\t%u\t%llu\n", g6(r.est).c_str(), g6(r.est_jack).c_str(), g6(r.se).c_str(), g6(r.z).c_str(), r.n_blocks,
+                             (unsigned long long)r.n_sites);
             }
         close_out(f, path);
     });

@@ -20,7 +20,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import (DSTAT_JACK_DTYPE, DSTAT_ROW_DTYPE, DSTAT_TOTAL_DTYPE, DXY_ROW_DTYPE, DXY_TOTAL_DTYPE, EXT_ROW_DTYPE, F3_JACK_DTYPE, F3_ROW_DTYPE, F3_TOTAL_DTYPE, FD_ROW_DTYPE, FD_TOTAL_DTYPE, FST_ROW_DTYPE, FST_TOTAL_DTYPE, HET_ROW_DTYPE, PBS_ROW_DTYPE, PBS_TOTAL_DTYPE, PGT_EXT_IHS,
+from ._lib import (DSTAT_JACK_DTYPE, DSTAT_ROW_DTYPE, DSTAT_TOTAL_DTYPE, DXY_ROW_DTYPE, DXY_TOTAL_DTYPE, EXT_ROW_DTYPE, F3_JACK_DTYPE, F3_ROW_DTYPE, F3_TOTAL_DTYPE, F4_JACK_DTYPE, F4_ROW_DTYPE, F4_TOTAL_DTYPE, FD_ROW_DTYPE, FD_TOTAL_DTYPE, FST_ROW_DTYPE, FST_TOTAL_DTYPE, HET_ROW_DTYPE, PBS_ROW_DTYPE, PBS_TOTAL_DTYPE, PGT_EXT_IHS,
                    PGT_EXT_XP_MAX, PGT_EXT_XP_MIN, PGT_STAT_DXY, PGT_STAT_EXT, PGT_STAT_FST, PGT_STAT_HET,
                    SEG_DTYPE, SHARD_DTYPE, WIN_DTYPE, PgtError, check)
 
@@ -269,8 +269,11 @@ class _PopsStat:
     max_pops: int = 8
     per_trio: bool = False  # one row table per ingroup trio i < j < k (trio_order); the last population is the outgroup
     all_trios: bool = False  # one row table per trio i < j < k of ALL populations (all_trio_order): no outgroup
+    all_quartets: bool = False  # one row table per quartet i < j < k < l of ALL populations (all_quartet_order)
 
     def tables(self, n_pops: int) -> int:
+        if self.all_quartets:
+            return n_pops * (n_pops - 1) * (n_pops - 2) * (n_pops - 3) // 24
         if self.all_trios:
             return n_pops * (n_pops - 1) * (n_pops - 2) // 6
         if self.per_trio:
@@ -289,6 +292,7 @@ _FST_HUDSON_POPS = _PopsStat("fst_hudson", 2, True, FST_ROW_DTYPE, FST_TOTAL_DTY
 _DSTAT_POPS = _PopsStat("dstat", 4, False, DSTAT_ROW_DTYPE, DSTAT_TOTAL_DTYPE, max_pops=7, per_trio=True)
 _FD_POPS = _PopsStat("fd", 4, False, FD_ROW_DTYPE, FD_TOTAL_DTYPE, max_pops=7, per_trio=True)
 _F3_POPS = _PopsStat("f3", 3, False, F3_ROW_DTYPE, F3_TOTAL_DTYPE, max_pops=6, all_trios=True)
+_F4_POPS = _PopsStat("f4", 4, False, F4_ROW_DTYPE, F4_TOTAL_DTYPE, max_pops=6, all_quartets=True)
 _PBS_POPS = _PopsStat("pbs", 3, False, PBS_ROW_DTYPE, PBS_TOTAL_DTYPE, max_pops=6, all_trios=True)
 _PBS_HUDSON_POPS = _PopsStat("pbs_hudson", 3, False, PBS_ROW_DTYPE, PBS_TOTAL_DTYPE, max_pops=6, all_trios=True)
 _PBS_ESTIMATORS = {"wc": _PBS_POPS, "hudson": _PBS_HUDSON_POPS}  # pbs_window_pops(estimator=...), Context.pbs_pops_reduce*(estimator=...)
@@ -458,6 +462,13 @@ class Context:
         Nothing is clamped: inf and nan are the IEEE results of FST = 1."""
         return self._pops_reduce(_pbs_estimator("pbs_pops_reduce", estimator), pos, freqs, ninds, minind, win)
 
+    def f4_pops_reduce(self, pos, freqs, ninds, minind, win):
+        """f4 rows of ALL quartets i<j<k<l of len(freqs) populations (all_quartet_order; no outgroup), every quartet in its three
+        pairings, from 4 ... 6 per-population numpy (freq, nInd) columns, one pass: -> (rows[n_quartets, n_win], totals[n_quartets])
+        (pgt_f4_pops_reduce).  A row carries the three SUMS f4_ij_kl, f4_ik_jl, f4_il_jk over its counted sites (pairing_order)
+        and their number n; f4 of the window is sum / n."""
+        return self._pops_reduce(_F4_POPS, pos, freqs, ninds, minind, win)
+
     def _jackknife(self, name: str, row: np.dtype, jack: np.dtype, rows) -> np.ndarray:
         """The numpy form of a block jackknife (pgt_<name>_jackknife) -> [n_trios, 3] of `jack`."""
         rows = np.ascontiguousarray(rows, dtype=row)
@@ -479,6 +490,12 @@ class Context:
         [n_trios, n_win] numpy table of F3_ROW_DTYPE rows (what f3_pops_reduce returns) over DISJOINT windows
         (pgt_f3_jackknife) -> [n_trios, 3] F3_JACK_DTYPE, the targets in target_order."""
         return self._jackknife("f3", F3_ROW_DTYPE, F3_JACK_DTYPE, rows)
+
+    def f4_jackknife(self, rows) -> np.ndarray:
+        """Block-jackknife f4 (the mean over the used blocks' sites), standard error and Z of every quartet and pairing from a
+        [n_quartets, n_win] numpy table of F4_ROW_DTYPE rows (what f4_pops_reduce returns) over DISJOINT windows
+        (pgt_f4_jackknife) -> [n_quartets, 3] F4_JACK_DTYPE, the pairings in pairing_order."""
+        return self._jackknife("f4", F4_ROW_DTYPE, F4_JACK_DTYPE, rows)
 
     # ---- device-resident columns (torch CUDA tensors) -------------------------------------
     @staticmethod
@@ -869,7 +886,7 @@ class Context:
         n_win, n_trios = int(n_win), int(n_trios)
         wb = int(getattr(self._lib, f"pgt_{name}_jackknife_work_bytes")(n_trios, n_win))
         if wb == 0:
-            raise PgtError(_lib.PGT_EARG, f"{who}: n_trios must be 1 ... 20")
+            raise PgtError(_lib.PGT_EARG, f"{who}: n_quartets must be 1 ... 15" if name == "f4" else f"{who}: n_trios must be 1 ... 20")
         self._room(f"{who}: rows", rows, n_trios * n_win * row.itemsize)
         if out is None:
             out = torch.empty(3 * n_trios * jack.itemsize, dtype=torch.uint8, device=rows.device)
@@ -925,6 +942,30 @@ class Context:
         Returns (out, work): out holds 3 * n_trios F3_JACK_DTYPE, item 3 t + c with c the target i / j / k
         (rows_from_device(out, F3_JACK_DTYPE)).  Asynchronous on `stream`; no allocation when out and work are given."""
         return self._jackknife_dev("f3", F3_ROW_DTYPE, F3_JACK_DTYPE, rows, n_win, n_trios, out, work, stream)
+
+    @staticmethod
+    def f4_pops_tree_bytes(n_pops: int, n_sites: int) -> int:
+        return int(_lib.load().pgt_f4_pops_tree_bytes(int(n_pops), int(n_sites)))
+
+    def f4_pops_reduce_dev(self, pos, freqs, ninds, minind, win, out=None, tot=None, tree=None, stream=None):
+        """f4 rows of ALL quartets of len(freqs) populations (quartet-major, all_quartet_order; no outgroup), every quartet in its
+        three pairings, in one pass over 4 ... 6 populations' own (freq, nInd) columns (pgt_f4_pops_reduce_dev).  freqs: float64
+        CUDA tensors, ninds: int32 CUDA tensors.  Rows of F4_ROW_DTYPE carry SUMS (f4 = sum / n), totals are F4_TOTAL_DTYPE.
+        tot: None = a fresh buffer of n_quartets totals is allocated and filled; False = no genome-wide lines.
+        Returns (out, tot, tree).  Asynchronous on `stream`."""
+        return self._pops_reduce_dev(_F4_POPS, pos, freqs, ninds, minind, win, out, tot, tree, stream)
+
+    @staticmethod
+    def f4_jackknife_work_bytes(n_quartets: int, n_win: int) -> int:
+        return int(_lib.load().pgt_f4_jackknife_work_bytes(int(n_quartets), int(n_win)))
+
+    def f4_jackknife_dev(self, rows, n_win, n_quartets, out=None, work=None, stream=None):
+        """Block-jackknife f4, standard error and Z of n_quartets quartets x 3 pairings from the device rows of
+        f4_pops_reduce_dev (uint8 CUDA tensor, quartet-major, n_quartets * n_win rows; the windows must be disjoint)
+        (pgt_f4_jackknife_dev).  Returns (out, work): out holds 3 * n_quartets F4_JACK_DTYPE, item 3 q + c with c the pairing
+        (ij;kl) / (ik;jl) / (il;jk) (rows_from_device(out, F4_JACK_DTYPE)).  Asynchronous on `stream`; no allocation when out
+        and work are given."""
+        return self._jackknife_dev("f4", F4_ROW_DTYPE, F4_JACK_DTYPE, rows, n_win, n_quartets, out, work, stream)
 
     def extreme_reduce_dev(self, pos, score, mode, cutoff, win, out=None, tree=None, stream=None):
         """ihsWindow / xpehhWindow rows from a device-resident score column (mode: PGT_EXT_*)."""
@@ -1231,6 +1272,19 @@ def target_order(i, j, k):
     return [(i, j, k), (j, i, k), (k, i, j)]
 
 
+def all_quartet_order(n_pops: int):
+    """The quartets (i, j, k, l), i < j < k < l < n_pops, of ALL populations in the order f4_pops_reduce* lays its rows out:
+    (0,1,2,3),(0,1,2,4),..,(0,1,3,4),.."""
+    g = int(n_pops)
+    return [(i, j, k, l) for i in range(g) for j in range(i + 1, g) for k in range(j + 1, g) for l in range(k + 1, g)]
+
+
+def pairing_order(i, j, k, l):
+    """The three pairings of quartet (i, j, k, l) in the order its row's sums and the block jackknife's items are laid out
+    (c = 0, 1, 2), each as ((a, b), (c, d)) of f4(a, b; c, d): (((i, j), (k, l)), ((i, k), (j, l)), ((i, l), (j, k)))."""
+    return ((i, j), (k, l)), ((i, k), (j, l)), ((i, l), (j, k))
+
+
 def topology_order(i, j, k):
     """The three topologies of trio (i, j, k) in the order the block jackknife lays its items out (c = 0, 1, 2), each as
     ((P1, P2), P3): [(i, j, k), (i, k, j), (j, k, i)] — D from (abba, baba), (bbaa, baba), (bbaa, abba) of the trio's row."""
@@ -1410,6 +1464,34 @@ def pbs_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: 
     st = _pbs_estimator("pbs_window_pops", estimator)
     win, rows, tot = _window_pops(st, chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx)
     return _results_by_pair(len(freqs), win, rows, tot, skip_missing, "n", keys=all_trio_order(len(freqs)))
+
+
+def f4_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: int = 1, fixedsite: int = 0,
+                   chr_len=None, skip_missing: int = 0, jackknife: bool = False, ctx: Context | None = None) -> dict:
+    """Windowed f4 (Reich et al. 2009; Patterson et al. 2012) for ALL quartets of len(freqs) already synchronised populations
+    (4 ... 6; no outgroup), every quartet in its three pairings, in one pass: {(i, j, k, l): WindowResult} in
+    all_quartet_order, with rows of (start, end, mid, n, reserved_, f4_ij_kl, f4_ik_jl, f4_il_jk) and the genome-wide sums as
+    total.  The three values are SUMS over the counted sites, one per pairing_order(i, j, k, l): f4 of a window is sum / n.
+    All columns must report the same allele.  f4(a, b; c, d) is 0 in expectation when ((a, b), (c, d)) is the tree: |Z| above
+    about 3 rejects that tree.
+    Window arguments and their errors are those of dxy_window_pops; -skip_missing drops a quartet's rows without counted sites
+    from that quartet's result only.  The per-site definition is pgt_f4_pops_reduce_dev's (include/pgtwin.h).
+    jackknife=True: the result gains the key "jackknife": {(i, j, k, l): 3 F4_JACK_DTYPE, one per pairing_order(i, j, k, l)} —
+    the delete-m_j block jackknife of the mean (pgt_f4_jackknife_dev, on the device rows of the same reduction) over ALL
+    windows of the table as blocks, whatever skip_missing is.  The windows must be disjoint: 0 < S < W and W == 0 are refused
+    with PGT_EARG before any device use.
+    Not computed: f4-ratio admixture proportions, user-chosen quartet lists."""
+    if jackknife and (W == 0 or 0 < S < W):
+        raise PgtError(_lib.PGT_EARG, f"f4_window_pops: the block jackknife needs disjoint windows as its blocks: "
+                                      f"winsize {W} must be positive and stepsize {S} at least the winsize")
+    keys = all_quartet_order(len(freqs))
+    if not jackknife:
+        win, rows, tot = _window_pops(_F4_POPS, chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx)
+        return _results_by_pair(len(freqs), win, rows, tot, skip_missing, "n", keys=keys)
+    win, rows, tot, jack = _trio_window_pops_jackknife(_F4_POPS, F4_JACK_DTYPE, chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx)
+    res = _results_by_pair(len(freqs), win, rows, tot, skip_missing, "n", keys=keys)
+    res["jackknife"] = {q: jack[t] for t, q in enumerate(keys)}
+    return res
 
 
 def pi_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: int = 1, fixedsite: int = 0,
