@@ -3,7 +3,7 @@
 # with staleness checks (a content hash beside the library: after a `make` of changed sources the Python
 # loader rebuilds once more and re-stamps); both leave libpgtwin.so and the host tools in the same places.
 #
-#   make            libpgtwin.so + bin/{fstWindow,hetWindow,dxyWindow,dxyWindowPops,fstWindowPops,piWindowPops,dstatWindowPops,f3WindowPops,f4WindowPops,pbsWindowPops,ihsWindow,xpehhWindow}   (needs hipcc, no GPU)
+#   make            libpgtwin.so + bin/{fstWindow,hetWindow,dxyWindow,dxyWindowPops,fstWindowPops,piWindowPops,dstatWindowPops,f3WindowPops,f4WindowPops,f4ratioWindowPops,pbsWindowPops,ihsWindow,xpehhWindow}   (needs hipcc, no GPU)
 #   make oracle     the test-only CPU restatement (+ the unmodified reference tools where /root/reference exists)
 #   make test       CPU test suite          make gputest   GPU parity suite (needs an MI355X)
 HIPCC    ?= hipcc
@@ -13,10 +13,10 @@ CSRC     := $(PKG)/csrc
 HOST     := $(PKG)/host
 BIN      := $(PKG)/bin
 LIB      := $(PKG)/libpgtwin.so
-LIBSRC   := $(CSRC)/pgt_kernels.hip $(CSRC)/pgt_af_kernels.hip $(CSRC)/pgt_dxy_pops_kernels.hip $(CSRC)/pgt_fst_pops_kernels.hip $(CSRC)/pgt_dstat_pops_kernels.hip $(CSRC)/pgt_fd_pops_kernels.hip $(CSRC)/pgt_f3_pops_kernels.hip $(CSRC)/pgt_f4_pops_kernels.hip $(CSRC)/pgt_pbs_pops_kernels.hip $(CSRC)/pgt_dstat_jack_kernels.hip $(CSRC)/pgt_align_kernels.hip $(CSRC)/pgt_ingest.hip $(CSRC)/pgt_api.cpp $(CSRC)/pgt_windows.cpp
+LIBSRC   := $(CSRC)/pgt_kernels.hip $(CSRC)/pgt_af_kernels.hip $(CSRC)/pgt_dxy_pops_kernels.hip $(CSRC)/pgt_fst_pops_kernels.hip $(CSRC)/pgt_dstat_pops_kernels.hip $(CSRC)/pgt_fd_pops_kernels.hip $(CSRC)/pgt_f3_pops_kernels.hip $(CSRC)/pgt_f4_pops_kernels.hip $(CSRC)/pgt_f4ratio_pops_kernels.hip $(CSRC)/pgt_pbs_pops_kernels.hip $(CSRC)/pgt_dstat_jack_kernels.hip $(CSRC)/pgt_align_kernels.hip $(CSRC)/pgt_ingest.hip $(CSRC)/pgt_api.cpp $(CSRC)/pgt_windows.cpp
 LIBHDR   := $(CSRC)/pgt_internal.h $(CSRC)/pgt_device.h $(CSRC)/pgt_pops_common.h $(CSRC)/pgt_pops_walk.h $(CSRC)/pgt_fst_site.h include/pgtwin.h
 LIBFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -ffp-contract=off -fPIC -shared
-TOOLS    := fstWindow hetWindow dxyWindow dxyWindowPops fstWindowPops piWindowPops dstatWindowPops f3WindowPops f4WindowPops pbsWindowPops ihsWindow xpehhWindow
+TOOLS    := fstWindow hetWindow dxyWindow dxyWindowPops fstWindowPops piWindowPops dstatWindowPops f3WindowPops f4WindowPops f4ratioWindowPops pbsWindowPops ihsWindow xpehhWindow
 
 all: $(LIB) $(addprefix $(BIN)/,$(TOOLS))
 

@@ -33,8 +33,8 @@
  *     has no counts: every site is counted; a NaN there stays in the rows of the pairs with that population.
  *   - genotypes: any int8 (non-missing is g >= 0, heterozygous g == 1, hetWindow.cpp:78-80); counts (n1, n2, nind[k]) and minind:
  *     any int32, compared as signed integers (dxyWindow.cpp:381).
- *   - the K-population entry points (pgt_dxy_pops / fst_pops / fst_hudson_pops / pi_pops / dstat_pops / fd_pops / f3_pops / pbs_pops / pbs_hudson_pops / f4_pops _reduce_dev;
- *     tests/test_special_values_pops.py): a NaN or an infinity in ONE population's frequency at a COUNTED site reaches exactly the
+ *   - the K-population entry points (pgt_dxy_pops / fst_pops / fst_hudson_pops / pi_pops / dstat_pops / fd_pops / f3_pops / pbs_pops / pbs_hudson_pops / f4_pops / f4ratio_pops _reduce_dev;
+ *     tests/test_special_values_pops.py, for f4ratio_pops tests/test_special_values_f4ratio.py): a NaN or an infinity in ONE population's frequency at a COUNTED site reaches exactly the
  *     rows (and genome-wide lines) of the items — pairs, trios, the population itself — that hold that population, and of them
  *     exactly the windows that hold the site, with the value the per-site definition gives on the IEEE operands, every operation
  *     rounded on its own (for pgt_fd_pops_reduce_dev the definition's comparisons are all false with a NaN, so NaN in P2 leaves
@@ -75,7 +75,10 @@ extern "C" {
  * Still 6: pgt_pbs_row, pgt_pbs_total, pgt_pbs_pops_work_bytes / pgt_pbs_pops_reduce_dev / pgt_pbs_hudson_pops_reduce_dev /
  *          pgt_pbs_pops_reduce / pgt_pbs_hudson_pops_reduce added (additive as well).
  * Still 6: pgt_f4_row, pgt_f4_total, pgt_f4_jack, pgt_f4_pops_tree_bytes / pgt_f4_pops_reduce_dev / pgt_f4_pops_reduce and
- *          pgt_f4_jackknife_work_bytes / pgt_f4_jackknife_dev / pgt_f4_jackknife added (additive as well). */
+ *          pgt_f4_jackknife_work_bytes / pgt_f4_jackknife_dev / pgt_f4_jackknife added (additive as well).
+ * Still 6: pgt_f4ratio_row, pgt_f4ratio_total, pgt_f4ratio_jack, pgt_f4ratio_pops_tree_bytes / pgt_f4ratio_pops_reduce_dev /
+ *          pgt_f4ratio_pops_reduce and pgt_f4ratio_jackknife_work_bytes / pgt_f4ratio_jackknife_dev / pgt_f4ratio_jackknife
+ *          added (additive as well). */
 #define PGT_ABI_VERSION 6
 
 enum {
@@ -192,6 +195,24 @@ typedef struct { /* block jackknife of one quartet and pairing: pgt_f4_jackknife
     uint64_t n_sites;          /* counted sites of the used blocks */
     uint32_t n_blocks, pad_;   /* used blocks (rows with n > 0) */
 } pgt_f4_jack;
+
+typedef struct { /* f4-ratio window row of one middle triple (i, j, k) between A and O: pgt_f4ratio_pops_reduce_dev (48 bytes) */
+    uint32_t start, end, mid, n;
+    double reserved_;          /* +0.0 */
+    double g_ij, g_ik, g_jk;   /* the three window SUMS of (p_A - p_O)(p_x - p_y), full precision, at the offsets of pgt_f4_row's
+                                  sums: f4(A,O; i,j), f4(A,O; i,k), f4(A,O; j,k) times n.  The six ratios are the caller's division */
+} pgt_f4ratio_row;
+
+typedef struct { /* the three sums of one middle triple over all its counted sites (40 bytes) */
+    double g_ij, g_ik, g_jk;
+    uint64_t neff, nskip;
+} pgt_f4ratio_total;
+
+typedef struct { /* block jackknife of one admixture proportion: pgt_f4ratio_jackknife_dev (48 bytes, the layout of pgt_f4_jack) */
+    double alpha, alpha_jack, se, z; /* alpha of all used blocks, its jackknife estimate, standard error, alpha_jack / se */
+    uint64_t n_sites;                /* counted sites of the used blocks */
+    uint32_t n_blocks, pad_;         /* used blocks (rows with n > 0) */
+} pgt_f4ratio_jack;
 
 typedef struct { /* population-branch-statistic window row of one trio (i, j, k): pgt_pbs_pops_reduce_dev (88 bytes) */
     uint32_t start, end, mid, n;    /* offsets 0, 4, 8, 12 */
@@ -721,8 +742,8 @@ int pgt_f3_jackknife(pgt_ctx *ctx, const pgt_f3_row *rows, uint64_t n_win, uint3
  * signs: against an exact evaluation a sum stays within 1e-9 * A + 1e-12, A the window's sum of |product| (of the same pairing);
  * no bound relative to the value is given.  "Values the columns admit" above holds as for the other K-population calls
  * (tests/test_special_values_f4.py).  Held to this definition, to an exact-rational fixture (tests/golden/f4_exact.json) and to
- * a NumPy model (tests/f4_pops_model.py).  f4-ratio admixture proportions, user-chosen quartet lists and K = 7 are not
- * computed; standard errors and Z come from pgt_f4_jackknife_dev below.
+ * a NumPy model (tests/f4_pops_model.py).  Not computed: user-chosen quartet lists and K = 7; standard errors and Z come
+ * from pgt_f4_jackknife_dev below, f4-ratio admixture proportions from pgt_f4ratio_pops_reduce_dev further down.
  * Host-buffer form: columns (host arrays of n_pops HOST pointers), table, rows and the Q totals in host memory. */
 size_t pgt_f4_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites);
 int pgt_f4_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq,
@@ -759,6 +780,93 @@ int pgt_f4_jackknife_dev(pgt_ctx *ctx, const pgt_f4_row *rows, uint64_t n_win, u
                          pgt_f4_jack *out /* 3 * n_quartets, item-major u = 3q + c */, size_t out_bytes,
                          void *work, size_t work_bytes, void *stream);
 int pgt_f4_jackknife(pgt_ctx *ctx, const pgt_f4_row *rows, uint64_t n_win, uint32_t n_quartets, pgt_f4_jack *out);
+
+/* ---- f4-ratio: the sums behind the admixture proportions of ALL middle triples between A and an outgroup ----------------- */
+/* The f4-ratio (Patterson et al. 2012; ADMIXTOOLS' qpF4ratio) answers "how much": alpha = f4(A,O; X,C) / f4(A,O; B,C) is the
+ * share of B-related ancestry in X, where A is a relative of B that took no part in the admixture, C the other source and O an
+ * outgroup.  Numerator and denominator must be counted over the SAME sites, all five populations present, and the standard error
+ * of the ratio needs a jackknife that drops a block from both together: neither can be had from the .f4 tables of
+ * pgt_f4_pops_reduce_dev, whose two quartets {A,O,X,C} and {A,O,B,C} are counted wherever their own four populations have data.
+ * From each population's own (freq, nInd) columns, the input of pgt_f4_pops_reduce_dev, in one pass (12 B/site/population).  It
+ * has NO counterpart in the reference: the definition below is the contract.
+ * n_pops = K populations, 5 <= K <= 7.  Roles come from the order of the columns: population 0 is A, population K-1 the outgroup
+ * O, populations 1 ... K-2 the m = K-2 MIDDLE populations.  An item is an unordered middle triple (i, j, k), 1 <= i < j < k <= K-2,
+ * numbered in lexicographic order; there are T = C(m, 3) = 1 / 4 / 10 of them at K = 5 / 6 / 7.  For triple (i, j, k) and site s:
+ *   counting   nind_x[s] >= minind for x = 0, K-1, i, j and k: FIVE populations (signed int32 compare; minind >= 1 required,
+ *              PGT_EARG otherwise); a site that is not counted is selected away, never multiplied (its frequencies may be NaN or
+ *              infinite, in A or O as well, its counts 0 or negative).  The counts enter through this predicate ONLY.
+ *   per site   p_x = freq_x[s]; every operation rounded on its own, no contraction, in exactly this grouping:
+ *                  e    = p_0 - p_{K-1}                           once per site
+ *                  d_ab = p_a - p_b                               per middle pair a < b, shared by the triples that hold it
+ *                  s0 = e * d_ij                                  f4(A,O; i,j)
+ *                  s1 = e * d_ik                                  f4(A,O; i,k)
+ *                  s2 = e * d_jk                                  f4(A,O; j,k)
+ *              In real arithmetic s0 - s1 + s2 = 0; the three are stored all the same, so that the row has the layout of
+ *              pgt_f4_row.  The values do not depend on which allele the columns report, provided all populations report the
+ *              same one (with frequencies that are multiples of 2^-10, bit for bit).
+ *   row        pgt_f4ratio_row (48 bytes): g_ij / g_ik / g_jk = the three SUMS of s0 / s1 / s2 over the window's counted sites,
+ *              each from +0.0; n = their number; start / end / mid as pgt_f4_row's are filled; reserved_ = +0.0.
+ *   ratios     NOT formed here.  With S0, S1, S2 the sums of a row (or of a total) and q(a, b) = b != 0 ? a / b : 0, the six
+ *              admixture proportions alpha(B, X, C) = f4(A,O; X,C) / f4(A,O; B,C) of the triple are the caller's division:
+ *                  c = 0  (B,X,C) = (i,j,k)  q(+S2, +S1)        c = 1  (j,i,k)  q(+S1, +S2)
+ *                  c = 2  (i,k,j)            q(-S2, +S0)        c = 3  (k,i,j)  q(+S0, -S2)
+ *                  c = 4  (j,k,i)            q(+S1, +S0)        c = 5  (k,j,i)  q(+S0, +S1)
+ *              Nothing is clamped: an alpha outside [0, 1] is what the data say.
+ *   out        T * n_win rows, triple-major: out[t * n_win + w]
+ *   tot        DEVICE array of T pgt_f4ratio_total (40 bytes: the same three sums over all counted sites, neff, nskip), or NULL;
+ *              n_win == 0 with tot: the global-only form
+ *   tree       pgt_f4ratio_pops_tree_bytes(n_pops, n) bytes (0 for n_pops outside 5 ... 7): a node is 3 T doubles (s0 of triple
+ *              0 .. T-1, then s1, then s2) and T u32.    5 <= n_pops <= 7, n < 2^32.
+ * A one-site window carries exactly the bits of s0, s1 and s2 above.  Arguments, alignment, refusals (PGT_EARG; messages begin
+ * "pgt_f4ratio_pops_reduce: " and name their argument; a refused call launches nothing and writes nothing), graph capture and
+ * the hints: those of pgt_f4_pops_reduce_dev.  Triple isolation: the rows of a triple are a function, bit for bit, of the columns
+ * of A, O and its own three populations and the window alone — not of the other middle populations, of K, or of the other rows
+ * of the table.  With the columns (A, i, j, O) and A's count zeroed wherever population k falls below minind,
+ * pgt_f4_pops_reduce_dev's f4_il_jk sum and n are g_ij and n, bit for bit on grid frequencies.  Sums are added in a fixed order
+ * that depends on the site index and the window alone (bitwise reproducible); against an exact evaluation a sum stays within
+ * 1e-9 * A + 1e-12, A the window's sum of |product|.  "Values the columns admit" above holds as for the other K-population calls
+ * (tests/test_special_values_f4ratio.py).  Held to this definition, to an exact-rational fixture
+ * (tests/golden/f4ratio_exact.json) and to a NumPy model (tests/f4ratio_pops_model.py).  User-chosen quintet lists, K = 8 and
+ * qpAdm-style multi-source fits are not computed.
+ * Host-buffer form: columns (host arrays of n_pops HOST pointers), table, rows and the T totals in host memory. */
+size_t pgt_f4ratio_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites);
+int pgt_f4ratio_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq,
+                                const int32_t *const *nind, uint32_t n_pops, uint64_t n, int minind,
+                                const pgt_win *win, uint64_t n_win, pgt_f4ratio_row *out, size_t out_bytes,
+                                pgt_f4ratio_total *tot, void *tree, size_t tree_bytes, void *stream);
+int pgt_f4ratio_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq,
+                            const int32_t *const *nind, uint32_t n_pops, uint64_t n, int minind,
+                            const pgt_win *win, uint64_t n_win, pgt_f4ratio_row *out, pgt_f4ratio_total *tot);
+
+/* ---- block-jackknife standard error and Z of the f4-ratio, all middle triples, six proportions each ---------------------- */
+/* The weighted block jackknife of pgt_dstat_jackknife_dev — h_j, theta_J, tau_j, sigma^2, the rule "used iff n > 0, weight
+ * m_j = n", the plan, the chunking and the order of every addition — with a third estimator, the SIGNED RATIO OF TWO BLOCK SUMS,
+ * over the window rows pgt_f4ratio_pops_reduce_dev wrote.  Numerator and denominator lose a block together:
+ *   rows     DEVICE pointer to the n_triples x n_win triple-major table, 16-byte aligned; every window is one block; the
+ *            caller guarantees that the windows are DISJOINT.  Only n and the three sums of a row are read.
+ *   items    triple t has SIX items u = 6 t + c, c the (B, X, C) of the table above with its (numerator, denominator) = (N_c,
+ *            D_c) among +-S0, +-S1, +-S2; with q(a, b) = b != 0 ? a / b : 0 and n_cj, d_cj the same of block j's row
+ *                theta(c) = q(N_c, D_c)           theta_-j(c) = q(N_c - n_cj, D_c - d_cj)
+ *            (negation is exact: the sign is applied to the sums before the subtraction)
+ *   blocks, per item: as pgt_dstat_jackknife_dev (a row that is not used is selected away, never added: its sums may be NaN)
+ *   out      pgt_f4ratio_jack per item, item-major: alpha = theta, alpha_jack = theta_J, se = sqrt(sigma^2),
+ *            z = se > 0 ? theta_J / se : NaN, n_blocks = g, n_sites = n, pad_ = 0.
+ *            g < 2: alpha_jack = alpha, se = z = NaN.  g == 0 (n_win == 0 included): alpha = alpha_jack = 0, se = z = NaN.
+ *   work     DEVICE workspace of pgt_f4ratio_jackknife_work_bytes(n_triples, n_win) bytes (0 for n_triples outside 1 ... 10),
+ *            16-byte aligned: the three-item estimators' layout with six partials per wave in phases 2 and 3.  Every byte of it
+ *            that is read is written earlier in the same call.
+ * 1 <= n_triples <= 10.  Bitwise reproducible; an item's outputs are a function, bit for bit, of its own triple's rows alone:
+ * not of n_triples, not of the other triples' rows.  Against an exact evaluation alpha, alpha_jack and se stay within 1e-9
+ * relative + 1e-12 while no denominator, whole or with a block left out, is close to zero against its terms
+ * (tests/f4ratio_jack_model.py).  Refusals (PGT_EARG, messages begin "pgt_f4ratio_jackknife: " and name their argument; nothing
+ * is launched, nothing written): those of pgt_dstat_jackknife_dev.  Asynchronous on `stream`; no allocation and no attribute
+ * call: it can be captured into a graph.
+ * Host-buffer form: rows and out in host memory; synchronous. */
+size_t pgt_f4ratio_jackknife_work_bytes(uint32_t n_triples, uint64_t n_win);
+int pgt_f4ratio_jackknife_dev(pgt_ctx *ctx, const pgt_f4ratio_row *rows, uint64_t n_win, uint32_t n_triples,
+                              pgt_f4ratio_jack *out /* 6 * n_triples, item-major u = 6t + c */, size_t out_bytes,
+                              void *work, size_t work_bytes, void *stream);
+int pgt_f4ratio_jackknife(pgt_ctx *ctx, const pgt_f4ratio_row *rows, uint64_t n_win, uint32_t n_triples, pgt_f4ratio_jack *out);
 
 /* ---- the population branch statistic (PBS) of ALL trios, every population of a trio as the focal one -------------------- */
 /* PBS (Yi et al. 2010), the windowed selection scan for a focal population against two others, from each population's own

@@ -55,6 +55,11 @@ F4_ROW_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("mid", "<u4"), ("n",
 F4_TOTAL_DTYPE = np.dtype([("f4_ij_kl", "<f8"), ("f4_ik_jl", "<f8"), ("f4_il_jk", "<f8"), ("neff", "<u8"), ("nskip", "<u8")])
 F4_JACK_DTYPE = np.dtype([("f4", "<f8"), ("f4_jack", "<f8"), ("se", "<f8"), ("z", "<f8"), ("n_sites", "<u8"),
                           ("n_blocks", "<u4"), ("pad_", "<u4")])  # pgt_f4_jack: one quartet and pairing
+F4RATIO_ROW_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("mid", "<u4"), ("n", "<u4"),
+                              ("reserved_", "<f8"), ("g_ij", "<f8"), ("g_ik", "<f8"), ("g_jk", "<f8")])  # pgt_f4ratio_row: the three SUMS of one middle triple
+F4RATIO_TOTAL_DTYPE = np.dtype([("g_ij", "<f8"), ("g_ik", "<f8"), ("g_jk", "<f8"), ("neff", "<u8"), ("nskip", "<u8")])
+F4RATIO_JACK_DTYPE = np.dtype([("alpha", "<f8"), ("alpha_jack", "<f8"), ("se", "<f8"), ("z", "<f8"), ("n_sites", "<u8"),
+                               ("n_blocks", "<u4"), ("pad_", "<u4")])  # pgt_f4ratio_jack: one admixture proportion of one middle triple
 EXT_ROW_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("nsites", "<u4"), ("nbig", "<u4"),
                           ("position", "<u4"), ("pad_", "<u4"), ("value", "<f8")])
 SHARD_DTYPE = np.dtype([("win_begin", "<u8"), ("win_end", "<u8"), ("site_lo", "<u8"), ("site_hi", "<u8")])
@@ -71,6 +76,8 @@ assert PBS_ROW_DTYPE.itemsize == 88 and PBS_TOTAL_DTYPE.itemsize == 88
 assert [F3_ROW_DTYPE.fields[k][1] for k in ("f3_i", "f3_j", "f3_k")] == [DSTAT_ROW_DTYPE.fields[k][1] for k in ("bbaa", "abba", "baba")]
 assert F4_ROW_DTYPE.itemsize == 48 and F4_TOTAL_DTYPE.itemsize == 40 and F4_JACK_DTYPE.itemsize == 48
 assert [F4_ROW_DTYPE.fields[k][1] for k in ("f4_ij_kl", "f4_ik_jl", "f4_il_jk")] == [F3_ROW_DTYPE.fields[k][1] for k in ("f3_i", "f3_j", "f3_k")]
+assert F4RATIO_ROW_DTYPE.itemsize == 48 and F4RATIO_TOTAL_DTYPE.itemsize == 40 and F4RATIO_JACK_DTYPE.itemsize == 48
+assert [F4RATIO_ROW_DTYPE.fields[k][1] for k in ("g_ij", "g_ik", "g_jk")] == [F4_ROW_DTYPE.fields[k][1] for k in ("f4_ij_kl", "f4_ik_jl", "f4_il_jk")]
 
 # every symbol include/pgtwin.h declares (tests/test_abi.py checks the list against the header)
 SYMBOLS = [
@@ -97,6 +104,8 @@ SYMBOLS = [
     "pgt_f3_jackknife_work_bytes", "pgt_f3_jackknife_dev", "pgt_f3_jackknife",
     "pgt_f4_pops_tree_bytes", "pgt_f4_pops_reduce_dev", "pgt_f4_pops_reduce",
     "pgt_f4_jackknife_work_bytes", "pgt_f4_jackknife_dev", "pgt_f4_jackknife",
+    "pgt_f4ratio_pops_tree_bytes", "pgt_f4ratio_pops_reduce_dev", "pgt_f4ratio_pops_reduce",
+    "pgt_f4ratio_jackknife_work_bytes", "pgt_f4ratio_jackknife_dev", "pgt_f4ratio_jackknife",
     "pgt_pbs_pops_work_bytes", "pgt_pbs_pops_reduce_dev", "pgt_pbs_hudson_pops_reduce_dev", "pgt_pbs_pops_reduce", "pgt_pbs_hudson_pops_reduce",
 ]
 PGT_TOK_CHR, PGT_TOK_SKIP, PGT_TOK_U32, PGT_TOK_F64, PGT_TOK_I8, PGT_TOK_I32, PGT_TOK_FREQ, PGT_TOK_CHR_PREFIX = range(8)
@@ -168,7 +177,7 @@ def load() -> C.CDLL:
     lib.pgt_af_tree_bytes.restype = sz
     lib.pgt_af_tree_bytes.argtypes = [u32, u64]
     lib.pgt_fst_af_reduce_dev.argtypes = [vp, vp, vp, vp, u32, u64, vp, u64, vp, sz, vp, sz, vp]
-    for stat in ("dxy", "fst", "pi", "fst_hudson", "dstat", "fd", "f3", "f4"):  # the K-population statistics over (freq, nInd) columns: one argument list each form
+    for stat in ("dxy", "fst", "pi", "fst_hudson", "dstat", "fd", "f3", "f4", "f4ratio"):  # the K-population statistics over (freq, nInd) columns: one argument list each form
         getattr(lib, f"pgt_{stat}_pops_tree_bytes").restype = sz
         getattr(lib, f"pgt_{stat}_pops_tree_bytes").argtypes = [u32, u64]
         getattr(lib, f"pgt_{stat}_pops_reduce_dev").argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, u64, vp, sz, vp, vp, sz, vp]
@@ -178,7 +187,7 @@ def load() -> C.CDLL:
     for stat in ("pbs", "pbs_hudson"):
         getattr(lib, f"pgt_{stat}_pops_reduce_dev").argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, u64, vp, sz, vp, vp, sz, vp]
         getattr(lib, f"pgt_{stat}_pops_reduce").argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, u64, vp, vp]
-    for stat in ("dstat", "f3", "f4"):  # the block jackknife of the three row types: one argument list each form
+    for stat in ("dstat", "f3", "f4", "f4ratio"):  # the block jackknife of the four row types: one argument list each form
         getattr(lib, f"pgt_{stat}_jackknife_work_bytes").restype = sz
         getattr(lib, f"pgt_{stat}_jackknife_work_bytes").argtypes = [u32, u64]
         getattr(lib, f"pgt_{stat}_jackknife_dev").argtypes = [vp, vp, u64, u32, vp, sz, vp, sz, vp]

@@ -19,8 +19,8 @@ BIN = os.path.join(PKG, "bin")
 LIB = os.path.join(PKG, "libpgtwin.so")
 FLAGS = os.path.join(PKG, "libpgtwin.flags")
 
-LIB_SOURCES = ["pgt_kernels.hip", "pgt_af_kernels.hip", "pgt_dxy_pops_kernels.hip", "pgt_fst_pops_kernels.hip", "pgt_dstat_pops_kernels.hip", "pgt_fd_pops_kernels.hip", "pgt_f3_pops_kernels.hip", "pgt_f4_pops_kernels.hip", "pgt_pbs_pops_kernels.hip", "pgt_dstat_jack_kernels.hip", "pgt_align_kernels.hip", "pgt_ingest.hip", "pgt_api.cpp", "pgt_windows.cpp"]
-HOST_TOOLS = ["fstWindow", "hetWindow", "dxyWindow", "dxyWindowPops", "fstWindowPops", "piWindowPops", "dstatWindowPops", "f3WindowPops", "f4WindowPops", "pbsWindowPops", "ihsWindow", "xpehhWindow"]
+LIB_SOURCES = ["pgt_kernels.hip", "pgt_af_kernels.hip", "pgt_dxy_pops_kernels.hip", "pgt_fst_pops_kernels.hip", "pgt_dstat_pops_kernels.hip", "pgt_fd_pops_kernels.hip", "pgt_f3_pops_kernels.hip", "pgt_f4_pops_kernels.hip", "pgt_f4ratio_pops_kernels.hip", "pgt_pbs_pops_kernels.hip", "pgt_dstat_jack_kernels.hip", "pgt_align_kernels.hip", "pgt_ingest.hip", "pgt_api.cpp", "pgt_windows.cpp"]
+HOST_TOOLS = ["fstWindow", "hetWindow", "dxyWindow", "dxyWindowPops", "fstWindowPops", "piWindowPops", "dstatWindowPops", "f3WindowPops", "f4WindowPops", "f4ratioWindowPops", "pbsWindowPops", "ihsWindow", "xpehhWindow"]
 
 
 def _hipcc() -> str:

@@ -455,7 +455,7 @@ pgt_ctx *pgt_open(int device) {
     if (init_kernels(&init_err) != PGT_OK || init_af_kernels(&init_err) != PGT_OK || init_dxy_pops_kernels(&init_err) != PGT_OK ||
         init_fst_pops_kernels(&init_err) != PGT_OK || init_dstat_pops_kernels(&init_err) != PGT_OK ||
         init_fd_pops_kernels(&init_err) != PGT_OK || init_f3_pops_kernels(&init_err) != PGT_OK || init_pbs_pops_kernels(&init_err) != PGT_OK ||
-        init_f4_pops_kernels(&init_err) != PGT_OK) {
+        init_f4_pops_kernels(&init_err) != PGT_OK || init_f4ratio_pops_kernels(&init_err) != PGT_OK) {
         set_global_error("pgt_open: " + init_err);
         return nullptr;
     }
@@ -781,10 +781,26 @@ int pgt_f4_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *cons
     return pops_reduce_dev(ctx, kF4Pops, launch_f4_pops, pos, freq, nind, n_pops, n, minind, win, n_win, out, out_bytes, tot, tree, tree_bytes, stream);
 }
 
+// The f4-ratio sums of ALL triples of the middle populations between the first population and the last: one more PopsStat;
+// three sums per triple.  minind >= 1: what pgt_f4_pops_reduce_dev accepts (the counts decide the predicate alone)
+static uint64_t pops_middle_triples(uint32_t n_pops) { return (uint64_t)(n_pops - 2) * (n_pops - 3) * (n_pops - 4) / 6; }
+static const PopsStat kF4RatioPops = {"pgt_f4ratio_pops_reduce", 5, true, pops_middle_triples, "n_triples", sizeof(pgt_f4ratio_row), pgt_f4ratio_pops_tree_bytes, 7};
+size_t pgt_f4ratio_pops_tree_bytes(uint32_t n_pops, uint64_t n_sites) { return pops_tree_bytes(kF4RatioPops, 3, n_pops, n_sites); }
+static_assert(sizeof(pgt_f4ratio_row) == 48 && offsetof(pgt_f4ratio_row, reserved_) == 16 && offsetof(pgt_f4ratio_row, g_ij) == offsetof(pgt_f4_row, f4_ij_kl) &&
+              offsetof(pgt_f4ratio_row, g_ik) == offsetof(pgt_f4_row, f4_ik_jl) && offsetof(pgt_f4ratio_row, g_jk) == offsetof(pgt_f4_row, f4_il_jk) &&
+              sizeof(pgt_f4ratio_total) == 40 && offsetof(pgt_f4ratio_total, neff) == 24 && sizeof(pgt_f4ratio_jack) == 48, "the documented layouts");
+
+int pgt_f4ratio_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind,
+                                uint32_t n_pops, uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_f4ratio_row *out,
+                                size_t out_bytes, pgt_f4ratio_total *tot, void *tree, size_t tree_bytes, void *stream) {
+    return pops_reduce_dev(ctx, kF4RatioPops, launch_f4ratio_pops, pos, freq, nind, n_pops, n, minind, win, n_win, out, out_bytes, tot, tree, tree_bytes, stream);
+}
+
 // Block jackknife of the rows above: its own checks (no columns, no window table), the message prefix of both forms.
 // One text for the estimators (D: pgt_dstat_jackknife; the mean of f3: pgt_f3_jackknife; the mean of f4: pgt_f4_jackknife): rows
 // and results of all are 48 bytes, so plan, workspace and every check are the same, under the entry's own prefix, name of the
-// tables and largest number of them.
+// tables and largest number of them.  The ratio of the f4-ratio (pgt_f4ratio_jackknife) goes through them too, with six items
+// per table where the others have three: its results and its workspace are larger by that.
 size_t pgt_dstat_jackknife_work_bytes(uint32_t n_trios, uint64_t n_win) {
     if (n_trios < 1 || n_trios > kJackMaxTrios) return 0;
     return jack_work(n_trios, n_win).bytes;
@@ -794,12 +810,18 @@ size_t pgt_f4_jackknife_work_bytes(uint32_t n_quartets, uint64_t n_win) {
     return n_quartets <= kJackMaxQuartets ? pgt_dstat_jackknife_work_bytes(n_quartets, n_win) : 0;
 }
 
-enum JackEstimator { kJackD, kJackF3Mean, kJackF4Mean };
-static const char *jack_who(JackEstimator est) {
-    return est == kJackD ? "pgt_dstat_jackknife: " : (est == kJackF3Mean ? "pgt_f3_jackknife: " : "pgt_f4_jackknife: ");
+size_t pgt_f4ratio_jackknife_work_bytes(uint32_t n_triples, uint64_t n_win) {
+    if (n_triples < 1 || n_triples > kJackMaxTriples) return 0;
+    return jack_work(n_triples, n_win, kJackRatioItems).bytes;
 }
-static const char *jack_tables_word(JackEstimator est) { return est == kJackF4Mean ? "n_quartets" : "n_trios"; }
-static uint32_t jack_max_tables(JackEstimator est) { return est == kJackF4Mean ? kJackMaxQuartets : kJackMaxTrios; }
+
+enum JackEstimator { kJackD, kJackF3Mean, kJackF4Mean, kJackF4Ratio };
+static const char *jack_who(JackEstimator est) {
+    return est == kJackD ? "pgt_dstat_jackknife: " : (est == kJackF3Mean ? "pgt_f3_jackknife: " : (est == kJackF4Mean ? "pgt_f4_jackknife: " : "pgt_f4ratio_jackknife: "));
+}
+static const char *jack_tables_word(JackEstimator est) { return est == kJackF4Mean ? "n_quartets" : (est == kJackF4Ratio ? "n_triples" : "n_trios"); }
+static uint32_t jack_max_tables(JackEstimator est) { return est == kJackF4Mean ? kJackMaxQuartets : (est == kJackF4Ratio ? kJackMaxTriples : kJackMaxTrios); }
+static int jack_items(JackEstimator est) { return est == kJackF4Ratio ? kJackRatioItems : kJackTopologies; }
 static_assert(kJackMaxQuartets <= kJackMaxTrios, "jack_work is sized for up to kJackMaxTrios tables");
 
 static int jack_check_range(pgt_ctx *ctx, JackEstimator est, uint32_t n_trios, uint64_t n_win) {
@@ -811,6 +833,7 @@ static int jack_check_range(pgt_ctx *ctx, JackEstimator est, uint32_t n_trios, u
 }
 static_assert(sizeof(pgt_f3_row) == sizeof(pgt_dstat_row) && sizeof(pgt_f3_jack) == sizeof(pgt_dstat_jack), "one set of jackknife checks");
 static_assert(sizeof(pgt_f4_row) == sizeof(pgt_dstat_row) && sizeof(pgt_f4_jack) == sizeof(pgt_dstat_jack), "one set of jackknife checks");
+static_assert(sizeof(pgt_f4ratio_row) == sizeof(pgt_dstat_row) && sizeof(pgt_f4ratio_jack) == sizeof(pgt_dstat_jack), "one set of jackknife checks");
 
 static int jackknife_dev(pgt_ctx *ctx, JackEstimator est, const void *rows, uint64_t n_win, uint32_t n_trios, void *out,
                          size_t out_bytes, void *work, size_t work_bytes, void *stream) {
@@ -822,8 +845,8 @@ static int jackknife_dev(pgt_ctx *ctx, JackEstimator est, const void *rows, uint
     if (!aligned16(rows)) return ctx_fail(ctx, PGT_EARG, who + "rows is not 16-byte aligned");
     if (reinterpret_cast<uintptr_t>(out) & 7u) return ctx_fail(ctx, PGT_EARG, who + "out is not 8-byte aligned");
     if (!aligned16(work)) return ctx_fail(ctx, PGT_EARG, who + "work is not 16-byte aligned");
-    if (int rc = room_check(ctx, (who + "out_bytes").c_str(), (uint64_t)n_trios * kJackTopologies, sizeof(pgt_dstat_jack), out_bytes)) return rc;
-    const size_t need = jack_work(n_trios, n_win).bytes;
+    if (int rc = room_check(ctx, (who + "out_bytes").c_str(), (uint64_t)n_trios * jack_items(est), sizeof(pgt_dstat_jack), out_bytes)) return rc;
+    const size_t need = jack_work(n_trios, n_win, jack_items(est)).bytes;
     if (work_bytes < need)
         return ctx_fail(ctx, PGT_EARG, who + "work_bytes too small (" + std::to_string(work_bytes) + " bytes, " + std::to_string(need) + " needed)");
     void *q0 = nullptr, *q1 = nullptr;
@@ -833,6 +856,8 @@ static int jackknife_dev(pgt_ctx *ctx, JackEstimator est, const void *rows, uint
         ctx->have_timing = true;
         ctx->timing_query_only = true;
     }
+    if (est == kJackF4Ratio)
+        return launch_f4ratio_jackknife(static_cast<const pgt_f4ratio_row *>(rows), n_win, n_trios, static_cast<pgt_f4ratio_jack *>(out), work, stream, q0, q1, &ctx->error);
     if (est == kJackF4Mean)
         return launch_f4_jackknife(static_cast<const pgt_f4_row *>(rows), n_win, n_trios, static_cast<pgt_f4_jack *>(out), work, stream, q0, q1, &ctx->error);
     if (est == kJackF3Mean)
@@ -858,6 +883,13 @@ int pgt_f4_jackknife_dev(pgt_ctx *ctx, const pgt_f4_row *rows, uint64_t n_win, u
                          size_t out_bytes, void *work, size_t work_bytes, void *stream) {
     PGT_USE_DEVICE(ctx);
     return jackknife_dev(ctx, kJackF4Mean, rows, n_win, n_quartets, out, out_bytes, work, work_bytes, stream);
+}
+
+// out: 6 n_triples items, u = 6 t + c with c the (B, X, C) of middle triple t
+int pgt_f4ratio_jackknife_dev(pgt_ctx *ctx, const pgt_f4ratio_row *rows, uint64_t n_win, uint32_t n_triples, pgt_f4ratio_jack *out,
+                              size_t out_bytes, void *work, size_t work_bytes, void *stream) {
+    PGT_USE_DEVICE(ctx);
+    return jackknife_dev(ctx, kJackF4Ratio, rows, n_win, n_triples, out, out_bytes, work, work_bytes, stream);
 }
 
 size_t pgt_align_workspace_bytes(uint32_t n_files, uint64_t n_rows_file0) {
@@ -1292,6 +1324,13 @@ int pgt_f4_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *f
     return pops_reduce_host(ctx, kF4Pops, pgt_f4_pops_reduce_dev, pos, freq, nind, n_pops, n, minind, win, n_win, out, tot);
 }
 
+/* the f4-ratio sums of all middle triples: the host-buffer form, as pgt_f4_pops_reduce */
+int pgt_f4ratio_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
+                            uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_f4ratio_row *out, pgt_f4ratio_total *tot) {
+    PGT_USE_DEVICE(ctx);
+    return pops_reduce_host(ctx, kF4RatioPops, pgt_f4ratio_pops_reduce_dev, pos, freq, nind, n_pops, n, minind, win, n_win, out, tot);
+}
+
 /* PBS of all trios: the host-buffer form, as pgt_f3_pops_reduce, one per FST estimator */
 int pgt_pbs_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
                         uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_pbs_row *out, pgt_pbs_total *tot) {
@@ -1305,13 +1344,13 @@ int pgt_pbs_hudson_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *
     return pops_reduce_host(ctx, kPbsPops, pgt_pbs_hudson_pops_reduce_dev, pos, freq, nind, n_pops, n, minind, win, n_win, out, tot);
 }
 
-/* block jackknife of a host table of rows: rows up, the device form on the cached workspace, 3 n_trios results down */
+/* block jackknife of a host table of rows: rows up, the device form on the cached workspace, 3 (f4-ratio: 6) n_trios results down */
 static int jackknife_host(pgt_ctx *ctx, JackEstimator est, const void *rows, uint64_t n_win, uint32_t n_trios, void *out) {
     const std::string who = jack_who(est);
     if (int rc = jack_check_range(ctx, est, n_trios, n_win)) return rc;
     if ((n_win && !rows) || !out) return ctx_fail(ctx, PGT_EARG, who + "NULL argument");
-    const size_t row_bytes = (size_t)n_trios * n_win * sizeof(pgt_dstat_row), out_bytes = (size_t)n_trios * kJackTopologies * sizeof(pgt_dstat_jack);
-    const size_t work_bytes = jack_work(n_trios, n_win).bytes;
+    const size_t row_bytes = (size_t)n_trios * n_win * sizeof(pgt_dstat_row), out_bytes = (size_t)n_trios * jack_items(est) * sizeof(pgt_dstat_jack);
+    const size_t work_bytes = jack_work(n_trios, n_win, jack_items(est)).bytes;
     void *drows = nullptr, *dwork = nullptr, *dout = nullptr;
     if (int rc = workspace(ctx, HostIo::kRows, row_bytes, &drows)) return rc;
     if (int rc = workspace(ctx, HostIo::kTree, work_bytes, &dwork)) return rc;
@@ -1336,6 +1375,11 @@ int pgt_f3_jackknife(pgt_ctx *ctx, const pgt_f3_row *rows, uint64_t n_win, uint3
 int pgt_f4_jackknife(pgt_ctx *ctx, const pgt_f4_row *rows, uint64_t n_win, uint32_t n_quartets, pgt_f4_jack *out) {
     PGT_USE_DEVICE(ctx);
     return jackknife_host(ctx, kJackF4Mean, rows, n_win, n_quartets, out);
+}
+
+int pgt_f4ratio_jackknife(pgt_ctx *ctx, const pgt_f4ratio_row *rows, uint64_t n_win, uint32_t n_triples, pgt_f4ratio_jack *out) {
+    PGT_USE_DEVICE(ctx);
+    return jackknife_host(ctx, kJackF4Ratio, rows, n_win, n_triples, out);
 }
 
 /* ---------------- window tables built on the device ---------------- */

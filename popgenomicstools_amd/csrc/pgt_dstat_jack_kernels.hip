@@ -18,14 +18,16 @@
 // h_j, theta_J, tau_j and sigma^2 as above.  The estimator (struct D, struct Mean below: F3Mean, and F4Mean over the rows of
 // pgt_f4_pops_reduce_dev) is a template parameter of the phases that look at an estimate; the totals, the plan, the chunking,
 // readd(), the workspace layout and the order of every addition are common, and all row types are 48 bytes with n and the three
-// sums at the same offsets.
+// sums at the same offsets.  A third estimator, the signed RATIO of two of a row's sums (struct Ratio: the f4-ratio's admixture
+// proportions, pgt_f4ratio_jackknife_dev), has SIX items per row where the others have three: the item count is a constant of
+// the estimator (kItems) that sizes the per-lane arrays and the partials of phases 2 and 3.
 //
 // Three dependent reductions over the rows and one closing kernel, all on the plan of jack_plan(n_win) (pgt_internal.h):
 //   phase 1  jack_totals_kernel   per wave Σbbaa, Σabba, Σbaba, Σn, g of its chunks                 -> 5 words per wave
 //   phase 2  jack_drop_kernel     re-adds phase 1's partials of its trio (theta), then per topology
-//                                 Σ (1 - m_j / n) theta_-j over its chunks                          -> 3 doubles per wave
+//                                 Σ (1 - m_j / n) theta_-j over its chunks                          -> 3 doubles per wave (Ratio: 6)
 //   phase 3  jack_var_kernel      re-adds phases 1 and 2 (theta_J), then per topology
-//                                 Σ (tau_j - theta_J)^2 / (h_j - 1) over its chunks                 -> 3 doubles per wave
+//                                 Σ (tau_j - theta_J)^2 / (h_j - 1) over its chunks                 -> 3 doubles per wave (Ratio: 6)
 //   close    jack_close_kernel    one wave per item: re-adds all three, writes pgt_dstat_jack
 // The grid is (ceil(n_partials / 4), n_trios) workgroups of 4 waves: blockIdx.y is the trio, wave p of it walks the chunks
 // [p * chunks_per_wave, (p + 1) * chunks_per_wave) — 64 consecutive 48-byte rows each, one row per lane, all three topologies
@@ -57,8 +59,8 @@ struct JackArgs {
     uint32_t n_partials;
     uint32_t n_trios;
     uint64_t *totals;          // [trio][5][n_partials]: Σbbaa, Σabba, Σbaba as f64 bits, Σn, g
-    double *drop;              // [trio][3][n_partials]
-    double *var;               // [trio][3][n_partials]
+    double *drop;              // [trio][Est::kItems][n_partials]: 3, or the 6 of Ratio
+    double *var;               // [trio][Est::kItems][n_partials]
 };
 
 __device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
@@ -82,6 +84,8 @@ __device__ __forceinline__ double topo_y(int c, double abba, double baba) { retu
 struct D {  // Patterson's D of topology c: ratio(x, y) of two of the three sums (the head of this file)
     using Row = pgt_dstat_row;
     using Out = pgt_dstat_jack;
+    static constexpr int kItems = kJackTopologies;
+    static constexpr bool kDropFromSums = false;
     static __device__ __forceinline__ double theta(int c, const double *s, double) { return ratio(topo_x(c, s[0], s[1]), topo_y(c, s[1], s[2])); }
     static __device__ __forceinline__ double theta_drop(int c, const double *s, double, double bbaa, double abba, double baba, double) {
         return ratio(__dsub_rn(topo_x(c, s[0], s[1]), topo_x(c, bbaa, abba)), __dsub_rn(topo_y(c, s[1], s[2]), topo_y(c, abba, baba)));
@@ -99,6 +103,8 @@ template <class RowT, class OutT>
 struct Mean {
     using Row = RowT;
     using Out = OutT;
+    static constexpr int kItems = kJackTopologies;
+    static constexpr bool kDropFromSums = false;
     static __device__ __forceinline__ double pick(int c, double x0, double x1, double x2) { return c == 0 ? x0 : (c == 1 ? x1 : x2); }
     static __device__ __forceinline__ double theta(int c, const double *s, double n) { return mean(pick(c, s[0], s[1], s[2]), n); }
     static __device__ __forceinline__ double theta_drop(int c, const double *s, double n, double x0, double x1, double x2, double m) {
@@ -108,6 +114,29 @@ struct Mean {
 };
 using F3Mean = Mean<pgt_f3_row, pgt_f3_jack>;  // item c: f3 with target c of the trio
 using F4Mean = Mean<pgt_f4_row, pgt_f4_jack>;  // item c: f4 of pairing c of the quartet, (ij;kl) / (ik;jl) / (il;jk)
+// The f4-ratio (pgt_f4ratio_jackknife_dev): the SIGNED RATIO OF TWO BLOCK SUMS, numerator and denominator losing a block together.
+// A row's sums are S0, S1, S2 = Σ e d_ij, Σ e d_ik, Σ e d_jk of middle triple (i, j, k); item c is alpha(B, X, C) =
+// f4(A,O; X,C) / f4(A,O; B,C), SIX per row:    c  (B,X,C)   N_c   D_c          c  (B,X,C)   N_c   D_c
+//                                              0  (i,j,k)   +S2   +S1          3  (k,i,j)   +S0   -S2
+//                                              1  (j,i,k)   +S1   +S2          4  (j,k,i)   +S1   +S0
+//                                              2  (i,k,j)   -S2   +S0          5  (k,j,i)   +S0   +S1
+//     theta = q(N_c, D_c)                             theta_-j = q(N_c - n_cj, D_c - d_cj)     q = mean above; the weight decides "used" alone
+// N_c and D_c are single sums under a sign, and negation is exact: taking block j out of the three sums first and reading the
+// item off the rest is the same value, so this estimator states theta alone (kDropFromSums; theta_without below).
+struct Ratio {
+    using Row = pgt_f4ratio_row;
+    using Out = pgt_f4ratio_jack;
+    static constexpr int kItems = kJackRatioItems;
+    static constexpr bool kDropFromSums = true;
+    static __device__ __forceinline__ double num(int c, double s0, double s1, double s2) {
+        return c == 0 ? s2 : (c == 1 || c == 4 ? s1 : (c == 2 ? -s2 : s0));
+    }
+    static __device__ __forceinline__ double den(int c, double s0, double s1, double s2) {
+        return c == 0 || c == 5 ? s1 : (c == 1 ? s2 : (c == 3 ? -s2 : s0));
+    }
+    static __device__ __forceinline__ double theta(int c, const double *s, double) { return mean(num(c, s[0], s[1], s[2]), den(c, s[0], s[1], s[2])); }
+    static __device__ __forceinline__ void set(Out &r, double th, double th_j, double se, double z) { r.alpha = th; r.alpha_jack = th_j; r.se = se; r.z = z; }
+};
 
 // Σ of n_partials doubles in index order per lane (l, l + 64, ..), then the butterfly: the same bits in every lane of every wave
 __device__ __forceinline__ double readd(const double *p, uint32_t n_partials, int lane) {
@@ -177,11 +206,30 @@ static_assert(offsetof(pgt_f4_row, n) == offsetof(pgt_f3_row, n) && offsetof(pgt
 static_assert(offsetof(pgt_f4_jack, f4) == offsetof(pgt_f3_jack, f3) && offsetof(pgt_f4_jack, f4_jack) == offsetof(pgt_f3_jack, f3_jack) &&
               offsetof(pgt_f4_jack, se) == offsetof(pgt_f3_jack, se) && offsetof(pgt_f4_jack, n_blocks) == offsetof(pgt_f3_jack, n_blocks),
               "pgt_f4_jack in pgt_f3_jack's layout");
+// ... and the rows of pgt_f4ratio_pops_reduce_dev; its results have the layout of pgt_f4_jack
+static_assert(sizeof(pgt_f4ratio_row) == sizeof(pgt_f4_row) && sizeof(pgt_f4ratio_jack) == sizeof(pgt_f4_jack), "one row loader, one result layout");
+static_assert(offsetof(pgt_f4ratio_row, n) == offsetof(pgt_f4_row, n) && offsetof(pgt_f4ratio_row, g_ij) == offsetof(pgt_f4_row, f4_ij_kl) &&
+              offsetof(pgt_f4ratio_row, g_ik) == offsetof(pgt_f4_row, f4_ik_jl) && offsetof(pgt_f4ratio_row, g_jk) == offsetof(pgt_f4_row, f4_il_jk),
+              "the three sums of an f4-ratio row at the offsets of f4_ij_kl / f4_ik_jl / f4_il_jk");
+static_assert(offsetof(pgt_f4ratio_jack, alpha) == offsetof(pgt_f4_jack, f4) && offsetof(pgt_f4ratio_jack, alpha_jack) == offsetof(pgt_f4_jack, f4_jack) &&
+              offsetof(pgt_f4ratio_jack, se) == offsetof(pgt_f4_jack, se) && offsetof(pgt_f4ratio_jack, n_blocks) == offsetof(pgt_f4_jack, n_blocks),
+              "pgt_f4ratio_jack in pgt_f4_jack's layout");
 
 // wave p of trio blockIdx.y; -1: a wave that pads the last workgroup (it returns: no barrier is ever used)
 __device__ __forceinline__ int64_t my_partial(const JackArgs &a) {
     const uint32_t p = blockIdx.x * (blockDim.x >> 6) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     return p < a.n_partials ? (int64_t)p : -1;
+}
+
+// theta_-j of item c: the estimator's own statement of it, or (kDropFromSums) its theta of the sums and the weight less block j's
+template <class Est>
+__device__ __forceinline__ double theta_without(int c, const Totals &t, double x0, double x1, double x2, double m) {
+    if constexpr (Est::kDropFromSums) {
+        const double rest[3] = {__dsub_rn(t.s[0], x0), __dsub_rn(t.s[1], x1), __dsub_rn(t.s[2], x2)};
+        return Est::theta(c, rest, __dsub_rn(t.n, m));
+    } else {
+        return Est::theta_drop(c, t.s, t.n, x0, x1, x2, m);
+    }
 }
 
 // ---- phase 1: the totals -----------------------------------------------------------------------------------------------------
@@ -224,19 +272,22 @@ __global__ __launch_bounds__(256) void jack_drop_kernel(JackArgs a) {
     if (pp < 0) return;
     const uint32_t p = (uint32_t)pp;
     const Totals t = read_totals(a, trio, lane);
-    double acc[kJackTopologies] = {0.0, 0.0, 0.0};
+    constexpr int kItems = Est::kItems;
+    double acc[kItems];
+#pragma unroll
+    for (int c = 0; c < kItems; ++c) acc[c] = 0.0;
     for_rows(a, trio, p, lane, [&](bool used, uint32_t m, double bbaa, double abba, double baba) {
         const double w = __dsub_rn(1.0, __ddiv_rn((double)m, t.n));
 #pragma unroll
-        for (int c = 0; c < kJackTopologies; ++c) {
-            const double th = Est::theta_drop(c, t.s, t.n, bbaa, abba, baba, (double)m);
+        for (int c = 0; c < kItems; ++c) {
+            const double th = theta_without<Est>(c, t, bbaa, abba, baba, (double)m);
             acc[c] = __dadd_rn(acc[c], used ? __dmul_rn(w, th) : 0.0);
         }
     });
 #pragma unroll
-    for (int c = 0; c < kJackTopologies; ++c) {
+    for (int c = 0; c < kItems; ++c) {
         const double v = dev::wave_sum(acc[c]);
-        if (lane == 0) a.drop[((uint64_t)trio * kJackTopologies + c) * a.n_partials + p] = v;
+        if (lane == 0) a.drop[((uint64_t)trio * kItems + c) * a.n_partials + p] = v;
     }
 }
 
@@ -244,7 +295,7 @@ __global__ __launch_bounds__(256) void jack_drop_kernel(JackArgs a) {
 template <class Est>
 __device__ __forceinline__ void estimates(const JackArgs &a, const Totals &t, uint32_t trio, int c, int lane, double *theta, double *theta_j) {
     *theta = Est::theta(c, t.s, t.n);
-    const double drop = readd(a.drop + ((uint64_t)trio * kJackTopologies + c) * a.n_partials, a.n_partials, lane);
+    const double drop = readd(a.drop + ((uint64_t)trio * Est::kItems + c) * a.n_partials, a.n_partials, lane);
     *theta_j = __dsub_rn(__dmul_rn((double)t.g, *theta), drop);
 }
 
@@ -257,23 +308,27 @@ __global__ __launch_bounds__(256) void jack_var_kernel(JackArgs a) {
     if (pp < 0) return;
     const uint32_t p = (uint32_t)pp;
     const Totals t = read_totals(a, trio, lane);
-    double theta[kJackTopologies], theta_j[kJackTopologies], acc[kJackTopologies] = {0.0, 0.0, 0.0};
+    constexpr int kItems = Est::kItems;
+    double theta[kItems], theta_j[kItems], acc[kItems];
 #pragma unroll
-    for (int c = 0; c < kJackTopologies; ++c) estimates<Est>(a, t, trio, c, lane, &theta[c], &theta_j[c]);
+    for (int c = 0; c < kItems; ++c) {
+        estimates<Est>(a, t, trio, c, lane, &theta[c], &theta_j[c]);
+        acc[c] = 0.0;
+    }
     for_rows(a, trio, p, lane, [&](bool used, uint32_t m, double bbaa, double abba, double baba) {
         const double hm1 = __dsub_rn(__ddiv_rn(t.n, (double)m), 1.0);  // an unused block: inf, selected away below
 #pragma unroll
-        for (int c = 0; c < kJackTopologies; ++c) {
-            const double th = Est::theta_drop(c, t.s, t.n, bbaa, abba, baba, (double)m);
+        for (int c = 0; c < kItems; ++c) {
+            const double th = theta_without<Est>(c, t, bbaa, abba, baba, (double)m);
             const double tau = __dadd_rn(theta[c], __dmul_rn(hm1, __dsub_rn(theta[c], th)));
             const double dv = __dsub_rn(tau, theta_j[c]);
             acc[c] = __dadd_rn(acc[c], used ? __ddiv_rn(__dmul_rn(dv, dv), hm1) : 0.0);
         }
     });
 #pragma unroll
-    for (int c = 0; c < kJackTopologies; ++c) {
+    for (int c = 0; c < kItems; ++c) {
         const double v = dev::wave_sum(acc[c]);
-        if (lane == 0) a.var[((uint64_t)trio * kJackTopologies + c) * a.n_partials + p] = v;
+        if (lane == 0) a.var[((uint64_t)trio * kItems + c) * a.n_partials + p] = v;
     }
 }
 
@@ -282,13 +337,13 @@ template <class Est>
 __global__ __launch_bounds__(256) void jack_close_kernel(JackArgs a, typename Est::Out *__restrict__ out) {
     const int lane = threadIdx.x & (kWave - 1);
     const uint32_t u = blockIdx.x * (blockDim.x >> 6) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    if (u >= a.n_trios * kJackTopologies) return;
-    const uint32_t trio = u / kJackTopologies;
-    const int c = (int)(u % kJackTopologies);
+    if (u >= a.n_trios * Est::kItems) return;
+    const uint32_t trio = u / Est::kItems;
+    const int c = (int)(u % Est::kItems);
     const Totals t = read_totals(a, trio, lane);  // without a partial (n_win == 0): zeros
     double theta, theta_j;
     estimates<Est>(a, t, trio, c, lane, &theta, &theta_j);
-    const double vs = readd(a.var + ((uint64_t)trio * kJackTopologies + c) * a.n_partials, a.n_partials, lane);
+    const double vs = readd(a.var + ((uint64_t)trio * Est::kItems + c) * a.n_partials, a.n_partials, lane);
     typename Est::Out r;
     r.n_sites = t.n_sites;
     r.n_blocks = t.g;
@@ -308,7 +363,7 @@ int launch_jackknife(const typename Est::Row *rows, uint64_t n_win, uint32_t n_t
                      void *stream, void *ev_query0, void *ev_query1, std::string *err) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     const JackPlan plan = jack_plan(n_win);
-    const JackWork w = jack_work(n_trios, n_win);
+    const JackWork w = jack_work(n_trios, n_win, Est::kItems);
     JackArgs a{};
     a.rows = reinterpret_cast<const char *>(rows);
     a.n_win = n_win;
@@ -329,7 +384,7 @@ int launch_jackknife(const typename Est::Row *rows, uint64_t n_win, uint32_t n_t
         hipLaunchKernelGGL(jack_var_kernel<Est>, grid, dim3(256), 0, s, a);
         if (int rc = hip_fail(hipGetLastError(), "jack_var_kernel", err)) return rc;
     }
-    hipLaunchKernelGGL(jack_close_kernel<Est>, dim3((n_trios * kJackTopologies + 3) / 4), dim3(256), 0, s, a, out);
+    hipLaunchKernelGGL(jack_close_kernel<Est>, dim3((n_trios * Est::kItems + 3) / 4), dim3(256), 0, s, a, out);
     if (int rc = hip_fail(hipGetLastError(), "jack_close_kernel", err)) return rc;
     return record_event(ev_query1, s, err);
 }
@@ -351,6 +406,12 @@ int launch_f3_jackknife(const pgt_f3_row *rows, uint64_t n_win, uint32_t n_trios
 int launch_f4_jackknife(const pgt_f4_row *rows, uint64_t n_win, uint32_t n_quartets, pgt_f4_jack *out, void *work,
                         void *stream, void *ev_query0, void *ev_query1, std::string *err) {
     return launch_jackknife<F4Mean>(rows, n_win, n_quartets, out, work, stream, ev_query0, ev_query1, err);
+}
+
+// the rows of pgt_f4ratio_pops_reduce_dev: item u = 6 t + c is admixture proportion c of middle triple t (Ratio)
+int launch_f4ratio_jackknife(const pgt_f4ratio_row *rows, uint64_t n_win, uint32_t n_triples, pgt_f4ratio_jack *out, void *work,
+                             void *stream, void *ev_query0, void *ev_query1, std::string *err) {
+    return launch_jackknife<Ratio>(rows, n_win, n_triples, out, work, stream, ev_query0, ev_query1, err);
 }
 
 }  // namespace pgt

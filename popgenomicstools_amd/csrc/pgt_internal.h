@@ -184,6 +184,7 @@ constexpr uint32_t kJackMaxPartials = 1024;  // waves, and partials of each phas
 constexpr uint32_t kJackMaxTrios = 20;       // C(6, 3): what pgt_dstat_pops_reduce_dev can write
 constexpr int kJackTotalWords = 5;           // phase 1 per wave: Σbbaa, Σabba, Σbaba (f64), Σn (u64), used blocks (u64)
 constexpr int kJackTopologies = 3;           // phases 2 and 3 per wave: one f64 per topology
+constexpr int kJackRatioItems = 6;           // ... and per admixture proportion of a middle triple (pgt_f4ratio_jackknife_dev)
 struct JackPlan {
     uint64_t chunks = 0;           // ceil(n_win / kJackChunk)
     uint64_t chunks_per_wave = 0;  // ceil(chunks / kJackMaxPartials)
@@ -205,15 +206,16 @@ struct JackWork {
     size_t totals = 0, drop = 0, var = 0;  // byte offsets of the three phases' partials
     size_t bytes = 0;
 };
-inline JackWork jack_work(uint32_t n_trios, uint64_t n_win) {
+// items: the estimator's items per table (kJackTopologies; the ratio of pgt_f4ratio_jackknife_dev: kJackRatioItems)
+inline JackWork jack_work(uint32_t n_trios, uint64_t n_win, int items = kJackTopologies) {
     JackWork w;
     const size_t per = (size_t)n_trios * jack_plan(n_win).n_partials * 8;
     w.totals = 0;
     w.drop = w.totals + per * kJackTotalWords;
-    w.var = w.drop + per * kJackTopologies;
+    w.var = w.drop + per * items;
     const JackPlan p = jack_plan(n_win);
     const size_t cap = (size_t)(p.chunks < kJackMaxPartials ? p.chunks : kJackMaxPartials);
-    w.bytes = (((size_t)n_trios * cap * 8 * (kJackTotalWords + 2 * kJackTopologies) + 255) / 256) * 256;
+    w.bytes = (((size_t)n_trios * cap * 8 * (kJackTotalWords + 2 * items) + 255) / 256) * 256;
     if (w.bytes == 0) w.bytes = 256;
     return w;
 }
@@ -227,6 +229,11 @@ int launch_f3_jackknife(const pgt_f3_row *rows, uint64_t n_win, uint32_t n_trios
 constexpr uint32_t kJackMaxQuartets = 15;    // C(6, 4): what pgt_f4_pops_reduce_dev can write
 int launch_f4_jackknife(const pgt_f4_row *rows, uint64_t n_win, uint32_t n_quartets, pgt_f4_jack *out, void *work,
                         void *stream, void *ev_query0, void *ev_query1, std::string *err);
+// the signed ratio of two block sums (Ratio), six items per table, over the rows of pgt_f4ratio_pops_reduce_dev:
+// 1 <= n_triples <= kJackMaxTriples; the workspace is jack_work(n_triples, n_win, kJackRatioItems)
+constexpr uint32_t kJackMaxTriples = 10;     // C(5, 3): what pgt_f4ratio_pops_reduce_dev can write
+int launch_f4ratio_jackknife(const pgt_f4ratio_row *rows, uint64_t n_win, uint32_t n_triples, pgt_f4ratio_jack *out, void *work,
+                             void *stream, void *ev_query0, void *ev_query1, std::string *err);
 
 // Speed-only hints of a context (pgt_set_max_window, pgt_set_window_step); 0 = unknown.
 struct Hints {
@@ -328,6 +335,13 @@ int launch_f4_pops(const uint32_t *pos, const double *const *freq, const int32_t
                    uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_f4_row *out, pgt_f4_total *tot,
                    void *tree, const LaunchEnv &e);
 
+// pgt_f4ratio_pops_kernels.hip: the f4-ratio sums of ALL triples of the middle populations 1 .. n_pops - 2, between population 0
+// (A) and the last one (the outgroup); tot = C(n_pops - 2, 3) device totals or NULL; 5 <= n_pops <= 7 and minind >= 1 (checked
+// by the caller); out = one table of n_win rows per triple, in lexicographic order; a node is 3 T doubles and T u32
+int launch_f4ratio_pops(const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops,
+                        uint64_t n, int minind, const pgt_win *win, uint64_t n_win, pgt_f4ratio_row *out, pgt_f4ratio_total *tot,
+                        void *tree, const LaunchEnv &e);
+
 // pgt_pbs_pops_kernels.hip: the population branch statistic of ALL trios, every population of a trio as the focal one, in two
 // passes of the walk (three numerators, then three denominators per trio) and a finishing kernel.  A pass writes scratch rows
 // and scratch totals; the workspace holds the tree of one pass (pgt_f3_pops_reduce_dev's: 3 T doubles and T u32 per node,
@@ -425,6 +439,7 @@ int init_fd_pops_kernels(std::string *err);     // pgt_fd_pops_kernels.hip
 int init_f3_pops_kernels(std::string *err);     // pgt_f3_pops_kernels.hip
 int init_pbs_pops_kernels(std::string *err);    // pgt_pbs_pops_kernels.hip
 int init_f4_pops_kernels(std::string *err);     // pgt_f4_pops_kernels.hip
+int init_f4ratio_pops_kernels(std::string *err);  // pgt_f4ratio_pops_kernels.hip
 
 // thread-local message for the ctx-less entry points
 void set_global_error(const std::string &msg);

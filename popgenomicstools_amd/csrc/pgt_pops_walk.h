@@ -37,6 +37,7 @@ static_assert(kPieces == 4, "the build walks a leaf as two pairs of pieces");
 constexpr int trio_count(int np) { return (np - 1) * (np - 2) * (np - 3) / 6; }  // C(np - 1, 3): ingroup trios, the last population is the outgroup
 constexpr int all_trio_count(int np) { return np * (np - 1) * (np - 2) / 6; }     // C(np, 3): the trios of ALL populations (f3: no outgroup)
 constexpr int all_quartet_count(int np) { return np * (np - 1) * (np - 2) * (np - 3) / 24; }  // C(np, 4): the quartets of ALL populations (f4)
+constexpr int middle_triple_count(int np) { return (np - 2) * (np - 3) * (np - 4) / 6; }  // C(np - 2, 3): the triples between the first and the last population (f4-ratio)
 
 struct PopCols {
     const double *f[kPopsMaxPops];

@@ -54,7 +54,7 @@ static void help(const DxyOptions &o) {
                 "* All input MAF files need to have the same chromosomes in the same order\n"
                 "* Assumes SNPs are biallelic\n"
                 "\nLimits:\n"
-                "* Not computed: f4-ratio admixture proportions, user-chosen quartet lists, K = 7\n"
+                "* Not computed: f4-ratio admixture proportions (see f4ratioWindowPops), user-chosen quartet lists, K = 7\n"
                 "* One GPU is used (the first entry of PGT_DEVICES)\n"
                 "* No passes mode: input whose parsed files plus aligned columns do not fit the GPU, or PGT_MAX_RESIDENT_SITES, is refused\n"
                 "* PGT_DXY_SYNC=reference is not offered: the reference's catch-up loops are defined for two files only\n"

@@ -1,4 +1,4 @@
-// pops_common.h — the K-population hosts (dxyWindowPops, fstWindowPops, piWindowPops, dstatWindowPops, f3WindowPops, f4WindowPops, pbsWindowPops) are one
+// pops_common.h — the K-population hosts (dxyWindowPops, fstWindowPops, piWindowPops, dstatWindowPops, f3WindowPops, f4WindowPops, f4ratioWindowPops, pbsWindowPops) are one
 // program, run_pops_tool<Tool>: the command line (dxyWindow's options, the tool's own, -out PREFIX, the tool's number of MAF
 // files), from the opened files to the aligned columns and the window table on the device (load_pops — open, parse on the host or
 // the device, the resident-size refusals, chromosome ids, pgt_align_segments, upload, pgt_sites_align, pgt_gather_dev, the runs of
@@ -8,8 +8,8 @@
 // Messages carry the tool's name.  A tool is a struct (derived from PopsTool, which holds what most tools leave alone) with
 //     name, min_files, max_files, help(options)      the help text is the tool's own, verbatim
 //     own(option, value, argc, argv)                  an option of this tool alone: taken (or refused by die()) -> true
-//     arity, outgroup                                 its tables: all pairs (2), each population (1), all trios (3), all quartets (4) of the K files —
-//                                                     of the K-1 before the last with an outgroup
+//     arity, outgroup, first_apart                    its tables: all pairs (2), each population (1), all trios (3), all quartets (4) of the K files —
+//                                                     of the K-1 before the last with an outgroup, of those behind the first with first_apart
 //     Row, Total, ext, global_ext, row_bytes, tree_bytes, reduce_dev    the reduction and its files; tree_bytes(K, sites), or
 //                                                     (K, sites, windows) where the workspace holds more than the tree
 //     line(row, sites of the window), total(total)    the numbers of a row behind `chr`, of a PREFIX.global line behind the indices
@@ -352,11 +352,11 @@ struct PopsIndex {
     int n;
     int pop[4];
 };
-// all i < j < .. of `pops` populations, `arity` of them each, in the library's table order: (0,1),(0,2),..,(1,2),..
+// all i < j < .. of the populations first .. pops - 1, `arity` of them each, in the library's table order: (0,1),(0,2),..,(1,2),..
 // (a loop beyond the arity runs once; what it leaves in `pop` is not looked at)
-inline std::vector<PopsIndex> pops_tuples(int arity, int pops) {
+inline std::vector<PopsIndex> pops_tuples(int arity, int pops, int first = 0) {
     std::vector<PopsIndex> t;
-    for (int a = 0; a < pops; ++a)
+    for (int a = first; a < pops; ++a)
         for (int b = arity > 1 ? a + 1 : pops - 1; b < pops; ++b)
             for (int c = arity > 2 ? b + 1 : pops - 1; c < pops; ++c)
                 for (int d = arity > 3 ? c + 1 : pops - 1; d < pops; ++d) t.push_back({arity, {a, b, c, d}});
@@ -454,16 +454,16 @@ typename Pass::Row *pops_pass(const Pass &pass, PopsRun &run) {
 
 // -jackknife 1: the delete-m_j block jackknife of every trio of the run on its rows still on the device, every window of the table
 // a block -> PREFIX.jackknife, three lines per trio (`P1 P2 P3 estimate jackknife_estimate SE Z nblocks nsites`) or quartet
-// (`P1 P2 P3 P4 ..`).  order[u]: which of the table's populations line u names first, second, third (and fourth).  The entry
-// points' results are one layout.
+// (`P1 P2 P3 P4 ..`); U lines per table where the estimator has U items (the f4-ratio: six).  order[u]: which of the table's
+// populations line u names first, second, third (and fourth).  The entry points' results are one layout.
 struct PopsJack {
     double est, est_jack, se, z;
     uint64_t n_sites;
     uint32_t n_blocks, pad_;
 };
-template <class Row, class Jack, size_t N>
+template <class Row, class Jack, size_t U, size_t N>
 void pops_jackknife(PopsRun &run, const Row *d_rows, int (*jackknife_dev)(pgt_ctx *, const Row *, uint64_t, uint32_t, Jack *, size_t, void *, size_t, void *),
-                    size_t (*work_bytes)(uint32_t, uint64_t), const int (&order)[3][N]) {
+                    size_t (*work_bytes)(uint32_t, uint64_t), const int (&order)[U][N]) {
     static_assert(sizeof(Jack) == sizeof(PopsJack) && offsetof(Jack, se) == offsetof(PopsJack, se) && offsetof(Jack, z) == offsetof(PopsJack, z) &&
                   offsetof(Jack, n_sites) == offsetof(PopsJack, n_sites) && offsetof(Jack, n_blocks) == offsetof(PopsJack, n_blocks),
                   "the estimate and its jackknife estimate, then se, z, n_sites, n_blocks");
@@ -472,18 +472,18 @@ void pops_jackknife(PopsRun &run, const Row *d_rows, int (*jackknife_dev)(pgt_ct
     const size_t bytes = work_bytes((uint32_t)n_trios, n_win);
     void *work = nullptr;
     check(pgt_dev_alloc(ctx, bytes, &work), ctx);
-    Jack *d_jack = pops_dev_alloc<Jack>(ctx, 3 * n_trios);
-    check(jackknife_dev(ctx, d_rows, n_win, (uint32_t)n_trios, d_jack, 3 * n_trios * sizeof(Jack), work, bytes, nullptr), ctx);
-    auto jack = std::make_shared<std::vector<PopsJack>>(3 * n_trios);
-    check(pgt_rowbuf_read(ctx, jack->data(), d_jack, 3 * n_trios * sizeof(Jack), nullptr), ctx);
+    Jack *d_jack = pops_dev_alloc<Jack>(ctx, U * n_trios);
+    check(jackknife_dev(ctx, d_rows, n_win, (uint32_t)n_trios, d_jack, U * n_trios * sizeof(Jack), work, bytes, nullptr), ctx);
+    auto jack = std::make_shared<std::vector<PopsJack>>(U * n_trios);
+    check(pgt_rowbuf_read(ctx, jack->data(), d_jack, U * n_trios * sizeof(Jack), nullptr), ctx);
     run.writers.push_back([&run, jack, &order] {  // (order: a constant of the tool)
         const std::string path = std::string(run.args.prefix) + ".jackknife";
         FILE *f = open_out(path);
         auto g6 = [](double v) { char b_[64]; if (v != v) return std::string("nan"); std::snprintf(b_, sizeof b_, "%g", v); return std::string(b_); };
         for (size_t t = 0; t < run.tables.size(); ++t)
-            for (int u = 0; u < 3; ++u) {
+            for (size_t u = 0; u < U; ++u) {
                 const int *pop = run.tables[t].pop;
-                const PopsJack &r = (*jack)[3 * t + (size_t)u];
+                const PopsJack &r = (*jack)[U * t + u];
                 for (size_t k = 0; k < N; ++k) std::fprintf(f, "%d\t", pop[order[u][k]] + 1);
                 std::fprintf(f, "%s\t%s\t%s\t%s\t%u\t%llu\n", g6(r.est).c_str(), g6(r.est_jack).c_str(), g6(r.se).c_str(), g6(r.z).c_str(), r.n_blocks,
                              (unsigned long long)r.n_sites);
@@ -497,6 +497,7 @@ void pops_jackknife(PopsRun &run, const Row *d_rows, int (*jackknife_dev)(pgt_ct
 struct PopsTool {
     static constexpr int max_files = 8;
     static constexpr bool outgroup = false;      // the LAST file is the outgroup: it is in no table
+    static constexpr bool first_apart = false;   // the FIRST file has a role of its own (the f4-ratio's A): it is in no table either
     static constexpr bool window_hints = false;  // the hints choose the query strategy, and rows may differ in their last bits between strategies
     static constexpr const char *global_ext = ".global";
     bool own(const char *, const char *, int, char **) { return false; }
@@ -512,7 +513,7 @@ int run_pops_tool(int argc, char **argv) {
     DeviceOpener device(std::vector<int>{devices_from_env()[0]});  // one GPU; HIP start-up runs beside the opening of the files
     const PopsSites s = load_pops(Tool::name, args, timer, device);
     pgt_ctx *ctx = s.ctx;
-    PopsRun run{args, s, pops_tuples(Tool::arity, args.K - (Tool::outgroup ? 1 : 0))};
+    PopsRun run{args, s, pops_tuples(Tool::arity, args.K - (Tool::outgroup ? 1 : 0), Tool::first_apart ? 1 : 0)};
     if constexpr (std::is_invocable_v<decltype(Tool::tree_bytes), uint32_t, uint64_t, uint64_t>)
         run.tree_bytes = Tool::tree_bytes((uint32_t)args.K, s.n_sites, s.win.size());  // the table is known here
     else

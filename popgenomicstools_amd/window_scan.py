@@ -20,7 +20,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import (DSTAT_JACK_DTYPE, DSTAT_ROW_DTYPE, DSTAT_TOTAL_DTYPE, DXY_ROW_DTYPE, DXY_TOTAL_DTYPE, EXT_ROW_DTYPE, F3_JACK_DTYPE, F3_ROW_DTYPE, F3_TOTAL_DTYPE, F4_JACK_DTYPE, F4_ROW_DTYPE, F4_TOTAL_DTYPE, FD_ROW_DTYPE, FD_TOTAL_DTYPE, FST_ROW_DTYPE, FST_TOTAL_DTYPE, HET_ROW_DTYPE, PBS_ROW_DTYPE, PBS_TOTAL_DTYPE, PGT_EXT_IHS,
+from ._lib import (DSTAT_JACK_DTYPE, DSTAT_ROW_DTYPE, DSTAT_TOTAL_DTYPE, DXY_ROW_DTYPE, DXY_TOTAL_DTYPE, EXT_ROW_DTYPE, F3_JACK_DTYPE, F3_ROW_DTYPE, F3_TOTAL_DTYPE, F4_JACK_DTYPE, F4_ROW_DTYPE, F4_TOTAL_DTYPE, F4RATIO_JACK_DTYPE, F4RATIO_ROW_DTYPE, F4RATIO_TOTAL_DTYPE, FD_ROW_DTYPE, FD_TOTAL_DTYPE, FST_ROW_DTYPE, FST_TOTAL_DTYPE, HET_ROW_DTYPE, PBS_ROW_DTYPE, PBS_TOTAL_DTYPE, PGT_EXT_IHS,
                    PGT_EXT_XP_MAX, PGT_EXT_XP_MIN, PGT_STAT_DXY, PGT_STAT_EXT, PGT_STAT_FST, PGT_STAT_HET,
                    SEG_DTYPE, SHARD_DTYPE, WIN_DTYPE, PgtError, check)
 
@@ -270,8 +270,11 @@ class _PopsStat:
     per_trio: bool = False  # one row table per ingroup trio i < j < k (trio_order); the last population is the outgroup
     all_trios: bool = False  # one row table per trio i < j < k of ALL populations (all_trio_order): no outgroup
     all_quartets: bool = False  # one row table per quartet i < j < k < l of ALL populations (all_quartet_order)
+    middle_triples: bool = False  # one row table per triple i < j < k of the populations between the first and the last (middle_triple_order)
 
     def tables(self, n_pops: int) -> int:
+        if self.middle_triples:
+            return (n_pops - 2) * (n_pops - 3) * (n_pops - 4) // 6
         if self.all_quartets:
             return n_pops * (n_pops - 1) * (n_pops - 2) * (n_pops - 3) // 24
         if self.all_trios:
@@ -293,6 +296,7 @@ _DSTAT_POPS = _PopsStat("dstat", 4, False, DSTAT_ROW_DTYPE, DSTAT_TOTAL_DTYPE, m
 _FD_POPS = _PopsStat("fd", 4, False, FD_ROW_DTYPE, FD_TOTAL_DTYPE, max_pops=7, per_trio=True)
 _F3_POPS = _PopsStat("f3", 3, False, F3_ROW_DTYPE, F3_TOTAL_DTYPE, max_pops=6, all_trios=True)
 _F4_POPS = _PopsStat("f4", 4, False, F4_ROW_DTYPE, F4_TOTAL_DTYPE, max_pops=6, all_quartets=True)
+_F4RATIO_POPS = _PopsStat("f4ratio", 5, False, F4RATIO_ROW_DTYPE, F4RATIO_TOTAL_DTYPE, max_pops=7, middle_triples=True)
 _PBS_POPS = _PopsStat("pbs", 3, False, PBS_ROW_DTYPE, PBS_TOTAL_DTYPE, max_pops=6, all_trios=True)
 _PBS_HUDSON_POPS = _PopsStat("pbs_hudson", 3, False, PBS_ROW_DTYPE, PBS_TOTAL_DTYPE, max_pops=6, all_trios=True)
 _PBS_ESTIMATORS = {"wc": _PBS_POPS, "hudson": _PBS_HUDSON_POPS}  # pbs_window_pops(estimator=...), Context.pbs_pops_reduce*(estimator=...)
@@ -469,13 +473,13 @@ class Context:
         and their number n; f4 of the window is sum / n."""
         return self._pops_reduce(_F4_POPS, pos, freqs, ninds, minind, win)
 
-    def _jackknife(self, name: str, row: np.dtype, jack: np.dtype, rows) -> np.ndarray:
-        """The numpy form of a block jackknife (pgt_<name>_jackknife) -> [n_trios, 3] of `jack`."""
+    def _jackknife(self, name: str, row: np.dtype, jack: np.dtype, rows, items: int = 3) -> np.ndarray:
+        """The numpy form of a block jackknife (pgt_<name>_jackknife) -> [n_trios, items] of `jack`."""
         rows = np.ascontiguousarray(rows, dtype=row)
         if rows.ndim != 2:
             raise PgtError(_lib.PGT_EARG, f"{name}_jackknife: rows must be a [n_trios, n_win] table")
         n_trios, n_win = rows.shape
-        out = np.zeros((n_trios, 3), dtype=jack)
+        out = np.zeros((n_trios, items), dtype=jack)
         self._check(getattr(self._lib, f"pgt_{name}_jackknife")(self._ctx, rows.ctypes.data if rows.size else None, n_win, n_trios, out.ctypes.data))
         return out
 
@@ -496,6 +500,21 @@ class Context:
         [n_quartets, n_win] numpy table of F4_ROW_DTYPE rows (what f4_pops_reduce returns) over DISJOINT windows
         (pgt_f4_jackknife) -> [n_quartets, 3] F4_JACK_DTYPE, the pairings in pairing_order."""
         return self._jackknife("f4", F4_ROW_DTYPE, F4_JACK_DTYPE, rows)
+
+    def f4ratio_pops_reduce(self, pos, freqs, ninds, minind, win):
+        """The f4-ratio sums of ALL triples i<j<k of the middle populations 1 ... len(freqs) - 2 (middle_triple_order), between
+        population 0 (A) and the last one (the outgroup O), from 5 ... 7 per-population numpy (freq, nInd) columns, one pass:
+        -> (rows[n_triples, n_win], totals[n_triples]) (pgt_f4ratio_pops_reduce).  A row carries the three SUMS g_ij, g_ik, g_jk of
+        (p_A - p_O)(p_x - p_y) over the sites where all FIVE populations have minind individuals, and their number n; the six
+        admixture proportions of ratio_order(i, j, k) are ratios of two of them (f4ratio_alphas)."""
+        return self._pops_reduce(_F4RATIO_POPS, pos, freqs, ninds, minind, win)
+
+    def f4ratio_jackknife(self, rows) -> np.ndarray:
+        """Block-jackknife admixture proportion (the ratio of two sums over the used blocks, both losing a block together),
+        standard error and Z of every middle triple and each of its six (B, X, C) from a [n_triples, n_win] numpy table of
+        F4RATIO_ROW_DTYPE rows (what f4ratio_pops_reduce returns) over DISJOINT windows (pgt_f4ratio_jackknife)
+        -> [n_triples, 6] F4RATIO_JACK_DTYPE, in ratio_order."""
+        return self._jackknife("f4ratio", F4RATIO_ROW_DTYPE, F4RATIO_JACK_DTYPE, rows, items=6)
 
     # ---- device-resident columns (torch CUDA tensors) -------------------------------------
     @staticmethod
@@ -879,20 +898,21 @@ class Context:
     def dstat_jackknife_work_bytes(n_trios: int, n_win: int) -> int:
         return int(_lib.load().pgt_dstat_jackknife_work_bytes(int(n_trios), int(n_win)))
 
-    def _jackknife_dev(self, name: str, row: np.dtype, jack: np.dtype, rows, n_win, n_trios, out, work, stream):
-        """The device form of a block jackknife (pgt_<name>_jackknife_dev) -> (out, work)."""
+    def _jackknife_dev(self, name: str, row: np.dtype, jack: np.dtype, rows, n_win, n_trios, out, work, stream, items: int = 3):
+        """The device form of a block jackknife (pgt_<name>_jackknife_dev) -> (out, work); `items` results per table."""
         import torch
         who = f"{name}_jackknife_dev"
         n_win, n_trios = int(n_win), int(n_trios)
         wb = int(getattr(self._lib, f"pgt_{name}_jackknife_work_bytes")(n_trios, n_win))
         if wb == 0:
-            raise PgtError(_lib.PGT_EARG, f"{who}: n_quartets must be 1 ... 15" if name == "f4" else f"{who}: n_trios must be 1 ... 20")
+            raise PgtError(_lib.PGT_EARG, f"{who}: n_quartets must be 1 ... 15" if name == "f4" else
+                           (f"{who}: n_triples must be 1 ... 10" if name == "f4ratio" else f"{who}: n_trios must be 1 ... 20"))
         self._room(f"{who}: rows", rows, n_trios * n_win * row.itemsize)
         if out is None:
-            out = torch.empty(3 * n_trios * jack.itemsize, dtype=torch.uint8, device=rows.device)
+            out = torch.empty(items * n_trios * jack.itemsize, dtype=torch.uint8, device=rows.device)
         if work is None:
             work = torch.empty(wb, dtype=torch.uint8, device=rows.device)
-        self._room(f"{who}: out", out, 3 * n_trios * jack.itemsize)
+        self._room(f"{who}: out", out, items * n_trios * jack.itemsize)
         self._room(f"{who}: work", work, wb)
         self._check(getattr(self._lib, f"pgt_{who}")(
             self._ctx, self._dev(rows, torch.uint8, "rows") if n_win else None, n_win, n_trios,
@@ -966,6 +986,31 @@ class Context:
         (ij;kl) / (ik;jl) / (il;jk) (rows_from_device(out, F4_JACK_DTYPE)).  Asynchronous on `stream`; no allocation when out
         and work are given."""
         return self._jackknife_dev("f4", F4_ROW_DTYPE, F4_JACK_DTYPE, rows, n_win, n_quartets, out, work, stream)
+
+    @staticmethod
+    def f4ratio_pops_tree_bytes(n_pops: int, n_sites: int) -> int:
+        return int(_lib.load().pgt_f4ratio_pops_tree_bytes(int(n_pops), int(n_sites)))
+
+    def f4ratio_pops_reduce_dev(self, pos, freqs, ninds, minind, win, out=None, tot=None, tree=None, stream=None):
+        """The f4-ratio sums of ALL triples of the middle populations (triple-major, middle_triple_order) between population 0 (A)
+        and the last one (the outgroup), in one pass over 5 ... 7 populations' own (freq, nInd) columns
+        (pgt_f4ratio_pops_reduce_dev).  freqs: float64 CUDA tensors, ninds: int32 CUDA tensors.  Rows of F4RATIO_ROW_DTYPE carry
+        SUMS over the sites all five populations cover (the ratios are the caller's: f4ratio_alphas), totals are
+        F4RATIO_TOTAL_DTYPE.  tot: None = a fresh buffer of n_triples totals is allocated and filled; False = no genome-wide lines.
+        Returns (out, tot, tree).  Asynchronous on `stream`."""
+        return self._pops_reduce_dev(_F4RATIO_POPS, pos, freqs, ninds, minind, win, out, tot, tree, stream)
+
+    @staticmethod
+    def f4ratio_jackknife_work_bytes(n_triples: int, n_win: int) -> int:
+        return int(_lib.load().pgt_f4ratio_jackknife_work_bytes(int(n_triples), int(n_win)))
+
+    def f4ratio_jackknife_dev(self, rows, n_win, n_triples, out=None, work=None, stream=None):
+        """Block-jackknife admixture proportion, standard error and Z of n_triples middle triples x 6 (B, X, C) from the device rows
+        of f4ratio_pops_reduce_dev (uint8 CUDA tensor, triple-major, n_triples * n_win rows; the windows must be disjoint)
+        (pgt_f4ratio_jackknife_dev).  Returns (out, work): out holds 6 * n_triples F4RATIO_JACK_DTYPE, item 6 t + c with c the
+        position in ratio_order (rows_from_device(out, F4RATIO_JACK_DTYPE)).  Asynchronous on `stream`; no allocation when out and
+        work are given."""
+        return self._jackknife_dev("f4ratio", F4RATIO_ROW_DTYPE, F4RATIO_JACK_DTYPE, rows, n_win, n_triples, out, work, stream, items=6)
 
     def extreme_reduce_dev(self, pos, score, mode, cutoff, win, out=None, tree=None, stream=None):
         """ihsWindow / xpehhWindow rows from a device-resident score column (mode: PGT_EXT_*)."""
@@ -1285,6 +1330,32 @@ def pairing_order(i, j, k, l):
     return ((i, j), (k, l)), ((i, k), (j, l)), ((i, l), (j, k))
 
 
+def middle_triple_order(n_pops: int):
+    """The triples (i, j, k), 1 <= i < j < k <= n_pops - 2, of the MIDDLE populations in the order f4ratio_pops_reduce* lays its
+    rows out (population 0 is A, the last one the outgroup): (1,2,3),(1,2,4),..,(1,3,4),.."""
+    g = int(n_pops) - 1
+    return [(i, j, k) for i in range(1, g) for j in range(i + 1, g) for k in range(j + 1, g)]
+
+
+def ratio_order(i, j, k):
+    """The six admixture proportions of middle triple (i, j, k) in the order f4ratio_alphas and the block jackknife lay them out
+    (c = 0 ... 5), each as (B, X, C) of alpha = f4(A,O; X,C) / f4(A,O; B,C), the share of B-related ancestry in X:
+    [(i, j, k), (j, i, k), (i, k, j), (k, i, j), (j, k, i), (k, j, i)]."""
+    return [(i, j, k), (j, i, k), (i, k, j), (k, i, j), (j, k, i), (k, j, i)]
+
+
+def f4ratio_alphas(rows) -> np.ndarray:
+    """The six admixture proportions of ratio_order from F4RATIO_ROW_DTYPE rows or F4RATIO_TOTAL_DTYPE totals (any shape)
+    -> float64 [..., 6]: (numerator, denominator) = (S2, S1), (S1, S2), (-S2, S0), (S0, -S2), (S1, S0), (S0, S1) of the sums
+    S0, S1, S2 = g_ij, g_ik, g_jk, each ratio 0 where its denominator is 0.  Nothing is clamped."""
+    rows = np.asarray(rows)
+    s0, s1, s2 = rows["g_ij"], rows["g_ik"], rows["g_jk"]
+    num = np.stack([s2, s1, -s2, s0, s1, s0], axis=-1)
+    den = np.stack([s1, s2, s0, -s2, s0, s1], axis=-1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(den != 0, num / np.where(den != 0, den, 1.0), 0.0)
+
+
 def topology_order(i, j, k):
     """The three topologies of trio (i, j, k) in the order the block jackknife lays its items out (c = 0, 1, 2), each as
     ((P1, P2), P3): [(i, j, k), (i, k, j), (j, k, i)] — D from (abba, baba), (bbaa, baba), (bbaa, abba) of the trio's row."""
@@ -1308,10 +1379,10 @@ def _window_pops(st: _PopsStat, chr_ids, pos, freqs, ninds, W, S, minind, fixeds
     return win, rows, tot
 
 
-def _trio_window_pops_jackknife(st: _PopsStat, jack_dtype, chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx):
+def _trio_window_pops_jackknife(st: _PopsStat, jack_dtype, chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx, items: int = 3):
     """_window_pops for the rows of a trio statistic (ABBA-BABA, f3) with the rows kept ON THE DEVICE between the reduction and
     the block jackknife (<name>_pops_reduce_dev under the hints the host-buffer form derives from the table: the same rows bit
-    for bit, then <name>_jackknife_dev on them) -> (win, rows[n_trios, n_win], totals[n_trios], jack[n_trios, 3])."""
+    for bit, then <name>_jackknife_dev on them) -> (win, rows[n_trios, n_win], totals[n_trios], jack[n_trios, items])."""
     _refuse_dxy_window_args(W, S, minind, fixedsite, chr_len)
     st.check_count(f"{st.name}_window_pops", freqs, ninds)
     chr_ids, pos = _host_col(chr_ids, None), _host_col(pos, np.uint32)
@@ -1331,10 +1402,10 @@ def _trio_window_pops_jackknife(st: _PopsStat, jack_dtype, chr_ids, pos, freqs, 
         with ctx.hints(longest, 0 if step >= 2 ** 63 else step, typical):
             out, tot, _ = ctx._pops_reduce_dev(st, up(pos.view(np.int32)), [up(f) for f in freqs], [up(c) for c in ninds], minind,
                                                windows_to_device(win, dev), None, None, None, None)
-        jack, _ = ctx._jackknife_dev(st.name, st.row, jack_dtype, out, win.size, n_trios, None, None, None)
+        jack, _ = ctx._jackknife_dev(st.name, st.row, jack_dtype, out, win.size, n_trios, None, None, None, items)
         rows = rows_from_device(out, st.row)[: n_trios * win.size].reshape(n_trios, win.size).copy()
         tot = rows_from_device(tot, st.total)[:n_trios].copy()
-        jack = rows_from_device(jack, jack_dtype)[: 3 * n_trios].reshape(n_trios, 3).copy()
+        jack = rows_from_device(jack, jack_dtype)[: items * n_trios].reshape(n_trios, items).copy()
     finally:
         if own:
             ctx.close()
@@ -1480,7 +1551,7 @@ def f4_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: i
     the delete-m_j block jackknife of the mean (pgt_f4_jackknife_dev, on the device rows of the same reduction) over ALL
     windows of the table as blocks, whatever skip_missing is.  The windows must be disjoint: 0 < S < W and W == 0 are refused
     with PGT_EARG before any device use.
-    Not computed: f4-ratio admixture proportions, user-chosen quartet lists."""
+    Not computed: user-chosen quartet lists; f4-ratio admixture proportions come from f4ratio_window_pops."""
     if jackknife and (W == 0 or 0 < S < W):
         raise PgtError(_lib.PGT_EARG, f"f4_window_pops: the block jackknife needs disjoint windows as its blocks: "
                                       f"winsize {W} must be positive and stepsize {S} at least the winsize")
@@ -1491,6 +1562,35 @@ def f4_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: i
     win, rows, tot, jack = _trio_window_pops_jackknife(_F4_POPS, F4_JACK_DTYPE, chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx)
     res = _results_by_pair(len(freqs), win, rows, tot, skip_missing, "n", keys=keys)
     res["jackknife"] = {q: jack[t] for t, q in enumerate(keys)}
+    return res
+
+
+def f4ratio_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: int = 1, fixedsite: int = 0,
+                        chr_len=None, skip_missing: int = 0, jackknife: bool = False, ctx: Context | None = None) -> dict:
+    """Windowed f4-ratio (Patterson et al. 2012; ADMIXTOOLS' qpF4ratio) for ALL triples of the middle populations of len(freqs)
+    already synchronised populations (5 ... 7): freqs[0] is A, freqs[-1] the outgroup O, and for every triple (i, j, k) of the
+    populations between them, in one pass: {(i, j, k): WindowResult} in middle_triple_order, with rows of (start, end, mid, n,
+    reserved_, g_ij, g_ik, g_jk) and the genome-wide sums as total.  The three values are SUMS of (p_A - p_O)(p_x - p_y) over
+    the sites where ALL FIVE populations have minind individuals; alpha(B, X, C) = f4(A,O; X,C) / f4(A,O; B,C), the share of
+    B-related ancestry in X, is a ratio of two of them: f4ratio_alphas(rows) gives the six of ratio_order(i, j, k), 0 where the
+    denominator is 0, never clamped to [0, 1].  All columns must report the same allele.
+    Window arguments and their errors are those of dxy_window_pops; -skip_missing drops a triple's rows without counted sites
+    from that triple's result only.  The per-site definition is pgt_f4ratio_pops_reduce_dev's (include/pgtwin.h).
+    jackknife=True: the result gains the key "jackknife": {(i, j, k): 6 F4RATIO_JACK_DTYPE, one per ratio_order(i, j, k)} — the
+    delete-m_j block jackknife of the ratio, numerator and denominator losing a block together (pgt_f4ratio_jackknife_dev, on
+    the device rows of the same reduction), over ALL windows of the table as blocks, whatever skip_missing is.  The windows must
+    be disjoint: 0 < S < W and W == 0 are refused with PGT_EARG before any device use.
+    Not computed: user-chosen quintet lists, 8 populations, qpAdm-style multi-source fits."""
+    if jackknife and (W == 0 or 0 < S < W):
+        raise PgtError(_lib.PGT_EARG, f"f4ratio_window_pops: the block jackknife needs disjoint windows as its blocks: "
+                                      f"winsize {W} must be positive and stepsize {S} at least the winsize")
+    keys = middle_triple_order(len(freqs))
+    if not jackknife:
+        win, rows, tot = _window_pops(_F4RATIO_POPS, chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx)
+        return _results_by_pair(len(freqs), win, rows, tot, skip_missing, "n", keys=keys)
+    win, rows, tot, jack = _trio_window_pops_jackknife(_F4RATIO_POPS, F4RATIO_JACK_DTYPE, chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx, items=6)
+    res = _results_by_pair(len(freqs), win, rows, tot, skip_missing, "n", keys=keys)
+    res["jackknife"] = {t: jack[n] for n, t in enumerate(keys)}
     return res
 
 

@@ -105,9 +105,10 @@ def one_k(ctx, k, n, pos, f, c, minind, win, n_win, dev, card, W, S):
     return True
 
 
-def main():
+def main(one_k=one_k, default_ks=(4, 5, 6)):
+    """one_k, default_ks: the legs of a K and the K to run (tools/measure_f4ratio_pops.py passes its own)"""
     n = int(float(sys.argv[1])) if len(sys.argv) > 1 else 100_000_000
-    ks = [int(x) for x in sys.argv[2].split(",")] if len(sys.argv) > 2 else [4, 5, 6]
+    ks = [int(x) for x in sys.argv[2].split(",")] if len(sys.argv) > 2 else list(default_ks)
     dev = torch.device("cuda", 0)
     W, S, minind = 50_000, 10_000, 5
     ctx = pgt.Context(0)
