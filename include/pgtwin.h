@@ -34,7 +34,8 @@
  *   - genotypes: any int8 (non-missing is g >= 0, heterozygous g == 1, hetWindow.cpp:78-80); counts (n1, n2, nind[k]) and minind:
  *     any int32, compared as signed integers (dxyWindow.cpp:381).
  *   - the K-population entry points (pgt_dxy_pops / fst_pops / fst_hudson_pops / pi_pops / dstat_pops / fd_pops / f3_pops / pbs_pops / pbs_hudson_pops / f4_pops / f4ratio_pops _reduce_dev;
- *     tests/test_special_values_pops.py, for f4ratio_pops tests/test_special_values_f4ratio.py): a NaN or an infinity in ONE population's frequency at a COUNTED site reaches exactly the
+ *     tests/test_special_values_pops.py, for f3_pops tests/test_special_values_f3.py, for pbs_pops / pbs_hudson_pops tests/test_special_values_pbs.py,
+ *     for f4_pops tests/test_special_values_f4.py, for f4ratio_pops tests/test_special_values_f4ratio.py): a NaN or an infinity in ONE population's frequency at a COUNTED site reaches exactly the
  *     rows (and genome-wide lines) of the items — pairs, trios, the population itself — that hold that population, and of them
  *     exactly the windows that hold the site, with the value the per-site definition gives on the IEEE operands, every operation
  *     rounded on its own (for pgt_fd_pops_reduce_dev the definition's comparisons are all false with a NaN, so NaN in P2 leaves
@@ -42,7 +43,11 @@
  *     unspecified order: a NaN term gives NaN, +inf and -inf together NaN, infinities of one sign that infinity.  Frequencies
  *     at the edge of [0, 1] (-0.0, denormals, 1 - 2^-53, 0, 1) are ordinary values; sums may be denormal; a ratio is 0 where its
  *     denominator sum is 0.  Counts and minind are any int32, compared signed; where the counts are values (fst_pops,
- *     fst_hudson_pops, pi_pops) any count from minind (>= 1) to INT32_MAX is converted exactly.  pgt_dxy_pops_reduce_dev takes
+ *     fst_hudson_pops, pi_pops, pbs_pops, pbs_hudson_pops) any count from minind (>= 1) to INT32_MAX is converted exactly.
+ *     The Weir-Cockerham values (fst_pops, pbs_pops) are an identity of their definition evaluated with one reciprocal per pair:
+ *     at a counted site with an INFINITE frequency a and a + b are non-finite (NaN or an infinity; which one is unspecified), so
+ *     a window that holds such a site and no NaN has non-finite sums for the pairs with that population, and a window that holds
+ *     a NaN frequency has NaN; Hudson's values are the definition's own operations (num = +inf, den = NaN there).  pgt_dxy_pops_reduce_dev takes
  *     minind < 1 as well; a site beyond n, padded into the last tile, never counts, whatever minind is.
  *   - pgt_dstat_jackknife_dev: a block's weight is any u32 (pgt_dstat_row.n); their sum is kept in u64 and is exact in the f64
  *     arithmetic while it stays below 2^53.
@@ -899,7 +904,9 @@ int pgt_f4ratio_jackknife(pgt_ctx *ctx, const pgt_f4ratio_row *rows, uint64_t n_
  *              0, PBSn1) applies it to the sums.
  *   out        T * n_win rows, trio-major: out[t * n_win + w]
  *   tot        DEVICE array of T pgt_pbs_total (88 bytes: the same nine doubles over all counted sites, neff, nskip), or NULL;
- *              n_win == 0 with tot: the global-only form
+ *              n_win == 0 with tot: the global-only form (no row is written).  n_win == 0 with tot == NULL and n > 0: the
+ *              tree-only call, as for the other K-population statistics — both passes build in `work`, the merging kernel is
+ *              not launched, out and tot are not touched, PGT_OK
  *   work       DEVICE workspace of pgt_pbs_pops_work_bytes(n_pops, n, n_win) bytes (0 for n_pops outside 3 ... 6), 16-byte
  *              aligned: the tree of pgt_f3_pops_reduce_dev (3 T doubles and T u32 per node) and, behind it, 2 T n_win scratch rows
  *              and 2 T scratch totals of 40 bytes.  The columns are walked twice (the numerators, then the denominators: six

@@ -151,9 +151,11 @@ int launch_pbs(const uint32_t *pos, const double *const *freq, const int32_t *co
     if (int rc = launch_pops<PbsPass<Est, 0>>(pos, freq, nind, n_pops, n, minind, win, n_win, rows[0], tots[0], work, first)) return rc;
     if (int rc = launch_pops<PbsPass<Est, 1>>(pos, freq, nind, n_pops, n, minind, win, n_win, rows[1], tots[1], work, second)) return rc;
     const uint64_t n_rows = (uint64_t)w.n_trios * n_win, n_threads = n_rows + (tot ? w.n_trios : 0);
-    hipLaunchKernelGGL(pbs_finish_kernel, dim3((unsigned)((n_threads + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(e.stream), rows[0], rows[1], n_rows, out,
-                       tots[0], tots[1], tot ? w.n_trios : 0u, tot);
-    if (int rc = hip_fail(hipGetLastError(), "pbs_finish_kernel", e.err)) return rc;
+    if (n_threads > 0) {  // n_win == 0 without tot: the tree-only call, which builds (both passes) and has nothing to finish
+        hipLaunchKernelGGL(pbs_finish_kernel, dim3((unsigned)((n_threads + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(e.stream), rows[0], rows[1], n_rows, out,
+                           tots[0], tots[1], tot ? w.n_trios : 0u, tot);
+        if (int rc = hip_fail(hipGetLastError(), "pbs_finish_kernel", e.err)) return rc;
+    }
     return record_event(e.ev_query1, static_cast<hipStream_t>(e.stream), e.err);
 }
 
@@ -168,7 +170,7 @@ int init_pbs_pops_kernels(std::string *err) {
     return hip_fail(hipGetLastError(), "hipFuncSetAttribute", err);
 }
 
-// 3 <= n_pops <= 6, minind >= 1, n_win > 0 or tot: checked by the caller
+// 3 <= n_pops <= 6, minind >= 1: checked by the caller (n_win == 0 without tot passes those checks whenever n > 0)
 int launch_pbs_pops(const uint32_t *pos, const double *const *freq, const int32_t *const *nind, uint32_t n_pops, uint64_t n,
                     int minind, const pgt_win *win, uint64_t n_win, pgt_pbs_row *out, pgt_pbs_total *tot, void *work,
                     const LaunchEnv &e, FstPopsEstimator estimator) {

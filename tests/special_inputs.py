@@ -271,6 +271,9 @@ POPS_PLANTED = (0, 511, 512, 4000, 4001, 8191, 8192, POPS_N - 1)
 POPS_EDGE_VALUES = (-0.0, 5e-324, 2.0 ** -1022, 1.0 - 2.0 ** -53, 0.0, 1.0)  # inside the contract: frequencies in [0, 1]
 POPS_SUMS = {"dxy": ("sum",), "pi": ("sum",), "fst": ("asum", "bsum"), "fst_hudson": ("asum", "bsum"),
              "dstat": ("bbaa", "abba", "baba"), "fd": ("num", "fd_den", "fdm_den")}
+# the population branch statistic (tests/test_special_values_pbs.py): a trio's six sums, the pair values of "fst" / "fst_hudson"
+POPS_SUMS["pbs"] = POPS_SUMS["pbs_hudson"] = ("num_ij", "num_ik", "num_jk", "den_ij", "den_ik", "den_jk")
+PBS_PAIR_STAT = {"pbs": "fst", "pbs_hudson": "fst_hudson"}
 POPS_SECTION1 = [("dxy", 3), ("dxy", 8), ("fst_hudson", 3), ("fst_hudson", 8), ("pi", 2), ("pi", 8), ("dstat", 4), ("dstat", 7),
                  ("fd", 4), ("fd", 5), ("fd", 7)]  # fd: the two-wave build, the one-wave build without recompute, kRecompute
 POPS_SMALLEST_LARGEST = [("dxy", 2), ("dxy", 8), ("fst", 2), ("fst", 8), ("fst_hudson", 2), ("fst_hudson", 8), ("pi", 1), ("pi", 8),
@@ -284,13 +287,17 @@ def pops_dtypes(stat):
     from popgenomicstools_amd import _lib
     return {"dxy": (_lib.DXY_ROW_DTYPE, _lib.DXY_TOTAL_DTYPE), "pi": (_lib.DXY_ROW_DTYPE, _lib.DXY_TOTAL_DTYPE),
             "fst": (_lib.FST_ROW_DTYPE, _lib.FST_TOTAL_DTYPE), "fst_hudson": (_lib.FST_ROW_DTYPE, _lib.FST_TOTAL_DTYPE),
-            "dstat": (_lib.DSTAT_ROW_DTYPE, _lib.DSTAT_TOTAL_DTYPE), "fd": (_lib.FD_ROW_DTYPE, _lib.FD_TOTAL_DTYPE)}[stat]
+            "dstat": (_lib.DSTAT_ROW_DTYPE, _lib.DSTAT_TOTAL_DTYPE), "fd": (_lib.FD_ROW_DTYPE, _lib.FD_TOTAL_DTYPE),
+            "pbs": (_lib.PBS_ROW_DTYPE, _lib.PBS_TOTAL_DTYPE), "pbs_hudson": (_lib.PBS_ROW_DTYPE, _lib.PBS_TOTAL_DTYPE)}[stat]
 
 
 def pops_items(stat, k):
-    """the populations every item of the call holds, in the order of the row tables: a population (pi), a pair, or a trio with
-    the outgroup (the last population) as its fourth"""
+    """the populations every item of the call holds, in the order of the row tables: a population (pi), a pair, a trio with
+    the outgroup (the last population) as its fourth, or (pbs) a trio i < j < k of all populations"""
     from popgenomicstools_amd.window_scan import pair_order, trio_order
+    if stat in PBS_PAIR_STAT:
+        from f3_pops_model import all_trio_order
+        return [tuple(t) for t in all_trio_order(k)]
     if stat == "pi":
         return [(i,) for i in range(k)]
     if stat in ("dstat", "fd"):
@@ -327,6 +334,10 @@ def pops_site_terms(stat, item, f, c):
         if stat == "fst_hudson":
             i, j = item
             return fst_hudson_model.site_components(f[i], f[j], c[i], c[j])
+        if stat in PBS_PAIR_STAT:  # the pair's two values for (i, j), (i, k), (j, k): the numerators, then the denominators
+            i, j, k = item
+            pairs = [pops_site_terms(PBS_PAIR_STAT[stat], p, f, c) for p in ((i, j), (i, k), (j, k))]
+            return tuple(x[0] for x in pairs) + tuple(x[1] for x in pairs)
         fn = dstat_pops_model.site_components if stat == "dstat" else fd_pops_model.site_terms
         return fn(*(f[x] for x in item))
 

@@ -326,6 +326,27 @@ def test_rows_under_every_hint_poison_and_guard(pgt, ctx, n, k, est):
                     assert_totals(got_t, want_t, A_tot, what)
                 else:  # identical under one hint, whatever the workspace held
                     assert got.tobytes() == first[0].tobytes() and got_t.tobytes() == first[1].tobytes(), what
+    # tot=None (no genome-wide lines: the totals buffer stays as it was), the global-only form (n_win = 0: no row is written) and
+    # the tree-only call (n_win = 0 without tot: both passes build, nothing is finished, PGT_OK as for every other statistic),
+    # under the last hint of the loop above, whose rows `first` holds; the workspace starts from 0xFF every time
+    with ctx.hints(hint, 0, 0):
+        for buf in (work, out, tot):
+            buf.fill_(0xFF)
+        ctx.pbs_pops_reduce_dev(tp, tf, tn, MININD, wd, estimator=est, out=out, tot=False, work=work)
+        g.check("tot = NULL")
+        assert rows_from_device(out, PBS_ROW_DTYPE).reshape(T, win.size).tobytes() == first[0].tobytes()
+        assert bool((tot == 0xFF).all()), "tot = NULL: the totals buffer is not written"
+        for buf in (work, out, tot):
+            buf.fill_(0xFF)
+        ctx.pbs_pops_reduce_dev(tp, tf, tn, MININD, wd[:0], estimator=est, out=out, tot=tot, work=work)
+        g.check("n_win = 0")
+        assert bool((out == 0xFF).all()), "n_win = 0: no row is written"
+        assert rows_from_device(tot, PBS_TOTAL_DTYPE).tobytes() == first[1].tobytes()
+        for buf in (work, out, tot):
+            buf.fill_(0xFF)
+        ctx.pbs_pops_reduce_dev(tp, tf, tn, MININD, wd[:0], estimator=est, out=out, tot=False, work=work)  # raises unless PGT_OK
+        g.check("n_win = 0 and tot = NULL")
+        assert bool((out == 0xFF).all()) and bool((tot == 0xFF).all()), "the tree-only call writes no row and no total"
 
 
 def test_graph_replay_rebuilds_from_new_columns(pgt, ctx):

@@ -3,6 +3,7 @@ GPU tests compare against, the model's identity with the pair models where the t
 workspace size, the declarations, and the refusals of the Python mirror and of the command line that come before the device is
 opened."""
 import os
+import re
 import subprocess
 import sys
 
@@ -13,6 +14,7 @@ import fst_hudson_model
 import fst_pops_model
 import helpers
 import pbs_pops_model
+import special_inputs as si
 from pbs_pops_model import PAIRS, PBS, SUMS
 from popgenomicstools_amd import _lib
 from popgenomicstools_amd._lib import WIN_DTYPE
@@ -198,6 +200,101 @@ def test_the_python_mirror_refuses_before_any_device_use():
         with pytest.raises(_lib.PgtError, match='pbs_window_pops: estimator must be "wc" or "hudson"') as e:
             pgt.pbs_window_pops(ids, pos, [z] * 3, [c] * 3, 2, 2, 1, 1, estimator=bad)
         assert e.value.code == _lib.PGT_EARG
+
+
+# ---- what the GPU modules of the grid strides and of the special values assume ---------------------------------------------------
+def test_the_grid_constants_are_the_ones_the_gpu_test_assumes():
+    """tests/test_pbs_pops_grid.py takes its tile counts from PbsPass' own kOneWaveFrom: K = 5 is a one-wave K with 1024 build
+    waves at most, K = 3 a two-wave K with 2048; the query kernel takes one wave per SIMD from K = 6."""
+    import pops_grid_shapes as shapes
+    src = open(os.path.join(ROOT, "popgenomicstools_amd", "csrc", "pgt_pbs_pops_kernels.hip")).read()
+    m = re.search(r"static constexpr int kOneWaveFrom = (\d+);", src)
+    assert m and int(m.group(1)) == 5 and src.count("kOneWaveFrom = ") == 1
+    assert re.search(r"static constexpr int kQueryOneWaveFrom = 6;", src) and re.search(r"kMinPops = 3, kMaxPops = 6;", src)
+    assert re.search(r"static constexpr const char \*kOneWaveKnob = nullptr;", src)  # no environment knob moves the occupancy
+    assert shapes.balanced_build(1025, shapes.ONE_WAVE_BUILD_WAVES) == (2, 513, 516)   # wc, K = 5
+    assert shapes.balanced_build(2049, shapes.MAX_BUILD_WAVES) == (2, 1025, 1028)      # hudson, K = 3
+    assert shapes.balanced_build(1024, shapes.ONE_WAVE_BUILD_WAVES)[0] == 1 and shapes.balanced_build(2048, shapes.MAX_BUILD_WAVES)[0] == 1
+    assert shapes.tiles_of_wave(1025, 516).max() == 2 and shapes.tiles_of_wave(2049, 1028).max() == 2
+    assert shapes.QUERY_N_WIN[-1] == shapes.QUERY_WAVES + 5 == 262_149
+
+
+def _trio_terms(stat, ijk, f, c, minind):
+    ok = si.pops_counted(ijk, c, minind)
+    return ok, [np.where(ok, x, 0.0) for x in si.pops_site_terms(stat, ijk, f, c)]
+
+
+def test_the_special_value_inputs_have_the_shapes_the_gpu_test_claims():
+    """The very inputs of tests/test_special_values_pbs.py, without a device: the planted sites are counted and the clean terms
+    finite and at most 8 (special_inputs.window_sums asserts it); the model's classes at a frequency of +-inf; every trio of the
+    count cases has counted and uncounted sites, the fewest counted as recorded, every counted term finite and at most 1; the
+    denormal columns reach denormal sums and counted rows with all three denominators 0, whose pbs is +0.0 by the model."""
+    from test_special_values_f3 import PLANTED
+    n = si.POPS_N
+    assert si.POPS_SUMS["pbs"] == si.POPS_SUMS["pbs_hudson"] == SUMS and si.pops_dtypes("pbs") == (_lib.PBS_ROW_DTYPE, _lib.PBS_TOTAL_DTYPE)
+    for k in (3, 6):
+        assert si.pops_items("pbs", k) == si.pops_items("pbs_hudson", k) == pbs_pops_model.all_trio_order(k)
+    sites = np.array(sorted(PLANTED))
+    # planted at counted sites: Hudson's sums are the definition's on the IEEE operands
+    for k, who in ((3, 1), (6, 1)):
+        f0, c = si.pops_clean_columns(n, k, 7100 + 10 * k + who, planted=tuple(PLANTED))
+        f = [x.copy() for x in f0]
+        for s, v in PLANTED.items():
+            f[who][s] = v
+        for ijk in pbs_pops_model.all_trio_order(k):
+            ok, terms = _trio_terms("pbs_hudson", ijk, f, c, si.POPS_MININD)
+            assert ok[sites].all()
+            for fld, x in zip(SUMS, terms):
+                _, A, _ = si.window_sums(x, [0], [n])  # finite terms at most 8
+                reads = who in dict(zip(pbs_pops_model.PAIRS, pbs_pops_model.pairs_of(*ijk)))[fld[4:]]
+                assert np.isfinite(np.delete(x, sites)).all() and np.isfinite(A).all()
+                if not reads:
+                    assert np.isfinite(x).all()
+                    continue
+                assert np.isnan(x[511]) and np.isfinite(x[n - 1])  # the NaN site; the denormal is an ordinary value
+                for s in (4001, 8192):  # +inf and -inf: num = +inf, den = NaN
+                    assert np.isposinf(x[s]) if fld.startswith("num") else np.isnan(x[s]), (ijk, fld, s)
+    # the division form of the Weir-Cockerham model gives NaN for both values at a frequency of +-inf, where the kernel's identity
+    # with a reciprocal gives a = +inf: the class of such a sum is left open, and the GPU test asks for a non-finite one
+    nine = np.array([9, 9], dtype=np.int32)
+    for v in (np.inf, -np.inf):
+        num, den = pbs_pops_model.site_values("wc", np.array([v, 0.25]), np.array([0.25, v]), nine, nine)
+        assert np.isnan(num).all() and np.isnan(den).all()
+        num, den = pbs_pops_model.site_values("hudson", np.array([v, 0.25]), np.array([0.25, v]), nine, nine)
+        assert np.isposinf(num).all() and np.isnan(den).all()
+    # counts as values
+    fewest = {(3, 1): 565, (3, 20): 302, (3, si.I32_MAX): 68, (6, 1): 503, (6, 20): 294, (6, si.I32_MAX): 62, (3, "realistic"): 8454, (6, "realistic"): 8427}
+    for (k, minind), want in fewest.items():
+        real = minind == "realistic"
+        m = si.REALISTIC_MININD if real else minind
+        f, c = si.count_case_columns("pbs", k, m, real)
+        counted = []
+        for ijk in pbs_pops_model.all_trio_order(k):
+            for stat in ("pbs", "pbs_hudson"):
+                ok, terms = _trio_terms(stat, ijk, f, c, m)
+                assert np.isfinite(np.stack(terms)).all() and np.abs(np.stack(terms)).max() <= 1.0, (k, minind, ijk, stat)
+            counted.append(int(ok.sum()))
+        assert 0 < min(counted) == want and max(counted) < n, (k, minind, min(counted), max(counted))
+    # denormal and zero sums
+    tiny = 2.0 ** -1022
+    f, c = si.denormal_columns(3)
+    name, win = si.denormal_tables()[0]
+    lo, hi = win["lo"].astype(np.int64), win["hi"].astype(np.int64)
+    assert name == "one site"
+    for stat, n_denormal in (("pbs", 646), ("pbs_hudson", 643)):
+        ok, terms = _trio_terms(stat, (0, 1, 2), f, c, si.POPS_MININD)
+        row = np.zeros(lo.size, dtype=_lib.PBS_ROW_DTYPE)
+        row["n"] = ok[lo]
+        for fld, x in zip(SUMS, terms):
+            row[fld], _, finite = si.window_sums(x, lo, hi)
+            assert finite.all()
+        assert sum(int(np.count_nonzero((np.abs(row[fld]) < tiny) & (row[fld] != 0))) for fld in SUMS) == n_denormal
+        zero = [(row["n"] > 0) & (row[f"den_{p}"] == 0) for p in pbs_pops_model.PAIRS]
+        # 182 zero denominators among the counted rows' pairs; in 56 of the 266 counted rows all three are 0
+        assert sum(int(z.sum()) for z in zero) == 182 and int((zero[0] & zero[1] & zero[2]).sum()) == 56 and int(ok.sum()) == 266
+        pbs, _ = pbs_pops_model.finish_rows(row)
+        for x in pbs:
+            assert np.isfinite(x).all() and not x[zero[0] & zero[1] & zero[2]].view(np.uint64).any()
 
 
 # ---- the command line -----------------------------------------------------------------------------------------------------
