@@ -83,7 +83,8 @@ extern "C" {
  *          pgt_f4_jackknife_work_bytes / pgt_f4_jackknife_dev / pgt_f4_jackknife added (additive as well).
  * Still 6: pgt_f4ratio_row, pgt_f4ratio_total, pgt_f4ratio_jack, pgt_f4ratio_pops_tree_bytes / pgt_f4ratio_pops_reduce_dev /
  *          pgt_f4ratio_pops_reduce and pgt_f4ratio_jackknife_work_bytes / pgt_f4ratio_jackknife_dev / pgt_f4ratio_jackknife
- *          added (additive as well). */
+ *          added (additive as well).
+ * Still 6: pgt_pbs_jack, pgt_pbs_jackknife_work_bytes / pgt_pbs_jackknife_dev / pgt_pbs_jackknife added (additive as well). */
 #define PGT_ABI_VERSION 6
 
 enum {
@@ -232,6 +233,12 @@ typedef struct { /* the same nine doubles of one trio over all its counted sites
     double den_ij, den_ik, den_jk;  /* offsets 48, 56, 64 */
     uint64_t neff, nskip;           /* offsets 72, 80 */
 } pgt_pbs_total;
+
+typedef struct { /* block jackknife of PBS or PBSn1 of one trio and focal population: pgt_pbs_jackknife_dev (48 bytes, the layout of pgt_f4_jack) */
+    double stat, stat_jack, se, z; /* the statistic of all used blocks, its jackknife estimate, standard error, stat_jack / se */
+    uint64_t n_sites;              /* counted sites of the used blocks */
+    uint32_t n_blocks, pad_;       /* used blocks (rows with n > 0) */
+} pgt_pbs_jack;
 
 /* ---- context ------------------------------------------------------------------------- */
 /* device: HIP ordinal, or -1 for the current device.  Fails (NULL, message via
@@ -922,8 +929,8 @@ int pgt_f4ratio_jackknife(pgt_ctx *ctx, const pgt_f4ratio_row *rows, uint64_t n_
  * alone (bitwise reproducible).  A one-site window carries, with the Hudson estimator, exactly the bits of num and den.
  * Against an exact evaluation a sum stays within 1e-9 * A + 1e-12, A the window's sum of the absolute values of the terms a
  * site's value is built from.  Held to this definition, to an exact-rational fixture (tests/golden/pbs_exact.json) and to a
- * NumPy model (tests/pbs_pops_model.py).  Not computed: PBSn1, truncation of negative FST, a block jackknife, user-chosen
- * trio lists, K = 7.
+ * NumPy model (tests/pbs_pops_model.py).  PBSn1 and the block jackknife of both: pgt_pbs_jackknife_dev below.  Not computed:
+ * truncation of negative FST, user-chosen trio lists, K = 7.
  * Host-buffer form: columns (host arrays of n_pops HOST pointers), table, rows and the T totals in host memory. */
 size_t pgt_pbs_pops_work_bytes(uint32_t n_pops, uint64_t n_sites, uint64_t n_win);
 int pgt_pbs_pops_reduce_dev(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq,
@@ -940,6 +947,46 @@ int pgt_pbs_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *
 int pgt_pbs_hudson_pops_reduce(pgt_ctx *ctx, const uint32_t *pos, const double *const *freq,
                                const int32_t *const *nind, uint32_t n_pops, uint64_t n, int minind,
                                const pgt_win *win, uint64_t n_win, pgt_pbs_row *out, pgt_pbs_total *tot);
+
+/* ---- block-jackknife standard error and Z of PBS and PBSn1, all trios, every focal population ------------------------------ */
+/* The weighted block jackknife of pgt_dstat_jackknife_dev — g, n, h_j, theta_J, tau_j, sigma^2, the rule "used iff n > 0, weight
+ * m_j = n", the plan, chunks of 64 rows with one row per lane, the order of every addition, no atomics — with a fourth
+ * estimator, a NON-LINEAR function of SIX block sums, over the window rows pgt_pbs_pops_reduce_dev (or its Hudson form) wrote:
+ *   rows     DEVICE pointer to the n_trios x n_win trio-major table, 8-byte aligned (an 88-byte row at an odd index is not
+ *            16-byte aligned); every window is one block; the caller guarantees that the windows are DISJOINT.  Only n and the
+ *            six sums of a row are read: the pbs_* fields and the coordinates are never looked at.
+ *   E(S)     of six sums S = (num_ij, num_ik, num_jk, den_ij, den_ik, den_jk), every operation ONE rounding, nothing contracted:
+ *                fst_xy  = den_xy != 0 ? num_xy / den_xy : 0
+ *                T_xy    = -log(1 - fst_xy)                       (double log of the device library, as in the rows)
+ *                pbs_i   = ((T_ij + T_ik) - T_jk) * 0.5 + 0.0     (pbs_j, pbs_k as in pgt_pbs_row)
+ *                s       = (pbs_i + pbs_j) + pbs_k
+ *                pbsn1_x = pbs_x / (1.0 + s)                      (PBSn1, Malaspinas et al. 2016; no clamp, no special case)
+ *   items    trio t has SIX items u = 6 t + c: c = 0, 1, 2 PBS with i, j, k as the focal population, c = 3, 4, 5 PBSn1 of the same;
+ *                theta(c) = E(S_total)[c]         theta_-j(c) = E(S_total - s_j)[c]
+ *            each of the six sums losing block j with one rounding.  S_total is the jackknife's own sum of the used rows' sums
+ *            in its own order: theta is the row arithmetic on THOSE sums and need not carry the bits of a pgt_pbs_total, whose
+ *            sums come from the tree.  E is evaluated once per block (three logs) for all six items.
+ *   blocks   as pgt_dstat_jackknife_dev (a row that is not used is selected away, never added: its sums may be NaN).  A NaN in
+ *            any sum of a USED block makes all six items of its trio NaN (every item reads all six sums), and no other trio's.
+ *   out      pgt_pbs_jack per item, item-major: stat = theta, stat_jack = theta_J, se = sqrt(sigma^2),
+ *            z = se > 0 ? theta_J / se : NaN, n_blocks = g, n_sites = n, pad_ = 0.  8-byte aligned.
+ *            g < 2: stat_jack = stat, se = z = NaN.  g == 0 (n_win == 0 included): stat = stat_jack = +0.0, se = z = NaN.
+ *            NOTHING IS CLAMPED: inf and NaN from FST = 1, whole or with a block left out, are the IEEE results and stand.
+ *   work     DEVICE workspace of pgt_pbs_jackknife_work_bytes(n_trios, n_win) bytes (0 for n_trios outside 1 ... 20), 16-byte
+ *            aligned: per wave 8 words of phase 1 (six sums, Σn, g) and 6 doubles each of phases 2 and 3, rounded up to 256
+ *            bytes.  Every byte of it that is read is written earlier in the same call.
+ * 1 <= n_trios <= 20.  Bitwise reproducible; an item's outputs are a function, bit for bit, of its own trio's rows alone: not of
+ * n_trios, not of the other trios' rows.  Against an exact evaluation stat, stat_jack and se stay within 1e-9 relative + 1e-12
+ * while no 1 - fst and no 1 + s, whole or with a block left out, is close to zero (tests/pbs_jack_model.py).  Refusals (PGT_EARG,
+ * messages begin "pgt_pbs_jackknife: " and name their argument, "n_trios must be 1 ... 20" among them; nothing is launched,
+ * nothing written): those of pgt_dstat_jackknife_dev, with "rows is not 8-byte aligned".  Asynchronous on `stream`; no
+ * allocation and no attribute call: it can be captured into a graph.
+ * Host-buffer form: rows and out in host memory; synchronous. */
+size_t pgt_pbs_jackknife_work_bytes(uint32_t n_trios, uint64_t n_win);
+int pgt_pbs_jackknife_dev(pgt_ctx *ctx, const pgt_pbs_row *rows, uint64_t n_win, uint32_t n_trios,
+                          pgt_pbs_jack *out /* 6 * n_trios, item-major u = 6t + c */, size_t out_bytes,
+                          void *work, size_t work_bytes, void *stream);
+int pgt_pbs_jackknife(pgt_ctx *ctx, const pgt_pbs_row *rows, uint64_t n_win, uint32_t n_trios, pgt_pbs_jack *out);
 
 /* ---- the sites common to K files, aligned on the device ------------------------------------------ */
 /* Replaces the two-file synchronisation of dxyWindow.cpp:315-331 (one current line per file; the file that is behind reads

@@ -25,7 +25,9 @@ from .window_scan import (  # noqa: F401
     f4_window_pops,
     f4ratio_alphas,
     f4ratio_window_pops,
+    pbs_item_order,
     pbs_window_pops,
+    pbsn1_of,
     fd_window_pops,
     fst_window,
     fst_window_pops,
@@ -45,4 +47,4 @@ from .window_scan import (  # noqa: F401
 )
 
 __all__ = ["Context", "build_windows_sites", "build_windows_bp", "fst_window", "het_window",
-           "dxy_window", "dxy_window_pops", "fst_window_pops", "pi_window_pops", "dstat_window_pops", "fd_window_pops", "f3_window_pops", "f4_window_pops", "f4ratio_window_pops", "f4ratio_alphas", "middle_triple_order", "ratio_order", "pbs_window_pops", "pair_order", "trio_order", "all_trio_order", "all_quartet_order", "pairing_order", "topology_order", "target_order", "align_segments", "align_segments_runs", "align_sites", "ihs_window", "xpehh_window", "build_windows_extreme", "plan_shards", "run_lengths"]
+           "dxy_window", "dxy_window_pops", "fst_window_pops", "pi_window_pops", "dstat_window_pops", "fd_window_pops", "f3_window_pops", "f4_window_pops", "f4ratio_window_pops", "f4ratio_alphas", "middle_triple_order", "ratio_order", "pbs_window_pops", "pbsn1_of", "pbs_item_order", "pair_order", "trio_order", "all_trio_order", "all_quartet_order", "pairing_order", "topology_order", "target_order", "align_segments", "align_segments_runs", "align_sites", "ihs_window", "xpehh_window", "build_windows_extreme", "plan_shards", "run_lengths"]

@@ -50,6 +50,8 @@ PBS_ROW_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("mid", "<u4"), ("n"
 PBS_TOTAL_DTYPE = np.dtype([("pbs_i", "<f8"), ("pbs_j", "<f8"), ("pbs_k", "<f8"),
                             ("num_ij", "<f8"), ("num_ik", "<f8"), ("num_jk", "<f8"),
                             ("den_ij", "<f8"), ("den_ik", "<f8"), ("den_jk", "<f8"), ("neff", "<u8"), ("nskip", "<u8")])
+PBS_JACK_DTYPE = np.dtype([("stat", "<f8"), ("stat_jack", "<f8"), ("se", "<f8"), ("z", "<f8"), ("n_sites", "<u8"),
+                           ("n_blocks", "<u4"), ("pad_", "<u4")])  # pgt_pbs_jack: PBS or PBSn1 of one trio and focal population
 F4_ROW_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("mid", "<u4"), ("n", "<u4"),
                          ("reserved_", "<f8"), ("f4_ij_kl", "<f8"), ("f4_ik_jl", "<f8"), ("f4_il_jk", "<f8")])  # pgt_f4_row: the three SUMS of one quartet
 F4_TOTAL_DTYPE = np.dtype([("f4_ij_kl", "<f8"), ("f4_ik_jl", "<f8"), ("f4_il_jk", "<f8"), ("neff", "<u8"), ("nskip", "<u8")])
@@ -72,7 +74,7 @@ assert SEG_DTYPE.itemsize == 16 and FST_TOTAL_DTYPE.itemsize == 32
 assert DSTAT_ROW_DTYPE.itemsize == 48 and DSTAT_TOTAL_DTYPE.itemsize == 40 and DSTAT_JACK_DTYPE.itemsize == 48
 assert FD_ROW_DTYPE.itemsize == 56 and FD_TOTAL_DTYPE.itemsize == 40
 assert F3_ROW_DTYPE.itemsize == 48 and F3_TOTAL_DTYPE.itemsize == 40 and F3_JACK_DTYPE.itemsize == 48
-assert PBS_ROW_DTYPE.itemsize == 88 and PBS_TOTAL_DTYPE.itemsize == 88
+assert PBS_ROW_DTYPE.itemsize == 88 and PBS_TOTAL_DTYPE.itemsize == 88 and PBS_JACK_DTYPE.itemsize == 48
 assert [F3_ROW_DTYPE.fields[k][1] for k in ("f3_i", "f3_j", "f3_k")] == [DSTAT_ROW_DTYPE.fields[k][1] for k in ("bbaa", "abba", "baba")]
 assert F4_ROW_DTYPE.itemsize == 48 and F4_TOTAL_DTYPE.itemsize == 40 and F4_JACK_DTYPE.itemsize == 48
 assert [F4_ROW_DTYPE.fields[k][1] for k in ("f4_ij_kl", "f4_ik_jl", "f4_il_jk")] == [F3_ROW_DTYPE.fields[k][1] for k in ("f3_i", "f3_j", "f3_k")]
@@ -107,6 +109,7 @@ SYMBOLS = [
     "pgt_f4ratio_pops_tree_bytes", "pgt_f4ratio_pops_reduce_dev", "pgt_f4ratio_pops_reduce",
     "pgt_f4ratio_jackknife_work_bytes", "pgt_f4ratio_jackknife_dev", "pgt_f4ratio_jackknife",
     "pgt_pbs_pops_work_bytes", "pgt_pbs_pops_reduce_dev", "pgt_pbs_hudson_pops_reduce_dev", "pgt_pbs_pops_reduce", "pgt_pbs_hudson_pops_reduce",
+    "pgt_pbs_jackknife_work_bytes", "pgt_pbs_jackknife_dev", "pgt_pbs_jackknife",
 ]
 PGT_TOK_CHR, PGT_TOK_SKIP, PGT_TOK_U32, PGT_TOK_F64, PGT_TOK_I8, PGT_TOK_I32, PGT_TOK_FREQ, PGT_TOK_CHR_PREFIX = range(8)
 
@@ -187,7 +190,7 @@ def load() -> C.CDLL:
     for stat in ("pbs", "pbs_hudson"):
         getattr(lib, f"pgt_{stat}_pops_reduce_dev").argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, u64, vp, sz, vp, vp, sz, vp]
         getattr(lib, f"pgt_{stat}_pops_reduce").argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, u64, vp, vp]
-    for stat in ("dstat", "f3", "f4", "f4ratio"):  # the block jackknife of the four row types: one argument list each form
+    for stat in ("dstat", "f3", "f4", "f4ratio", "pbs"):  # the block jackknife of the five row types: one argument list each form
         getattr(lib, f"pgt_{stat}_jackknife_work_bytes").restype = sz
         getattr(lib, f"pgt_{stat}_jackknife_work_bytes").argtypes = [u32, u64]
         getattr(lib, f"pgt_{stat}_jackknife_dev").argtypes = [vp, vp, u64, u32, vp, sz, vp, sz, vp]

@@ -815,25 +815,37 @@ size_t pgt_f4ratio_jackknife_work_bytes(uint32_t n_triples, uint64_t n_win) {
     return jack_work(n_triples, n_win, kJackRatioItems).bytes;
 }
 
-enum JackEstimator { kJackD, kJackF3Mean, kJackF4Mean, kJackF4Ratio };
+// PBS and PBSn1 (pgt_pbs_jackknife) go through them as well, over rows of 88 bytes with six sums: the row size, the rows'
+// alignment (8 bytes) and the sums of the workspace are the estimator's.
+size_t pgt_pbs_jackknife_work_bytes(uint32_t n_trios, uint64_t n_win) {
+    if (n_trios < 1 || n_trios > kJackMaxTrios) return 0;
+    return jack_work(n_trios, n_win, kJackPbsItems, kJackPbsSums).bytes;
+}
+
+enum JackEstimator { kJackD, kJackF3Mean, kJackF4Mean, kJackF4Ratio, kJackPbs };
 static const char *jack_who(JackEstimator est) {
+    if (est == kJackPbs) return "pgt_pbs_jackknife: ";
     return est == kJackD ? "pgt_dstat_jackknife: " : (est == kJackF3Mean ? "pgt_f3_jackknife: " : (est == kJackF4Mean ? "pgt_f4_jackknife: " : "pgt_f4ratio_jackknife: "));
 }
 static const char *jack_tables_word(JackEstimator est) { return est == kJackF4Mean ? "n_quartets" : (est == kJackF4Ratio ? "n_triples" : "n_trios"); }
 static uint32_t jack_max_tables(JackEstimator est) { return est == kJackF4Mean ? kJackMaxQuartets : (est == kJackF4Ratio ? kJackMaxTriples : kJackMaxTrios); }
-static int jack_items(JackEstimator est) { return est == kJackF4Ratio ? kJackRatioItems : kJackTopologies; }
+static int jack_items(JackEstimator est) { return est == kJackF4Ratio ? kJackRatioItems : (est == kJackPbs ? kJackPbsItems : kJackTopologies); }
+static int jack_sums(JackEstimator est) { return est == kJackPbs ? kJackPbsSums : kJackSums; }
+static size_t jack_row_bytes(JackEstimator est) { return est == kJackPbs ? sizeof(pgt_pbs_row) : sizeof(pgt_dstat_row); }
 static_assert(kJackMaxQuartets <= kJackMaxTrios, "jack_work is sized for up to kJackMaxTrios tables");
 
 static int jack_check_range(pgt_ctx *ctx, JackEstimator est, uint32_t n_trios, uint64_t n_win) {
     const std::string who = jack_who(est), word = jack_tables_word(est);
     if (n_trios < 1 || n_trios > jack_max_tables(est))
         return ctx_fail(ctx, PGT_EARG, who + word + " must be 1 ... " + std::to_string(jack_max_tables(est)));
-    if (n_win > (UINT64_MAX / sizeof(pgt_dstat_row)) / n_trios) return ctx_fail(ctx, PGT_EARG, who + word + " * n_win overflows");
+    if (n_win > (UINT64_MAX / jack_row_bytes(est)) / n_trios) return ctx_fail(ctx, PGT_EARG, who + word + " * n_win overflows");
     return PGT_OK;
 }
 static_assert(sizeof(pgt_f3_row) == sizeof(pgt_dstat_row) && sizeof(pgt_f3_jack) == sizeof(pgt_dstat_jack), "one set of jackknife checks");
 static_assert(sizeof(pgt_f4_row) == sizeof(pgt_dstat_row) && sizeof(pgt_f4_jack) == sizeof(pgt_dstat_jack), "one set of jackknife checks");
 static_assert(sizeof(pgt_f4ratio_row) == sizeof(pgt_dstat_row) && sizeof(pgt_f4ratio_jack) == sizeof(pgt_dstat_jack), "one set of jackknife checks");
+static_assert(sizeof(pgt_pbs_row) == 88 && sizeof(pgt_pbs_jack) == sizeof(pgt_dstat_jack) && offsetof(pgt_pbs_jack, stat_jack) == 8 && offsetof(pgt_pbs_jack, n_blocks) == 40,
+              "one set of jackknife checks: the results of all estimators are one layout");
 
 static int jackknife_dev(pgt_ctx *ctx, JackEstimator est, const void *rows, uint64_t n_win, uint32_t n_trios, void *out,
                          size_t out_bytes, void *work, size_t work_bytes, void *stream) {
@@ -842,11 +854,15 @@ static int jackknife_dev(pgt_ctx *ctx, JackEstimator est, const void *rows, uint
     if (n_win && !rows) return ctx_fail(ctx, PGT_EARG, who + "rows is NULL");
     if (!out) return ctx_fail(ctx, PGT_EARG, who + "out is NULL");
     if (!work) return ctx_fail(ctx, PGT_EARG, who + "work is NULL");
-    if (!aligned16(rows)) return ctx_fail(ctx, PGT_EARG, who + "rows is not 16-byte aligned");
+    if (est == kJackPbs) {  // an 88-byte row at an odd index is not 16-byte aligned: its loads are 8 bytes wide
+        if (reinterpret_cast<uintptr_t>(rows) & 7u) return ctx_fail(ctx, PGT_EARG, who + "rows is not 8-byte aligned");
+    } else if (!aligned16(rows)) {
+        return ctx_fail(ctx, PGT_EARG, who + "rows is not 16-byte aligned");
+    }
     if (reinterpret_cast<uintptr_t>(out) & 7u) return ctx_fail(ctx, PGT_EARG, who + "out is not 8-byte aligned");
     if (!aligned16(work)) return ctx_fail(ctx, PGT_EARG, who + "work is not 16-byte aligned");
     if (int rc = room_check(ctx, (who + "out_bytes").c_str(), (uint64_t)n_trios * jack_items(est), sizeof(pgt_dstat_jack), out_bytes)) return rc;
-    const size_t need = jack_work(n_trios, n_win, jack_items(est)).bytes;
+    const size_t need = jack_work(n_trios, n_win, jack_items(est), jack_sums(est)).bytes;
     if (work_bytes < need)
         return ctx_fail(ctx, PGT_EARG, who + "work_bytes too small (" + std::to_string(work_bytes) + " bytes, " + std::to_string(need) + " needed)");
     void *q0 = nullptr, *q1 = nullptr;
@@ -856,6 +872,8 @@ static int jackknife_dev(pgt_ctx *ctx, JackEstimator est, const void *rows, uint
         ctx->have_timing = true;
         ctx->timing_query_only = true;
     }
+    if (est == kJackPbs)
+        return launch_pbs_jackknife(static_cast<const pgt_pbs_row *>(rows), n_win, n_trios, static_cast<pgt_pbs_jack *>(out), work, stream, q0, q1, &ctx->error);
     if (est == kJackF4Ratio)
         return launch_f4ratio_jackknife(static_cast<const pgt_f4ratio_row *>(rows), n_win, n_trios, static_cast<pgt_f4ratio_jack *>(out), work, stream, q0, q1, &ctx->error);
     if (est == kJackF4Mean)
@@ -890,6 +908,13 @@ int pgt_f4ratio_jackknife_dev(pgt_ctx *ctx, const pgt_f4ratio_row *rows, uint64_
                               size_t out_bytes, void *work, size_t work_bytes, void *stream) {
     PGT_USE_DEVICE(ctx);
     return jackknife_dev(ctx, kJackF4Ratio, rows, n_win, n_triples, out, out_bytes, work, work_bytes, stream);
+}
+
+// out: 6 n_trios items, u = 6 t + c: PBS (c < 3) and PBSn1 (c >= 3) with population c % 3 of trio t as the focal one
+int pgt_pbs_jackknife_dev(pgt_ctx *ctx, const pgt_pbs_row *rows, uint64_t n_win, uint32_t n_trios, pgt_pbs_jack *out,
+                          size_t out_bytes, void *work, size_t work_bytes, void *stream) {
+    PGT_USE_DEVICE(ctx);
+    return jackknife_dev(ctx, kJackPbs, rows, n_win, n_trios, out, out_bytes, work, work_bytes, stream);
 }
 
 size_t pgt_align_workspace_bytes(uint32_t n_files, uint64_t n_rows_file0) {
@@ -1349,8 +1374,8 @@ static int jackknife_host(pgt_ctx *ctx, JackEstimator est, const void *rows, uin
     const std::string who = jack_who(est);
     if (int rc = jack_check_range(ctx, est, n_trios, n_win)) return rc;
     if ((n_win && !rows) || !out) return ctx_fail(ctx, PGT_EARG, who + "NULL argument");
-    const size_t row_bytes = (size_t)n_trios * n_win * sizeof(pgt_dstat_row), out_bytes = (size_t)n_trios * jack_items(est) * sizeof(pgt_dstat_jack);
-    const size_t work_bytes = jack_work(n_trios, n_win, jack_items(est)).bytes;
+    const size_t row_bytes = (size_t)n_trios * n_win * jack_row_bytes(est), out_bytes = (size_t)n_trios * jack_items(est) * sizeof(pgt_dstat_jack);
+    const size_t work_bytes = jack_work(n_trios, n_win, jack_items(est), jack_sums(est)).bytes;
     void *drows = nullptr, *dwork = nullptr, *dout = nullptr;
     if (int rc = workspace(ctx, HostIo::kRows, row_bytes, &drows)) return rc;
     if (int rc = workspace(ctx, HostIo::kTree, work_bytes, &dwork)) return rc;
@@ -1380,6 +1405,11 @@ int pgt_f4_jackknife(pgt_ctx *ctx, const pgt_f4_row *rows, uint64_t n_win, uint3
 int pgt_f4ratio_jackknife(pgt_ctx *ctx, const pgt_f4ratio_row *rows, uint64_t n_win, uint32_t n_triples, pgt_f4ratio_jack *out) {
     PGT_USE_DEVICE(ctx);
     return jackknife_host(ctx, kJackF4Ratio, rows, n_win, n_triples, out);
+}
+
+int pgt_pbs_jackknife(pgt_ctx *ctx, const pgt_pbs_row *rows, uint64_t n_win, uint32_t n_trios, pgt_pbs_jack *out) {
+    PGT_USE_DEVICE(ctx);
+    return jackknife_host(ctx, kJackPbs, rows, n_win, n_trios, out);
 }
 
 /* ---------------- window tables built on the device ---------------- */

@@ -17,20 +17,23 @@
 // mean(a, b) = b != 0 ? a / b : 0:     theta = mean(X, n)     theta_-j = mean(X - x_j, n - m_j)     (n, m_j as f64)
 // h_j, theta_J, tau_j and sigma^2 as above.  The estimator (struct D, struct Mean below: F3Mean, and F4Mean over the rows of
 // pgt_f4_pops_reduce_dev) is a template parameter of the phases that look at an estimate; the totals, the plan, the chunking,
-// readd(), the workspace layout and the order of every addition are common, and all row types are 48 bytes with n and the three
+// readd(), the workspace layout and the order of every addition are common, and the row types of these three are 48 bytes with n and the three
 // sums at the same offsets.  A third estimator, the signed RATIO of two of a row's sums (struct Ratio: the f4-ratio's admixture
 // proportions, pgt_f4ratio_jackknife_dev), has SIX items per row where the others have three: the item count is a constant of
-// the estimator (kItems) that sizes the per-lane arrays and the partials of phases 2 and 3.
+// the estimator (kItems) that sizes the per-lane arrays and the partials of phases 2 and 3.  A fourth, the population branch
+// statistic (struct Pbs: PBS and PBSn1 of the three focal populations, pgt_pbs_jackknife_dev), reads rows of another type: 88
+// bytes with SIX sums.  The number of sums and the loads of a row are constants of the estimator's ROWS (Rows48, RowsPbs:
+// kSums sizes the totals and phase 1's partials), and Pbs states all its items of a set of sums at once (kJoint: three logs).
 //
 // Three dependent reductions over the rows and one closing kernel, all on the plan of jack_plan(n_win) (pgt_internal.h):
-//   phase 1  jack_totals_kernel   per wave Σbbaa, Σabba, Σbaba, Σn, g of its chunks                 -> 5 words per wave
+//   phase 1  jack_totals_kernel   per wave Σbbaa, Σabba, Σbaba, Σn, g of its chunks                 -> 5 words per wave (Pbs: six sums, 8)
 //   phase 2  jack_drop_kernel     re-adds phase 1's partials of its trio (theta), then per topology
-//                                 Σ (1 - m_j / n) theta_-j over its chunks                          -> 3 doubles per wave (Ratio: 6)
+//                                 Σ (1 - m_j / n) theta_-j over its chunks                          -> 3 doubles per wave (Ratio, Pbs: 6)
 //   phase 3  jack_var_kernel      re-adds phases 1 and 2 (theta_J), then per topology
-//                                 Σ (tau_j - theta_J)^2 / (h_j - 1) over its chunks                 -> 3 doubles per wave (Ratio: 6)
+//                                 Σ (tau_j - theta_J)^2 / (h_j - 1) over its chunks                 -> 3 doubles per wave (Ratio, Pbs: 6)
 //   close    jack_close_kernel    one wave per item: re-adds all three, writes pgt_dstat_jack
 // The grid is (ceil(n_partials / 4), n_trios) workgroups of 4 waves: blockIdx.y is the trio, wave p of it walks the chunks
-// [p * chunks_per_wave, (p + 1) * chunks_per_wave) — 64 consecutive 48-byte rows each, one row per lane, all three topologies
+// [p * chunks_per_wave, (p + 1) * chunks_per_wave) — 64 consecutive rows (48 bytes; Pbs: 88) each, one row per lane, all items
 // from that one read.  A lane adds its rows in chunk order, the wave closes with the fixed butterfly of wave_sum, and partials
 // are re-added by readd(): lane l adds partials l, l + 64, .. in turn, then the same butterfly.  No atomics; every order is a
 // function of n_win alone, and a wave touches its own trio's rows and partials only: an item's bits do not depend on n_trios
@@ -52,13 +55,13 @@ namespace {
 using namespace dev;
 
 struct JackArgs {
-    const char *rows;          // n_trios x n_win pgt_dstat_row, trio-major
+    const char *rows;          // n_trios x n_win rows of the estimator's type, trio-major
     uint64_t n_win;
     uint64_t chunks;           // jack_plan(n_win)
     uint64_t chunks_per_wave;
     uint32_t n_partials;
     uint32_t n_trios;
-    uint64_t *totals;          // [trio][5][n_partials]: Σbbaa, Σabba, Σbaba as f64 bits, Σn, g
+    uint64_t *totals;          // [trio][kSums + 2][n_partials]: the sums (Σbbaa, Σabba, Σbaba; Pbs: six) as f64 bits, Σn, g
     double *drop;              // [trio][Est::kItems][n_partials]: 3, or the 6 of Ratio
     double *var;               // [trio][Est::kItems][n_partials]
 };
@@ -78,17 +81,51 @@ __device__ __forceinline__ double ratio(double a, double b) {
 __device__ __forceinline__ double topo_x(int c, double bbaa, double abba) { return c == 0 ? abba : bbaa; }
 __device__ __forceinline__ double topo_y(int c, double abba, double baba) { return c == 2 ? abba : baba; }
 
-// ---- the estimators: what theta is of three sums and a weight; everything else in this file is common to them -------------------
-// theta(c, s, n): item c's estimate from the sums s[3] and the weight n of the used blocks; theta_drop(c, s, n, x0, x1, x2, m):
-// the same with one block (its three sums, its weight m as f64) taken out.
+// ---- the rows: how many sums a row carries, and how a lane loads the weight n and the sums x[kSums] of its row -------------------
+// the 48-byte rows (pgt_dstat_row and the types with n and the three sums at its offsets): three plain 16-byte vector loads;
+// start / end / mid / d are not looked at
+struct Rows48 {
+    static constexpr int kSums = 3;
+    static constexpr size_t kBytes = sizeof(pgt_dstat_row);
+    static __device__ __forceinline__ void load(const char *r, uint32_t &m, double *x) {
+        const uint4 head = *reinterpret_cast<const uint4 *>(r);           // start, end, mid, n
+        const double2 v0 = *reinterpret_cast<const double2 *>(r + 16);    // d, bbaa
+        const double2 v1 = *reinterpret_cast<const double2 *>(r + 32);    // abba, baba
+        m = head.w;
+        x[0] = v0.y;
+        x[1] = v1.x;
+        x[2] = v1.y;
+    }
+};
+// pgt_pbs_row: 88 bytes, so a row at an odd index is 8-byte aligned only: n and the six sums by plain 4- and 8-byte loads per
+// lane (no LDS stage and so no barrier: a padding wave returns at once; profiles/r20/pbs_jack.md).  The coordinates and the
+// three pbs are not looked at.
+struct RowsPbs {
+    static constexpr int kSums = 6;
+    static constexpr size_t kBytes = sizeof(pgt_pbs_row);
+    static __device__ __forceinline__ void load(const char *r, uint32_t &m, double *x) {
+        m = *reinterpret_cast<const uint32_t *>(r + offsetof(pgt_pbs_row, n));
+        const double *sums = reinterpret_cast<const double *>(r + offsetof(pgt_pbs_row, num_ij));  // num_ij, num_ik, num_jk, den_ij, den_ik, den_jk
+#pragma unroll
+        for (int k = 0; k < kSums; ++k) x[k] = sums[k];
+    }
+};
+static_assert(sizeof(pgt_pbs_row) == 88 && offsetof(pgt_pbs_row, n) == 12 && offsetof(pgt_pbs_row, num_ij) == 40 && offsetof(pgt_pbs_row, den_jk) == 80 &&
+              sizeof(pgt_pbs_jack) == sizeof(pgt_f4_jack), "the row layout RowsPbs::load assumes; results in the layout of pgt_f4_jack");
+
+// ---- the estimators: what theta is of the sums and a weight; everything else in this file is common to them ---------------------
+// theta(c, s, n): item c's estimate from the sums s[kSums] and the weight n of the used blocks; theta_drop(c, s, n, x, m):
+// the same with one block (its sums x, its weight m as f64) taken out.  An estimator whose items share their costly part
+// (kJoint) states all(s, n, th) instead: every item of one set of sums.
 struct D {  // Patterson's D of topology c: ratio(x, y) of two of the three sums (the head of this file)
     using Row = pgt_dstat_row;
     using Out = pgt_dstat_jack;
+    using Rows = Rows48;
     static constexpr int kItems = kJackTopologies;
-    static constexpr bool kDropFromSums = false;
+    static constexpr bool kDropFromSums = false, kJoint = false;
     static __device__ __forceinline__ double theta(int c, const double *s, double) { return ratio(topo_x(c, s[0], s[1]), topo_y(c, s[1], s[2])); }
-    static __device__ __forceinline__ double theta_drop(int c, const double *s, double, double bbaa, double abba, double baba, double) {
-        return ratio(__dsub_rn(topo_x(c, s[0], s[1]), topo_x(c, bbaa, abba)), __dsub_rn(topo_y(c, s[1], s[2]), topo_y(c, abba, baba)));
+    static __device__ __forceinline__ double theta_drop(int c, const double *s, double, const double *x /* bbaa, abba, baba */, double) {
+        return ratio(__dsub_rn(topo_x(c, s[0], s[1]), topo_x(c, x[0], x[1])), __dsub_rn(topo_y(c, s[1], s[2]), topo_y(c, x[1], x[2])));
     }
     static __device__ __forceinline__ void set(Out &r, double th, double th_j, double se, double z) { r.d = th; r.d_jack = th_j; r.se = se; r.z = z; }
 };
@@ -103,12 +140,13 @@ template <class RowT, class OutT>
 struct Mean {
     using Row = RowT;
     using Out = OutT;
+    using Rows = Rows48;
     static constexpr int kItems = kJackTopologies;
-    static constexpr bool kDropFromSums = false;
+    static constexpr bool kDropFromSums = false, kJoint = false;
     static __device__ __forceinline__ double pick(int c, double x0, double x1, double x2) { return c == 0 ? x0 : (c == 1 ? x1 : x2); }
     static __device__ __forceinline__ double theta(int c, const double *s, double n) { return mean(pick(c, s[0], s[1], s[2]), n); }
-    static __device__ __forceinline__ double theta_drop(int c, const double *s, double n, double x0, double x1, double x2, double m) {
-        return mean(__dsub_rn(pick(c, s[0], s[1], s[2]), pick(c, x0, x1, x2)), __dsub_rn(n, m));
+    static __device__ __forceinline__ double theta_drop(int c, const double *s, double n, const double *x, double m) {
+        return mean(__dsub_rn(pick(c, s[0], s[1], s[2]), pick(c, x[0], x[1], x[2])), __dsub_rn(n, m));
     }
     static __device__ __forceinline__ void set(Out &r, double th, double th_j, double se, double z) { set_estimates(r, th, th_j); r.se = se; r.z = z; }
 };
@@ -126,8 +164,9 @@ using F4Mean = Mean<pgt_f4_row, pgt_f4_jack>;  // item c: f4 of pairing c of the
 struct Ratio {
     using Row = pgt_f4ratio_row;
     using Out = pgt_f4ratio_jack;
+    using Rows = Rows48;
     static constexpr int kItems = kJackRatioItems;
-    static constexpr bool kDropFromSums = true;
+    static constexpr bool kDropFromSums = true, kJoint = false;
     static __device__ __forceinline__ double num(int c, double s0, double s1, double s2) {
         return c == 0 ? s2 : (c == 1 || c == 4 ? s1 : (c == 2 ? -s2 : s0));
     }
@@ -136,6 +175,27 @@ struct Ratio {
     }
     static __device__ __forceinline__ double theta(int c, const double *s, double) { return mean(num(c, s[0], s[1], s[2]), den(c, s[0], s[1], s[2])); }
     static __device__ __forceinline__ void set(Out &r, double th, double th_j, double se, double z) { r.alpha = th; r.alpha_jack = th_j; r.se = se; r.z = z; }
+};
+// The population branch statistic (pgt_pbs_jackknife_dev) over the rows of pgt_pbs_pops_reduce_dev: a NON-LINEAR function of SIX
+// block sums S = (num_ij, num_ik, num_jk, den_ij, den_ik, den_jk).  E(S): the row arithmetic of pgt_pbs_row (pbs_of,
+// pgt_pops_common.h: fst_xy = den_xy != 0 ? num_xy / den_xy : 0, T_xy = -log(1 - fst_xy), three logs) gives pbs_i, pbs_j, pbs_k,
+// items 0 ... 2; items 3 ... 5 are PBSn1 (Malaspinas et al. 2016) of the same focal populations,
+//     s = (pbs_i + pbs_j) + pbs_k        pbsn1_x = pbs_x / (1.0 + s)
+// Nothing is clamped.  theta = E(Σ S), theta_-j = E(Σ S - s_j), each of the six sums losing the block with one rounding
+// (kDropFromSums); E is evaluated once per block for all six items (kJoint).  The weight decides "used" alone.
+struct Pbs {
+    using Row = pgt_pbs_row;
+    using Out = pgt_pbs_jack;
+    using Rows = RowsPbs;
+    static constexpr int kItems = kJackPbsItems;
+    static constexpr bool kDropFromSums = true, kJoint = true;
+    static __device__ __forceinline__ void all(const double *s, double, double *th) {
+        pbs_of(s, s + 3, th[0], th[1], th[2]);
+        const double one_s = __dadd_rn(1.0, __dadd_rn(__dadd_rn(th[0], th[1]), th[2]));
+#pragma unroll
+        for (int k = 0; k < 3; ++k) th[3 + k] = __ddiv_rn(th[k], one_s);
+    }
+    static __device__ __forceinline__ void set(Out &r, double th, double th_j, double se, double z) { r.stat = th; r.stat_jack = th_j; r.se = se; r.z = z; }
 };
 
 // Σ of n_partials doubles in index order per lane (l, l + 64, ..), then the butterfly: the same bits in every lane of every wave
@@ -150,49 +210,44 @@ __device__ __forceinline__ uint64_t readd(const uint64_t *p, uint32_t n_partials
     return wave_sum(a);
 }
 
+template <int NS>
 struct Totals {
-    double s[3];  // Σbbaa, Σabba, Σbaba over the used blocks
-    double n;     // Σ m_j as f64 (exact below 2^53 sites)
+    double s[NS];  // the sums over the used blocks (Σbbaa, Σabba, Σbaba; the six of a pgt_pbs_row)
+    double n;      // Σ m_j as f64 (exact below 2^53 sites)
     uint64_t n_sites;
     uint32_t g;
 };
-__device__ __forceinline__ Totals read_totals(const JackArgs &a, uint32_t trio, int lane) {
-    const uint64_t *base = a.totals + (uint64_t)trio * kJackTotalWords * a.n_partials;
-    Totals t;
+template <int NS>
+__device__ __forceinline__ Totals<NS> read_totals(const JackArgs &a, uint32_t trio, int lane) {
+    const uint64_t *base = a.totals + (uint64_t)trio * jack_total_words(NS) * a.n_partials;
+    Totals<NS> t;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) t.s[k] = readd(reinterpret_cast<const double *>(base + (uint64_t)k * a.n_partials), a.n_partials, lane);
-    t.n_sites = readd(base + 3ull * a.n_partials, a.n_partials, lane);
-    t.g = (uint32_t)readd(base + 4ull * a.n_partials, a.n_partials, lane);
+    for (int k = 0; k < NS; ++k) t.s[k] = readd(reinterpret_cast<const double *>(base + (uint64_t)k * a.n_partials), a.n_partials, lane);
+    t.n_sites = readd(base + (uint64_t)NS * a.n_partials, a.n_partials, lane);
+    t.g = (uint32_t)readd(base + (uint64_t)(NS + 1) * a.n_partials, a.n_partials, lane);
     t.n = (double)t.n_sites;
     return t;
 }
 
-// the wave's rows, one per lane and chunk, in chunk order: f(used, m_j, bbaa, abba, baba); a lane beyond the table sees an
-// unused block of zeros.  Rows are read by three plain 16-byte vector loads; start / end / mid / d are not looked at.
-template <class F>
+// the wave's rows, one per lane and chunk, in chunk order: f(used, m_j, x[kSums]); a lane beyond the table sees an unused block
+// of zeros.  Rows::load reads a row.
+template <class Rows, class F>
 __device__ __forceinline__ void for_rows(const JackArgs &a, uint32_t trio, uint32_t p, int lane, F f) {
-    const char *rows_t = a.rows + (uint64_t)trio * a.n_win * sizeof(pgt_dstat_row);
+    const char *rows_t = a.rows + (uint64_t)trio * a.n_win * Rows::kBytes;
     const uint64_t c0 = (uint64_t)p * a.chunks_per_wave;
     const uint64_t c1 = c0 + a.chunks_per_wave < a.chunks ? c0 + a.chunks_per_wave : a.chunks;
 #pragma unroll 2
     for (uint64_t c = c0; c < c1; ++c) {
         const uint64_t j = c * kJackChunk + (uint64_t)lane;
         uint32_t m = 0;
-        double bbaa = 0.0, abba = 0.0, baba = 0.0;
-        if (j < a.n_win) {
-            const char *r = rows_t + j * sizeof(pgt_dstat_row);
-            const uint4 head = *reinterpret_cast<const uint4 *>(r);           // start, end, mid, n
-            const double2 v0 = *reinterpret_cast<const double2 *>(r + 16);    // d, bbaa
-            const double2 v1 = *reinterpret_cast<const double2 *>(r + 32);    // abba, baba
-            m = head.w;
-            bbaa = v0.y;
-            abba = v1.x;
-            baba = v1.y;
-        }
-        f(m > 0, m, bbaa, abba, baba);
+        double x[Rows::kSums];
+#pragma unroll
+        for (int k = 0; k < Rows::kSums; ++k) x[k] = 0.0;
+        if (j < a.n_win) Rows::load(rows_t + j * Rows::kBytes, m, x);
+        f(m > 0, m, x);
     }
 }
-static_assert(sizeof(pgt_dstat_row) == 48 && sizeof(pgt_dstat_jack) == 48, "the row layout the loads above assume");
+static_assert(sizeof(pgt_dstat_row) == 48 && sizeof(pgt_dstat_jack) == 48, "the row layout Rows48::load assumes");
 // the rows of pgt_f3_pops_reduce_dev go through the same loads: n and the three sums sit where pgt_dstat_row has them
 static_assert(sizeof(pgt_f3_row) == sizeof(pgt_dstat_row) && sizeof(pgt_f3_jack) == sizeof(pgt_dstat_jack), "one row loader, one result layout");
 static_assert(offsetof(pgt_f3_row, n) == offsetof(pgt_dstat_row, n) && offsetof(pgt_f3_row, f3_i) == offsetof(pgt_dstat_row, bbaa) &&
@@ -221,45 +276,78 @@ __device__ __forceinline__ int64_t my_partial(const JackArgs &a) {
     return p < a.n_partials ? (int64_t)p : -1;
 }
 
-// theta_-j of item c: the estimator's own statement of it, or (kDropFromSums) its theta of the sums and the weight less block j's
 template <class Est>
-__device__ __forceinline__ double theta_without(int c, const Totals &t, double x0, double x1, double x2, double m) {
-    if constexpr (Est::kDropFromSums) {
-        const double rest[3] = {__dsub_rn(t.s[0], x0), __dsub_rn(t.s[1], x1), __dsub_rn(t.s[2], x2)};
-        return Est::theta(c, rest, __dsub_rn(t.n, m));
+using TotalsOf = Totals<Est::Rows::kSums>;
+
+// every item's theta of one set of sums: the estimator's joint statement (kJoint), or item after item
+template <class Est>
+__device__ __forceinline__ void thetas(const double *s, double n, double *th) {
+    if constexpr (Est::kJoint) {
+        Est::all(s, n, th);
     } else {
-        return Est::theta_drop(c, t.s, t.n, x0, x1, x2, m);
+#pragma unroll
+        for (int c = 0; c < Est::kItems; ++c) th[c] = Est::theta(c, s, n);
+    }
+}
+// theta of item c alone (c need not be a constant: the items are selected, never indexed)
+template <class Est>
+__device__ __forceinline__ double theta_of(int c, const TotalsOf<Est> &t) {
+    if constexpr (Est::kJoint) {
+        double th[Est::kItems];
+        Est::all(t.s, t.n, th);
+        double v = th[0];
+#pragma unroll
+        for (int k = 1; k < Est::kItems; ++k) v = c == k ? th[k] : v;
+        return v;
+    } else {
+        return Est::theta(c, t.s, t.n);
+    }
+}
+// theta_-j of every item: the estimator's own statement of it, or (kDropFromSums) its thetas of the sums and the weight less block j's
+template <class Est>
+__device__ __forceinline__ void thetas_without(const TotalsOf<Est> &t, const double *x, double m, double *th) {
+    if constexpr (Est::kDropFromSums) {
+        constexpr int NS = Est::Rows::kSums;
+        double rest[NS];
+#pragma unroll
+        for (int k = 0; k < NS; ++k) rest[k] = __dsub_rn(t.s[k], x[k]);
+        thetas<Est>(rest, __dsub_rn(t.n, m), th);
+    } else {
+#pragma unroll
+        for (int c = 0; c < Est::kItems; ++c) th[c] = Est::theta_drop(c, t.s, t.n, x, m);
     }
 }
 
 // ---- phase 1: the totals -----------------------------------------------------------------------------------------------------
+// a function of the rows alone (their sum count and loads): one instance for the 48-byte rows, one for pgt_pbs_row
+template <class Rows>
 __global__ __launch_bounds__(256) void jack_totals_kernel(JackArgs a) {
     const int lane = threadIdx.x & (kWave - 1);
     const uint32_t trio = blockIdx.y;
     const int64_t pp = my_partial(a);
     if (pp < 0) return;
     const uint32_t p = (uint32_t)pp;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    constexpr int NS = Rows::kSums;
+    double s[NS];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) s[k] = 0.0;
     uint64_t n = 0, g = 0;
-    for_rows(a, trio, p, lane, [&](bool used, uint32_t m, double bbaa, double abba, double baba) {
-        s0 = __dadd_rn(s0, used ? bbaa : 0.0);
-        s1 = __dadd_rn(s1, used ? abba : 0.0);
-        s2 = __dadd_rn(s2, used ? baba : 0.0);
+    for_rows<Rows>(a, trio, p, lane, [&](bool used, uint32_t m, const double *x) {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) s[k] = __dadd_rn(s[k], used ? x[k] : 0.0);
         n += m;  // an unused block has m == 0
         g += used ? 1u : 0u;
     });
-    s0 = dev::wave_sum(s0);
-    s1 = dev::wave_sum(s1);
-    s2 = dev::wave_sum(s2);
+#pragma unroll
+    for (int k = 0; k < NS; ++k) s[k] = dev::wave_sum(s[k]);
     n = wave_sum(n);
     g = wave_sum(g);
     if (lane == 0) {
-        uint64_t *base = a.totals + (uint64_t)trio * kJackTotalWords * a.n_partials + p;
-        reinterpret_cast<double *>(base)[0] = s0;
-        reinterpret_cast<double *>(base)[(uint64_t)a.n_partials] = s1;
-        reinterpret_cast<double *>(base)[2ull * a.n_partials] = s2;
-        base[3ull * a.n_partials] = n;
-        base[4ull * a.n_partials] = g;
+        uint64_t *base = a.totals + (uint64_t)trio * jack_total_words(NS) * a.n_partials + p;
+#pragma unroll
+        for (int k = 0; k < NS; ++k) reinterpret_cast<double *>(base)[(uint64_t)k * a.n_partials] = s[k];
+        base[(uint64_t)NS * a.n_partials] = n;
+        base[(uint64_t)(NS + 1) * a.n_partials] = g;
     }
 }
 
@@ -271,18 +359,17 @@ __global__ __launch_bounds__(256) void jack_drop_kernel(JackArgs a) {
     const int64_t pp = my_partial(a);
     if (pp < 0) return;
     const uint32_t p = (uint32_t)pp;
-    const Totals t = read_totals(a, trio, lane);
+    const TotalsOf<Est> t = read_totals<Est::Rows::kSums>(a, trio, lane);
     constexpr int kItems = Est::kItems;
     double acc[kItems];
 #pragma unroll
     for (int c = 0; c < kItems; ++c) acc[c] = 0.0;
-    for_rows(a, trio, p, lane, [&](bool used, uint32_t m, double bbaa, double abba, double baba) {
+    for_rows<typename Est::Rows>(a, trio, p, lane, [&](bool used, uint32_t m, const double *x) {
         const double w = __dsub_rn(1.0, __ddiv_rn((double)m, t.n));
+        double th[kItems];
+        thetas_without<Est>(t, x, (double)m, th);
 #pragma unroll
-        for (int c = 0; c < kItems; ++c) {
-            const double th = theta_without<Est>(c, t, bbaa, abba, baba, (double)m);
-            acc[c] = __dadd_rn(acc[c], used ? __dmul_rn(w, th) : 0.0);
-        }
+        for (int c = 0; c < kItems; ++c) acc[c] = __dadd_rn(acc[c], used ? __dmul_rn(w, th[c]) : 0.0);
     });
 #pragma unroll
     for (int c = 0; c < kItems; ++c) {
@@ -291,12 +378,11 @@ __global__ __launch_bounds__(256) void jack_drop_kernel(JackArgs a) {
     }
 }
 
-// theta and theta_J of topology c from the re-added partials (the same bits wherever it is called)
+// theta_J of item c from its theta and the re-added partials of phase 2 (the same bits wherever it is called)
 template <class Est>
-__device__ __forceinline__ void estimates(const JackArgs &a, const Totals &t, uint32_t trio, int c, int lane, double *theta, double *theta_j) {
-    *theta = Est::theta(c, t.s, t.n);
+__device__ __forceinline__ double jack_estimate(const JackArgs &a, const TotalsOf<Est> &t, uint32_t trio, int c, int lane, double theta) {
     const double drop = readd(a.drop + ((uint64_t)trio * Est::kItems + c) * a.n_partials, a.n_partials, lane);
-    *theta_j = __dsub_rn(__dmul_rn((double)t.g, *theta), drop);
+    return __dsub_rn(__dmul_rn((double)t.g, theta), drop);
 }
 
 // ---- phase 3: Σ (tau_j - theta_J)^2 / (h_j - 1) -----------------------------------------------------------------------------
@@ -307,20 +393,22 @@ __global__ __launch_bounds__(256) void jack_var_kernel(JackArgs a) {
     const int64_t pp = my_partial(a);
     if (pp < 0) return;
     const uint32_t p = (uint32_t)pp;
-    const Totals t = read_totals(a, trio, lane);
+    const TotalsOf<Est> t = read_totals<Est::Rows::kSums>(a, trio, lane);
     constexpr int kItems = Est::kItems;
     double theta[kItems], theta_j[kItems], acc[kItems];
+    thetas<Est>(t.s, t.n, theta);  // every item of the totals from ONE evaluation of the estimator
 #pragma unroll
     for (int c = 0; c < kItems; ++c) {
-        estimates<Est>(a, t, trio, c, lane, &theta[c], &theta_j[c]);
+        theta_j[c] = jack_estimate<Est>(a, t, trio, c, lane, theta[c]);
         acc[c] = 0.0;
     }
-    for_rows(a, trio, p, lane, [&](bool used, uint32_t m, double bbaa, double abba, double baba) {
+    for_rows<typename Est::Rows>(a, trio, p, lane, [&](bool used, uint32_t m, const double *x) {
         const double hm1 = __dsub_rn(__ddiv_rn(t.n, (double)m), 1.0);  // an unused block: inf, selected away below
+        double th[kItems];
+        thetas_without<Est>(t, x, (double)m, th);
 #pragma unroll
         for (int c = 0; c < kItems; ++c) {
-            const double th = theta_without<Est>(c, t, bbaa, abba, baba, (double)m);
-            const double tau = __dadd_rn(theta[c], __dmul_rn(hm1, __dsub_rn(theta[c], th)));
+            const double tau = __dadd_rn(theta[c], __dmul_rn(hm1, __dsub_rn(theta[c], th[c])));
             const double dv = __dsub_rn(tau, theta_j[c]);
             acc[c] = __dadd_rn(acc[c], used ? __ddiv_rn(__dmul_rn(dv, dv), hm1) : 0.0);
         }
@@ -340,9 +428,9 @@ __global__ __launch_bounds__(256) void jack_close_kernel(JackArgs a, typename Es
     if (u >= a.n_trios * Est::kItems) return;
     const uint32_t trio = u / Est::kItems;
     const int c = (int)(u % Est::kItems);
-    const Totals t = read_totals(a, trio, lane);  // without a partial (n_win == 0): zeros
-    double theta, theta_j;
-    estimates<Est>(a, t, trio, c, lane, &theta, &theta_j);
+    const TotalsOf<Est> t = read_totals<Est::Rows::kSums>(a, trio, lane);  // without a partial (n_win == 0): zeros
+    const double theta = theta_of<Est>(c, t);
+    const double theta_j = jack_estimate<Est>(a, t, trio, c, lane, theta);
     const double vs = readd(a.var + ((uint64_t)trio * Est::kItems + c) * a.n_partials, a.n_partials, lane);
     typename Est::Out r;
     r.n_sites = t.n_sites;
@@ -363,7 +451,7 @@ int launch_jackknife(const typename Est::Row *rows, uint64_t n_win, uint32_t n_t
                      void *stream, void *ev_query0, void *ev_query1, std::string *err) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     const JackPlan plan = jack_plan(n_win);
-    const JackWork w = jack_work(n_trios, n_win, Est::kItems);
+    const JackWork w = jack_work(n_trios, n_win, Est::kItems, Est::Rows::kSums);
     JackArgs a{};
     a.rows = reinterpret_cast<const char *>(rows);
     a.n_win = n_win;
@@ -377,7 +465,7 @@ int launch_jackknife(const typename Est::Row *rows, uint64_t n_win, uint32_t n_t
     if (int rc = record_event(ev_query0, s, err)) return rc;
     if (plan.n_partials > 0) {
         const dim3 grid((plan.n_partials + 3) / 4, n_trios);
-        hipLaunchKernelGGL(jack_totals_kernel, grid, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(jack_totals_kernel<typename Est::Rows>, grid, dim3(256), 0, s, a);
         if (int rc = hip_fail(hipGetLastError(), "jack_totals_kernel", err)) return rc;
         hipLaunchKernelGGL(jack_drop_kernel<Est>, grid, dim3(256), 0, s, a);
         if (int rc = hip_fail(hipGetLastError(), "jack_drop_kernel", err)) return rc;
@@ -412,6 +500,13 @@ int launch_f4_jackknife(const pgt_f4_row *rows, uint64_t n_win, uint32_t n_quart
 int launch_f4ratio_jackknife(const pgt_f4ratio_row *rows, uint64_t n_win, uint32_t n_triples, pgt_f4ratio_jack *out, void *work,
                              void *stream, void *ev_query0, void *ev_query1, std::string *err) {
     return launch_jackknife<Ratio>(rows, n_win, n_triples, out, work, stream, ev_query0, ev_query1, err);
+}
+
+// the rows of pgt_pbs_pops_reduce_dev (either FST estimator): item u = 6 t + c is PBS (c < 3) or PBSn1 (c >= 3) of trio t with
+// population c % 3 (i / j / k) as the focal one (Pbs)
+int launch_pbs_jackknife(const pgt_pbs_row *rows, uint64_t n_win, uint32_t n_trios, pgt_pbs_jack *out, void *work,
+                         void *stream, void *ev_query0, void *ev_query1, std::string *err) {
+    return launch_jackknife<Pbs>(rows, n_win, n_trios, out, work, stream, ev_query0, ev_query1, err);
 }
 
 }  // namespace pgt

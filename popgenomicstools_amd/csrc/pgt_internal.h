@@ -185,6 +185,11 @@ constexpr uint32_t kJackMaxTrios = 20;       // C(6, 3): what pgt_dstat_pops_red
 constexpr int kJackTotalWords = 5;           // phase 1 per wave: Σbbaa, Σabba, Σbaba (f64), Σn (u64), used blocks (u64)
 constexpr int kJackTopologies = 3;           // phases 2 and 3 per wave: one f64 per topology
 constexpr int kJackRatioItems = 6;           // ... and per admixture proportion of a middle triple (pgt_f4ratio_jackknife_dev)
+constexpr int kJackPbsItems = 6;             // ... and per PBS / PBSn1 of a trio's three focal populations (pgt_pbs_jackknife_dev)
+constexpr int kJackSums = 3;                 // sums of a 48-byte row; a pgt_pbs_row has kJackPbsSums
+constexpr int kJackPbsSums = 6;
+constexpr int jack_total_words(int sums) { return sums + 2; }  // phase 1 per wave: the sums (f64), Σn (u64), used blocks (u64)
+static_assert(jack_total_words(kJackSums) == kJackTotalWords, "the three-sum rows keep their five words");
 struct JackPlan {
     uint64_t chunks = 0;           // ceil(n_win / kJackChunk)
     uint64_t chunks_per_wave = 0;  // ceil(chunks / kJackMaxPartials)
@@ -198,24 +203,25 @@ inline JackPlan jack_plan(uint64_t n_win) {
     p.n_partials = (uint32_t)((p.chunks + p.chunks_per_wave - 1) / p.chunks_per_wave);
     return p;
 }
-// The workspace, in 8-byte words: [trio][word k < 5][partial] of phase 1, then [trio][topology][partial] of phase 2 and the same
-// of phase 3.  Its SIZE is that of min(chunks, kJackMaxPartials) partials — what n_partials never exceeds, and monotone in n_win
+// The workspace, in 8-byte words: [trio][word k < 5][partial] of phase 1 (jack_total_words(sums): 8 for the six sums of a
+// pgt_pbs_row), then [trio][topology][partial] of phase 2 and the same of phase 3.  Its SIZE is that of min(chunks, kJackMaxPartials) partials — what n_partials never exceeds, and monotone in n_win
 // where n_partials itself is not (1025 chunks make 513 waves of two) — and 256 bytes at least (a call without blocks reads and
 // writes none of it).
 struct JackWork {
     size_t totals = 0, drop = 0, var = 0;  // byte offsets of the three phases' partials
     size_t bytes = 0;
 };
-// items: the estimator's items per table (kJackTopologies; the ratio of pgt_f4ratio_jackknife_dev: kJackRatioItems)
-inline JackWork jack_work(uint32_t n_trios, uint64_t n_win, int items = kJackTopologies) {
+// items: the estimator's items per table (kJackTopologies; the ratio of pgt_f4ratio_jackknife_dev: kJackRatioItems; PBS:
+// kJackPbsItems); sums: the sums of a row (kJackSums; a pgt_pbs_row: kJackPbsSums — 8 + 6 + 6 = 20 words per partial)
+inline JackWork jack_work(uint32_t n_trios, uint64_t n_win, int items = kJackTopologies, int sums = kJackSums) {
     JackWork w;
     const size_t per = (size_t)n_trios * jack_plan(n_win).n_partials * 8;
     w.totals = 0;
-    w.drop = w.totals + per * kJackTotalWords;
+    w.drop = w.totals + per * jack_total_words(sums);
     w.var = w.drop + per * items;
     const JackPlan p = jack_plan(n_win);
     const size_t cap = (size_t)(p.chunks < kJackMaxPartials ? p.chunks : kJackMaxPartials);
-    w.bytes = (((size_t)n_trios * cap * 8 * (kJackTotalWords + 2 * items) + 255) / 256) * 256;
+    w.bytes = (((size_t)n_trios * cap * 8 * (jack_total_words(sums) + 2 * items) + 255) / 256) * 256;
     if (w.bytes == 0) w.bytes = 256;
     return w;
 }
@@ -234,6 +240,10 @@ int launch_f4_jackknife(const pgt_f4_row *rows, uint64_t n_win, uint32_t n_quart
 constexpr uint32_t kJackMaxTriples = 10;     // C(5, 3): what pgt_f4ratio_pops_reduce_dev can write
 int launch_f4ratio_jackknife(const pgt_f4ratio_row *rows, uint64_t n_win, uint32_t n_triples, pgt_f4ratio_jack *out, void *work,
                              void *stream, void *ev_query0, void *ev_query1, std::string *err);
+// PBS and PBSn1 of a trio's three focal populations (Pbs), six items per table from the SIX sums of the 88-byte rows of
+// pgt_pbs_pops_reduce_dev: 1 <= n_trios <= kJackMaxTrios; the workspace is jack_work(n_trios, n_win, kJackPbsItems, kJackPbsSums)
+int launch_pbs_jackknife(const pgt_pbs_row *rows, uint64_t n_win, uint32_t n_trios, pgt_pbs_jack *out, void *work,
+                         void *stream, void *ev_query0, void *ev_query1, std::string *err);
 
 // Speed-only hints of a context (pgt_set_max_window, pgt_set_window_step); 0 = unknown.
 struct Hints {

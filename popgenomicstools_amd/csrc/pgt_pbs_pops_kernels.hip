@@ -95,18 +95,7 @@ struct PbsPass {
     }
 };
 
-// T = -log(1 - fst), fst = den != 0 ? num / den : 0 (fstWindow.cpp:85): a negative fst gives a negative T, fst == 1 gives +inf
-__device__ __forceinline__ double branch(double num, double den) {
-    const double fst = den != 0.0 ? __ddiv_rn(num, den) : 0.0;
-    return -log(__dsub_rn(1.0, fst));
-}
-// the three branch statistics from the six sums (inf - inf is NaN: the IEEE results stand)
-__device__ __forceinline__ void pbs_of(const double *num, const double *den, double &pbs_i, double &pbs_j, double &pbs_k) {
-    const double t_ij = branch(num[0], den[0]), t_ik = branch(num[1], den[1]), t_jk = branch(num[2], den[2]);
-    pbs_i = __dadd_rn(__dmul_rn(__dsub_rn(__dadd_rn(t_ij, t_ik), t_jk), 0.5), 0.0);
-    pbs_j = __dadd_rn(__dmul_rn(__dsub_rn(__dadd_rn(t_ij, t_jk), t_ik), 0.5), 0.0);
-    pbs_k = __dadd_rn(__dmul_rn(__dsub_rn(__dadd_rn(t_ik, t_jk), t_ij), 0.5), 0.0);
-}
+// branch, pbs_of: the closing arithmetic of a row (pgt_pops_common.h, shared with the block jackknife of these rows)
 
 // One thread per scratch row (n_rows = T * n_win, trio-major as the passes wrote them) and, behind them, per scratch total
 // (n_tot = T, or 0): the two passes' sums side by side, and the closing arithmetic.  Both passes counted the same sites.

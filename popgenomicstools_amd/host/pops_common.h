@@ -15,6 +15,7 @@
 //     line(row, sites of the window), total(total)    the numbers of a row behind `chr`, of a PREFIX.global line behind the indices
 //     window_hints                                    the window table's hints are set before the reduction (piWindowPops alone)
 //     more(run, rows on the device)                   further device work on the same columns: pops_jackknife, a second pops_pass
+//     host_rows                                       more() also gets the pass's rows and totals on the host (further files from them)
 // and its main is `return run_pops_tool<Tool>(argc, argv);`.
 #pragma once
 
@@ -81,20 +82,22 @@ inline PopsArgs parse_pops_args(Tool &tool, int argc, char **argv) {
 
 // -jackknife 0|1 of the trio tools.  With 1 the run is refused here, while the options are read and before any file is opened,
 // unless its windows exist and are disjoint: they are the blocks (the option pairs are walked as parse_pops_args walks them, so
-// the last value of -winsize / -stepsize counts wherever -jackknife stands).
+// the last value of -winsize / -stepsize counts wherever -jackknife stands).  `name`: the option's name where it is not
+// -jackknife (pbsWindowPops: -blockjack); the messages name it.
 struct JackknifeOption {
     bool on = false;
-    bool take(const char *o, const char *v, int argc, char **argv) {
-        if (std::strcmp(o, "-jackknife")) return false;
-        if (std::strcmp(v, "0") && std::strcmp(v, "1")) die(std::string("-jackknife must be 0 or 1 (given: ") + v + ")");
+    bool take(const char *o, const char *v, int argc, char **argv, const char *name = "-jackknife") {
+        const std::string opt = name;
+        if (std::strcmp(o, name)) return false;
+        if (std::strcmp(v, "0") && std::strcmp(v, "1")) die(opt + " must be 0 or 1 (given: " + v + ")");
         on = v[0] == '1';
         if (!on) return true;
         DxyOptions w;
         for (int i = 1; i + 1 < argc && argv[i][0] == '-' && argv[i][1] != '\0'; i += 2)
             if (!std::strcmp(argv[i], "-winsize") || !std::strcmp(argv[i], "-stepsize")) dxy_option(w, argv[i], argv[i + 1]);
-        if (w.W == 0) die("-jackknife 1 needs windows as its blocks: -winsize must be > 0");
+        if (w.W == 0) die(opt + " 1 needs windows as its blocks: -winsize must be > 0");
         if (w.S < w.W)
-            die("-jackknife 1 needs windows that do not overlap: -stepsize (" + std::to_string(w.S) + ") must not be below -winsize (" + std::to_string(w.W) + ")");
+            die(opt + " 1 needs windows that do not overlap: -stepsize (" + std::to_string(w.S) + ") must not be below -winsize (" + std::to_string(w.W) + ")");
         return true;
     }
 };
@@ -404,11 +407,20 @@ struct PopsRun {
     size_t tree_bytes = 0;
     std::vector<std::function<void()>> writers;
 };
+// the rows and totals of one pass on the host, for a tool whose more() writes further files from them (Tool::host_rows)
+template <class Row, class Total>
+struct PopsHostRows {
+    std::shared_ptr<RowArray<Row>> rows;
+    std::shared_ptr<std::vector<Total>> tot;
+};
+
+template <class Files, class Row, class Total>
+void pops_queue_files(PopsRun &run, std::shared_ptr<RowArray<Row>> rows, std::shared_ptr<std::vector<Total>> tot);
 
 // One reduction of the aligned columns over all tables of the run, and its files: PREFIX.<table><ext> per table (not with
-// -winsize 0) and PREFIX<global_ext>.  -> the rows on the device, table after table
+// -winsize 0) and PREFIX<global_ext>.  -> the rows on the device, table after table; host, where given: the same rows and the totals
 template <class Pass>
-typename Pass::Row *pops_pass(const Pass &pass, PopsRun &run) {
+typename Pass::Row *pops_pass(const Pass &pass, PopsRun &run, PopsHostRows<typename Pass::Row, typename Pass::Total> *host = nullptr) {
     using Row = typename Pass::Row;
     using Total = typename Pass::Total;
     const PopsSites &s = run.s;
@@ -422,6 +434,17 @@ typename Pass::Row *pops_pass(const Pass &pass, PopsRun &run) {
     auto tot = std::make_shared<std::vector<Total>>(n_tab);
     check(pgt_rowbuf_read(ctx, rows->data(), d_rows, n_tab * n_win * sizeof(Row), nullptr), ctx);
     check(pgt_rowbuf_read(ctx, tot->data(), d_tot, n_tab * sizeof(Total), nullptr), ctx);
+    if (host) *host = {rows, tot};
+    pops_queue_files<Pass>(run, rows, tot);
+    return d_rows;
+}
+
+// The files of one set of rows and totals on the host, queued behind the run's reductions.  Files: ext, global_ext, row_bytes,
+// line(row, sites of the window), total(total) — a pass itself, or further columns a tool derives from its rows (PBSn1)
+template <class Files, class Row, class Total>
+void pops_queue_files(PopsRun &run, std::shared_ptr<RowArray<Row>> rows, std::shared_ptr<std::vector<Total>> tot) {
+    using Pass = Files;
+    const size_t n_win = run.s.win.size();
     run.writers.push_back([&run, rows, tot, n_win] {
         const char *prefix = run.args.prefix;
         const int skip_missing = run.args.opt.skip_missing;
@@ -449,13 +472,13 @@ typename Pass::Row *pops_pass(const Pass &pass, PopsRun &run) {
         }
         close_out(global, global_path);
     });
-    return d_rows;
 }
 
 // -jackknife 1: the delete-m_j block jackknife of every trio of the run on its rows still on the device, every window of the table
 // a block -> PREFIX.jackknife, three lines per trio (`P1 P2 P3 estimate jackknife_estimate SE Z nblocks nsites`) or quartet
 // (`P1 P2 P3 P4 ..`); U lines per table where the estimator has U items (the f4-ratio: six).  order[u]: which of the table's
-// populations line u names first, second, third (and fourth).  The entry points' results are one layout.
+// populations line u names first, second, third (and fourth).  label[u], where given, stands in front of line u (the name of
+// its statistic).  The entry points' results are one layout.
 struct PopsJack {
     double est, est_jack, se, z;
     uint64_t n_sites;
@@ -463,7 +486,7 @@ struct PopsJack {
 };
 template <class Row, class Jack, size_t U, size_t N>
 void pops_jackknife(PopsRun &run, const Row *d_rows, int (*jackknife_dev)(pgt_ctx *, const Row *, uint64_t, uint32_t, Jack *, size_t, void *, size_t, void *),
-                    size_t (*work_bytes)(uint32_t, uint64_t), const int (&order)[U][N]) {
+                    size_t (*work_bytes)(uint32_t, uint64_t), const int (&order)[U][N], const char *const *label = nullptr) {
     static_assert(sizeof(Jack) == sizeof(PopsJack) && offsetof(Jack, se) == offsetof(PopsJack, se) && offsetof(Jack, z) == offsetof(PopsJack, z) &&
                   offsetof(Jack, n_sites) == offsetof(PopsJack, n_sites) && offsetof(Jack, n_blocks) == offsetof(PopsJack, n_blocks),
                   "the estimate and its jackknife estimate, then se, z, n_sites, n_blocks");
@@ -476,7 +499,7 @@ void pops_jackknife(PopsRun &run, const Row *d_rows, int (*jackknife_dev)(pgt_ct
     check(jackknife_dev(ctx, d_rows, n_win, (uint32_t)n_trios, d_jack, U * n_trios * sizeof(Jack), work, bytes, nullptr), ctx);
     auto jack = std::make_shared<std::vector<PopsJack>>(U * n_trios);
     check(pgt_rowbuf_read(ctx, jack->data(), d_jack, U * n_trios * sizeof(Jack), nullptr), ctx);
-    run.writers.push_back([&run, jack, &order] {  // (order: a constant of the tool)
+    run.writers.push_back([&run, jack, &order, label] {  // (order, label: constants of the tool)
         const std::string path = std::string(run.args.prefix) + ".jackknife";
         FILE *f = open_out(path);
         auto g6 = [](double v) { char b_[64]; if (v != v) return std::string("nan"); std::snprintf(b_, sizeof b_, "%g", v); return std::string(b_); };
@@ -484,6 +507,7 @@ void pops_jackknife(PopsRun &run, const Row *d_rows, int (*jackknife_dev)(pgt_ct
             for (size_t u = 0; u < U; ++u) {
                 const int *pop = run.tables[t].pop;
                 const PopsJack &r = (*jack)[U * t + u];
+                if (label) std::fprintf(f, "%s\t", label[u]);
                 for (size_t k = 0; k < N; ++k) std::fprintf(f, "%d\t", pop[order[u][k]] + 1);
                 std::fprintf(f, "%s\t%s\t%s\t%s\t%u\t%llu\n", g6(r.est).c_str(), g6(r.est_jack).c_str(), g6(r.se).c_str(), g6(r.z).c_str(), r.n_blocks,
                              (unsigned long long)r.n_sites);
@@ -500,6 +524,7 @@ struct PopsTool {
     static constexpr bool first_apart = false;   // the FIRST file has a role of its own (the f4-ratio's A): it is in no table either
     static constexpr bool window_hints = false;  // the hints choose the query strategy, and rows may differ in their last bits between strategies
     static constexpr const char *global_ext = ".global";
+    static constexpr bool host_rows = false;     // more(run, rows on the device, PopsHostRows) instead of more(run, rows on the device)
     bool own(const char *, const char *, int, char **) { return false; }
     template <class Row>
     void more(PopsRun &, const Row *) {}
@@ -526,7 +551,13 @@ int run_pops_tool(int argc, char **argv) {
         check(pgt_set_typical_window(ctx, typical), ctx);
         check(pgt_set_window_step(ctx, step), ctx);
     }
-    tool.more(run, pops_pass(tool, run));
+    if constexpr (Tool::host_rows) {
+        PopsHostRows<typename Tool::Row, typename Tool::Total> host;
+        const typename Tool::Row *d_rows = pops_pass(tool, run, &host);
+        tool.more(run, d_rows, host);
+    } else {
+        tool.more(run, pops_pass(tool, run));
+    }
     timer.lap("gpu reduce");
     for (const auto &write : run.writers) write();
     finish(timer);

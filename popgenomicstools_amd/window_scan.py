@@ -20,7 +20,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import (DSTAT_JACK_DTYPE, DSTAT_ROW_DTYPE, DSTAT_TOTAL_DTYPE, DXY_ROW_DTYPE, DXY_TOTAL_DTYPE, EXT_ROW_DTYPE, F3_JACK_DTYPE, F3_ROW_DTYPE, F3_TOTAL_DTYPE, F4_JACK_DTYPE, F4_ROW_DTYPE, F4_TOTAL_DTYPE, F4RATIO_JACK_DTYPE, F4RATIO_ROW_DTYPE, F4RATIO_TOTAL_DTYPE, FD_ROW_DTYPE, FD_TOTAL_DTYPE, FST_ROW_DTYPE, FST_TOTAL_DTYPE, HET_ROW_DTYPE, PBS_ROW_DTYPE, PBS_TOTAL_DTYPE, PGT_EXT_IHS,
+from ._lib import (DSTAT_JACK_DTYPE, DSTAT_ROW_DTYPE, DSTAT_TOTAL_DTYPE, DXY_ROW_DTYPE, DXY_TOTAL_DTYPE, EXT_ROW_DTYPE, F3_JACK_DTYPE, F3_ROW_DTYPE, F3_TOTAL_DTYPE, F4_JACK_DTYPE, F4_ROW_DTYPE, F4_TOTAL_DTYPE, F4RATIO_JACK_DTYPE, F4RATIO_ROW_DTYPE, F4RATIO_TOTAL_DTYPE, FD_ROW_DTYPE, FD_TOTAL_DTYPE, FST_ROW_DTYPE, FST_TOTAL_DTYPE, HET_ROW_DTYPE, PBS_JACK_DTYPE, PBS_ROW_DTYPE, PBS_TOTAL_DTYPE, PGT_EXT_IHS,
                    PGT_EXT_XP_MAX, PGT_EXT_XP_MIN, PGT_STAT_DXY, PGT_STAT_EXT, PGT_STAT_FST, PGT_STAT_HET,
                    SEG_DTYPE, SHARD_DTYPE, WIN_DTYPE, PgtError, check)
 
@@ -515,6 +515,13 @@ class Context:
         F4RATIO_ROW_DTYPE rows (what f4ratio_pops_reduce returns) over DISJOINT windows (pgt_f4ratio_jackknife)
         -> [n_triples, 6] F4RATIO_JACK_DTYPE, in ratio_order."""
         return self._jackknife("f4ratio", F4RATIO_ROW_DTYPE, F4RATIO_JACK_DTYPE, rows, items=6)
+
+    def pbs_jackknife(self, rows) -> np.ndarray:
+        """Block-jackknife PBS and PBSn1 (the branch statistic of the six sums over the used blocks, each sum losing a block with
+        one rounding), standard error and Z of every trio and focal population from a [n_trios, n_win] numpy table of
+        PBS_ROW_DTYPE rows (what pbs_pops_reduce returns, either estimator) over DISJOINT windows (pgt_pbs_jackknife)
+        -> [n_trios, 6] PBS_JACK_DTYPE, in pbs_item_order."""
+        return self._jackknife("pbs", PBS_ROW_DTYPE, PBS_JACK_DTYPE, rows, items=6)
 
     # ---- device-resident columns (torch CUDA tensors) -------------------------------------
     @staticmethod
@@ -1012,6 +1019,18 @@ class Context:
         work are given."""
         return self._jackknife_dev("f4ratio", F4RATIO_ROW_DTYPE, F4RATIO_JACK_DTYPE, rows, n_win, n_triples, out, work, stream, items=6)
 
+    @staticmethod
+    def pbs_jackknife_work_bytes(n_trios: int, n_win: int) -> int:
+        return int(_lib.load().pgt_pbs_jackknife_work_bytes(int(n_trios), int(n_win)))
+
+    def pbs_jackknife_dev(self, rows, n_win, n_trios, out=None, work=None, stream=None):
+        """Block-jackknife PBS and PBSn1, standard error and Z of n_trios trios x 6 items from the device rows of
+        pbs_pops_reduce_dev, either estimator (uint8 CUDA tensor, trio-major, n_trios * n_win rows of 88 bytes; the windows must be
+        disjoint) (pgt_pbs_jackknife_dev).  Returns (out, work): out holds 6 * n_trios PBS_JACK_DTYPE, item 6 t + c with c the
+        position in pbs_item_order (rows_from_device(out, PBS_JACK_DTYPE)).  Asynchronous on `stream`; no allocation when out and
+        work are given."""
+        return self._jackknife_dev("pbs", PBS_ROW_DTYPE, PBS_JACK_DTYPE, rows, n_win, n_trios, out, work, stream, items=6)
+
     def extreme_reduce_dev(self, pos, score, mode, cutoff, win, out=None, tree=None, stream=None):
         """ihsWindow / xpehhWindow rows from a device-resident score column (mode: PGT_EXT_*)."""
         import torch
@@ -1356,6 +1375,24 @@ def f4ratio_alphas(rows) -> np.ndarray:
         return np.where(den != 0, num / np.where(den != 0, den, 1.0), 0.0)
 
 
+def pbs_item_order(i, j, k):
+    """The six items of trio (i, j, k) in the order the block jackknife of PBS lays them out (c = 0 ... 5), each as (statistic,
+    focal population): [("pbs", i), ("pbs", j), ("pbs", k), ("pbsn1", i), ("pbsn1", j), ("pbsn1", k)]."""
+    return [("pbs", i), ("pbs", j), ("pbs", k), ("pbsn1", i), ("pbsn1", j), ("pbsn1", k)]
+
+
+def pbsn1_of(rows) -> np.ndarray:
+    """PBSn1 (Malaspinas et al. 2016), the branch statistic normalised by the trio's whole tree, of the three focal populations
+    from PBS_ROW_DTYPE rows or PBS_TOTAL_DTYPE totals (any shape) -> float64 [..., 3]: from the row's own pbs_i, pbs_j, pbs_k
+        s = (pbs_i + pbs_j) + pbs_k        pbsn1_x = pbs_x / (1.0 + s)
+    every operation one rounding, in this order.  Nothing is clamped: inf and nan are the IEEE results."""
+    rows = np.asarray(rows)
+    p = np.stack([rows["pbs_i"], rows["pbs_j"], rows["pbs_k"]], axis=-1).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        one_s = 1.0 + ((p[..., 0] + p[..., 1]) + p[..., 2])
+        return p / one_s[..., None]
+
+
 def topology_order(i, j, k):
     """The three topologies of trio (i, j, k) in the order the block jackknife lays its items out (c = 0, 1, 2), each as
     ((P1, P2), P3): [(i, j, k), (i, k, j), (j, k, i)] — D from (abba, baba), (bbaa, baba), (bbaa, abba) of the trio's row."""
@@ -1379,10 +1416,13 @@ def _window_pops(st: _PopsStat, chr_ids, pos, freqs, ninds, W, S, minind, fixeds
     return win, rows, tot
 
 
-def _trio_window_pops_jackknife(st: _PopsStat, jack_dtype, chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx, items: int = 3):
+def _trio_window_pops_jackknife(st: _PopsStat, jack_dtype, chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx, items: int = 3,
+                                jack_name: str | None = None, work_bytes=None, work_word: str = "tree"):
     """_window_pops for the rows of a trio statistic (ABBA-BABA, f3) with the rows kept ON THE DEVICE between the reduction and
     the block jackknife (<name>_pops_reduce_dev under the hints the host-buffer form derives from the table: the same rows bit
-    for bit, then <name>_jackknife_dev on them) -> (win, rows[n_trios, n_win], totals[n_trios], jack[n_trios, items])."""
+    for bit, then <name>_jackknife_dev on them) -> (win, rows[n_trios, n_win], totals[n_trios], jack[n_trios, items]).
+    jack_name: the jackknife's name where it is not the reduction's (both PBS estimators: "pbs"); work_bytes, work_word: the
+    library's size function of a reduction whose workspace holds more than the tree."""
     _refuse_dxy_window_args(W, S, minind, fixedsite, chr_len)
     st.check_count(f"{st.name}_window_pops", freqs, ninds)
     chr_ids, pos = _host_col(chr_ids, None), _host_col(pos, np.uint32)
@@ -1401,8 +1441,9 @@ def _trio_window_pops_jackknife(st: _PopsStat, jack_dtype, chr_ids, pos, freqs, 
         longest, typical, step = table_hints(win)
         with ctx.hints(longest, 0 if step >= 2 ** 63 else step, typical):
             out, tot, _ = ctx._pops_reduce_dev(st, up(pos.view(np.int32)), [up(f) for f in freqs], [up(c) for c in ninds], minind,
-                                               windows_to_device(win, dev), None, None, None, None)
-        jack, _ = ctx._jackknife_dev(st.name, st.row, jack_dtype, out, win.size, n_trios, None, None, None, items)
+                                               windows_to_device(win, dev), None, None, None, None,
+                                               getattr(ctx._lib, work_bytes) if work_bytes else None, work_word)
+        jack, _ = ctx._jackknife_dev(jack_name or st.name, st.row, jack_dtype, out, win.size, n_trios, None, None, None, items)
         rows = rows_from_device(out, st.row)[: n_trios * win.size].reshape(n_trios, win.size).copy()
         tot = rows_from_device(tot, st.total)[:n_trios].copy()
         jack = rows_from_device(jack, jack_dtype)[: items * n_trios].reshape(n_trios, items).copy()
@@ -1522,7 +1563,8 @@ def _pbs_estimator(who: str, estimator) -> _PopsStat:
 
 
 def pbs_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: int = 1, fixedsite: int = 0,
-                    chr_len=None, skip_missing: int = 0, estimator: str = "wc", ctx: Context | None = None) -> dict:
+                    chr_len=None, skip_missing: int = 0, estimator: str = "wc", ctx: Context | None = None,
+                    jackknife: bool = False) -> dict:
     """Windowed population branch statistic (Yi et al. 2010) for ALL trios of len(freqs) already synchronised populations
     (3 ... 6), every population of a trio as the focal one: {(i, j, k): WindowResult} in all_trio_order, with rows of (start,
     end, mid, n, pbs_i, pbs_j, pbs_k, num_ij, num_ik, num_jk, den_ij, den_ik, den_jk) and the genome-wide line as total.  The
@@ -1531,10 +1573,25 @@ def pbs_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: 
     Nothing is clamped: a negative FST gives a negative branch, FST = 1 gives inf, inf - inf gives nan.
     Window arguments and their errors are those of dxy_window_pops; -skip_missing drops a trio's rows without counted sites
     from that trio's result only.  The definition is pgt_pbs_pops_reduce_dev's (include/pgtwin.h).
-    Not computed: PBSn1, truncation of negative FST, a block jackknife, user-chosen trio lists."""
+    PBSn1 of rows or totals: pbsn1_of(rows).
+    jackknife=True: the result gains the key "jackknife": {(i, j, k): 6 PBS_JACK_DTYPE, one per pbs_item_order(i, j, k)} — the
+    delete-m_j block jackknife of PBS and PBSn1 of the genome-wide sums, all six sums losing a block together
+    (pgt_pbs_jackknife_dev, on the device rows of the same reduction), over ALL windows of the table as blocks, whatever
+    skip_missing is.  The windows must be disjoint: 0 < S < W and W == 0 are refused with PGT_EARG before any device use.
+    Not computed: truncation of negative FST, user-chosen trio lists."""
     st = _pbs_estimator("pbs_window_pops", estimator)
-    win, rows, tot = _window_pops(st, chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx)
-    return _results_by_pair(len(freqs), win, rows, tot, skip_missing, "n", keys=all_trio_order(len(freqs)))
+    if jackknife and (W == 0 or 0 < S < W):
+        raise PgtError(_lib.PGT_EARG, f"pbs_window_pops: the block jackknife needs disjoint windows as its blocks: "
+                                      f"winsize {W} must be positive and stepsize {S} at least the winsize")
+    keys = all_trio_order(len(freqs))
+    if not jackknife:
+        win, rows, tot = _window_pops(st, chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx)
+        return _results_by_pair(len(freqs), win, rows, tot, skip_missing, "n", keys=keys)
+    win, rows, tot, jack = _trio_window_pops_jackknife(st, PBS_JACK_DTYPE, chr_ids, pos, freqs, ninds, W, S, minind, fixedsite, chr_len, ctx, items=6,
+                                                       jack_name="pbs", work_bytes="pgt_pbs_pops_work_bytes", work_word="work")
+    res = _results_by_pair(len(freqs), win, rows, tot, skip_missing, "n", keys=keys)
+    res["jackknife"] = {t: jack[n] for n, t in enumerate(keys)}
+    return res
 
 
 def f4_window_pops(chr_ids, pos, freqs, ninds, W: int = 0, S: int = 0, minind: int = 1, fixedsite: int = 0,
